@@ -17,7 +17,9 @@ scaling.  `--workload colpart` instead runs ONE tableau column-partitioned over 
 the per-pivot RCCL exchange (all-gather of the local pricing winners + broadcast of the entering
 column); see linear-programming_amd/colpart.py.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `--dump-outputs DIR` also writes what the timed steps computed (the pivot
+sequence, the final basis / objective row / RHS column and a fixed sample of tableau rows) as DIR/*.npy, so
+that two builds can be compared output for output: the inputs depend on the arguments only.
 """
 import argparse
 import ctypes
@@ -102,7 +104,85 @@ def parse():
                     help="colpart, N > 1: skip the same-workload one-GPU figure measured on rank 0 first")
     ap.add_argument("--no-colpart-ab", action="store_true",
                     help="colpart over RCCL: skip the second leg with the rooted-broadcast exchange")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float64, at most "
+                         "64 MB in all): rank 0, single-tableau workloads and cfg4")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.workload == "colpart" or
+                              (args.gpus > 1 and args.workload == "cfg3" and args.multi_gpu == "colpart")):
+        ap.error("--dump-outputs: not available for the column-partitioned workload")
+    return args
+
+
+DUMP_BUDGET = 63 * 10 ** 6      # --dump-outputs: bytes of array data in all (under 64 MB with the .npy headers)
+DUMP_SAMPLE_SEED = 20260928     # the fixed draw of tableau rows / batch LPs when the whole does not fit
+
+
+def _write_outputs(out_dir, arrays):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def dump_tableau_outputs(out_dir, lp, L, handles, steps_per_handle):
+    """--dump-outputs, single-tableau workloads: what a caller of the timed path receives after its last
+    step.  pivot_trace: (entering column, pivot row) of every timed step, handles in launch order.  Of
+    the handle that made the last step: status and pivot count, basis, objective row, RHS column, and the
+    whole tableau -- or, when that exceeds the budget, a fixed seeded sample of its rows (tableau_rows,
+    their indices in tableau_row_index).  Read after the timed region; reading whole rows rebuilds the
+    dense tableau, which the handle's next request compacts again (the untimed warm blocks)."""
+    import numpy as np
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)                                   # noqa: E731
+    traces = []
+    for hk, k in zip(handles, steps_per_handle):
+        n = ctypes.c_int64(0)
+        lp.capi.check(L.mi355x_tab_trace(hk, None, None, 0, ctypes.byref(n)), "trace length")
+        total = n.value
+        assert k <= total <= (1 << 20), (k, total)
+        ec = np.empty(total, dtype=np.int64); cr = np.empty(total, dtype=np.int64)
+        lp.capi.check(L.mi355x_tab_trace(hk, vp(ec), vp(cr), total, ctypes.byref(n)), "trace")
+        traces.append(np.stack([ec[total - k:], cr[total - k:]], axis=1))
+    h = handles[-1]
+    rows, cols = ctypes.c_int64(0), ctypes.c_int64(0)
+    lp.capi.check(L.mi355x_tab_shape(h, ctypes.byref(rows), ctypes.byref(cols), None), "shape")
+    R, C = rows.value, cols.value
+    npv = ctypes.c_int64(0)
+    status = L.mi355x_tab_sync(h, ctypes.byref(npv))
+    basis = np.empty(R - 1, dtype=np.int64); obj = np.empty(C); rhs = np.empty(R)
+    lp.capi.check(L.mi355x_tab_download(h, None, vp(basis), vp(obj), vp(rhs)), "download")
+    out = {"pivot_trace": np.concatenate(traces), "status_and_pivots": np.array([status, npv.value]),
+           "basis": basis, "objective_row": obj, "rhs_column": rhs}
+    room = DUMP_BUDGET - sum(8 * np.asarray(a).size for a in out.values()) - 8 * R      # (8 * R: the row index)
+    n_rows = min(R, room // (8 * C))
+    idx = np.arange(R) if n_rows == R else \
+        np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(R, n_rows, replace=False))
+    block = np.empty((n_rows, C))
+    for i, r in enumerate(idx):
+        lp.capi.check(L.mi355x_tab_download_block(h, int(r), 1, 0, C, vp(block[i])), "tableau row")
+    out["tableau_rows"] = block
+    out["tableau_row_index"] = idx
+    _write_outputs(out_dir, out)
+
+
+def dump_batch_outputs(out_dir, batch, st, npv):
+    """--dump-outputs, cfg4: status and pivot count of every LP, and the final tableau and basis of every
+    LP -- or, when they exceed the budget, of a fixed seeded sample of the LPs (indices in tableau_lp_index)."""
+    import numpy as np
+    nl = len(st)
+    per_lp = 8 * (batch.rows * batch.cols + batch.rows - 1 + 1)
+    n_lps = min(nl, (DUMP_BUDGET - 16 * nl) // per_lp)
+    idx = np.arange(nl) if n_lps == nl else \
+        np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(nl, n_lps, replace=False))
+    got = [batch.download(int(i)) for i in idx]
+    _write_outputs(out_dir, {"status": st, "pivots": npv,
+                             "tableaux": np.stack([g[0] for g in got]), "bases": np.stack([g[1] for g in got]),
+                             "tableau_lp_index": idx})
 
 
 F64_VALU_PEAK_TFLOPS = 39.3     # non-FMA f64 vector rate: 256 CUs x 64 lanes x 2.4 GHz x 1 flop
@@ -547,6 +627,8 @@ def bench_batch(args, lp, rank, local_rank, N, barrier, torch, dist):
     nlch, sm, mn = ctypes.c_int64(0), ctypes.c_double(0), ctypes.c_double(0)
     L.mi355x_batch_timing_read(batch._h, ctypes.byref(nlch), ctypes.byref(sm), ctypes.byref(mn))
     assert (st == 0).all(), "not every LP reached optimality"
+    if args.dump_outputs and rank == 0:
+        dump_batch_outputs(args.dump_outputs, batch, st, npv)
     tot = torch.tensor([float(npv.sum()), elapsed], dtype=torch.float64,
                        device="cuda" if dist.get_backend() == "nccl" else "cpu") if N > 1 else None
     if N > 1:
@@ -693,11 +775,12 @@ def main():
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    left, done = args.steps, 0
+    left, done, ks = args.steps, 0, []
     for hk in handles:
         k = min(left, per_lp)
         lp.capi.check(L.mi355x_tab_solve_async(hk, 1, 1024.0, k, 0), "timed steps")
         left -= k
+        ks.append(k)
     for hk in handles:
         rc = L.mi355x_tab_sync(hk, ctypes.byref(npv))  # waits for the launch stream
         if rc != lp.capi.MI_RUNNING:
@@ -721,6 +804,8 @@ def main():
     resident = bool(L.mi355x_tab_resident(h))      # the stored tableau in registers: one launch per request
     if resident:
         block = 1
+    if args.dump_outputs and rank == 0:
+        dump_tableau_outputs(args.dump_outputs, lp, L, handles, ks)
 
     def read_events(kind):
         tot_n, tot_ms, mn_ms = 0, 0.0, None

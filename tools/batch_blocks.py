@@ -2,7 +2,7 @@
 k_batch_block, three repetitions each in one process (the first launch of a kernel pays one-time
 costs).  python tools/batch_blocks.py"""
 import ctypes, os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from tests.helpers import lp_amd
 lp = lp_amd(); L = lp.capi.lib()

@@ -2,9 +2,9 @@
 glue imports from (src/simplex.lisp, src/problem.lisp, src/solver.lisp, src/conditions.lisp of
 neil-lindquist/linear-programming).  The fixture is DATA -- package name -> exported symbol names, i.e. the
 reference's public API surface -- so that the glue's (:import-from ...) lists can be checked where the
-reference tree is absent (the GPU box); tests/test_capi_symbols.py re-derives it from /root/reference where
-that exists and fails if the fixture has gone stale.
-    python tools/gen_reference_exports.py [/root/reference]"""
+reference tree is absent; tests/test_capi_symbols.py checks the glue against it.  Rerun it on a checkout of
+the reference whenever that changes:
+    python tools/gen_reference_exports.py REFERENCE_TREE"""
 import json
 import os
 import re
@@ -43,7 +43,9 @@ def derive(ref):
 
 
 if __name__ == "__main__":
-    ref = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
+    if len(sys.argv) != 2:
+        sys.exit("usage: python tools/gen_reference_exports.py REFERENCE_TREE")
+    ref = sys.argv[1]
     data = derive(ref)
     dst = os.path.join(ROOT, "tests", "golden", "reference_exports.json")
     json.dump(data, open(dst, "w"), indent=1, sort_keys=True)

@@ -6,7 +6,7 @@
 # handler for the rest of the lease).  Everything lands under gpurun_out/evidence/ ; tools/summarize_evidence.py copies what should be
 # judged into profiles/.
 set -u
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/evidence
 rm -rf $O; mkdir -p $O
 cd $R

@@ -4,7 +4,7 @@
 # (separate runs), the steady-state A/Bs and the pass's timeline.  tools/summarize_evidence.py copies what should
 # be judged into profiles/ (it leaves alone what this run did not produce).
 set -u
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/evidence
 rm -rf $O; mkdir -p $O
 cd $R

@@ -20,7 +20,7 @@ form is WALKED with the lexical environment a compiler would keep:
 
 What it cannot see: types, run-time values, macro-expansion subtleties of LOOP beyond the clauses handled here.
     python tools/lisp_lint.py [file.lisp]          # prints the findings, exit status 1 if any
-    python tools/lisp_lint.py --signatures [/root/reference]   # regenerates tests/golden/reference_signatures.json
+    python tools/lisp_lint.py --signatures REFERENCE_TREE   # regenerates tests/golden/reference_signatures.json
 """
 import json
 import os
@@ -1266,7 +1266,9 @@ def lint(path=GLUE, reference=None, features=None, text=None):
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--signatures":
-        ref = sys.argv[2] if len(sys.argv) > 2 else "/root/reference"
+        if len(sys.argv) != 3:
+            sys.exit("usage: python tools/lisp_lint.py --signatures REFERENCE_TREE")
+        ref = sys.argv[2]
         data = reference_signatures(ref)
         json.dump(data, open(SIGNATURES, "w"), indent=1, sort_keys=True)
         print(SIGNATURES, {k: (len(v["functions"]), len(v["conditions"])) for k, v in data.items()})

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Does the gpurun box let one MI355X appear as several devices (compute partitioning: CPX exposes
-# the 8 XCDs as 8 devices), so that RCCL could run with > 1 real rank?  Read-only probes first;
-# the one mode change that is tried is undone at the end.  Every step under its own timeout.
+# the 8 XCDs as 8 devices), so that RCCL could run with > 1 real rank?  Read-only probes: the partition
+# mode is reported, never changed.  Every step under its own timeout.
 set -u
 O=${GRAFT_REPO_ROOT:-/root/repo}/gpurun_out/partition_probe
 mkdir -p $O
@@ -16,13 +16,7 @@ echo "== sysfs"
 for f in /sys/class/drm/card*/device/current_compute_partition /sys/class/drm/card*/device/available_compute_partition /sys/class/drm/card*/device/current_memory_partition; do
   [ -e "$f" ] && { echo "$f: $(cat $f 2>&1)"; ls -l $f; }
 done
-echo "== torch device count before"; timeout 120 python -c "import torch; print(torch.cuda.device_count())"
-echo "== try: amd-smi set --gpu 0 --compute-partition CPX"
-timeout 120 amd-smi set --gpu 0 --compute-partition CPX 2>&1 | tail -5; echo "rc=$?"
-echo "== try: rocm-smi --setcomputepartition CPX"
-timeout 120 rocm-smi --setcomputepartition CPX 2>&1 | tail -5; echo "rc=$?"
-timeout 60 rocm-smi --showcomputepartition 2>&1 | tail -4
-echo "== torch device count after"; timeout 120 python -c "import torch; print(torch.cuda.device_count())"
+echo "== torch device count"; timeout 120 python -c "import torch; print(torch.cuda.device_count())"
 NDEV=$(timeout 120 python -c "import torch; print(torch.cuda.device_count())" 2>/dev/null | tail -1)
 if [ "${NDEV:-1}" -gt 1 ]; then
   echo "== $NDEV devices: the multi-device RCCL tests"
@@ -30,9 +24,5 @@ if [ "${NDEV:-1}" -gt 1 ]; then
   timeout 900 python -m pytest tests/test_gpu_fullsize.py -q -x -k "rccl_on_real_devices" 2>&1 | tail -15
   timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 --colpart-vars 4096 2>&1 | tail -5
 fi
-echo "== back to SPX"
-timeout 120 amd-smi set --gpu 0 --compute-partition SPX 2>&1 | tail -3
-timeout 120 rocm-smi --setcomputepartition SPX 2>&1 | tail -3
-timeout 60 rocm-smi --showcomputepartition 2>&1 | tail -4
 } > $O/probe.log 2>&1
 cat $O/probe.log

@@ -1,5 +1,5 @@
-import ctypes, sys, time
-sys.path.insert(0, "/root/repo")
+import ctypes, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests.helpers import lp_amd
 lp = lp_amd(); L = lp.capi.lib()
 for cfg, (n, m) in {3: (8192, 4096), 2: (1024, 512)}.items():
