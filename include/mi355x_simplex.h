@@ -304,6 +304,49 @@ int  mi355x_simplex_solver_many_begin(const mi355x_problem *const *problems, int
 int  mi355x_simplex_solver_many_step(mi355x_solve_many *job, int64_t max_pivots, int32_t *status);
 int  mi355x_simplex_solver_many_finish(mi355x_solve_many *job, int32_t *status, mi355x_solution **out);
 void mi355x_simplex_solver_many_abandon(mi355x_solve_many *job);
+/* Branch-and-bound (simplex-solver with integer variables, src/simplex.lisp:462-542) as a resumable job.
+ * Opt-in: every other entry point still declines integer problems with MI_UNSUPPORTED.  The search is the
+ * reference's node for node -- a depth-first walk over an explicit stack of entries, each node the problem
+ * with the entry's rows (newest first) in front of its own constraints, the first integer variable of
+ * int_order (problem-integer-vars, in order) whose value is not integral branched on, the `<=` child on
+ * top, an integral node kept only when strictly better, a non-integral one dropped when not better than
+ * the incumbent.  Node LPs are solved ahead of time, up to `width` of them side by side (same-shape
+ * nodes in one multi-device batch over n_devices GPUs, device_ids NULL = 0 .. n_devices-1); the result,
+ * the trace and every value are the same for every width.
+ * Integrality of the double-float path: a value is integral iff it is an integer-valued double
+ * (v == floor(v), the f64 reading of integerp); int_tolerance > 0 (in units of CL's double-float-epsilon,
+ * like fp_tolerance) counts |v - round(v)| <= int_tolerance * epsilon as integral instead.  The value
+ * tested is mi355x_solution_variable's; the branching bounds are floor(v) and ceiling(v).
+ * begin: arguments checked (MI_BAD_ARG), then MI_NO_DEVICE without a device; nothing is solved yet.
+ * step: processes at most max_nodes nodes (0 = no cap); *n_nodes = nodes processed by this call.  Returns
+ * MI_MAX_PIVOTS while the search is running (call again: the continuation is exactly what one call would
+ * do), otherwise the final status: MI_OPTIMAL (an incumbent), MI_INFEASIBLE (none), MI_UNBOUNDED /
+ * MI_ART_NONZERO / MI_ART_STUCK (a node LP ended so, raised when that node is reached in DFS order), or
+ * MI_CANCELLED after mi355x_simplex_solver_bb_cancel from another thread (a further step carries on).
+ * finish: the incumbent's solution (only after MI_OPTIMAL, MI_BAD_ARG otherwise); consumes the job, as
+ * does abandon.  stats: nodes processed, node LPs solved (speculative ones included), deepest node
+ * processed.  trace: the processed nodes in order -- parent (its index in the trace, -1 for the root),
+ * the branching row that made the node (var, sense 0 `<=` / 1 `>=`, bound; var -1 for the root), the
+ * outcome (MI_BB_*) and the node's objective value (NaN without one); at most cap rows, *n = all. */
+#define MI_BB_INFEASIBLE  0   /* the node LP is infeasible: dropped                              */
+#define MI_BB_PRUNED      1   /* not integral and not better than the incumbent: dropped         */
+#define MI_BB_BRANCHED    2   /* not integral: its two children pushed                           */
+#define MI_BB_INCUMBENT   3   /* integral and better: the new incumbent                          */
+#define MI_BB_NOT_BETTER  4   /* integral, not better than the incumbent                         */
+#define MI_BB_FAILED      5   /* the node LP ended the search (unbounded, artificial variables)  */
+typedef struct mi355x_bb mi355x_bb;
+int  mi355x_simplex_solver_bb_begin(const mi355x_problem *p, const int64_t *int_order, int64_t n_int,
+                                    double fp_tolerance, double int_tolerance, int64_t width, int n_devices,
+                                    const int *device_ids, mi355x_bb **out);
+int  mi355x_simplex_solver_bb_step(mi355x_bb *job, int64_t max_nodes, int64_t *n_nodes);
+int  mi355x_simplex_solver_bb_cancel(mi355x_bb *job);
+int  mi355x_simplex_solver_bb_finish(mi355x_bb *job, mi355x_solution **out);
+void mi355x_simplex_solver_bb_abandon(mi355x_bb *job);
+int  mi355x_simplex_solver_bb_stats(const mi355x_bb *job, int64_t *n_processed, int64_t *n_solved,
+                                    int64_t *max_depth);
+int  mi355x_simplex_solver_bb_trace(const mi355x_bb *job, int64_t *parent, int64_t *var, int32_t *sense,
+                                    double *bound, int32_t *outcome, double *objective, int64_t cap,
+                                    int64_t *n);
 /* tableau-objective-value / tableau-variable / tableau-reduced-cost (src/simplex.lisp:74-120).
  * reduced_cost fails with MI_BAD_ARG for a variable without a lower bound, as the reference. */
 int  mi355x_solution_objective_value(const mi355x_solution *s, double *out);

@@ -13,6 +13,8 @@ MI_UNBOUNDED, MI_INFEASIBLE, MI_MAX_PIVOTS, MI_ART_NONZERO, MI_ART_STUCK = 1, 2,
 MI_NONFINITE = 6
 MI_CANCELLED = 7
 MI_RUNNING = 100
+# branch-and-bound trace outcomes (mi355x_simplex_solver_bb_trace)
+MI_BB_INFEASIBLE, MI_BB_PRUNED, MI_BB_BRANCHED, MI_BB_INCUMBENT, MI_BB_NOT_BETTER, MI_BB_FAILED = 0, 1, 2, 3, 4, 5
 MI_BAD_ARG, MI_HIP_ERROR, MI_RCCL_ERROR, MI_NO_DEVICE, MI_NO_MEMORY, MI_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 
 _i64, _dbl, _p, _int = ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_int
@@ -71,6 +73,13 @@ SIGNATURES = {
     "mi355x_simplex_solver_cancel": (_int, [_p]),
     "mi355x_simplex_solver_finish": (_int, [_p, _pp]),
     "mi355x_simplex_solver_abandon": (None, [_p]),
+    "mi355x_simplex_solver_bb_begin": (_int, [_p, _p, _i64, _dbl, _dbl, _i64, _int, _p, _pp]),
+    "mi355x_simplex_solver_bb_step": (_int, [_p, _i64, _p]),
+    "mi355x_simplex_solver_bb_cancel": (_int, [_p]),
+    "mi355x_simplex_solver_bb_finish": (_int, [_p, _pp]),
+    "mi355x_simplex_solver_bb_abandon": (None, [_p]),
+    "mi355x_simplex_solver_bb_stats": (_int, [_p, _p, _p, _p]),
+    "mi355x_simplex_solver_bb_trace": (_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "mi355x_simplex_solver_many_begin": (_int, [_p, _i64, _dbl, _int, _p, _pp]),
     "mi355x_simplex_solver_many_step": (_int, [_p, _i64, _p]),
     "mi355x_simplex_solver_many_finish": (_int, [_p, _p, _p]),
@@ -172,6 +181,7 @@ _EXTRA = {
     "mi355x_tune_set_lookahead_mode": (_int, [_int]),
     "mi355x_tune_set_batch_block": (_int, [_int]),
     "mi355x_tune_set_sweep_shape": (_int, [_int, _int]),
+    "mi355x_bb_debug_assemble": (_int, [_p, _i64, _i64, _p, _p, _p, _int, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 # fault injection: only in the TEST build of the library (-DMI355X_TEST_HOOKS,

@@ -11,7 +11,8 @@
 // The solution object keeps only what the read-back needs -- objective row, RHS column, basis,
 // var-mapping -- so a 400 MB tableau is never downloaded.
 // Variables are identified by their index in problem-vars.  Integer variables are declined
-// (MI_UNSUPPORTED -> unsupported-constraint-error): branch-and-bound stays with the reference.
+// (MI_UNSUPPORTED -> unsupported-constraint-error) by every entry point but the opt-in
+// branch-and-bound job of host_bb.inc (mi355x_simplex_solver_bb_*).
 #include "../../include/mi355x_simplex.h"
 
 extern "C" void mi355x_set_last_error_(const char *msg);   // simplex_capi.hip (thread-local message)
@@ -25,6 +26,17 @@ extern "C" int mi355x_tab_create_compact_streamed_(mi355x_tab **out, int64_t row
 // simplex_capi.hip (same library, not exported): cancel plumbing of a two-phase job
 extern "C" void mi355x_tab_link_cancel_(mi355x_tab *a, mi355x_tab *b);
 extern "C" void mi355x_tab_clear_cancel_(mi355x_tab *t);
+
+// simplex_capi.hip (same library, not exported): branch-and-bound node batches assembled on the devices
+struct mi355x_bb_base;
+struct mi355x_multibatch;
+extern "C" int mi355x_bb_base_create_(mi355x_bb_base **out, int64_t rows, int64_t cols, const double *M,
+                                      const int32_t *flip, const int64_t *basis, int64_t ncv, int64_t nb,
+                                      int64_t n_vars, const int32_t *kind, const int64_t *vcol, const double *voff);
+extern "C" void mi355x_bb_base_destroy_(mi355x_bb_base *b);
+extern "C" int mi355x_bb_assemble_(mi355x_bb_base *b, int64_t n, int64_t d, const int64_t *var, const int32_t *sense,
+                                   const double *bound, int64_t n_art, int n_devices, const int *device_ids,
+                                   mi355x_multibatch **main_out, mi355x_multibatch **art_out);
 
 #include <algorithm>
 #include <chrono>
@@ -89,10 +101,16 @@ struct Built {
     HostTableau main_tab, art;
     std::vector<Mapping> map;
     int status = MI_OK;                       // MI_UNBOUNDED from the no-constraint special case
+    // general form only: rows pushed for doubly-bounded variables, structural columns, and per
+    // constraint row whether it was negated (rhs < 0, :243-252) -- what branch-and-bound's device
+    // assembly of node tableaux needs (host_bb.inc)
+    int64_t nb = 0, ncv = 0;
+    std::vector<int32_t> flip;
 };
 
-// build-tableau, src/simplex.lisp:142-328 (line numbers in the comments below)
-Built build(const mi355x_problem &p)
+// build-tableau, src/simplex.lisp:142-328 (line numbers in the comments below).  general: never the
+// no-constraint special case (:153-186) -- the general form, possibly without constraint rows
+Built build(const mi355x_problem &p, bool general = false)
 {
     Built b;
     const int64_t n = p.n_vars;
@@ -102,7 +120,7 @@ Built build(const mi355x_problem &p)
     std::vector<Constraint> pushed;
     std::vector<const Constraint *> cons;
 
-    if (p.constraints.empty()) {                                          // :153-186
+    if (p.constraints.empty() && !general) {                              // :153-186
         HostTableau &t = b.main_tab;
         t.rows = n + 1; t.cols = n + 1;
         t.M.assign((size_t)t.rows * t.cols, 0.0);
@@ -156,6 +174,7 @@ Built build(const mi355x_problem &p)
     for (const auto &c : pushed) cons.push_back(&c);
     for (const auto &c : p.constraints) cons.push_back(&c);
     const int64_t m = (int64_t)cons.size();                                // :214-221
+    b.nb = (int64_t)pushed.size(); b.ncv = ncv;
     int64_t num_slack = 0;
     for (const Constraint *c : cons) if (c->op != 2) ++num_slack;
     const int64_t num_cols = ncv + num_slack + 1;
@@ -183,6 +202,7 @@ Built build(const mi355x_problem &p)
                 t.at(row, mp.col + 1) = -coef;
             }
         }
+        b.flip.push_back(t.at(row, num_cols - 1) < 0.0 ? 1 : 0);
         if (t.at(row, num_cols - 1) < 0.0) {                               // :243-252
             for (int64_t cc = 0; cc < num_cols; ++cc) t.at(row, cc) = -t.at(row, cc);
             op = (op == 0) ? 1 : (op == 1) ? 0 : 2;
@@ -933,3 +953,6 @@ int mi355x_solution_pivots(const mi355x_solution *s, int64_t *phase1, int64_t *p
 }
 
 }  // extern "C"
+
+// branch-and-bound for integer problems (src/simplex.lisp:462-542): mi355x_simplex_solver_bb_*
+#include "host_bb.inc"

@@ -283,6 +283,26 @@ void launch_ctl_publish(const TabView &t, int64_t n, void *host_dst, unsigned lo
 // `from` -> kRunning (kNeedDense: after the host has rebuilt the dense tableau; kSyncLost: after
 // it has switched the handle to the two-launch look-ahead)
 void launch_ctl_resume(const TabView &t, hipStream_t s, int32_t from);
+// branch-and-bound node tableaux (kernels_bb.inc): the base problem's GENERAL-form main tableau
+// (tight rows x cols, last row = objective), per base row the build-tableau negation flag, its basis,
+// and the var-mapping; the node rows of LPs [first, first + n_lps) of the descriptor arrays
+struct BBBaseView {
+    const double  *M;                 // rows x cols, tight
+    int64_t        rows, cols, ncv, nb;
+    const int32_t *flip;              // rows - 1
+    const int64_t *basis;             // rows - 1 (== cols for an artificial row)
+    const int32_t *kind;              // per variable: 0 positive, 1 negative, 2 signed
+    const int64_t *vcol;
+    const double  *voff;
+};
+struct BBNodeRows {
+    const int64_t *var;               // (node, k) at node * d + k, newest row first
+    const int32_t *sense;             // 0 `<=`, 1 `>=`
+    const double  *bound;
+    int64_t        d, first;
+};
+void launch_bb_assemble(const TabView &mt, const TabView &at, const BBBaseView &b, const BBNodeRows &nr,
+                        int32_t *scratch, hipStream_t s);
 // synthetic LP straight into HBM
 void launch_synth_fill(const TabView &t, int64_t n_vars, int64_t n_cons, uint64_t seed,
                        const uint64_t *dev_seeds, int64_t col_begin, int64_t col_end, hipStream_t s);

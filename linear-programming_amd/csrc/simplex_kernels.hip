@@ -68,6 +68,7 @@
 //     kernels_batch.inc           k_batch_solve, k_batch_block
 //     kernels_resident.inc        k_resident
 //     kernels_layout.inc          dense <-> compact, control block, two-phase hand-over, synthetic LPs
+//     kernels_bb.inc              branch-and-bound node tableaux assembled in HBM (k_bb_assemble)
 //     kernels_launch.inc          host-side launchers, tuning state
 #include "simplex_kernels.h"
 #include <type_traits>
@@ -84,6 +85,7 @@ namespace mi355x {
 #include "kernels_batch.inc"
 #include "kernels_resident.inc"
 #include "kernels_layout.inc"
+#include "kernels_bb.inc"
 #include "kernels_launch.inc"
 
 }  // namespace mi355x

@@ -158,6 +158,14 @@
 (cffi:defcfun ("mi355x_simplex_solver_many_finish" %solver-many-finish) :int
   (job :pointer) (status :pointer) (out :pointer))
 (cffi:defcfun ("mi355x_simplex_solver_many_abandon" %solver-many-abandon) :void (job :pointer))
+(cffi:defcfun ("mi355x_simplex_solver_bb_begin" %bb-begin) :int
+  (problem :pointer) (int-order :pointer) (n-int :int64) (fp-tolerance :double) (int-tolerance :double)
+  (width :int64) (n-devices :int) (device-ids :pointer) (out :pointer))
+(cffi:defcfun ("mi355x_simplex_solver_bb_step" %bb-step) :int
+  (job :pointer) (max-nodes :int64) (n-nodes :pointer))
+(cffi:defcfun ("mi355x_simplex_solver_bb_finish" %bb-finish) :int
+  (job :pointer) (out :pointer))
+(cffi:defcfun ("mi355x_simplex_solver_bb_abandon" %bb-abandon) :void (job :pointer))
 (cffi:defcfun ("mi355x_solution_objective_value" %solution-objective-value) :int
   (solution :pointer) (out :pointer))
 (cffi:defcfun ("mi355x_solution_variable" %solution-variable) :int
@@ -668,6 +676,47 @@ Returns a MI355X-SOLUTION or signals the reference's conditions."
                (unless consumed (%solver-abandon job)))))
       (%problem-destroy problem-handle))))
 
+(defun solve-branch-and-bound (problem factor int-tolerance width devices max-nodes)
+  "simplex-solver with integer variables (src/simplex.lisp:462-542) behind the C ABI: marshal,
+mi355x_simplex_solver_bb_begin with problem-integer-vars IN ORDER (the order decides which variable
+is branched on), ..._bb_step in bounded chunks of nodes (never an unbounded foreign call),
+..._bb_finish (the incumbent).  The search is the reference's node for node; up to WIDTH node LPs
+are solved side by side.  Returns a MI355X-SOLUTION or signals the reference's conditions."
+  (multiple-value-bind (problem-handle var-index) (marshal-problem problem)
+    (unwind-protect
+         (let* ((int-vars (problem-integer-vars problem))
+                (n-int (length int-vars))
+                (n-dev (device-count-of devices)))
+           (cffi:with-foreign-objects ((order :int64 (max n-int 1)) (ids :int (max n-dev 1))
+                                       (out :pointer) (n-nodes :int64))
+             (loop for var in int-vars for k from 0
+                   do (setf (cffi:mem-aref order :int64 k) (gethash var var-index)))
+             (when (listp devices)
+               (loop for d in devices for i from 0 do (setf (cffi:mem-aref ids :int i) d)))
+             (check (with-foreign-fp-mode
+                      (%bb-begin problem-handle order n-int factor (coerce int-tolerance 'double-float)
+                                 width n-dev (if (listp devices) ids (cffi:null-pointer)) out)))
+             (let ((job (cffi:mem-ref out :pointer))
+                   (consumed nil)
+                   (done 0))
+               (unwind-protect
+                    (let ((status
+                            (loop
+                              (let* ((cap (if (plusp max-nodes) (min 256 (- max-nodes done)) 256))
+                                     (rc (check (with-foreign-fp-mode (%bb-step job cap n-nodes)))))
+                                (incf done (cffi:mem-ref n-nodes :int64))
+                                (when (or (/= rc +mi-max-pivots+)
+                                          (and (plusp max-nodes) (>= done max-nodes)))
+                                  (return rc))))))
+                      (when (= status +mi-max-pivots+)
+                        (error 'mi355x-error :code status :message "node cap reached"))
+                      (signal-outcome status)
+                      (setf consumed t)              ; finish consumes the job whatever it returns
+                      (check (%bb-finish job out))
+                      (make-solution problem (cffi:mem-ref out :pointer) var-index))
+                 (unless consumed (%bb-abandon job))))))
+      (%problem-destroy problem-handle))))
+
 (defun solve-problems-natively (problems factor devices max-pivots)
   "A LIST of problems entirely behind the C ABI: every problem marshalled (mi355x_problem_*), ONE job of
 the library for the list (mi355x_simplex_solver_many_begin groups the members by tableau shape and
@@ -758,7 +807,8 @@ phases together.  Returns the final status."
 
 (defun mi355x-simplex-solver (problem &rest args
                               &key (fp-tolerance 1024) (device 0) (devices 1) (max-pivots 0)
-                                full-tableau (native :auto)
+                                full-tableau (native :auto) branch-and-bound (bb-width 1)
+                                (int-tolerance 0) (max-nodes 0)
                               &allow-other-keys)
   "Solver interface function for the MI355X backend (the value of
 linear-programming:*solver*, src/solver.lisp:39-49).  Takes a problem and backend keyword
@@ -774,8 +824,19 @@ build-tableau route) -- and returns a solution object answering solution-problem
 solution-objective-value, solution-variable and solution-reduced-cost (src/solver.lisp:40-45): a
 MI355X-SOLUTION on the native route, a solved `tableau` otherwise.  solve-problem forwards these
 keywords (src/solver.lisp:53-56):
-  (solve-problem problem :devices 8)        (solve-problem problem :devices '(4 5 6 7))"
+  (solve-problem problem :devices 8)        (solve-problem problem :devices '(4 5 6 7))
+:branch-and-bound T (opt-in; without it integer problems are declined as before) solves an integer
+problem with the reference's branch-and-bound (src/simplex.lisp:462-542), node for node, in the
+library: :bb-width node LPs side by side (default 1; results do not depend on it), :int-tolerance
+(0, the default: a value is integral iff it is an integer-valued double; > 0: within that many
+double-float-epsilons of an integer), :max-nodes (0 = no cap)."
   (declare (ignore args))
+  ;; :branch-and-bound T (opt-in): integer problems through the library's branch-and-bound job
+  ;; (:bb-width node LPs side by side, :int-tolerance 0 = exact integrality, :max-nodes 0 = no cap)
+  (when (and branch-and-bound (problem-integer-vars problem))
+    (return-from mi355x-simplex-solver
+      (solve-branch-and-bound problem (coerce fp-tolerance 'double-float) int-tolerance bb-width devices
+                              max-nodes)))
   (when (problem-integer-vars problem)
     (error 'unsupported-constraint-error
            :constraint (cons 'integer (problem-integer-vars problem))

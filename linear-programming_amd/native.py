@@ -170,6 +170,85 @@ class NativeSolution:
             capi.lib().mi355x_solution_destroy(h)
 
 
+class BranchAndBound:
+    """The glue's `solve-branch-and-bound`, call for call: a NativeProblem, ONE
+    mi355x_simplex_solver_bb_begin with problem-integer-vars in their order, ..._bb_step in bounded
+    chunks of nodes, ..._bb_finish (the incumbent's light solution).  `cancel()` may be called from
+    another thread while `run()` is stepping; `trace()` and `stats()` read the job (before finish)."""
+
+    def __init__(self, problem, fp_tolerance=1024, int_tolerance=0, width=64, devices=1, device_ids=None):
+        L = capi.lib()
+        self.nproblem = NativeProblem(problem)
+        order, op = _arr([self.nproblem.index[v] for v in problem.integer_vars], np.int64)
+        self._order = order
+        ids = None if device_ids is None else (ctypes.c_int * len(device_ids))(*[int(d) for d in device_ids])
+        n_dev = int(devices) if device_ids is None else len(device_ids)
+        h = ctypes.c_void_p()
+        capi.check(L.mi355x_simplex_solver_bb_begin(self.nproblem._h, op if len(order) else None, len(order),
+                                                    float(fp_tolerance), float(int_tolerance), int(width),
+                                                    n_dev, ids, ctypes.byref(h)),
+                   "mi355x_simplex_solver_bb_begin")
+        self._h = h
+
+    def step(self, max_nodes):
+        """One bounded call: -> (status, nodes processed by it)."""
+        n = ctypes.c_int64(0)
+        rc = capi.check(capi.lib().mi355x_simplex_solver_bb_step(self._h, int(max_nodes), ctypes.byref(n)),
+                        "mi355x_simplex_solver_bb_step")
+        return rc, int(n.value)
+
+    def cancel(self):
+        """mi355x_simplex_solver_bb_cancel (any thread; see bb_inspect.py)."""
+        from . import bb_inspect
+        bb_inspect.cancel(self)
+
+    def run(self, max_nodes=0, chunk=256):
+        """Steps of at most `chunk` nodes until the search ends or max_nodes (0: no cap) are processed;
+        -> the last status."""
+        done = 0
+        while True:
+            cap = min(chunk, max_nodes - done) if max_nodes > 0 else chunk
+            rc, k = self.step(cap)
+            done += k
+            if rc != capi.MI_MAX_PIVOTS or (max_nodes > 0 and done >= max_nodes):
+                return rc
+
+    def stats(self):
+        from . import bb_inspect
+        return bb_inspect.stats(self)
+
+    def trace(self):
+        """[(parent, var name or None, sense, bound, outcome, objective)] of the processed nodes."""
+        from . import bb_inspect
+        return bb_inspect.trace(self)
+
+    def finish(self):
+        """The incumbent as a NativeSolution; consumes the job."""
+        h, self._h = self._h, None
+        s = ctypes.c_void_p()
+        capi.check(capi.lib().mi355x_simplex_solver_bb_finish(h, ctypes.byref(s)), "mi355x_simplex_solver_bb_finish")
+        return NativeSolution(self.nproblem, s)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            capi.lib().mi355x_simplex_solver_bb_abandon(h)
+
+
+def solve_branch_and_bound(problem, fp_tolerance=1024, int_tolerance=0, width=64, devices=1, device_ids=None,
+                           max_nodes=0, chunk=256):
+    """simplex-solver with integer variables (src/simplex.lisp:506-542) through the library's
+    branch-and-bound job: returns the incumbent's NativeSolution or raises the reference's errors."""
+    from .simplex import _raise_for
+    bb = BranchAndBound(problem, fp_tolerance=fp_tolerance, int_tolerance=int_tolerance, width=width,
+                        devices=devices, device_ids=device_ids)
+    rc = bb.run(max_nodes=max_nodes, chunk=chunk)
+    if rc == capi.MI_MAX_PIVOTS:
+        raise SolverError("node cap reached (max_nodes=%d)" % max_nodes)
+    _raise_for(rc)
+    return bb.finish()
+
+
 def solve_many(problems, fp_tolerance=1024, devices=1, device_ids=None, max_pivots=0, chunk=None):
     """The glue's native `mi355x-solve-problems`, call for call: every problem marshalled
     (mi355x_problem_*), ONE mi355x_simplex_solver_many_begin for the list (the library groups the

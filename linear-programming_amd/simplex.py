@@ -589,19 +589,29 @@ def _native_numbers(problem):
 
 
 def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_pivots=0,
-                          full_tableau=False, native="auto", chunk=None, **_ignored):
+                          full_tableau=False, native="auto", chunk=None, branch_and_bound=False,
+                          bb_width=1, int_tolerance=0, max_nodes=0, **_ignored):
     """What the Lisp glue installs as `*solver*` (src/solver.lisp:39-56): takes a problem and
     backend keyword arguments, returns a solution object answering the four solution-*
     generics -- on the NATIVE route (default whenever the problem's numbers are floats / integers
     and neither full_tableau nor devices > 1 asks for the tableau itself; native=True forces it,
     native=False never takes it) a NativeSolution (the glue's MI355X-SOLUTION: problem marshalled
     through mi355x_problem_*, mi355x_simplex_solver_begin / _step in bounded chunks / _finish), on
-    the build-tableau route a solved Tableau.  LP only: integer/binary variables are declined the way a backend must
-    (unsupported-constraint-error, src/conditions.lisp:69-77); branch-and-bound
-    (src/simplex.lisp:506-542) stays with the reference's own solver.  devices > 1: the tableau
+    the build-tableau route a solved Tableau.  By default integer/binary variables are declined the way a backend must
+    (unsupported-constraint-error, src/conditions.lisp:69-77); branch_and_bound=True opts in (below).  devices > 1: the tableau
     (single-phase problems) or the artificial tableau (two-phase problems: phase 1, the hand-over
     and phase 2 all stay partitioned) is column-partitioned over that many GPUs (logical shards of
-    one GPU when fewer are visible); tableaux that overflow run on `device`."""
+    one GPU when fewer are visible); tableaux that overflow run on `device`.
+    branch_and_bound=True (opt-in) solves integer problems instead: the reference's branch-and-bound
+    (src/simplex.lisp:462-542) node for node through the library's job (mi355x_simplex_solver_bb_*,
+    stepped in bounded chunks of nodes), up to bb_width node LPs side by side on `devices` GPUs
+    (logical devices of one GPU when fewer are visible); int_tolerance > 0 counts values within
+    int_tolerance * epsilon of an integer as integral (0: exact); max_nodes caps the nodes
+    processed (0: no cap).  Returns the incumbent's NativeSolution."""
+    if problem.integer_vars and branch_and_bound:
+        from .native import solve_branch_and_bound
+        return solve_branch_and_bound(problem, fp_tolerance=fp_tolerance, int_tolerance=int_tolerance,
+                                      width=bb_width, devices=devices, max_nodes=max_nodes)
     if problem.integer_vars:
         raise UnsupportedConstraintError(("integer",) + tuple(problem.integer_vars),
                                          "mi355x-simplex")
