@@ -62,6 +62,8 @@ extern "C" {
 #define MI_NO_DEVICE    -4
 #define MI_NO_MEMORY    -5
 #define MI_UNSUPPORTED  -6   /* -> unsupported-constraint-error (integer / binary variables) */
+#define MI_EXACT_OVERFLOW -7 /* exact tableaux: a value needs more than 128 bits -> unsupported-constraint-error */
+#define MI_EXACT_INEXACT  -8 /* exact tableaux: a fraction-free division left a remainder (an internal error) */
 
 typedef struct mi355x_tab   mi355x_tab;     /* one tableau resident in HBM              */
 typedef struct mi355x_batch mi355x_batch;   /* a batch of same-shape tableaux in HBM    */
@@ -69,6 +71,7 @@ typedef struct mi355x_problem  mi355x_problem;   /* a parsed LP, src/problem.lis
 typedef struct mi355x_solution mi355x_solution;  /* what the read-back needs of a solved tableau */
 typedef struct mi355x_solve    mi355x_solve;     /* a problem on its way to a solution (resumable)  */
 typedef struct mi355x_solve_many mi355x_solve_many; /* a LIST of problems on their way to solutions   */
+typedef struct mi355x_xtab     mi355x_xtab;      /* one exact (fraction-free integer) tableau in HBM */
 
 /* ---- library / device ------------------------------------------------------------- */
 int         mi355x_abi_version(void);
@@ -304,6 +307,51 @@ int  mi355x_simplex_solver_many_begin(const mi355x_problem *const *problems, int
 int  mi355x_simplex_solver_many_step(mi355x_solve_many *job, int64_t max_pivots, int32_t *status);
 int  mi355x_simplex_solver_many_finish(mi355x_solve_many *job, int32_t *status, mi355x_solution **out);
 void mi355x_simplex_solver_many_abandon(mi355x_solve_many *job);
+/* ---- exact rational tableaux  (the reference's `rational` dispatch, src/utils.lisp:84-124) -------
+ * A tableau whose entries are all rational is solved with exact arithmetic: the device holds one
+ * integer matrix T and one integer D > 0 with t_ij = T_ij / D (fraction-free, Bareiss), so pricing,
+ * the ratio test and the phase-1 tests are the reference's exact comparisons and every value read back
+ * is the exact rational the reference's tableau holds.  Pivot sequence, basis and entries are those of
+ * src/simplex.lisp:337-461 under the rational dispatch.  Values are stored as 64-bit integers (128-bit
+ * products) or 128-bit integers (256-bit products); a solve that overflows 64 bits restarts from the
+ * initial tableau(s) at 128 bits (results do not depend on the width), one that overflows 128 bits ends
+ * with MI_EXACT_OVERFLOW and the handle can only be destroyed.
+ * Start state: with L_i the LCM of row i's denominators and the objective row's LCM multiplied into the
+ * first constraint row's, D0 = prod L_i and T0 = D0 * t0 -- the state after the slack identity has been
+ * pivoted, which needs the basis columns to be exact unit columns and the objective row zero on them
+ * (what build-tableau produces, src/simplex.lisp:142-328); a solve of a tableau without that start returns
+ * MI_UNSUPPORTED. */
+/* Upload a build-tableau result: num / den are rows*cols (den > 0), basis has rows-1 entries (entries
+ * outside [0, cols-1) are build-tableau's placeholders for artificial rows).  min_bits 0 or 64: start at
+ * 64 bits when T0 fits, 128: start at 128.  MI_EXACT_OVERFLOW when T0 needs more than 128 bits. */
+int  mi355x_xtab_create(mi355x_xtab **out, int64_t rows, int64_t cols, const int64_t *num,
+                        const int64_t *den, const int64_t *basis, int device, int min_bits);
+/* n-solve-tableau, single phase (src/simplex.lisp:453-461): at most max_pivots pivots (0 = no cap),
+ * *n_pivots = pivots made by this call.  MI_OPTIMAL / MI_UNBOUNDED / MI_MAX_PIVOTS (a further call
+ * carries on exactly) / MI_CANCELLED (mi355x_xtab_cancel from another thread; whole pivots only). */
+int  mi355x_xtab_solve(mi355x_xtab *t, int is_max, int64_t max_pivots, int64_t *n_pivots);
+/* n-solve-tableau, two-phase branch (src/simplex.lisp:402-452): phase 1 on `art` (a min problem), the
+ * exact feasibility test, the drive-out pivots (first non-basic column with a non-zero entry, negative
+ * pivots included), the hand-over into `main_tab` (its objective row re-eliminated from the original
+ * one: D * c - sum_i c[b_i] * T_i, after the constraint rows and D are multiplied by the LCM of c's
+ * denominators) and phase 2.  max_pivots caps both phases together (0 = no cap); a call after
+ * MI_MAX_PIVOTS or MI_CANCELLED carries on where the job stopped.  n_pivots[0] = phase-1 pivots made by
+ * this call (drive-out pivots included; they are not in the trace, as in the reference's loop),
+ * n_pivots[1] = phase-2 pivots.  Outcomes as mi355x_solve_two_phase. */
+int  mi355x_xtab_solve_two_phase(mi355x_xtab *art, mi355x_xtab *main_tab, int main_is_max,
+                                 int64_t max_pivots, int64_t *n_pivots);
+/* tableau-matrix / tableau-basis-columns (src/simplex.lisp:48-58): the raw T as (low, high) 64-bit
+ * limbs of a two's complement 128-bit integer per entry (rows*cols*2), D likewise (2), the basis
+ * (rows-1).  t_ij = T_ij / D.  Any pointer may be NULL. */
+int  mi355x_xtab_download(mi355x_xtab *t, int64_t *num_lo_hi, int64_t *den_lo_hi, int64_t *basis);
+/* the (entering column, row) of every pivot chosen by the solve loops since the start, in order (the
+ * drive-out pivots are not in it); at most cap, *n = all. */
+int  mi355x_xtab_trace(mi355x_xtab *t, int64_t *entering_cols, int64_t *pivot_rows, int64_t cap, int64_t *n);
+/* the width in use: 64 or 128 */
+int  mi355x_xtab_bits(const mi355x_xtab *t, int *bits);
+/* mi355x_tab_cancel for the exact solves (any thread) */
+int  mi355x_xtab_cancel(mi355x_xtab *t);
+void mi355x_xtab_destroy(mi355x_xtab *t);
 /* Branch-and-bound (simplex-solver with integer variables, src/simplex.lisp:462-542) as a resumable job.
  * Opt-in: every other entry point still declines integer problems with MI_UNSUPPORTED.  The search is the
  * reference's node for node -- a depth-first walk over an explicit stack of entries, each node the problem

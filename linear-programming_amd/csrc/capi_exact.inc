@@ -1,0 +1,459 @@
+// capi_exact.inc -- mi355x_xtab_*: exact rational solves on fraction-free integer tableaux
+// (kernels_exact.inc).  Part of simplex_capi.hip (ONE translation unit: included there, in this order).
+//
+// The handle keeps the caller's rationals on the host: a solve that overflows 64 bits starts again,
+// both phases, from them at 128 bits.  What stays on the host: the start state (row LCMs, one pass
+// over the input), the phase-1 feasibility test and the drive-out decisions (one element, the basis and
+// the row of each artificial variable still basic: a sequential scan over a handful of rows, once per
+// solve), and the hand-over's multipliers (the LCM of the objective row's denominators and c[b_i]).
+
+struct mi355x_xtab {
+    int         device = 0;
+    hipStream_t stream = nullptr;
+    int64_t     rows = 0, cols = 0;
+    std::vector<int64_t> num, den, basis0;   // the caller's tableau, t0 = num / den
+    bool        start_ok = false;            // basis columns exact unit columns, objective row zero on them
+    int         bits = 0;                    // width of the device buffers (0: none yet)
+    XView       v{};
+    XCtl        h{};                         // host mirror of v.ctl, current whenever no call is running
+    void       *aux = nullptr;               // hand-over multipliers: rows + cols values of the width
+    bool        dead = false;                // overflowed 128 bits: only destroy is left
+    bool        derived = false;             // the main tableau of a two-phase job
+    // two-phase job, kept on the artificial tableau
+    mi355x_xtab *tp_main = nullptr;
+    int         tp_phase = 0;                // 0 phase 1, 1 phase 2, 2 the hand-over ended the job (tp_status)
+    int         tp_status = MI_OK;
+    int64_t     tp_driveouts = 0;
+    std::atomic<int> cancel{0};
+};
+
+namespace {
+
+constexpr int64_t kXTraceCap = 1 << 18;
+
+typedef unsigned __int128 u128_t;
+typedef __int128 i128_t;
+const i128_t INT128_MIN_ = (i128_t)((u128_t)1 << 127);
+
+int use_device_id(int device)
+{
+    HIP_TRY(hipSetDevice(device));
+    return MI_OK;
+}
+
+bool x_mul(i128_t a, i128_t b, i128_t *r) { return !__builtin_mul_overflow(a, b, r); }
+u128_t x_gcd(u128_t a, u128_t b) { while (b) { u128_t t = a % b; a = b; b = t; } return a; }
+// lcm of positive values, false on overflow of the symmetric 128-bit range
+bool x_lcm(i128_t a, i128_t b, i128_t *r) { return x_mul(a / (i128_t)x_gcd((u128_t)a, (u128_t)b), b, r) && *r != INT128_MIN_; }
+bool x_fits(i128_t x, int bits)
+{
+    if (bits == 64) return x > (i128_t)INT64_MIN && x <= (i128_t)INT64_MAX;
+    return x != INT128_MIN_;
+}
+
+int x_take_cancel(mi355x_xtab *a, mi355x_xtab *b = nullptr)
+{
+    int c = a->cancel.exchange(0, std::memory_order_acq_rel);
+    if (b) c |= b->cancel.exchange(0, std::memory_order_acq_rel);
+    return c;
+}
+
+int x_read_ctl(mi355x_xtab *t)
+{
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&t->h, t->v.ctl, sizeof(XCtl), hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    return MI_OK;
+}
+int x_write_ctl(mi355x_xtab *t)
+{
+    HIP_TRY(hipMemcpyAsync(t->v.ctl, &t->h, sizeof(XCtl), hipMemcpyHostToDevice, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    return MI_OK;
+}
+
+void x_free_width(mi355x_xtab *t)
+{
+    (void)hipFree(t->v.T); (void)hipFree(t->v.col); (void)hipFree(t->v.prow); (void)hipFree(t->aux);
+    t->v.T = t->v.col = t->v.prow = t->aux = nullptr;
+}
+
+// The start state at `bits`: D0 = prod L_i (the objective row's LCM folded into the first constraint
+// row's), T0 = D0 * t0.  MI_OK, or kXOverflow when it does not fit the width.
+int x_start_state(const mi355x_xtab *t, int bits, std::vector<i128_t> &T0, i128_t *D0)
+{
+    const int64_t R = t->rows, C = t->cols, m = R - 1;
+    std::vector<i128_t> L(R, 1);
+    for (int64_t i = 0; i < R; ++i)
+        for (int64_t j = 0; j < C; ++j)
+            if (!x_lcm(L[i], t->den[i * C + j], &L[i])) return kXOverflow;
+    i128_t D = 1;
+    if (m > 0 && !x_mul(L[0], L[m], &L[0])) return kXOverflow;
+    if (m == 0) D = L[0];
+    for (int64_t i = 0; i < m; ++i)
+        if (!x_mul(D, L[i], &D)) return kXOverflow;
+    if (!x_fits(D, bits)) return kXOverflow;
+    T0.assign((size_t)(R * C), 0);
+    for (int64_t k = 0; k < R * C; ++k) {
+        i128_t x;
+        if (!x_mul(D / t->den[k], t->num[k], &x) || !x_fits(x, bits)) return kXOverflow;
+        T0[k] = x;
+    }
+    *D0 = D;
+    return MI_OK;
+}
+
+// (re)load the start state at `bits`: device buffers of that width, T0, basis, a fresh control block
+int x_reset(mi355x_xtab *t, int bits)
+{
+    std::vector<i128_t> T0;
+    i128_t D0 = 0;
+    if (x_start_state(t, bits, T0, &D0) != MI_OK) return kXOverflow;
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    const size_t w = bits / 8, R = (size_t)t->rows, C = (size_t)t->cols;
+    if (t->bits != bits) {
+        x_free_width(t);
+        HIP_TRY(hipMalloc(&t->v.T, R * C * w));
+        HIP_TRY(hipMalloc(&t->v.col, R * w));
+        HIP_TRY(hipMalloc(&t->v.prow, C * w));
+        HIP_TRY(hipMalloc(&t->aux, (R + C) * w));
+        t->bits = t->v.bits = bits;
+    }
+    std::vector<unsigned char> stage(R * C * w);
+    for (size_t k = 0; k < R * C; ++k) {
+        if (bits == 64) { const int64_t x = (int64_t)T0[k]; memcpy(&stage[k * w], &x, w); }
+        else            memcpy(&stage[k * w], &T0[k], w);
+    }
+    HIP_TRY(hipMemcpyAsync(t->v.T, stage.data(), stage.size(), hipMemcpyHostToDevice, t->stream));
+    if (R > 1) HIP_TRY(hipMemcpyAsync(t->v.basis, t->basis0.data(), (R - 1) * sizeof(int64_t), hipMemcpyHostToDevice, t->stream));
+    t->h = XCtl{};
+    t->h.status = MI_OPTIMAL;
+    t->h.D = D0;
+    return x_write_ctl(t);                    // (synchronises: `stage` may go)
+}
+
+// one solve of the handle's tableau, blind enqueue of (select, update) pairs in growing chunks with one
+// control-block read per chunk: the status, MI_CANCELLED, kXOverflow or kXInexact
+int x_run(mi355x_xtab *t, int is_max, int64_t cap_at, mi355x_xtab *peer)
+{
+    t->h.status = kRunning;
+    t->h.err = 0;
+    t->h.apply = 0;
+    t->h.cap_at = cap_at;
+    int rc = x_write_ctl(t);
+    if (rc != MI_OK) return rc;
+    for (int64_t chunk = 8;; chunk = std::min<int64_t>(chunk * 2, 512)) {
+        for (int64_t k = 0; k < chunk; ++k) {
+            launch_x_select(t->v, is_max, t->stream);
+            launch_x_update(t->v, t->stream);
+        }
+        rc = x_read_ctl(t);
+        if (rc != MI_OK) return rc;
+        if (t->h.err) return t->h.err;
+        if (t->h.status != kRunning) return t->h.status;
+        if (x_take_cancel(t, peer)) return MI_CANCELLED;    // (the chunk ended on an update: whole pivots)
+    }
+}
+
+int x_download_values(mi355x_xtab *t, int64_t r0, int64_t n, std::vector<i128_t> &out)
+{
+    const size_t w = t->bits / 8;
+    std::vector<unsigned char> buf((size_t)n * w);
+    if (n > 0)
+        HIP_TRY(hipMemcpyAsync(buf.data(), (const unsigned char *)t->v.T + (size_t)r0 * w, buf.size(),
+                               hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    out.resize((size_t)n);
+    for (int64_t k = 0; k < n; ++k) {
+        if (t->bits == 64) { int64_t x; memcpy(&x, &buf[k * w], w); out[k] = x; }
+        else               memcpy(&out[k], &buf[k * w], w);
+    }
+    return MI_OK;
+}
+
+// between the phases (src/simplex.lisp:405-451): MI_OK (main ready for phase 2), MI_INFEASIBLE,
+// MI_ART_NONZERO, MI_ART_STUCK, kXOverflow, kXInexact, or an error
+int x_handover(mi355x_xtab *a, mi355x_xtab *mt)
+{
+    const int64_t m = a->rows - 1, C = a->cols, nav = C - 1, nv = mt->cols - 1;
+    std::vector<i128_t> row;
+    int rc = x_download_values(a, m * C + nav, 1, row);                  // the artificial objective value
+    if (rc != MI_OK) return rc;
+    if (row[0] != 0) return MI_INFEASIBLE;
+    std::vector<int64_t> basis((size_t)m);
+    if (m > 0) HIP_TRY(hipMemcpy(basis.data(), a->v.basis, m * sizeof(int64_t), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < m; ++i) {
+        if (basis[i] < nv) continue;
+        rc = x_download_values(a, i * C, C, row);
+        if (rc != MI_OK) return rc;
+        if (row[nav] != 0) return MI_ART_NONZERO;
+        int64_t j = 0;
+        for (; j < nv; ++j)
+            if (row[j] != 0 && std::find(basis.begin(), basis.end(), j) == basis.end()) break;
+        if (j == nv) return MI_ART_STUCK;
+        launch_x_force(a->v, j, i, a->stream);
+        launch_x_update(a->v, a->stream);
+        rc = x_read_ctl(a);
+        if (rc != MI_OK) return rc;
+        if (a->h.err) return a->h.err;
+        basis[i] = j;
+        a->tp_driveouts += 1;
+    }
+    // multipliers of the re-elimination: L_c (LCM of the original objective row's denominators),
+    // w_i = L_c * c[b_i], cl_j = L_c * c_j
+    const int64_t Cm = mt->cols;
+    const int64_t *cn = &mt->num[m * Cm], *cd = &mt->den[m * Cm];
+    i128_t lc = 1;
+    for (int64_t j = 0; j < Cm; ++j)
+        if (!x_lcm(lc, cd[j], &lc)) return kXOverflow;
+    std::vector<i128_t> mult((size_t)(m + Cm));
+    for (int64_t i = 0; i < m; ++i)
+        if (!x_mul(lc / cd[basis[i]], cn[basis[i]], &mult[i])) return kXOverflow;
+    for (int64_t j = 0; j < Cm; ++j)
+        if (!x_mul(lc / cd[j], cn[j], &mult[m + j])) return kXOverflow;
+    if (!x_fits(lc, mt->bits)) return kXOverflow;
+    for (auto x : mult)
+        if (!x_fits(x, mt->bits)) return kXOverflow;
+    const size_t w = mt->bits / 8;
+    std::vector<unsigned char> stage(mult.size() * w);
+    for (size_t k = 0; k < mult.size(); ++k) {
+        if (mt->bits == 64) { const int64_t x = (int64_t)mult[k]; memcpy(&stage[k * w], &x, w); }
+        else                memcpy(&stage[k * w], &mult[k], w);
+    }
+    HIP_TRY(hipMemcpyAsync(mt->aux, stage.data(), stage.size(), hipMemcpyHostToDevice, mt->stream));
+    if (m > 0) HIP_TRY(hipMemcpyAsync(mt->v.basis, basis.data(), m * sizeof(int64_t), hipMemcpyHostToDevice, mt->stream));
+    mt->h = XCtl{};
+    mt->h.status = MI_OPTIMAL;
+    rc = x_write_ctl(mt);                      // (synchronises: `stage` may go)
+    if (rc != MI_OK) return rc;
+    launch_x_handover(a->v, mt->v, mt->aux, (const unsigned char *)mt->aux + m * w, lc, mt->stream);
+    rc = x_read_ctl(mt);
+    if (rc != MI_OK) return rc;
+    return mt->h.err ? mt->h.err : MI_OK;
+}
+
+// the two-phase job from where it stands up to `target` pivots of both phases together (0: no cap)
+int x_two_phase(mi355x_xtab *a, mi355x_xtab *mt, int is_max, int64_t target)
+{
+    if (a->tp_phase == 2) return a->tp_status;
+    if (a->tp_phase == 0) {
+        const int st = x_run(a, 0, target, mt);
+        if (st != MI_OPTIMAL) return st;
+        const int rc = x_handover(a, mt);
+        if (rc == kXOverflow || rc == kXInexact || rc < 0) return rc;
+        if (rc != MI_OK) { a->tp_phase = 2; a->tp_status = rc; return rc; }
+        a->tp_phase = 1;
+    }
+    const int64_t n1 = a->h.n_pivots + a->tp_driveouts;
+    if (target > 0 && target - n1 <= mt->h.n_pivots) return MI_MAX_PIVOTS;
+    return x_run(mt, is_max, target > 0 ? target - n1 : 0, a);
+}
+
+int x_check_device(int device)
+{
+    const int ndev = device_count_checked();
+    if (ndev <= 0) return fail(MI_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(MI_BAD_ARG, "device %d out of range (%d visible)", device, ndev);
+    return MI_OK;
+}
+
+int x_status(mi355x_xtab *t, int st)
+{
+    if (st == kXInexact) return fail(MI_EXACT_INEXACT, "a fraction-free division left a remainder (internal error)");
+    if (st == kXOverflow) { t->dead = true; return fail(MI_EXACT_OVERFLOW, "an entry of the exact tableau needs more than 128 bits"); }
+    return st;
+}
+
+}  // namespace
+
+int mi355x_xtab_create(mi355x_xtab **out, int64_t rows, int64_t cols, const int64_t *num, const int64_t *den,
+                       const int64_t *basis, int device, int min_bits)
+{
+    if (!out) return fail(MI_BAD_ARG, "out is NULL");
+    *out = nullptr;
+    if (rows < 1 || cols < 1 || !num || !den || (rows > 1 && !basis))
+        return fail(MI_BAD_ARG, "bad shape or NULL array");
+    if (min_bits != 0 && min_bits != 64 && min_bits != 128) return fail(MI_BAD_ARG, "min_bits must be 0, 64 or 128");
+    for (int64_t k = 0; k < rows * cols; ++k)
+        if (den[k] <= 0) return fail(MI_BAD_ARG, "denominator %lld of entry %lld is not positive", (long long)den[k], (long long)k);
+    int rc = x_check_device(device);
+    if (rc != MI_OK) return rc;
+    mi355x_xtab *t = new (std::nothrow) mi355x_xtab;
+    if (!t) return fail(MI_NO_MEMORY, "host allocation failed");
+    t->device = device;
+    t->rows = rows;
+    t->cols = cols;
+    t->num.assign(num, num + rows * cols);
+    t->den.assign(den, den + rows * cols);
+    t->basis0.assign(basis ? basis : num, basis ? basis + (rows - 1) : num);
+    // the start the fraction-free state assumes: every basis column is an exact unit column, the
+    // objective row zero on it
+    const int64_t m = rows - 1;
+    bool ok = true;
+    for (int64_t i = 0; i < m && ok; ++i) {
+        const int64_t b = t->basis0[i];
+        if (b < 0 || b >= cols - 1) { ok = false; break; }
+        for (int64_t r = 0; r <= m && ok; ++r) ok = t->num[r * cols + b] == (r == i ? t->den[r * cols + b] : 0);
+    }
+    t->start_ok = ok;
+    auto undo = [&](int code) { mi355x_xtab_destroy(t); return code; };
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess)
+        return undo(fail(MI_HIP_ERROR, "stream creation failed"));
+    if (hipMalloc(&t->v.ctl, sizeof(XCtl)) != hipSuccess ||
+        (m > 0 && hipMalloc(&t->v.basis, m * sizeof(int64_t)) != hipSuccess) ||
+        hipMalloc(&t->v.trace_ec, kXTraceCap * sizeof(int64_t)) != hipSuccess ||
+        hipMalloc(&t->v.trace_cr, kXTraceCap * sizeof(int64_t)) != hipSuccess)
+        return undo(fail(MI_NO_MEMORY, "device allocation failed"));
+    t->v.rows = rows;
+    t->v.cols = cols;
+    t->v.trace_cap = kXTraceCap;
+    rc = min_bits == 128 ? kXOverflow : x_reset(t, 64);
+    if (rc == kXOverflow) rc = x_reset(t, 128);
+    if (rc == kXOverflow) return undo(fail(MI_EXACT_OVERFLOW, "the start state needs more than 128 bits"));
+    if (rc != MI_OK) return undo(rc);
+    *out = t;
+    return MI_OK;
+}
+
+int mi355x_xtab_solve(mi355x_xtab *t, int is_max, int64_t max_pivots, int64_t *n_pivots)
+{
+    if (!t) return fail(MI_BAD_ARG, "handle is NULL");
+    if (max_pivots < 0) return fail(MI_BAD_ARG, "max_pivots < 0");
+    if (n_pivots) *n_pivots = 0;
+    if (t->dead) return fail(MI_EXACT_OVERFLOW, "the tableau overflowed 128 bits");
+    if (t->derived || t->tp_main) return fail(MI_BAD_ARG, "a tableau of a two-phase job: use mi355x_xtab_solve_two_phase");
+    if (!t->start_ok) return fail(MI_UNSUPPORTED, "the basis columns are not exact unit columns with a zero objective entry");
+    int rc = use_device_id(t->device);
+    if (rc != MI_OK) return rc;
+    const int64_t k0 = t->h.n_pivots, cap = max_pivots > 0 ? k0 + max_pivots : 0;
+    int st;
+    for (;;) {
+        st = x_run(t, is_max, cap, nullptr);
+        if (st == kXOverflow && t->bits == 64) {
+            // the whole solve again from the start at 128 bits: the same pivots, up to the same count
+            rc = x_reset(t, 128);
+            if (rc == kXOverflow) { st = rc; break; }
+            if (rc != MI_OK) return rc;
+            continue;
+        }
+        break;
+    }
+    if (n_pivots) *n_pivots = std::max<int64_t>(0, t->h.n_pivots - k0);
+    return x_status(t, st);
+}
+
+int mi355x_xtab_solve_two_phase(mi355x_xtab *art, mi355x_xtab *mt, int main_is_max, int64_t max_pivots,
+                                int64_t *n_pivots)
+{
+    if (!art || !mt || art == mt) return fail(MI_BAD_ARG, "two distinct handles are needed");
+    if (max_pivots < 0) return fail(MI_BAD_ARG, "max_pivots < 0");
+    if (n_pivots) n_pivots[0] = n_pivots[1] = 0;
+    if (art->rows != mt->rows || mt->cols > art->cols || art->device != mt->device)
+        return fail(MI_BAD_ARG, "the tableaux do not belong to one problem");
+    if (art->derived || mt->tp_main) return fail(MI_BAD_ARG, "handles used in another role");
+    if (art->tp_main && art->tp_main != mt) return fail(MI_BAD_ARG, "the artificial tableau belongs to another job");
+    if (art->dead || mt->dead) return fail(MI_EXACT_OVERFLOW, "the tableaux overflowed 128 bits");
+    if (!art->start_ok) return fail(MI_UNSUPPORTED, "the basis columns are not exact unit columns with a zero objective entry");
+    int rc = use_device_id(art->device);
+    if (rc != MI_OK) return rc;
+    if (!art->tp_main) {
+        art->tp_main = mt;
+        mt->derived = true;
+        if (art->bits != mt->bits) {                 // one width for the job (both still at their start)
+            rc = x_reset(art->bits < mt->bits ? art : mt, 128);
+            if (rc == kXOverflow) { art->dead = mt->dead = true; return x_status(art, rc); }
+            if (rc != MI_OK) return rc;
+        }
+    }
+    const int64_t n1 = art->h.n_pivots + art->tp_driveouts, n2 = art->tp_phase == 1 ? mt->h.n_pivots : 0;
+    const int64_t target = max_pivots > 0 ? n1 + n2 + max_pivots : 0;
+    int st;
+    for (;;) {
+        st = x_two_phase(art, mt, main_is_max, target);
+        if (st == kXOverflow && art->bits == 64) {
+            // both phases again from the start at 128 bits, up to the same pivot count
+            rc = x_reset(art, 128);
+            if (rc == MI_OK) rc = x_reset(mt, 128);
+            if (rc == kXOverflow) { st = rc; break; }
+            if (rc != MI_OK) return rc;
+            art->tp_phase = 0;
+            art->tp_driveouts = 0;
+            continue;
+        }
+        if (st < 0 && st != kXOverflow && st != kXInexact) return st;
+        break;
+    }
+    if (st == kXOverflow) mt->dead = true;
+    if (n_pivots) {
+        n_pivots[0] = std::max<int64_t>(0, art->h.n_pivots + art->tp_driveouts - n1);
+        n_pivots[1] = art->tp_phase == 1 ? std::max<int64_t>(0, mt->h.n_pivots - n2) : 0;
+    }
+    return x_status(art, st);
+}
+
+int mi355x_xtab_download(mi355x_xtab *t, int64_t *num_lo_hi, int64_t *den_lo_hi, int64_t *basis)
+{
+    if (!t) return fail(MI_BAD_ARG, "handle is NULL");
+    if (t->dead) return fail(MI_EXACT_OVERFLOW, "the tableau overflowed 128 bits");
+    int rc = use_device_id(t->device);
+    if (rc != MI_OK) return rc;
+    if (num_lo_hi) {
+        std::vector<i128_t> vals;
+        rc = x_download_values(t, 0, t->rows * t->cols, vals);
+        if (rc != MI_OK) return rc;
+        for (size_t k = 0; k < vals.size(); ++k) {
+            num_lo_hi[2 * k] = (int64_t)(uint64_t)(u128_t)vals[k];
+            num_lo_hi[2 * k + 1] = (int64_t)(vals[k] >> 64);
+        }
+    }
+    if (den_lo_hi) {
+        den_lo_hi[0] = (int64_t)(uint64_t)(u128_t)t->h.D;
+        den_lo_hi[1] = (int64_t)(t->h.D >> 64);
+    }
+    if (basis && t->rows > 1)
+        HIP_TRY(hipMemcpy(basis, t->v.basis, (t->rows - 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return MI_OK;
+}
+
+int mi355x_xtab_trace(mi355x_xtab *t, int64_t *ecs, int64_t *crs, int64_t cap, int64_t *n)
+{
+    if (!t) return fail(MI_BAD_ARG, "handle is NULL");
+    int rc = use_device_id(t->device);
+    if (rc != MI_OK) return rc;
+    const int64_t total = t->h.trace_n;
+    if (n) *n = total;
+    const int64_t k = std::min<int64_t>(std::min<int64_t>(total, cap), kXTraceCap);
+    if (k > 0 && ecs) HIP_TRY(hipMemcpyAsync(ecs, t->v.trace_ec, k * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
+    if (k > 0 && crs) HIP_TRY(hipMemcpyAsync(crs, t->v.trace_cr, k * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    return MI_OK;
+}
+
+int mi355x_xtab_bits(const mi355x_xtab *t, int *bits)
+{
+    if (!t || !bits) return fail(MI_BAD_ARG, "NULL argument");
+    *bits = t->bits;
+    return MI_OK;
+}
+
+int mi355x_xtab_cancel(mi355x_xtab *t)
+{
+    if (!t) return fail(MI_BAD_ARG, "handle is NULL");
+    t->cancel.store(1, std::memory_order_release);
+    return MI_OK;
+}
+
+void mi355x_xtab_destroy(mi355x_xtab *t)
+{
+    if (!t) return;
+    (void)hipSetDevice(t->device);
+    if (t->stream) (void)hipStreamSynchronize(t->stream);
+    x_free_width(t);
+    (void)hipFree(t->v.ctl);
+    (void)hipFree(t->v.basis);
+    (void)hipFree(t->v.trace_ec);
+    (void)hipFree(t->v.trace_cr);
+    if (t->stream) (void)hipStreamDestroy(t->stream);
+    delete t;
+}

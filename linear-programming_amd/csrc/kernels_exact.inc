@@ -1,0 +1,370 @@
+// kernels_exact.inc -- exact rational solves on fraction-free (Bareiss) integer tableaux.
+// Part of simplex_kernels.hip (ONE translation unit: included there, in this order, inside namespace mi355x).
+//
+// The reference's `rational` dispatch of fp=, fp<, fp> is plain =, <, > (src/utils.lisp:84-124), and
+// its tableau then holds ratios.  Here the tableau is one integer matrix T and one integer D > 0 with
+// t_ij = T_ij / D for every row (simplex_kernels.h, XCtl / XView):
+//   pricing     compares T directly (D > 0): lowest-index strict arg-min (max) / arg-max (min) of the
+//               objective row over [0, var_count); the column enters iff its value is < 0 (> 0)
+//   ratio test  rows with T_ie > 0; rhs_a / a_a < rhs_b / a_b as rhs_a * a_b < rhs_b * a_a at double
+//               width; strict, the lowest row wins a tie
+//   pivot       (r, e), p = T_re:  T'_rj = sgn(p) T_rj,
+//                                   T'_ij = (T_ij |p| - sgn(p) T_ie T_rj) / D   (i != r),   D' = |p|
+// Every division is exact (Sylvester's identity).  It is done as: shift out the 2^k factor of D,
+// multiply by the inverse of its odd part modulo 2^W, and verify q * D == N at double width.  A
+// failed check tells overflow (the quotient does not fit the width) from a remainder (a bug) by a
+// slow bitwise remainder, which only ever runs on that path.
+//
+// W = 64: int64_t storage, __int128 products.  W = 128: __int128 storage, 256-bit products as two
+// 128-bit limbs (S256 below).  Plain C++ throughout.
+//
+//   k_x_select<T>    one workgroup: pricing, ratio test, pivot record, snapshots col / prow
+//   k_x_force<T>     one workgroup: the same record and snapshots for a given pivot (drive-out)
+//   k_x_update<T>    the rank-1 update with the exact division (every element once)
+//   k_x_handover<T>  main tableau of the two-phase hand-over: constraint rows scaled by L_c and the
+//                    objective row re-eliminated, D_main = L_c * D_art
+
+typedef unsigned __int128 xu128;
+
+// ---- 256-bit two's complement: value = hi * 2^128 + lo -------------------------------------
+struct S256 { xu128 lo; __int128 hi; };
+
+__device__ inline S256 s256_of(__int128 x) { S256 r; r.lo = (xu128)x; r.hi = x < 0 ? -1 : 0; return r; }
+__device__ inline S256 s256_neg(S256 x)
+{
+    S256 r;
+    r.lo = ~x.lo + 1;
+    r.hi = (__int128)(~(xu128)x.hi + (r.lo == 0 ? 1 : 0));
+    return r;
+}
+__device__ inline S256 s256_add(S256 a, S256 b)
+{
+    S256 r;
+    r.lo = a.lo + b.lo;
+    r.hi = (__int128)((xu128)a.hi + (xu128)b.hi + (r.lo < a.lo ? 1 : 0));
+    return r;
+}
+__device__ inline S256 s256_sub(S256 a, S256 b)
+{
+    S256 r;
+    r.lo = a.lo - b.lo;
+    r.hi = (__int128)((xu128)a.hi - (xu128)b.hi - (a.lo < b.lo ? 1 : 0));
+    return r;
+}
+__device__ inline bool s256_lt(S256 a, S256 b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
+__device__ inline bool s256_eq(S256 a, S256 b) { return a.hi == b.hi && a.lo == b.lo; }
+// |a| * |b| for magnitudes below 2^127
+__device__ inline S256 u128_mul(xu128 a, xu128 b)
+{
+    const uint64_t a0 = (uint64_t)a, a1 = (uint64_t)(a >> 64), b0 = (uint64_t)b, b1 = (uint64_t)(b >> 64);
+    const xu128 p00 = (xu128)a0 * b0, p01 = (xu128)a0 * b1, p10 = (xu128)a1 * b0, p11 = (xu128)a1 * b1;
+    const xu128 mid = (p00 >> 64) + (uint64_t)p01 + (uint64_t)p10;
+    S256 r;
+    r.lo = (mid << 64) | (uint64_t)p00;
+    r.hi = (__int128)(p11 + (p01 >> 64) + (p10 >> 64) + (mid >> 64));
+    return r;
+}
+
+// ---- width-generic operations: int64_t -> __int128 products, __int128 -> S256 products ----------
+__device__ inline __int128 xmul(int64_t a, int64_t b) { return (__int128)a * b; }
+__device__ inline S256 xmul(__int128 a, __int128 b)
+{
+    const bool neg = (a < 0) != (b < 0);
+    const S256 p = u128_mul(a < 0 ? -(xu128)a : (xu128)a, b < 0 ? -(xu128)b : (xu128)b);
+    return neg ? s256_neg(p) : p;
+}
+__device__ inline __int128 xsub(__int128 a, __int128 b) { return a - b; }   // operands below 2^126 in magnitude
+__device__ inline S256 xsub(S256 a, S256 b) { return s256_sub(a, b); }       // operands below 2^254 in magnitude
+__device__ inline bool xlt(__int128 a, __int128 b) { return a < b; }
+__device__ inline bool xlt(S256 a, S256 b) { return s256_lt(a, b); }
+__device__ inline bool xeq(__int128 a, __int128 b) { return a == b; }
+__device__ inline bool xeq(S256 a, S256 b) { return s256_eq(a, b); }
+// accumulation that may overflow the double width (the hand-over's sums): false on overflow
+__device__ inline bool xsub_ovf(__int128 &acc, __int128 b) { return !__builtin_sub_overflow(acc, b, &acc); }
+__device__ inline bool xsub_ovf(S256 &acc, S256 b)
+{
+    const S256 r = s256_sub(acc, b);
+    const bool ovf = ((acc.hi < 0) != (b.hi < 0)) && ((r.hi < 0) != (acc.hi < 0));
+    acc = r;
+    return !ovf;
+}
+// a double-width value -> the storage width, inside the symmetric range
+__device__ inline bool xfit(__int128 x, int64_t *out)
+{
+    if (x <= -(__int128)INT64_MAX - 1 || x > (__int128)INT64_MAX) return false;
+    *out = (int64_t)x;
+    return true;
+}
+__device__ inline bool xfit(S256 x, __int128 *out)
+{
+    const __int128 lo = (__int128)x.lo;
+    if (x.hi != (lo < 0 ? -1 : 0)) return false;
+    if (x.lo == ((xu128)1 << 127)) return false;                 // -2^127: outside the symmetric range
+    *out = lo;
+    return true;
+}
+__device__ inline bool xsym(int64_t x) { return x != INT64_MIN; }
+__device__ inline bool xsym(__int128 x) { return (xu128)x != ((xu128)1 << 127); }
+
+// |N| mod d by shift and subtract (the failure path only): N below 2^255 in magnitude, 0 < d < 2^127
+__device__ inline xu128 xrem(S256 N, xu128 d)
+{
+    if (N.hi < 0) N = s256_neg(N);
+    xu128 r = 0;
+    for (int b = 255; b >= 0; --b) {
+        const xu128 bit = b >= 128 ? (((xu128)N.hi >> (b - 128)) & 1) : ((N.lo >> b) & 1);
+        r = (r << 1) | bit;
+        if (r >= d) r -= d;
+    }
+    return r;
+}
+
+// q = N / D exactly, D = 2^shift * odd, inv = odd^-1 mod 2^W.  0, kXOverflow or kXInexact.
+__device__ inline int xdiv(__int128 N, int64_t D, int shift, uint64_t inv, int64_t *q)
+{
+    if (shift && ((uint64_t)N & ((1ull << shift) - 1))) return kXInexact;
+    const int64_t qs = (int64_t)((uint64_t)(N >> shift) * inv);
+    if (xsym(qs) && (__int128)qs * D == N) { *q = qs; return 0; }
+    return xrem(s256_of(N), (xu128)D) == 0 ? kXOverflow : kXInexact;
+}
+__device__ inline int xdiv(S256 N, __int128 D, int shift, xu128 inv, __int128 *q)
+{
+    if (shift && (N.lo & ((((xu128)1) << shift) - 1))) return kXInexact;
+    xu128 lo = N.lo;
+    if (shift) lo = (N.lo >> shift) | ((xu128)N.hi << (128 - shift));
+    const __int128 qs = (__int128)(lo * inv);
+    if (xsym(qs) && s256_eq(xmul(qs, D), N)) { *q = qs; return 0; }
+    return xrem(N, (xu128)D) == 0 ? kXOverflow : kXInexact;
+}
+
+template <class U> __device__ inline U xinv_odd(U d)
+{
+    U x = d;                                  // correct to 3 bits; each Newton step doubles them
+    for (int i = 0; i < 7; ++i) x *= (U)2 - d * x;
+    return x;
+}
+__device__ inline int xctz(xu128 d)
+{
+    const uint64_t lo = (uint64_t)d;
+    return lo ? __builtin_ctzll(lo) : 64 + __builtin_ctzll((uint64_t)(d >> 64));
+}
+
+template <class T> struct XUnsigned;
+template <> struct XUnsigned<int64_t>  { typedef uint64_t type; };
+template <> struct XUnsigned<__int128> { typedef xu128 type; };
+
+// the pivot record of (ec, cr) -- thread 0 only; the snapshots follow in x_snapshot
+template <class T> __device__ inline void x_record(XCtl *c, const T *M, int64_t cols, int64_t ec, int64_t cr)
+{
+    typedef typename XUnsigned<T>::type U;
+    const T p = M[cr * cols + ec];
+    c->ec = ec;
+    c->cr = cr;
+    c->sgn = p < 0 ? -1 : 1;
+    c->pa = (__int128)(p < 0 ? -p : p);
+    c->dold = c->D;
+    const int sh = xctz((xu128)c->dold);
+    c->shift = sh;
+    c->inv = (__int128)xinv_odd<U>((U)(c->dold >> sh));
+    c->D = c->pa;
+    c->apply = 1;
+}
+template <class T> __device__ inline void x_snapshot(const XView &v, const XCtl *c)
+{
+    const T *M = (const T *)v.T;
+    T *col = (T *)v.col, *prow = (T *)v.prow;
+    const int64_t ec = c->ec, cr = c->cr;
+    const int sgn = c->sgn;
+    for (int64_t i = threadIdx.x; i < v.rows; i += blockDim.x) {
+        const T a = M[i * v.cols + ec];
+        col[i] = sgn < 0 ? -a : a;
+    }
+    for (int64_t j = threadIdx.x; j < v.cols; j += blockDim.x) prow[j] = M[cr * v.cols + j];
+}
+
+constexpr int kXSelectThreads = 256;
+
+template <class T> __global__ __launch_bounds__(kXSelectThreads) void k_x_select(XView v, int is_max)
+{
+    XCtl *c = v.ctl;
+    const T *M = (const T *)v.T;
+    const int tid = threadIdx.x;
+    const int64_t m = v.rows - 1, nv = v.cols - 1, C = v.cols;
+    __shared__ int go;
+    __shared__ T sv[kXSelectThreads], sa[kXSelectThreads];
+    __shared__ int64_t si[kXSelectThreads];
+    if (tid == 0) {
+        int g = 0;
+        c->apply = 0;
+        if (c->status == kRunning) {
+            if (c->err) c->status = c->err;
+            else if (c->cap_at > 0 && c->n_pivots >= c->cap_at) c->status = 3;           // MI_MAX_PIVOTS
+            else g = 1;
+        }
+        go = g;
+    }
+    __syncthreads();
+    if (!go) return;
+    // find-entering-column (src/simplex.lisp:362-379), rational dispatch
+    const T *obj = M + m * C;
+    int64_t bi = -1;
+    T bv = 0;
+    for (int64_t j = tid; j < nv; j += kXSelectThreads) {
+        const T x = obj[j];
+        if (bi < 0 || (is_max ? x < bv : x > bv)) { bv = x; bi = j; }
+    }
+    sv[tid] = bv; si[tid] = bi;
+    __syncthreads();
+    for (int s = kXSelectThreads / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            const int o = tid + s;
+            if (si[o] >= 0 && (si[tid] < 0 || (is_max ? sv[o] < sv[tid] : sv[o] > sv[tid]) ||
+                               (sv[o] == sv[tid] && si[o] < si[tid]))) { sv[tid] = sv[o]; si[tid] = si[o]; }
+        }
+        __syncthreads();
+    }
+    const int64_t ec = si[0];
+    if (ec < 0 || !(is_max ? sv[0] < 0 : sv[0] > 0)) {
+        if (tid == 0) c->status = 0;                                                        // MI_OPTIMAL
+        return;
+    }
+    __syncthreads();
+    // find-pivoting-row (src/simplex.lisp:382-389), cross-multiplied
+    bi = -1;
+    T br = 0, ba = 0;
+    for (int64_t i = tid; i < m; i += kXSelectThreads) {
+        const T a = M[i * C + ec];
+        if (a > 0) {
+            const T r = M[i * C + nv];
+            if (bi < 0 || xlt(xmul(r, ba), xmul(br, a))) { br = r; ba = a; bi = i; }
+        }
+    }
+    sv[tid] = br; sa[tid] = ba; si[tid] = bi;
+    __syncthreads();
+    for (int s = kXSelectThreads / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            const int o = tid + s;
+            if (si[o] >= 0) {
+                bool better = si[tid] < 0;
+                if (!better) {
+                    const auto lhs = xmul(sv[o], sa[tid]), rhs = xmul(sv[tid], sa[o]);
+                    better = xlt(lhs, rhs) || (xeq(lhs, rhs) && si[o] < si[tid]);
+                }
+                if (better) { sv[tid] = sv[o]; sa[tid] = sa[o]; si[tid] = si[o]; }
+            }
+        }
+        __syncthreads();
+    }
+    const int64_t cr = si[0];
+    if (cr < 0) {
+        if (tid == 0) c->status = 1;                                                        // MI_UNBOUNDED
+        return;
+    }
+    if (tid == 0) {
+        x_record<T>(c, M, C, ec, cr);
+        v.basis[cr] = ec;
+        if (c->trace_n < v.trace_cap) { v.trace_ec[c->trace_n] = ec; v.trace_cr[c->trace_n] = cr; }
+        c->trace_n += 1;
+        c->n_pivots += 1;
+    }
+    __syncthreads();
+    x_snapshot<T>(v, c);
+}
+
+// a pivot given by the host (the drive-out of src/simplex.lisp:418-436): not counted, not traced
+template <class T> __global__ __launch_bounds__(kXSelectThreads) void k_x_force(XView v, int64_t ec, int64_t cr)
+{
+    XCtl *c = v.ctl;
+    if (threadIdx.x == 0) {
+        x_record<T>(c, (const T *)v.T, v.cols, ec, cr);
+        v.basis[cr] = ec;
+    }
+    __syncthreads();
+    x_snapshot<T>(v, c);
+}
+
+template <class T> __global__ __launch_bounds__(256) void k_x_update(XView v)
+{
+    typedef typename XUnsigned<T>::type U;
+    XCtl *c = v.ctl;
+    if (!c->apply) return;
+    T *M = (T *)v.T;
+    const T *col = (const T *)v.col, *prow = (const T *)v.prow;
+    const int64_t cr = c->cr, C = v.cols;
+    const int sgn = c->sgn, sh = c->shift;
+    const T pa = (T)c->pa, dold = (T)c->dold;
+    const U inv = (U)c->inv;
+    int err = 0;
+    for (int64_t r = blockIdx.y; r < v.rows; r += gridDim.y) {
+        const T cv = col[r];
+        for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < C; j += (int64_t)gridDim.x * blockDim.x) {
+            if (r == cr) { M[r * C + j] = sgn < 0 ? -prow[j] : prow[j]; continue; }
+            T q;
+            const int e = xdiv(xsub(xmul(M[r * C + j], pa), xmul(cv, prow[j])), dold, sh, inv, &q);
+            if (e) err = e > err ? e : err;
+            else M[r * C + j] = q;
+        }
+    }
+    if (err) atomicMax(&c->err, err);
+}
+
+template <class T> __global__ __launch_bounds__(256) void k_x_handover(XView a, XView mt, const T *w, const T *cl, T lc)
+{
+    const int64_t m = a.rows - 1, nv = mt.cols - 1, nav = a.cols - 1;
+    const T *A = (const T *)a.T;
+    T *M = (T *)mt.T;
+    const T D = (T)a.ctl->D;
+    int err = 0;
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < mt.cols; j += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t src = j < nv ? j : nav;
+        auto acc = xmul(D, cl[j]);
+        bool ok = true;
+        for (int64_t r = 0; r < m; ++r) {
+            const T x = A[r * a.cols + src];
+            T y = 0;
+            if (!xfit(xmul(lc, x), &y)) ok = false;
+            M[r * mt.cols + j] = y;
+            if (!xsub_ovf(acc, xmul(w[r], x))) ok = false;
+        }
+        T o = 0;
+        if (!xfit(acc, &o)) ok = false;
+        M[m * mt.cols + j] = o;
+        if (!ok) err = kXOverflow;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        T d = 0;
+        if (!xfit(xmul(lc, D), &d)) err = kXOverflow;
+        mt.ctl->D = (__int128)d;
+    }
+    if (err) atomicMax(&mt.ctl->err, err);
+}
+
+static unsigned x_grid_x(int64_t cols) { const int64_t g = (cols + 255) / 256; return (unsigned)(g < 64 ? g : 64); }
+static unsigned x_grid_y(int64_t rows) { return (unsigned)(rows < 4096 ? rows : 4096); }
+
+void launch_x_select(const XView &v, int is_max, hipStream_t s)
+{
+    if (v.bits == 64) hipLaunchKernelGGL(k_x_select<int64_t>, dim3(1), dim3(kXSelectThreads), 0, s, v, is_max);
+    else              hipLaunchKernelGGL(k_x_select<__int128>, dim3(1), dim3(kXSelectThreads), 0, s, v, is_max);
+}
+void launch_x_force(const XView &v, int64_t ec, int64_t cr, hipStream_t s)
+{
+    if (v.bits == 64) hipLaunchKernelGGL(k_x_force<int64_t>, dim3(1), dim3(kXSelectThreads), 0, s, v, ec, cr);
+    else              hipLaunchKernelGGL(k_x_force<__int128>, dim3(1), dim3(kXSelectThreads), 0, s, v, ec, cr);
+}
+void launch_x_update(const XView &v, hipStream_t s)
+{
+    const dim3 grid(x_grid_x(v.cols), x_grid_y(v.rows));
+    if (v.bits == 64) hipLaunchKernelGGL(k_x_update<int64_t>, grid, dim3(256), 0, s, v);
+    else              hipLaunchKernelGGL(k_x_update<__int128>, grid, dim3(256), 0, s, v);
+}
+void launch_x_handover(const XView &art, const XView &mt, const void *w, const void *cl, __int128 lc, hipStream_t s)
+{
+    const dim3 grid((unsigned)((mt.cols + 255) / 256));
+    if (mt.bits == 64)
+        hipLaunchKernelGGL(k_x_handover<int64_t>, grid, dim3(256), 0, s, art, mt, (const int64_t *)w,
+                           (const int64_t *)cl, (int64_t)lc);
+    else
+        hipLaunchKernelGGL(k_x_handover<__int128>, grid, dim3(256), 0, s, art, mt, (const __int128 *)w,
+                           (const __int128 *)cl, lc);
+}

@@ -328,6 +328,46 @@ void   set_resident_fault(int on);      // test hook: the last workgroup of ever
 void   set_resident_lds(int mode);      // tuning hook: 1 = part of the strip in LDS (three workgroups per CU), 0 = never
 void   set_resident_poll(int mode);     // tuning hook: who polls the exchange records (0 by size, 1 wave 0, 2 every wave)
 
+// Exact (fraction-free, Bareiss) tableaux: kernels_exact.inc, capi_exact.inc.  The tableau is an
+// integer matrix T and one positive integer D with t_ij = T_ij / D (objective row included),
+// stored as int64_t (bits 64) or __int128 (bits 128).  Every stored value stays inside the
+// symmetric range (-2^(W-1), 2^(W-1)), so products and their differences never overflow the
+// double-width intermediates.
+constexpr int32_t kXOverflow = 110;    // a value left the width in use: restart wider or MI_EXACT_OVERFLOW
+constexpr int32_t kXInexact  = 111;    // a Bareiss division left a remainder: a bug (MI_EXACT_INEXACT)
+struct XCtl {
+    int32_t  status;      // kRunning, or MI_OPTIMAL / MI_UNBOUNDED / MI_MAX_PIVOTS / kXOverflow / kXInexact
+    int32_t  err;         // 0, or kXOverflow / kXInexact raised by an update (the larger one wins)
+    int32_t  apply;       // the last select / force chose a pivot for the update that follows it
+    int32_t  sgn;         // sign of that pivot
+    int32_t  shift;       // trailing zero bits of dold
+    int32_t  pad_;
+    int64_t  ec, cr;      // the pivot
+    int64_t  n_pivots;    // pivots chosen by k_x_select since the tableau's start (cumulative)
+    int64_t  cap_at;      // k_x_select stops with MI_MAX_PIVOTS once n_pivots reaches it (0: no cap)
+    int64_t  trace_n;     // pivots recorded (trace buffers hold the first trace_cap)
+    __int128 D;           // the common denominator, > 0
+    __int128 dold;        // D before the pivot being applied
+    __int128 pa;          // |pivot|
+    __int128 inv;         // inverse of the odd part of dold modulo 2^W
+};
+struct XView {
+    void    *T;           // rows x cols, row-major, no padding
+    void    *col;         // rows: sgn * T[i][ec] before the pivot
+    void    *prow;        // cols: T[cr][j] before the pivot
+    int64_t *basis;       // rows - 1
+    XCtl    *ctl;
+    int64_t *trace_ec, *trace_cr;
+    int64_t  rows, cols, trace_cap;
+    int      bits;        // 64 or 128
+};
+void launch_x_select(const XView &v, int is_max, hipStream_t s);
+void launch_x_force(const XView &v, int64_t ec, int64_t cr, hipStream_t s);
+void launch_x_update(const XView &v, hipStream_t s);
+// main[r][j] = lc * art[r][src(j)] (r < m); main[m][j] = D_art * cl[j] - sum_r w[r] * art[r][src(j)];
+// main D = lc * D_art.  w (m) and cl (main cols) hold values of the handles' width.
+void launch_x_handover(const XView &art, const XView &mt, const void *w, const void *cl, __int128 lc, hipStream_t s);
+
 int         update_variant_count();
 const char *update_variant_name(int v);
 void        set_update_variant(int v);      // tuning hook (bench / microbench only)

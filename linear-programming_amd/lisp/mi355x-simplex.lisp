@@ -29,7 +29,11 @@
 ;;;; Scope: LP, double-float.  Problems with integer / binary variables are declined with
 ;;;; unsupported-constraint-error (src/conditions.lisp:69-77) as the hook's contract expects of
 ;;;; a backend (src/solver.lisp:40-45); rational problems are solved in double-float (every
-;;;; entry is coerced), which is the documented behaviour of this backend.
+;;;; entry is coerced), which is the documented behaviour of this backend -- unless :exact t asks
+;;;; for the reference's rational semantics: a problem whose numbers are all rational is then
+;;;; solved on exact fraction-free integer tableaux (mi355x_xtab_*) and the tableau's matrix holds
+;;;; the exact ratios afterwards.  Entries beyond (signed-byte 64), or values that outgrow 128 bits
+;;;; during the solve, are declined with unsupported-constraint-error.
 ;;;;
 ;;;; NOTE: could not be executed in the build image (no Lisp there); reviewed against
 ;;;; include/mi355x_simplex.h and the reference sources cited inline.
@@ -75,7 +79,8 @@
 (defconstant +mi-art-stuck+ 5)
 (defconstant +mi-nonfinite+ 6)   ; column shards only: the tableau overflowed (see solve-column-partitioned)
 (defconstant +mi-cancelled+ 7)   ; mi355x_*_cancel from another thread (never from this single-threaded glue)
-(defconstant +mi-running+ 100)   ; per-LP status of a batch member a capped / cancelled solve left unfinished
+(defconstant +mi-running+ 100)
+(defconstant +mi-exact-overflow+ -7)   ; an exact tableau outgrew 128 bits   ; per-LP status of a batch member a capped / cancelled solve left unfinished
 
 (cffi:defcfun ("mi355x_device_count" device-count) :int)
 (cffi:defcfun ("mi355x_last_error" %last-error) :string)
@@ -175,6 +180,16 @@
 (cffi:defcfun ("mi355x_solution_pivots" %solution-pivots) :int
   (solution :pointer) (phase1 :pointer) (phase2 :pointer))
 (cffi:defcfun ("mi355x_solution_destroy" %solution-destroy) :void (solution :pointer))
+(cffi:defcfun ("mi355x_xtab_create" %xtab-create) :int
+  (out :pointer) (rows :int64) (cols :int64) (num :pointer) (den :pointer) (basis :pointer)
+  (device :int) (min-bits :int))
+(cffi:defcfun ("mi355x_xtab_solve" %xtab-solve) :int
+  (tab :pointer) (is-max :int) (max-pivots :int64) (n-pivots :pointer))
+(cffi:defcfun ("mi355x_xtab_solve_two_phase" %xtab-solve-two-phase) :int
+  (art :pointer) (main :pointer) (main-is-max :int) (max-pivots :int64) (n-pivots :pointer))
+(cffi:defcfun ("mi355x_xtab_download" %xtab-download) :int
+  (tab :pointer) (num-lo-hi :pointer) (den-lo-hi :pointer) (basis :pointer))
+(cffi:defcfun ("mi355x_xtab_destroy" %xtab-destroy) :void (tab :pointer))
 
 (define-condition mi355x-error (solver-error)
   ((code :initarg :code :reader mi355x-error-code)
@@ -479,6 +494,100 @@ Leaves the total in N-PIVOTS[0] and returns the last status."
                   (and (plusp max-pivots) (>= total max-pivots)))
           (setf (cffi:mem-aref n-pivots :int64 0) total)
           (return status))))))
+
+;;; ------------------------------------------------------------------ exact rational solves
+;;; :exact t.  The reference's build-tableau already yields the rational matrix; its numerators and
+;;; denominators cross the boundary, the library solves on a fraction-free integer tableau T with one
+;;; denominator D (include/mi355x_simplex.h, mi355x_xtab_*), and (/ T D) is written back into the
+;;; same `tableau`, which the reference's own methods then serve (src/solver.lisp:61-80).
+(defun rational-numbers-p (problem)
+  (flet ((expression-ok (alist) (every (lambda (term) (rationalp (cdr term))) alist)))
+    (and (expression-ok (problem-objective-func problem))
+         (every (lambda (entry)
+                  (destructuring-bind (lb . ub) (cdr entry)
+                    (and (or (null lb) (rationalp lb)) (or (null ub) (rationalp ub)))))
+                (problem-var-bounds problem))
+         (every (lambda (constraint)
+                  (and (expression-ok (second constraint)) (rationalp (third constraint))))
+                (problem-constraints problem)))))
+
+(defun exact-declined (what)
+  (error 'unsupported-constraint-error :constraint (cons 'exact what) :solver-name "mi355x-simplex"))
+
+(defun upload-exact-tableau (tableau device)
+  "mi355x_xtab_create from the tableau's rational matrix; declines entries beyond (signed-byte 64)."
+  (let* ((matrix (tableau-matrix tableau))
+         (rows (array-dimension matrix 0))
+         (cols (array-dimension matrix 1)))
+    (cffi:with-foreign-objects ((num :int64 (* rows cols)) (den :int64 (* rows cols))
+                                (basis :int64 (max 1 (1- rows))) (out :pointer))
+      (dotimes (r rows)
+        (dotimes (c cols)
+          (let ((x (aref matrix r c)))
+            (unless (and (typep (numerator x) '(signed-byte 64)) (typep (denominator x) '(signed-byte 64)))
+              (exact-declined (list 'coefficient x)))
+            (setf (cffi:mem-aref num :int64 (+ (* r cols) c)) (numerator x)
+                  (cffi:mem-aref den :int64 (+ (* r cols) c)) (denominator x)))))
+      (dotimes (r (1- rows))
+        (setf (cffi:mem-aref basis :int64 r) (aref (tableau-basis-columns tableau) r)))
+      (let ((status (%xtab-create out rows cols num den basis device 0)))
+        (when (= status +mi-exact-overflow+) (exact-declined '(overflow 128)))
+        (check status)
+        (cffi:mem-ref out :pointer)))))
+
+(defun download-exact-tableau (handle tableau)
+  "(/ T D) into the tableau's matrix, T and D rebuilt from their two 64-bit limbs; the basis."
+  (let* ((matrix (tableau-matrix tableau))
+         (rows (array-dimension matrix 0))
+         (cols (array-dimension matrix 1)))
+    (flet ((limbs (ptr k)
+             (+ (logand (cffi:mem-aref ptr :int64 (* 2 k)) (1- (ash 1 64)))
+                (ash (cffi:mem-aref ptr :int64 (1+ (* 2 k))) 64))))
+      (cffi:with-foreign-objects ((num :int64 (* 2 rows cols)) (den :int64 2) (basis :int64 (max 1 (1- rows))))
+        (check (%xtab-download handle num den basis))
+        (let ((d (limbs den 0)))
+          (dotimes (r rows)
+            (dotimes (c cols)
+              (setf (aref matrix r c) (/ (limbs num (+ (* r cols) c)) d)))))
+        (dotimes (r (1- rows))
+          (setf (aref (tableau-basis-columns tableau) r) (cffi:mem-aref basis :int64 r)))
+        tableau))))
+
+(defun exact-status (status)
+  (when (= status +mi-exact-overflow+) (exact-declined '(overflow 128)))
+  status)
+
+(defun solve-exactly (problem device max-pivots)
+  "build-tableau, then n-solve-tableau on exact tableaux in bounded calls; returns the tableau."
+  (let ((tableaus (build-tableau problem problem)))
+    (cffi:with-foreign-object (n-pivots :int64 2)
+      (if (listp tableaus)
+          (destructuring-bind (art-tab main-tab) tableaus
+            (let ((art (upload-exact-tableau art-tab device)))
+              (unwind-protect
+                   (let ((main (upload-exact-tableau main-tab device)))
+                     (unwind-protect
+                          (let* ((matrix (tableau-matrix art-tab))
+                                 (status (solve-in-chunks
+                                          (lambda (cap)
+                                            (prog1 (exact-status (%xtab-solve-two-phase art main (max-problem-p main-tab)
+                                                                                        cap n-pivots))
+                                              (incf (cffi:mem-aref n-pivots :int64 0) (cffi:mem-aref n-pivots :int64 1))))
+                                          (array-dimension matrix 0) (array-dimension matrix 1)
+                                          max-pivots n-pivots)))
+                            (signal-outcome status)
+                            (download-exact-tableau main main-tab))
+                       (%xtab-destroy main)))
+                (%xtab-destroy art))))
+          (let ((handle (upload-exact-tableau tableaus device)))
+            (unwind-protect
+                 (let ((status (solve-in-chunks
+                                (lambda (cap) (exact-status (%xtab-solve handle (max-problem-p tableaus) cap n-pivots)))
+                                (1+ (tableau-constraint-count tableaus)) (1+ (tableau-var-count tableaus))
+                                max-pivots n-pivots)))
+                   (signal-outcome status)
+                   (download-exact-tableau handle tableaus))
+              (%xtab-destroy handle)))))))
 
 ;;; ------------------------------------------------------------------ the native route
 ;;; SURVEY 8(f) rows 2-3: at 8192 x 4096 the reference's build-tableau conses a boxed 4097 x 12289
@@ -808,7 +917,7 @@ phases together.  Returns the final status."
 (defun mi355x-simplex-solver (problem &rest args
                               &key (fp-tolerance 1024) (device 0) (devices 1) (max-pivots 0)
                                 full-tableau (native :auto) branch-and-bound (bb-width 1)
-                                (int-tolerance 0) (max-nodes 0)
+                                (int-tolerance 0) (max-nodes 0) exact
                               &allow-other-keys)
   "Solver interface function for the MI355X backend (the value of
 linear-programming:*solver*, src/solver.lisp:39-49).  Takes a problem and backend keyword
@@ -829,14 +938,23 @@ keywords (src/solver.lisp:53-56):
 problem with the reference's branch-and-bound (src/simplex.lisp:462-542), node for node, in the
 library: :bb-width node LPs side by side (default 1; results do not depend on it), :int-tolerance
 (0, the default: a value is integral iff it is an integer-valued double; > 0: within that many
-double-float-epsilons of an integer), :max-nodes (0 = no cap)."
+double-float-epsilons of an integer), :max-nodes (0 = no cap).
+:exact T (opt-in) solves a problem whose numbers are all rational with the reference's rational
+semantics (src/utils.lisp:84-124) on exact integer tableaux and returns the solved `tableau`, its
+matrix holding the exact ratios; any float in the problem means the double-float routes above,
+unchanged.  Not together with :branch-and-bound (declined)."
   (declare (ignore args))
+  (when (and exact branch-and-bound)
+    (exact-declined '(branch-and-bound)))
   ;; :branch-and-bound T (opt-in): integer problems through the library's branch-and-bound job
   ;; (:bb-width node LPs side by side, :int-tolerance 0 = exact integrality, :max-nodes 0 = no cap)
   (when (and branch-and-bound (problem-integer-vars problem))
     (return-from mi355x-simplex-solver
       (solve-branch-and-bound problem (coerce fp-tolerance 'double-float) int-tolerance bb-width devices
                               max-nodes)))
+  ;; :exact T (opt-in): all-rational problems on exact tableaux (integer problems are declined below)
+  (when (and exact (null (problem-integer-vars problem)) (rational-numbers-p problem))
+    (return-from mi355x-simplex-solver (solve-exactly problem device max-pivots)))
   (when (problem-integer-vars problem)
     (error 'unsupported-constraint-error
            :constraint (cons 'integer (problem-integer-vars problem))

@@ -12,6 +12,7 @@ The tableau lives in HBM behind ``Tableau._h``; ``Tableau.matrix`` / ``basis_col
 host copies refreshed lazily after every device-side mutation.
 """
 import ctypes
+from fractions import Fraction
 
 import numpy as np
 
@@ -30,6 +31,7 @@ def _ptr(a):
 class Tableau:
     """The `tableau` struct (src/simplex.lisp:48-58): problem, instance-problem, matrix,
     basis-columns, var-count, constraint-count, var-mapping, fp-tolerance-factor."""
+    exact = False                       # (exact.ExactTableau: the same read-back in Fractions)
 
     def __init__(self, problem, instance_problem, matrix, basis_columns, var_count,
                  constraint_count, var_mapping, fp_tolerance_factor=1024, device=0, _handle=None):
@@ -144,15 +146,20 @@ def copy_tableau(tableau):
 
 
 # ------------------------------------------------------------------ read-back (host, O(n))
+def _value(tableau, x):
+    """An entry as the read-back returns it: a double, or the exact Fraction of an ExactTableau."""
+    return Fraction(x) if tableau.exact else float(x)
+
+
 def tableau_objective_value(tableau):
     """tableau-objective-value (src/simplex.lisp:74-78)."""
-    return float(tableau._readback()[0][tableau.var_count])
+    return _value(tableau, tableau._readback()[0][tableau.var_count])
 
 
 def _basic_value(tableau, col):
     _, rhs, basis = tableau._readback()
     pos = np.nonzero(basis == col)[0]                       # `position`: first match
-    return float(rhs[pos[0]]) if pos.size else 0.0
+    return _value(tableau, rhs[pos[0]] if pos.size else 0)
 
 
 def tableau_variable(tableau, var):
@@ -177,7 +184,7 @@ def tableau_reduced_cost(tableau, var):
         raise KeyError("%s is not a variable in the tableau" % (var,))
     if mapping[0] != "positive":
         raise ValueError("%s has no lower bound" % (var,))
-    return float(tableau._readback()[0][mapping[1]])
+    return _value(tableau, tableau._readback()[0][mapping[1]])
 
 
 def with_tableau_variables(var_list, tableau):
@@ -192,15 +199,25 @@ def with_tableau_variables(var_list, tableau):
 
 
 # ------------------------------------------------------------------ build-tableau (host)
-def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, device=0):
+def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, device=0, exact=False, min_bits=0):
     """build-tableau (src/simplex.lisp:142-328) in double-float: returns a Tableau, or
     [art_tableau, main_tableau] when the trivial basis is infeasible.
 
     This is the producer of what crosses the boundary; in the Lisp deployment the reference's
-    own build-tableau does this job and the glue converts the result to double-float."""
+    own build-tableau does this job and the glue converts the result to double-float.
+    exact=True: the same steps in exact rationals (Fraction object matrices, Fraction mapping
+    offsets), the reference's own build-tableau on rational input; the result is an ExactTableau
+    (exact.py, min_bits: its starting width) or a list of two."""
     if instance_problem is None:
         instance_problem = problem
-    f = float
+    if exact:
+        from fractions import Fraction
+        f, zero, one = Fraction, Fraction(0), Fraction(1)
+
+        def zeros(shape):
+            return np.full(shape, Fraction(0), dtype=object)
+    else:
+        f, zero, one, zeros = float, 0.0, 1.0, np.zeros
     constraints = [(op, list(expr), rhs) for op, expr, rhs in instance_problem.constraints]
     pvars = list(problem.vars)
     n = len(pvars)
@@ -208,19 +225,22 @@ def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, devi
     mappings = {}
 
     def mk(matrix, basis, var_count, ccount, inst):
+        if exact:
+            from .exact import ExactTableau
+            return ExactTableau(problem, inst, matrix, basis, var_count, ccount, mappings, device, min_bits)
         return Tableau(problem, inst, matrix, basis, var_count, ccount, mappings,
                        fp_tolerance_factor, device)
 
     if not constraints:                                                  # :153-186
-        M = np.zeros((n + 1, n + 1))
+        M = zeros((n + 1, n + 1))
         basis = np.arange(n, dtype=np.int64)
         objd = dict(problem.objective_func)
         is_max = problem.type == "max"
-        objective_value = 0.0
+        objective_value = zero
         for i, var in enumerate(pvars):
             coef = objd[var]
             lb, ub = bounds.get(var, (None, None))
-            M[i, i] = 1.0
+            M[i, i] = one
             if (0 <= coef) == is_max:
                 if ub is None:
                     raise UnboundedProblemError()
@@ -238,7 +258,7 @@ def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, devi
     column = 0
     for var in pvars:
         if var not in bounds:
-            mappings[var] = ("positive", column, 0.0)
+            mappings[var] = ("positive", column, zero)
         else:
             lb, ub = bounds[var]
             if lb is not None and ub is not None:
@@ -260,7 +280,7 @@ def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, devi
     m = len(constraints)                                                 # :214-221
     num_slack = sum(1 for c in constraints if c[0] != "=")
     num_cols = ncv + num_slack + 1
-    M = np.zeros((m + 1, num_cols))
+    M = zeros((m + 1, num_cols))
     basis = np.zeros(m, dtype=np.int64)
     art_rows = []
     col_offset = 0
@@ -281,12 +301,12 @@ def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, devi
             M[row, :] = -M[row, :]
             op = {"<=": ">=", ">=": "<=", "=": "="}.get(op, op)
         if op == "<=":                                                   # :254-265
-            M[row, ncv + col_offset] = 1.0
+            M[row, ncv + col_offset] = one
             basis[row] = ncv + col_offset
             col_offset += 1
         elif op == ">=":
             art_rows.insert(0, row)
-            M[row, ncv + col_offset] = -1.0
+            M[row, ncv + col_offset] = -one
             basis[row] = num_cols
             col_offset += 1
         elif op == "=":
@@ -310,15 +330,15 @@ def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, devi
         return main
     num_art = len(art_rows)                                              # :292-325
     nac = num_cols + num_art
-    A = np.zeros((m + 1, nac))
+    A = zeros((m + 1, nac))
     abasis = basis.copy()
     for i, row in enumerate(art_rows):
         abasis[row] = num_cols - 1 + i
-        A[row, num_cols - 1 + i] = 1.0
+        A[row, num_cols - 1 + i] = one
     A[:m, :num_cols - 1] = M[:m, :num_cols - 1]
     A[:m, nac - 1] = M[:m, num_cols - 1]
     for c in list(range(num_cols - 1)) + [nac - 1]:
-        s = 0.0
+        s = zero
         for r in range(m):                                               # same summation order
             if r in art_rows:
                 s = s + A[r, c]
@@ -590,7 +610,7 @@ def _native_numbers(problem):
 
 def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_pivots=0,
                           full_tableau=False, native="auto", chunk=None, branch_and_bound=False,
-                          bb_width=1, int_tolerance=0, max_nodes=0, **_ignored):
+                          bb_width=1, int_tolerance=0, max_nodes=0, exact=False, exact_bits=0, **_ignored):
     """What the Lisp glue installs as `*solver*` (src/solver.lisp:39-56): takes a problem and
     backend keyword arguments, returns a solution object answering the four solution-*
     generics -- on the NATIVE route (default whenever the problem's numbers are floats / integers
@@ -607,7 +627,14 @@ def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_p
     stepped in bounded chunks of nodes), up to bb_width node LPs side by side on `devices` GPUs
     (logical devices of one GPU when fewer are visible); int_tolerance > 0 counts values within
     int_tolerance * epsilon of an integer as integral (0: exact); max_nodes caps the nodes
-    processed (0: no cap).  Returns the incumbent's NativeSolution."""
+    processed (0: no cap).  Returns the incumbent's NativeSolution.
+    exact=True (opt-in): a problem whose numbers are all rational (int or Fraction) is solved with the
+    reference's rational semantics (src/utils.lisp:84-124) on exact integer tableaux (exact.py) and the
+    solved ExactTableau is returned, its read-back in Fractions; exact_bits 128 starts at 128 bits
+    instead of 64.  Any float in the problem means the double path, unchanged.  Not together with
+    branch_and_bound (declined)."""
+    if exact and branch_and_bound:
+        raise UnsupportedConstraintError(("exact", "branch-and-bound"), "mi355x-simplex")
     if problem.integer_vars and branch_and_bound:
         from .native import solve_branch_and_bound
         return solve_branch_and_bound(problem, fp_tolerance=fp_tolerance, int_tolerance=int_tolerance,
@@ -615,6 +642,10 @@ def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_p
     if problem.integer_vars:
         raise UnsupportedConstraintError(("integer",) + tuple(problem.integer_vars),
                                          "mi355x-simplex")
+    if exact:
+        from .exact import rational_problem, solve_exact
+        if rational_problem(problem):
+            return solve_exact(problem, device=device, max_pivots=max_pivots, min_bits=exact_bits, chunk=chunk)
     if native and not full_tableau and devices <= 1 and len(problem.vars) > 0 and \
             (native is True or _native_numbers(problem)):
         from .native import NativeProblem

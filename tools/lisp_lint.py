@@ -392,6 +392,7 @@ CL_FUNCTIONS = {
     "make-instance": _sig(1), "slot-value": _sig(2, 2), "slot-boundp": _sig(2, 2), "class-of": _sig(1, 1),
     "symbol-name": _sig(1, 1), "symbol-value": _sig(1, 1), "symbol-function": _sig(1, 1), "intern": _sig(1, 2), "find-symbol": _sig(1, 2),
     "string=": _sig(2), "string-equal": _sig(2), "string": _sig(1, 1), "string-upcase": _sig(1), "string-downcase": _sig(1),
+    "numerator": _sig(1, 1), "denominator": _sig(1, 1),
     "concatenate": _sig(1), "ash": _sig(2, 2), "logand": _sig(0), "logior": _sig(0), "logxor": _sig(0),
     "constantly": _sig(1, 1), "complement": _sig(1, 1), "get-internal-real-time": _sig(0, 0), "sleep": _sig(1, 1),
     "asdf:load-system": _sig(1),
