@@ -17,6 +17,13 @@ scaling.  `--workload colpart` instead runs ONE tableau column-partitioned over 
 the per-pivot RCCL exchange (all-gather of the local pricing winners + broadcast of the entering
 column); see linear-programming_amd/colpart.py.
 
+A plain run does what the headline needs and nothing else: it sets up, warms up, times the K steps, writes
+`--dump-outputs` if asked and prints the line.  `--full` adds everything else the benchmark measures and checks,
+outside the timed region: on one GPU the per-pivot kernel record, the CPU baseline with the in-run parity check,
+the other BASELINE configurations (`other_configs`) and, behind a short timed region, the warm full blocks the
+per-kernel roofline figures are read from; for the column-partitioned workload its one-GPU baseline (N > 1)
+and the A/B of its exchange modes.  The `--no-*` switches below leave out single parts of a `--full` run.
+
 Prints ONE JSON line on rank 0.  `--dump-outputs DIR` also writes what the timed steps computed (the pivot
 sequence, the final basis / objective row / RHS column and a fixed sample of tableau rows) as DIR/*.npy, so
 that two builds can be compared output for output: the inputs depend on the arguments only.
@@ -87,7 +94,11 @@ def parse():
                     help="N > 1, default workload: headline = ONE config-5 tableau column-partitioned over the "
                          "N GPUs with the RCCL exchanges (strong scaling; the independent-LPs figure is "
                          "attached as a secondary field), or independent config-3 LPs only (weak scaling)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="outside the timed region, also measure and check everything beyond the headline (per-pivot "
+                         "kernel, CPU baseline + in-run parity, other configurations, warm blocks for the roofline "
+                         "figures of a short run, the column partition's one-GPU baseline and exchange-mode A/B)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline and parity_in_run")
     ap.add_argument("--cpu-pivots", type=int, default=400,
                     help="cpu_baseline: pivots timed with all host threads (a quarter of it single-threaded)")
     ap.add_argument("--no-events", action="store_true",
@@ -96,20 +107,23 @@ def parse():
                     help="bracket every k-th block of the timed region with HIP event pairs (0 = every "
                          "block of a short run, ~50 samples of a long one)")
     ap.add_argument("--no-per-pivot", action="store_true",
-                    help="skip the extra per-pivot (k_update) measurement after the timed region")
+                    help="--full: skip the extra per-pivot (k_update) measurement after the timed region")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="N = 1, cfg3: skip the `other_configs` records (configs 2, 4, 5 and the config-3 "
+                    help="--full, N = 1, cfg3: skip the `other_configs` records (configs 2, 4, 5 and the config-3 "
                          "steady state measured after the timed region)")
     ap.add_argument("--no-colpart-baseline", action="store_true",
-                    help="colpart, N > 1: skip the same-workload one-GPU figure measured on rank 0 first")
+                    help="--full, colpart, N > 1: skip the same-workload one-GPU figure measured on rank 0 first")
     ap.add_argument("--no-colpart-ab", action="store_true",
-                    help="colpart over RCCL: skip the second leg with the rooted-broadcast exchange")
+                    help="--full, colpart over RCCL: skip the legs with the other exchange modes")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what they computed as DIR/<name>.npy (float64, at most "
                          "64 MB in all): rank 0, single-tableau workloads and cfg4")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:               # a plain run: the headline only (main() also skips the warm blocks of --full)
+        args.no_cpu_baseline = args.no_per_pivot = args.no_other_configs = True
+        args.no_colpart_baseline = args.no_colpart_ab = True
     if args.dump_outputs and (args.workload == "colpart" or
                               (args.gpus > 1 and args.workload == "cfg3" and args.multi_gpu == "colpart")):
         ap.error("--dump-outputs: not available for the column-partitioned workload")
@@ -763,7 +777,7 @@ def main():
             # every k-th launch of a long run (~50 event pairs per kernel class: the event records are
             # host work inside the timed region); a short run (the driver's 20 steps are one full
             # block + 4) records nothing inside the timed region -- its kernel statistics come from
-            # the full blocks run right AFTER it (below)
+            # the full blocks run right AFTER it (below, --full)
             launches = max(1, args.steps // max(L.mi355x_tab_block_size(h), 1))
             stride = args.event_stride if args.event_stride > 0 else max(1, launches // 50)
             if launches >= 8 or args.event_stride > 0:
@@ -824,7 +838,7 @@ def main():
     if not args.no_events:
         upd_n, upd_avg_ms, upd_min_ms = read_events(0)
         la_n, la_avg_ms, la_min_ms = read_events(1)
-        if upd_n < 8 and block > 1:
+        if upd_n < 8 and block > 1 and args.full:
             # a short run (the driver's 20 steps are ONE block, cut short): the kernel statistics come from
             # WARM full blocks run right AFTER the timed region on the same tableau -- not part of `value`.
             # Two untimed blocks first (the first full blocks behind a short request run a kernel form the

@@ -576,7 +576,7 @@ def test_colpart_p2p_exchange_logical_shards_bitwise(n, m, seed, n_devices, pers
 
 
 def test_bench_colpart_one_rank_through_the_multi_gpu_entry():
-    """`bench.py --workload colpart --gpus 1` forced through the branch N > 1 takes (unique id ->
+    """`bench.py --workload colpart --gpus 1 --full` forced through the branch N > 1 takes (unique id ->
     create_synthetic_rank -> ncclCommInitRank -> collectives on a one-rank communicator), incl. the
     second leg with the rooted-broadcast exchange and the steady-state figure."""
     import json
@@ -584,7 +584,7 @@ def test_bench_colpart_one_rank_through_the_multi_gpu_entry():
     import sys
     env = dict(os.environ, MI355X_COLPART_FORCE_RCCL="1", BENCH_COLPART_RANK_ENTRY="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "colpart", "--gpus", "1",
-                          "--steps", "20", "--warmup", "5", "--colpart-vars", "4096"],
+                          "--steps", "20", "--warmup", "5", "--colpart-vars", "4096", "--full"],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -670,9 +670,9 @@ def _bench_two_ranks(extra_env, extra_args=()):
 
 def test_bench_two_ranks_headline_is_the_column_partition():
     """`bench.py --gpus 2` as the driver launches it (two ranks; here both on the one GPU with the
-    scalar reductions over gloo, where the shards' exchanges are staged through the host): ONE JSON
-    line, the strong-scaling column-partition record with the independent LPs attached."""
-    rec = _bench_two_ranks({})
+    scalar reductions over gloo, where the shards' exchanges are staged through the host), with `--full`:
+    ONE JSON line, the strong-scaling column-partition record with the independent LPs attached."""
+    rec = _bench_two_ranks({}, ["--full"])
     assert rec["n_gpus"] == 2 and rec["scaling"] == "strong" and rec["steps"] == 20
     assert rec["value"] > 0 and "column-partitioned" in rec["config"]["workload"]
     # the ranks share the one GPU: the library's own loop runs in exchange mode 2 (P2P push) without a

@@ -10,8 +10,8 @@ rm -rf $O; mkdir -p $O
 cd $R
 python -m pytest tests -m gpu -x -q --durations=12 > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest_gpu.log
 grep -A 14 "slowest 12 durations" $O/pytest_gpu.log > $O/pytest_gpu_summary.log; tail -1 $O/pytest_gpu.log >> $O/pytest_gpu_summary.log
-python bench.py > $O/bench.log 2>&1; echo "bench rc=$?"; tail -1 $O/bench.log | cut -c1-400
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_flags.log 2>&1; echo "bench (driver flags) rc=$?"
+python bench.py --full > $O/bench.log 2>&1; echo "bench rc=$?"; tail -1 $O/bench.log | cut -c1-400
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_flags.log 2>&1; echo "bench (driver flags) rc=$?"
 MI355X_E2E_TIMING=1 python tools/native_end_to_end.py --init > $O/native_end_to_end.log 2>&1; echo "native end to end rc=$?"; tail -4 $O/native_end_to_end.log
 (python tools/steady_gap.py --repeat 3 --pivots 4200; python tools/steady_gap.py --repeat 3 --pivots 4200 --skew 0; python tools/steady_gap.py --repeat 3 --pivots 4200 --load 0.25; python tools/steady_gap.py --repeat 3 --pivots 4200 --ring 0; python tools/steady_gap.py --repeat 4 --pivots 20 --events 0) 2>&1 | grep -v amdgpu.ids > $O/steady_gap.log; echo "steady gap rc=$?"
 (for sk in -1 0; do echo "== mi355x_tune_set_sweep_skew($sk)"; python tools/sweep_timeline.py --skew $sk; done) 2>&1 | grep -v amdgpu.ids > $O/sweep_timeline.log; echo "sweep timeline rc=$?"
