@@ -207,6 +207,23 @@ int         mi355x_tune_set_la_fault(int step_plus_1);       /* > 0: the last wo
                                                                 -step_plus_1 - 1 and then gives up
                                                                 alone (the leader commits a pivot
                                                                 that workgroup never stored)     */
+/* Arithmetic probe: one primitive of the exact kernels' wide integer arithmetic (kernels_exact.inc, the very
+ * functions the solve kernels call) applied to n operand tuples in one launch.  Element i of a, b and out is
+ * four little-endian 64-bit limbs at [4 i, 4 i + 4), two's complement; a 64-bit value takes limb 0, a 128-bit
+ * value limbs 0 and 1 (unused operand limbs are ignored, unused result limbs are zero).  rc[i] is the
+ * primitive's own status, or -1 where an operand breaks the precondition stated below.  op:
+ *    0 xmul 64 x 64 -> 128          1 xmul 128 x 128 -> 256
+ *    2 s256_add   3 s256_sub   4 s256_neg (a)   5 s256_lt -> out limb 0 (256-bit a, b; wrapping)
+ *    6 xsub_ovf: 128-bit a - b      7 xsub_ovf: 256-bit a - b         rc 1: the difference left the width
+ *    8 xfit 128 -> 64 (a)           9 xfit 256 -> 128 (a)             rc 1: outside the symmetric range
+ *   10 xdiv: 128-bit a / 64-bit b  11 xdiv: 256-bit a / 128-bit b     b > 0; shift and inverse derived from b
+ *                                                                     as a pivot record derives them; rc 0,
+ *                                                                     110 (quotient too wide) or 111 (remainder)
+ *   12 xrem: |256-bit a| mod 128-bit b (0 < b < 2^127)
+ *   13 xinv_odd modulo 2^64 (a)    14 xinv_odd modulo 2^128 (a)       a odd
+ *   15 xctz of the 128-bit a (non-zero) -> out limb 0 */
+int         mi355x_test_xarith(int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out,
+                               int32_t *rc, int device);
 #endif
 
 #ifdef __cplusplus

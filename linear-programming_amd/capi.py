@@ -199,6 +199,8 @@ _TEST_HOOKS = {
     "mi355x_tune_set_resident_fault": (_int, [_int]),
     "mi355x_tune_set_la_fault": (_int, [_int]),
     "mi355x_tune_set_shard_la_fault": (_int, [_int]),
+    # one primitive of the exact kernels' wide integer arithmetic over arrays of operands
+    "mi355x_test_xarith": (_int, [_int, _i64, _p, _p, _p, _p, _int]),
 }
 TEST_LIB_PATH = os.path.join(HERE, "libmi355x_simplex_test.so")
 

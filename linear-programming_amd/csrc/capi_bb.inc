@@ -89,6 +89,11 @@ extern "C" __attribute__((visibility("hidden"))) int mi355x_bb_assemble_(mi355x_
         void *mem = nullptr;
         hipError_t e = hipSuccess;
         if (rc == MI_OK) e = hipMalloc(&mem, nrow * (8 + 4 + 8) + (size_t)(k1 - k0) * 2 * (rows - 1) * 4 + 64);
+        // alloc_tab left memsets of the artificial batch's basis and control blocks on ITS stream; the assembly
+        // below writes both from the main batch's stream, so those memsets have to be over first
+        // (which stream the hardware serves first decided the outcome: no deterministic test can show it; the
+        // random searches of tests/test_gpu_branch_and_bound.py failed now and then without this wait)
+        if (rc == MI_OK && e == hipSuccess && t[1]) e = hipStreamSynchronize(t[1]->stream);
         if (rc == MI_OK && e == hipSuccess) {
             char *p = (char *)mem;
             int64_t *dv = (int64_t *)p; double *db = (double *)(p + nrow * 8); int32_t *ds = (int32_t *)(p + nrow * 16);

@@ -100,5 +100,33 @@ int         mi355x_tab_path_counts(const mi355x_tab *t, int64_t *out8)
     for (int i = 0; i < 8; ++i) out8[i] = t->path_counts[i];
     return MI_OK;
 }
+#ifdef MI355X_TEST_HOOKS
+// one arithmetic primitive of the exact kernels (kernels_exact.inc) over n operand tuples, one launch
+int         mi355x_test_xarith(int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out, int32_t *rc, int device)
+{
+    if (op < 0 || op >= kXProbeOps || n < 1 || n > (1 << 24) || !a || !b || !out || !rc) return fail(MI_BAD_ARG, "bad opcode, count or NULL array");
+    int st = x_check_device(device);
+    if (st != MI_OK) return st;
+    if (hipSetDevice(device) != hipSuccess) return fail(MI_HIP_ERROR, "hipSetDevice failed");
+    const size_t bytes = (size_t)n * 4 * sizeof(int64_t);
+    int64_t *da = nullptr, *db = nullptr, *dout = nullptr;
+    int32_t *drc = nullptr;
+    hipError_t e = hipMalloc(&da, bytes);
+    if (e == hipSuccess) e = hipMalloc(&db, bytes);
+    if (e == hipSuccess) e = hipMalloc(&dout, bytes);
+    if (e == hipSuccess) e = hipMalloc(&drc, (size_t)n * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(da, a, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(db, b, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_x_arith_probe(op, n, da, db, dout, drc, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(rc, drc, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
+    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout); (void)hipFree(drc);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "mi355x_test_xarith: %s", hipGetErrorString(e));
+    return MI_OK;
+}
+#endif
 
 }  // extern "C"

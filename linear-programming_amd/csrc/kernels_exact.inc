@@ -153,19 +153,25 @@ template <class T> struct XUnsigned;
 template <> struct XUnsigned<int64_t>  { typedef uint64_t type; };
 template <> struct XUnsigned<__int128> { typedef xu128 type; };
 
+// what xdiv takes besides D = 2^shift * odd, D > 0: the shift and the inverse of the odd part modulo 2^W
+template <class T> __device__ inline void x_div_setup(__int128 D, int32_t *shift, __int128 *inv)
+{
+    typedef typename XUnsigned<T>::type U;
+    const int sh = xctz((xu128)D);
+    *shift = sh;
+    *inv = (__int128)xinv_odd<U>((U)(D >> sh));
+}
+
 // the pivot record of (ec, cr) -- thread 0 only; the snapshots follow in x_snapshot
 template <class T> __device__ inline void x_record(XCtl *c, const T *M, int64_t cols, int64_t ec, int64_t cr)
 {
-    typedef typename XUnsigned<T>::type U;
     const T p = M[cr * cols + ec];
     c->ec = ec;
     c->cr = cr;
     c->sgn = p < 0 ? -1 : 1;
     c->pa = (__int128)(p < 0 ? -p : p);
     c->dold = c->D;
-    const int sh = xctz((xu128)c->dold);
-    c->shift = sh;
-    c->inv = (__int128)xinv_odd<U>((U)(c->dold >> sh));
+    x_div_setup<T>(c->dold, &c->shift, &c->inv);
     c->D = c->pa;
     c->apply = 1;
 }
@@ -368,3 +374,71 @@ void launch_x_handover(const XView &art, const XView &mt, const void *w, const v
         hipLaunchKernelGGL(k_x_handover<__int128>, grid, dim3(256), 0, s, art, mt, (const __int128 *)w,
                            (const __int128 *)cl, lc);
 }
+
+#ifdef MI355X_TEST_HOOKS
+// ---- the arithmetic above, one primitive per launch, element-wise (test build only) -------------
+// Element i of a, b and out is four little-endian 64-bit limbs at [4 i, 4 i + 4); a narrower value
+// takes the low limbs (out: the rest is zero).  rc[i]: the primitive's own status or flag, -1 for an
+// operand outside the primitive's precondition (a divisor <= 0, xctz of 0), which is then not called.
+__device__ inline __int128 xp_i128(const int64_t *p) { return (__int128)(((xu128)(uint64_t)p[1] << 64) | (uint64_t)p[0]); }
+__device__ inline S256 xp_s256(const int64_t *p) { S256 r; r.lo = (xu128)xp_i128(p); r.hi = xp_i128(p + 2); return r; }
+__device__ inline void xp_put(int64_t *o, __int128 x) { o[0] = (int64_t)(uint64_t)(xu128)x; o[1] = (int64_t)(x >> 64); }
+__device__ inline void xp_put(int64_t *o, S256 x) { xp_put(o, (__int128)x.lo); xp_put(o + 2, x.hi); }
+
+__global__ __launch_bounds__(256) void k_x_arith_probe(int op, int64_t n, const int64_t *a, const int64_t *b,
+                                                       int64_t *out, int32_t *rc)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t *pa = a + 4 * i, *pb = b + 4 * i;
+        int64_t *o = out + 4 * i;
+        int32_t st = 0;
+        o[0] = o[1] = o[2] = o[3] = 0;
+        switch (op) {
+        case kXProbeMul64:  xp_put(o, xmul(pa[0], pb[0])); break;
+        case kXProbeMul128: xp_put(o, xmul(xp_i128(pa), xp_i128(pb))); break;
+        case kXProbeAdd256: xp_put(o, s256_add(xp_s256(pa), xp_s256(pb))); break;
+        case kXProbeSub256: xp_put(o, s256_sub(xp_s256(pa), xp_s256(pb))); break;
+        case kXProbeNeg256: xp_put(o, s256_neg(xp_s256(pa))); break;
+        case kXProbeLt256:  o[0] = s256_lt(xp_s256(pa), xp_s256(pb)) ? 1 : 0; break;
+        case kXProbeSubOvf64:  { __int128 acc = xp_i128(pa); st = xsub_ovf(acc, xp_i128(pb)) ? 0 : 1; xp_put(o, acc); break; }
+        case kXProbeSubOvf128: { S256 acc = xp_s256(pa); st = xsub_ovf(acc, xp_s256(pb)) ? 0 : 1; xp_put(o, acc); break; }
+        case kXProbeFit64:  { int64_t y = 0; st = xfit(xp_i128(pa), &y) ? 0 : 1; o[0] = y; break; }
+        case kXProbeFit128: { __int128 y = 0; st = xfit(xp_s256(pa), &y) ? 0 : 1; xp_put(o, y); break; }
+        case kXProbeDiv64: {
+            int32_t sh; __int128 inv; int64_t q = 0;
+            if (pb[0] <= 0) { st = -1; break; }
+            x_div_setup<int64_t>((__int128)pb[0], &sh, &inv);
+            st = xdiv(xp_i128(pa), pb[0], sh, (uint64_t)inv, &q);
+            o[0] = q;
+            break;
+        }
+        case kXProbeDiv128: {
+            int32_t sh; __int128 inv, q = 0;
+            if (xp_i128(pb) <= 0) { st = -1; break; }
+            x_div_setup<__int128>(xp_i128(pb), &sh, &inv);
+            st = xdiv(xp_s256(pa), xp_i128(pb), sh, (xu128)inv, &q);
+            xp_put(o, q);
+            break;
+        }
+        case kXProbeRem:
+            if (xp_i128(pb) <= 0) { st = -1; break; }
+            xp_put(o, (__int128)xrem(xp_s256(pa), (xu128)xp_i128(pb)));
+            break;
+        case kXProbeInv64:  o[0] = (int64_t)xinv_odd<uint64_t>((uint64_t)pa[0]); break;
+        case kXProbeInv128: xp_put(o, (__int128)xinv_odd<xu128>((xu128)xp_i128(pa))); break;
+        case kXProbeCtz:
+            if (xp_i128(pa) == 0) { st = -1; break; }
+            o[0] = xctz((xu128)xp_i128(pa));
+            break;
+        default: st = -1;
+        }
+        rc[i] = st;
+    }
+}
+
+void launch_x_arith_probe(int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out, int32_t *rc, hipStream_t s)
+{
+    const int64_t g = (n + 255) / 256;
+    hipLaunchKernelGGL(k_x_arith_probe, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, s, op, n, a, b, out, rc);
+}
+#endif

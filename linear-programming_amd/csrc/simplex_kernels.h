@@ -367,6 +367,14 @@ void launch_x_update(const XView &v, hipStream_t s);
 // main[r][j] = lc * art[r][src(j)] (r < m); main[m][j] = D_art * cl[j] - sum_r w[r] * art[r][src(j)];
 // main D = lc * D_art.  w (m) and cl (main cols) hold values of the handles' width.
 void launch_x_handover(const XView &art, const XView &mt, const void *w, const void *cl, __int128 lc, hipStream_t s);
+#ifdef MI355X_TEST_HOOKS
+// test build: one arithmetic primitive of kernels_exact.inc applied element-wise (k_x_arith_probe; the
+// opcodes and the limb layout are mi355x_test_xarith's, include/mi355x_simplex_tune.h).  Device pointers.
+enum XProbeOp { kXProbeMul64 = 0, kXProbeMul128, kXProbeAdd256, kXProbeSub256, kXProbeNeg256, kXProbeLt256,
+                kXProbeSubOvf64, kXProbeSubOvf128, kXProbeFit64, kXProbeFit128, kXProbeDiv64, kXProbeDiv128,
+                kXProbeRem, kXProbeInv64, kXProbeInv128, kXProbeCtz, kXProbeOps };
+void launch_x_arith_probe(int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out, int32_t *rc, hipStream_t s);
+#endif
 
 int         update_variant_count();
 const char *update_variant_name(int v);

@@ -5,6 +5,8 @@ import random
 from fractions import Fraction
 from math import gcd
 
+import numpy as np
+
 import oracle.rational_ref as rr
 
 
@@ -114,20 +116,47 @@ def start_state(matrix):
     return T, D
 
 
+def new_stats():
+    return {"inexact": 0, "negative_pivots": 0, "driveouts": 0, "max_bits": 0, "pivots": 0, "over64": None}
+
+
+def note_bits(stats, stage, bits):
+    """max_bits, and where it first exceeded 64: over64 = (stage, index of the pivot whose result did it,
+    counted over both phases and the drive-outs; for the hand-over: the pivots applied before it)."""
+    stats["max_bits"] = max(stats["max_bits"], bits)
+    if stats["max_bits"] > 64 and stats["over64"] is None:
+        stats["over64"] = (stage, stats["pivots"])
+
+
 class Model:
     """The Bareiss state (T, D) of one tableau and the kernels' steps on it."""
+
+    stage = "phase1"
 
     def __init__(self, matrix, basis, var_count):
         self.T, self.D = start_state(matrix)
         self.basis = list(basis)
         self.nv = var_count
-        self.stats = {"inexact": 0, "negative_pivots": 0, "driveouts": 0, "max_bits": 0}
+        self.stats = new_stats()
         self.track(self.T, [self.D])
+
+    @classmethod
+    def from_state(cls, T, D, basis, var_count, stats=None, stage="phase1", extra=()):
+        """A model that starts from integer rows T and their common denominator D."""
+        t = cls.__new__(cls)
+        t.T, t.D, t.basis, t.nv = [list(row) for row in T], D, list(basis), var_count
+        t.stats, t.stage = (new_stats() if stats is None else stats), stage
+        t.track(t.T, [t.D] + list(extra))
+        return t
+
+    def rows(self):
+        """T as lists of Python ints."""
+        return self.T
 
     def track(self, rows, extra=()):
         """max_bits: the width (sign bit included) the largest value stored so far needs."""
         vals = [abs(int(x)) for row in rows for x in row] + [abs(int(x)) for x in extra]
-        self.stats["max_bits"] = max([self.stats["max_bits"]] + [v.bit_length() + 1 for v in vals])
+        note_bits(self.stats, self.stage, max([0] + [v.bit_length() + 1 for v in vals]))
 
     def _div(self, N):
         q, r = divmod(N, self.D)
@@ -151,6 +180,7 @@ class Model:
         self.T, self.D = out, abs(p)
         self.basis[r] = e
         self.track(out, [self.D])
+        self.stats["pivots"] += 1
 
     def matrix(self):
         return [[Fraction(x, self.D) for x in row] for row in self.T]
@@ -173,8 +203,13 @@ class Model:
                 best = i
         return best
 
-    def solve(self, is_max, trace):
+    def solve(self, is_max, trace, max_pivots=0):
+        """Pivots until the tableau is optimal or unbounded, or ("max_pivots") max_pivots > 0 were made."""
+        k = 0
         while True:
+            if max_pivots and k >= max_pivots:
+                return "max_pivots"
+            k += 1
             e = self.price(is_max)
             if e is None:
                 return "optimal"
@@ -185,27 +220,34 @@ class Model:
             self.pivot(e, r)
 
 
-def model_solve(tabs):
-    """(status, trace, final Model or None, stats) of the fraction-free model on rational_ref's
-    build_tableau result (a Tableau or an (art, main) pair)."""
+def model_solve(tabs, cls=None, keep=None, phase2_pivots=0):
+    """(status, trace, final model or None, stats) of the fraction-free model (cls: Model or VecModel) on
+    rational_ref's build_tableau result (a Tableau or an (art, main) pair).  keep: a dict that receives
+    the artificial model ("art") and the trace's length at the end of phase 1 ("n1").  phase2_pivots > 0
+    caps phase 2 of a two-phase solve: status "max_pivots", the main model as it stands."""
+    cls = cls or Model
     trace = []
     if not isinstance(tabs, tuple):
-        t = Model(tabs.matrix, tabs.basis, tabs.var_count)
+        t = cls(tabs.matrix, tabs.basis, tabs.var_count)
         st = t.solve(tabs.is_max, trace)
         return st, trace, (t if st == "optimal" else None), t.stats
     art_t, main_t = tabs
-    a = Model(art_t.matrix, art_t.basis, art_t.var_count)
+    a = cls(art_t.matrix, art_t.basis, art_t.var_count)
     st = a.solve(False, trace)
+    if keep is not None:
+        keep["art"], keep["n1"] = a, len(trace)
     if st != "optimal":
         return st, trace, None, a.stats
-    if a.T[-1][a.nv] != 0:
+    if a.rows()[-1][a.nv] != 0:
         return "infeasible", trace, None, a.stats
     nv, m = main_t.var_count, main_t.constraint_count
+    a.stage = "driveout"
     for i in range(m):
         if a.basis[i] >= nv:
-            if a.T[i][a.nv] != 0:
+            row = a.rows()[i]
+            if row[a.nv] != 0:
                 return "art_nonzero", trace, None, a.stats
-            j = next((j for j in range(nv) if a.T[i][j] != 0 and j not in a.basis), None)
+            j = next((j for j in range(nv) if row[j] != 0 and j not in a.basis), None)
             if j is None:
                 return "art_stuck", trace, None, a.stats
             a.stats["driveouts"] += 1
@@ -216,19 +258,17 @@ def model_solve(tabs):
     for x in c:
         lc = _lcm(lc, x.denominator)
     src = list(range(nv)) + [a.nv]
-    mm = Model.__new__(Model)
-    mm.nv, mm.basis, mm.stats = nv, list(a.basis), a.stats
-    mm.D = a.D * lc
-    mm.T = [[a.T[i][s] * lc for s in src] for i in range(m)]
-    obj = []
-    for k, s in enumerate(src):
-        v = a.D * (c[k] * lc) - sum(c[a.basis[i]] * lc * a.T[i][s] for i in range(m))
-        assert v.denominator == 1
-        obj.append(int(v))
-    mm.T.append(obj)
-    mm.track(mm.T, [mm.D, lc] + [c[a.basis[i]] * lc for i in range(m)] + [x * lc for x in c])
-    st = mm.solve(main_t.is_max, trace)
-    return st, trace, (mm if st == "optimal" else None), mm.stats
+    AT = a.rows()
+    T = [[AT[i][s] * lc for s in src] for i in range(m)]
+    w = [c[a.basis[i]] * lc for i in range(m)]
+    cl = [x * lc for x in c]
+    assert all(x.denominator == 1 for x in w + cl)
+    w, cl = [int(x) for x in w], [int(x) for x in cl]
+    T.append([a.D * cl[k] - sum(w[i] * AT[i][s] for i in range(m) if w[i]) for k, s in enumerate(src)])
+    mm = cls.from_state(T, a.D * lc, a.basis, nv, stats=a.stats, stage="handover", extra=[lc] + w + cl)
+    mm.stage = "phase2"
+    st = mm.solve(main_t.is_max, trace, phase2_pivots)
+    return st, trace, (mm if st in ("optimal", "max_pivots") else None), mm.stats
 
 
 def wide_problem(lp, seed, e):
@@ -251,3 +291,182 @@ def beale(lp):
                       constraints=[("<=", [("x1", F(1, 4)), ("x2", F(-8)), ("x3", F(-1)), ("x4", F(9))], F(0)),
                                    ("<=", [("x1", F(1, 2)), ("x2", F(-12)), ("x3", F(-1, 2)), ("x4", F(3))], F(0)),
                                    ("<=", [("x3", F(1))], F(1))])
+
+
+# ---- the same model on a numpy matrix, for tableaux of many workgroups ----------------------------
+class VecModel:
+    """Model's rules (price / ratio / pivot, the same ties) with the rank-1 update done by numpy: int64
+    while every intermediate of a pivot provably stays below 2^62, Python ints (dtype object) beyond.
+    tests/test_exact_host.py pins it to Model, and so to oracle/rational_ref.py."""
+    stage = "phase1"
+
+    def __init__(self, matrix, basis, var_count):
+        T, D = start_state(matrix)
+        self._init(T, D, basis, var_count, None, "phase1", ())
+
+    @classmethod
+    def from_state(cls, T, D, basis, var_count, stats=None, stage="phase1", extra=()):
+        t = cls.__new__(cls)
+        t._init(T, D, basis, var_count, stats, stage, extra)
+        return t
+
+    def _init(self, T, D, basis, var_count, stats, stage, extra):
+        if isinstance(T, np.ndarray) and T.dtype == np.int64:
+            self.T = T.copy()
+        else:
+            self.T = np.array(T, dtype=object)
+            if self._maxabs() < 1 << 62:
+                self.T = self.T.astype(np.int64)
+        self.D, self.basis, self.nv = int(D), [int(b) for b in basis], int(var_count)
+        self.stats, self.stage = (new_stats() if stats is None else stats), stage
+        self.track(extra)
+
+    def _maxabs(self):
+        if self.T.dtype == object:
+            return max(abs(x) for x in self.T.flat)
+        return max(int(self.T.max()), -int(self.T.min()))
+
+    def track(self, extra=()):
+        vals = [self._maxabs(), self.D] + [abs(int(x)) for x in extra]
+        note_bits(self.stats, self.stage, max(v.bit_length() + 1 for v in vals))
+
+    def rows(self):
+        return self.T.tolist()
+
+    def price(self, is_max):
+        if self.nv == 0:
+            return None
+        obj = self.T[-1, :self.nv]
+        best = int(np.argmin(obj) if is_max else np.argmax(obj))         # (the first of equal values)
+        return best if ((obj[best] < 0) if is_max else (obj[best] > 0)) else None
+
+    def ratio(self, e):
+        col, rhs = self.T[:-1, e], self.T[:-1, self.nv]
+        best = ba = br = None
+        for i in np.nonzero(col > 0)[0].tolist():
+            a, r = int(col[i]), int(rhs[i])
+            if best is None or r * ba < br * a:
+                best, ba, br = i, a, r
+        return best
+
+    def pivot(self, e, r):
+        T = self.T
+        p = int(T[r, e])
+        s, ap = (-1 if p < 0 else 1), abs(p)
+        if p < 0:
+            self.stats["negative_pivots"] += 1
+        if T.dtype != object and (2 * self._maxabs() ** 2 >= 1 << 62 or self.D >= 1 << 62):
+            T = T.astype(object)
+        prow = T[r].copy()
+        c = s * T[:, e]
+        N = T * ap
+        N -= np.multiply.outer(c, prow)
+        if self.D != 1:
+            Q = N // self.D
+            self.stats["inexact"] += int(((N - Q * self.D) != 0).sum())
+        else:
+            Q = N
+        Q[r] = s * prow
+        self.T, self.D = Q, ap
+        self.basis[r] = e
+        self.track()
+        self.stats["pivots"] += 1
+
+    solve = Model.solve
+
+
+def slack_tableau(m, n, seed, entries=(0, 3), rhs=(1, 9), obj=(1, 3), density=1.0):
+    """A seeded slack-form start [A | I | b] over the objective row -c, as int64: m rows of n variables
+    with small non-negative entries, so that exact ties in pricing and in the ratio test are the rule and
+    the fraction-free entries (minors of A) stay narrow; density < 1 zeroes entries of A at random, so that
+    different variables meet different rows.  (T ((m + 1) x (n + m + 1)), basis)."""
+    rng = np.random.default_rng(seed)
+    T = np.zeros((m + 1, n + m + 1), dtype=np.int64)
+    T[:m, :n] = rng.integers(entries[0], entries[1] + 1, size=(m, n))
+    if density < 1.0:
+        T[:m, :n] *= rng.random(size=(m, n)) < density
+    T[np.arange(m), n + np.arange(m)] = 1
+    T[:m, -1] = rng.integers(rhs[0], rhs[1] + 1, size=m)
+    T[m, :n] = -rng.integers(obj[0], obj[1] + 1, size=n)
+    return T, np.arange(n, n + m, dtype=np.int64)
+
+
+def mixed_problem(lp, n, m_le, m_ge, m_eq, seed, paired=2):
+    """A feasible all-integer LP with <=, >= and = rows (small entries; x = 1 is feasible) and `paired`
+    rows that stand twice, as a . x <= b and further down as a . x = b: the two tie in every ratio test,
+    the slack of the first leaves, and the artificial variable of the second stays basic at zero over a
+    row that is not zero -- it has to be driven out after phase 1."""
+    rng = random.Random(seed)
+    names = ["x%d" % i for i in range(n)]
+    cons, twice = [], []
+    for _ in range(paired):
+        a = [rng.randint(0, 3) for _ in names]
+        cons.append(("<=", list(zip(names, a)), sum(a)))
+        twice.append(("=", list(zip(names, a)), sum(a)))
+    for op, count in (("<=", m_le), (">=", m_ge), ("=", m_eq)):
+        for _ in range(count):
+            a = [rng.randint(0, 3) for _ in names]
+            tot = sum(a)
+            rhs = tot + rng.randint(1, 6) if op == "<=" else (max(tot - rng.randint(1, 6), 0) if op == ">=" else tot)
+            cons.append((op, list(zip(names, a)), rhs))
+    return lp.Problem(type="max", vars=names, objective_var="w",
+                      objective_func=[(v, rng.randint(1, 3)) for v in names], constraints=cons + twice)
+
+
+def wide_mixed_problem(lp, seed, e):
+    """wide_problem with a >= and an = row among its four (x = 1 is feasible): a two-phase job whose
+    fraction-free entries outgrow 64 bits on the way -- where, depends on e and the seed."""
+    rng = random.Random(seed)
+    names = ["x%d" % i for i in range(4)]
+    cons = []
+    for op in ("<=", ">=", "=", "<="):
+        a = [rng.randint(1 << e, 1 << (e + 1)) for _ in names]
+        d = rng.randint(1 << e, 1 << (e + 1))
+        cons.append((op, list(zip(names, a)), sum(a) + (d if op == "<=" else -d if op == ">=" else 0)))
+    return lp.Problem(type="max", vars=names, objective_var="w",
+                      objective_func=[(v, rng.randint(1, 1 << e)) for v in names], constraints=cons)
+
+
+# ---- k_x_select's two reductions, thread for thread ------------------------------------------------
+def select_tree(n, better, equal, tie_clause=True, threads=256):
+    """The index k_x_select's reduction pattern picks among 0 .. n-1.  better(a, b): candidate a strictly
+    beats b (b = -1: none yet; a candidate that may not take part beats nothing); equal(a, b): a tie.
+    Every thread scans tid, tid + threads, ... and keeps the first best; a tree over the threads' keeps then
+    takes the other element when it is strictly better or, with tie_clause, equal with a lower index.
+    Without tie_clause (a kernel that lost the clause) the element at the lower thread position survives a
+    tie, whatever its index."""
+    keep = [-1] * threads
+    for t in range(threads):
+        for j in range(t, n, threads):
+            if better(j, keep[t]):
+                keep[t] = j
+    s = threads // 2
+    while s:
+        for t in range(s):
+            o = t + s
+            if keep[o] >= 0 and (keep[t] < 0 or better(keep[o], keep[t]) or
+                                 (tie_clause and equal(keep[o], keep[t]) and keep[o] < keep[t])):
+                keep[t] = keep[o]
+        s //= 2
+    return keep[0]
+
+
+def select_price(obj, is_max, tie_clause=True):
+    """The pricing reduction over the objective entries obj[0 .. nv): the index at the tree's root (the
+    kernel then tests its sign)."""
+    obj = [int(x) for x in obj]
+
+    def better(a, b):
+        return b < 0 or (obj[a] < obj[b] if is_max else obj[a] > obj[b])
+    return select_tree(len(obj), better, lambda a, b: obj[a] == obj[b], tie_clause)
+
+
+def select_ratio(col, rhs, tie_clause=True):
+    """The ratio-test reduction over rows with col > 0, cross-multiplied; -1: no row."""
+    col, rhs = [int(x) for x in col], [int(x) for x in rhs]
+
+    def better(a, b):
+        if col[a] <= 0:
+            return False
+        return b < 0 or rhs[a] * col[b] < rhs[b] * col[a]
+    return select_tree(len(col), better, lambda a, b: rhs[a] * col[b] == rhs[b] * col[a], tie_clause)

@@ -4,6 +4,7 @@ exact kernels implement (start state, folded objective LCM, sign-normalised pivo
 ratio test, hand-over with the full L_c) reproduces the Fraction oracle pivot for pivot."""
 from fractions import Fraction
 
+import numpy as np
 import pytest
 
 import oracle.rational_ref as rr
@@ -100,6 +101,53 @@ def test_fraction_free_model_reproduces_the_oracle():
     for _, p in _golden_problems():
         if p.constraints:
             _model_matches_oracle(p)
+
+
+def test_vectorised_model_equals_the_model_and_the_oracle():
+    """exact_cases.VecModel (the reference of the multi-workgroup shapes, tests/test_gpu_exact_shapes.py)
+    against exact_cases.Model on the 200 seeds -- status, trace, basis, T, D and the statistics -- and
+    directly against the Fraction oracle's final tableau."""
+    outcomes, two_phase = set(), 0
+    for seed in SEEDS:
+        tabs = rr.build_tableau(ec.to_dict(ec.random_problem(lp, seed)))
+        st, trace, mm, stats = ec.model_solve(tabs)
+        vst, vtrace, vm, vstats = ec.model_solve(tabs, cls=ec.VecModel)
+        assert (vst, vtrace, vstats) == (st, trace, stats), seed
+        assert (vm is None) == (mm is None)
+        outcomes.add(st)
+        two_phase += isinstance(tabs, tuple)
+        if mm is not None:
+            assert vm.basis == mm.basis and vm.D == mm.D and vm.rows() == mm.T, seed
+            _, _, t = ec.oracle_outcome(tabs)
+            assert [[Fraction(x, vm.D) for x in row] for row in vm.rows()] == t.matrix and vm.basis == t.basis
+    assert {"optimal", "unbounded", "infeasible"} <= outcomes and two_phase >= 50
+    # both storage forms of the vectorised model: int64 and, past 62 bits, Python ints
+    wide = rr.build_tableau(ec.to_dict(ec.wide_problem(lp, 0, 40)))
+    st, trace, mm, stats = ec.model_solve(wide)
+    vst, vtrace, vm, vstats = ec.model_solve(wide, cls=ec.VecModel)
+    assert stats["max_bits"] > 64 and vm.T.dtype == object
+    assert (vst, vtrace, vstats) == (st, trace, stats) and vm.rows() == mm.T and vm.D == mm.D
+    # ties: the first of equal objective entries and of equal ratios, for max and for min
+    T, basis = ec.slack_tableau(12, 9, 3)
+    T[-1, :9] = -2
+    T[:12, 0], T[:12, -1] = 3, 1
+    for is_max in (True, False):
+        S = T if is_max else np.concatenate([T[:-1], -T[-1:]])
+        a, b = ec.Model.from_state(S.tolist(), 1, basis, 21), ec.VecModel.from_state(S, 1, basis, 21)
+        ta, tb = [], []
+        assert a.solve(is_max, ta) == b.solve(is_max, tb) and ta == tb and ta[0] == (0, 0)
+        assert a.T == b.rows() and a.D == b.D and a.basis == b.basis
+
+
+def test_model_records_where_64_bits_are_first_exceeded():
+    tabs = rr.build_tableau(ec.to_dict(ec.wide_problem(lp, 0, 40)))
+    t = ec.Model(tabs.matrix, tabs.basis, tabs.var_count)
+    assert t.stats["over64"] is None and t.stats["max_bits"] <= 64
+    trace, k = [], 0
+    while t.stats["max_bits"] <= 64:
+        assert t.solve(tabs.is_max, trace, max_pivots=1) == "max_pivots"
+        k += 1
+    assert t.stats["over64"] == ("phase1", k - 1) and t.stats["pivots"] == k
 
 
 def test_exact_route_selection():

@@ -1,7 +1,14 @@
 """Exact mode on the GPU (solve_problem(p, exact=True)): fraction-free integer tableaux
 (kernels_exact.inc) against the Fraction oracle (oracle/rational_ref.py) -- status, pivot sequence,
-basis and every final entry -- plus the width escalation, the 128-bit limit, bounded calls, cancel and
-handle cycles."""
+basis and every final entry -- plus the width escalation (also inside a two-phase job and under bounded
+calls), the 128-bit limit, bounded calls, cancel, the trace buffer's cap and handle cycles.
+
+MI_EXACT_INEXACT is not tested here: no input reaches it through the public entry points.  A solve is
+refused (MI_UNSUPPORTED) unless the basis columns are exact unit columns, and from such a start every
+fraction-free division is exact (D0 is the product of the rows' denominator LCMs, so every 2 x 2 minor of
+D0 * t0 is a multiple of D0; Sylvester's identity carries that on); the main tableau of a two-phase job
+is rebuilt from the artificial one.  The kXInexact / kXOverflow split of a failed division is pinned on
+the arithmetic itself, in tests/test_gpu_exact_arith.py (xdiv with planted remainders)."""
 import ctypes
 import json
 import os
@@ -224,3 +231,85 @@ def test_exact_handle_cycles_do_not_lose_device_memory():
         cycle()
     torch.cuda.synchronize()
     assert free0 - torch.cuda.mem_get_info()[0] < 32 << 20
+
+
+def _escalating_two_phase_problems():
+    """By the model: a two-phase problem whose entries first outgrow 64 bits in phase 1, and one where that
+    happens later (a drive-out, the hand-over or phase 2).  {where: (problem, trace, stats, n1)}"""
+    found = {}
+    for e in (24, 28):
+        for seed in range(8):
+            p = ec.wide_mixed_problem(lp, seed, e)
+            tabs = rr.build_tableau(ec.to_dict(p))
+            keep = {}
+            st, trace, _, stats = ec.model_solve(tabs, keep=keep)
+            if st != "optimal" or stats["over64"] is None or stats["max_bits"] > 128 or stats["inexact"]:
+                continue
+            where = "phase1" if stats["over64"][0] == "phase1" else "later"
+            assert (stats["over64"][1] < keep["n1"]) == (where == "phase1")
+            found.setdefault(where, (p, trace, stats, keep["n1"]))
+    return found
+
+
+@pytest.mark.parametrize("where", ["phase1", "later"])
+def test_64_bit_overflow_inside_a_two_phase_job_restarts_both_phases(where):
+    found = _escalating_two_phase_problems()
+    assert where in found
+    p, trace, stats, n1 = found[where]
+    counts = (n1 + stats["driveouts"], len(trace) - n1)
+    tabs = lp.build_tableau(p, exact=True)
+    assert [t.bits for t in tabs] == [64, 64]                  # (the start fits: the overflow comes on the way)
+    _, sol = _check_against_oracle(p)
+    assert sol.bits == 128 and sol.phase1.bits == 128
+    assert _trace(sol) == trace and tuple(sol.n_pivots) == counts
+    # one pivot per call: the restart at 128 bits replays the pivots of the earlier calls, and counts none twice
+    calls = []
+    L = lp.capi.lib()
+    art, main = tabs
+    npv = (ctypes.c_int64 * 2)()
+    while True:
+        rc = L.mi355x_xtab_solve_two_phase(art._h, main._h, 1, 1, npv)
+        calls.append((rc, npv[0], npv[1]))
+        assert len(calls) <= sum(counts) + 2
+        if rc != lp.capi.MI_MAX_PIVOTS:
+            break
+    assert rc == lp.capi.MI_OPTIMAL
+    assert (sum(c[1] for c in calls), sum(c[2] for c in calls)) == counts
+    assert all(c[1] + c[2] <= max(1, stats["driveouts"]) for c in calls)
+    art._touch()
+    main._touch()
+    assert art.bits == 128 and main.bits == 128
+    assert [tuple(x) for x in art.pivot_trace().tolist()] + [tuple(x) for x in main.pivot_trace().tolist()] == trace
+    assert main.matrix.tolist() == sol.matrix.tolist() and main.basis_columns.tolist() == sol.basis_columns.tolist()
+    # and through the package's own bounded calls
+    part = lp.exact.n_solve_exact(lp.build_tableau(p, exact=True), chunk=1)
+    assert part.bits == 128 and part.phase1.bits == 128
+    assert _trace(part) == trace and tuple(part.n_pivots) == counts
+    assert part.matrix.tolist() == sol.matrix.tolist()
+
+
+def test_trace_buffer_stops_at_its_cap_while_the_count_goes_on():
+    CAP = 1 << 18
+    total = CAP + 60
+    t = lp.build_tableau(ec.beale(lp), exact=True)
+    L = lp.capi.lib()
+    n = ctypes.c_int64(0)
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    assert L.mi355x_xtab_solve(t._h, 1, total, ctypes.byref(n)) == lp.capi.MI_MAX_PIVOTS and n.value == total
+    period = [(0, 0), (1, 1), (2, 0), (3, 1), (4, 0), (5, 1)]
+    want = np.array(period * (CAP // 6 + 1), dtype=np.int64)[:CAP]
+    e, r = np.full(CAP + 1000, -7, dtype=np.int64), np.full(CAP + 1000, -7, dtype=np.int64)
+    assert L.mi355x_xtab_trace(t._h, ptr(e), ptr(r), e.size, ctypes.byref(n)) == lp.capi.MI_OK
+    assert n.value == total                                                  # the count goes on past the buffer
+    assert (e[CAP:] == -7).all() and (r[CAP:] == -7).all()                   # exactly 2^18 entries are filled
+    assert np.array_equal(e[:CAP], want[:, 0]) and np.array_equal(r[:CAP], want[:, 1])
+    e, r = np.full(200, -7, dtype=np.int64), np.full(200, -7, dtype=np.int64)
+    assert L.mi355x_xtab_trace(t._h, ptr(e), ptr(r), 100, ctypes.byref(n)) == lp.capi.MI_OK and n.value == total
+    assert np.array_equal(e[:100], want[:100, 0]) and np.array_equal(r[:100], want[:100, 1])
+    assert (e[100:] == -7).all() and (r[100:] == -7).all()
+    t._touch()
+    ref = rr.build_tableau(ec.to_dict(ec.beale(lp)))
+    for _ in range(total % 6):                                               # the cycle's state after `total` pivots
+        c = rr.price(ref)
+        rr.pivot(ref, c, rr.ratio(ref, c))
+    assert t.matrix.tolist() == ref.matrix and t.basis_columns.tolist() == ref.basis
