@@ -64,6 +64,9 @@ extern "C" {
 #define MI_UNSUPPORTED  -6   /* -> unsupported-constraint-error (integer / binary variables) */
 #define MI_EXACT_OVERFLOW -7 /* exact tableaux: a value needs more than 128 bits -> unsupported-constraint-error */
 #define MI_EXACT_INEXACT  -8 /* exact tableaux: a fraction-free division left a remainder (an internal error) */
+/* batches of exact tableaux (mi355x_xbatch_*, below) */
+#define MI355X_XBATCH_WORKGROUP 256    /* threads of the workgroup that owns a member */
+#define MI355X_XBATCH_TRACE_CAP 1024   /* pivots a member's trace buffers hold (mi355x_xbatch_trace) */
 
 typedef struct mi355x_tab   mi355x_tab;     /* one tableau resident in HBM              */
 typedef struct mi355x_batch mi355x_batch;   /* a batch of same-shape tableaux in HBM    */
@@ -72,6 +75,7 @@ typedef struct mi355x_solution mi355x_solution;  /* what the read-back needs of 
 typedef struct mi355x_solve    mi355x_solve;     /* a problem on its way to a solution (resumable)  */
 typedef struct mi355x_solve_many mi355x_solve_many; /* a LIST of problems on their way to solutions   */
 typedef struct mi355x_xtab     mi355x_xtab;      /* one exact (fraction-free integer) tableau in HBM */
+typedef struct mi355x_xbatch   mi355x_xbatch;    /* many exact tableaux of one shape, one workgroup per member */
 
 /* ---- library / device ------------------------------------------------------------- */
 int         mi355x_abi_version(void);
@@ -352,6 +356,51 @@ int  mi355x_xtab_bits(const mi355x_xtab *t, int *bits);
 /* mi355x_tab_cancel for the exact solves (any thread) */
 int  mi355x_xtab_cancel(mi355x_xtab *t);
 void mi355x_xtab_destroy(mi355x_xtab *t);
+/* ---- batches of exact rational tableaux  (n-solve-tableau, src/simplex.lisp:399-461, under the rational
+ * dispatch of src/utils.lisp:84-124, for many problems of one shape at once) ------------------------------
+ * n_lps tableaux of one shape, each solved exactly as mi355x_xtab_* solves one -- the same pivot sequence,
+ * basis and entries -- but side by side: one workgroup owns one member for its whole solve
+ * (src/simplex.lisp:453-461 inside one launch), and everything between the phases (src/simplex.lisp:405-451:
+ * feasibility test, drive-out pivots, hand-over) runs on the device per member as well.
+ * Status per member (status[], n_lps entries, may be NULL): MI_OPTIMAL / MI_UNBOUNDED / MI_INFEASIBLE /
+ * MI_ART_NONZERO / MI_ART_STUCK / MI_MAX_PIVOTS, MI_EXACT_OVERFLOW for a member that needs more than 128 bits,
+ * MI_UNSUPPORTED for one whose start is not unit basis columns over a zero objective entry, MI_RUNNING for
+ * one a cancel left unfinished.  One member's outcome never changes another's; the calls themselves return
+ * MI_OK, MI_CANCELLED or an error.
+ * Width: every member starts at 64 bits when its start state fits (min_bits as for mi355x_xtab_create); a
+ * member that overflows 64 bits starts again from its own start state at 128 bits, both phases of a
+ * two-phase job, and replays up to the same cumulative pivot count beside the other restarted members.
+ * Results never depend on the width.
+ * A shape whose pivot-row and entering-column snapshots ((rows + cols) values of 128 bits) do not fit the
+ * LDS a workgroup may have is declined by create with MI_UNSUPPORTED.  (MI355X_XBATCH_WORKGROUP and
+ * MI355X_XBATCH_TRACE_CAP, above: the workgroup's threads and the pivots a member's trace buffers hold.) */
+/* num / den / basis: the members back to back, each as for mi355x_xtab_create. */
+int  mi355x_xbatch_create(mi355x_xbatch **out, int64_t n_lps, int64_t rows, int64_t cols,
+                          const int64_t *num, const int64_t *den, const int64_t *basis,
+                          int device, int min_bits);
+/* Single phase (src/simplex.lisp:453-461): at most max_pivots pivots per member by this call (0 = no cap);
+ * a further call carries every unfinished member on exactly where it stopped.  n_pivots (n_lps entries, may
+ * be NULL): pivots made by this call. */
+int  mi355x_xbatch_solve(mi355x_xbatch *b, int is_max, int64_t max_pivots,
+                         int32_t *status, int64_t *n_pivots);
+/* Two-phase (src/simplex.lisp:402-452), member q of `art` with member q of `main_b`: max_pivots caps both
+ * phases of a member together, the drive-out pivots counted in phase 1 (they are not in the trace).  The
+ * drive-out pivots of a member are made in one step, as by mi355x_xtab_solve_two_phase: the call that ends
+ * a member's phase 1 may exceed max_pivots by its drive-outs (phase 2 then waits for the next call);
+ * n_pivots holds 2 values per member (phase 1, phase 2), the pivots made by this call. */
+int  mi355x_xbatch_solve_two_phase(mi355x_xbatch *art, mi355x_xbatch *main_b, int main_is_max,
+                                   int64_t max_pivots, int32_t *status, int64_t *n_pivots);
+/* member lp_index as mi355x_xtab_download returns one tableau */
+int  mi355x_xbatch_download(mi355x_xbatch *b, int64_t lp_index, int64_t *num_lo_hi,
+                            int64_t *den_lo_hi, int64_t *basis);
+/* member lp_index's pivots as mi355x_xtab_trace: the buffers hold the first MI355X_XBATCH_TRACE_CAP, *n = all */
+int  mi355x_xbatch_trace(mi355x_xbatch *b, int64_t lp_index, int64_t *entering_cols,
+                         int64_t *pivot_rows, int64_t cap, int64_t *n);
+/* the width member lp_index uses: 64 or 128 */
+int  mi355x_xbatch_bits(const mi355x_xbatch *b, int64_t lp_index, int *bits);
+/* any thread: the call running on the batch returns MI_CANCELLED after its current launches (whole pivots) */
+int  mi355x_xbatch_cancel(mi355x_xbatch *b);
+void mi355x_xbatch_destroy(mi355x_xbatch *b);
 /* Branch-and-bound (simplex-solver with integer variables, src/simplex.lisp:462-542) as a resumable job.
  * Opt-in: every other entry point still declines integer problems with MI_UNSUPPORTED.  The search is the
  * reference's node for node -- a depth-first walk over an explicit stack of entries, each node the problem

@@ -80,13 +80,14 @@ void x_free_width(mi355x_xtab *t)
 
 // The start state at `bits`: D0 = prod L_i (the objective row's LCM folded into the first constraint
 // row's), T0 = D0 * t0.  MI_OK, or kXOverflow when it does not fit the width.
-int x_start_state(const mi355x_xtab *t, int bits, std::vector<i128_t> &T0, i128_t *D0)
+int x_start_state(int64_t R, int64_t C, const int64_t *num, const int64_t *den, int bits, std::vector<i128_t> &T0,
+                  i128_t *D0)
 {
-    const int64_t R = t->rows, C = t->cols, m = R - 1;
+    const int64_t m = R - 1;
     std::vector<i128_t> L(R, 1);
     for (int64_t i = 0; i < R; ++i)
         for (int64_t j = 0; j < C; ++j)
-            if (!x_lcm(L[i], t->den[i * C + j], &L[i])) return kXOverflow;
+            if (!x_lcm(L[i], den[i * C + j], &L[i])) return kXOverflow;
     i128_t D = 1;
     if (m > 0 && !x_mul(L[0], L[m], &L[0])) return kXOverflow;
     if (m == 0) D = L[0];
@@ -96,11 +97,40 @@ int x_start_state(const mi355x_xtab *t, int bits, std::vector<i128_t> &T0, i128_
     T0.assign((size_t)(R * C), 0);
     for (int64_t k = 0; k < R * C; ++k) {
         i128_t x;
-        if (!x_mul(D / t->den[k], t->num[k], &x) || !x_fits(x, bits)) return kXOverflow;
+        if (!x_mul(D / den[k], num[k], &x) || !x_fits(x, bits)) return kXOverflow;
         T0[k] = x;
     }
     *D0 = D;
     return MI_OK;
+}
+
+// the start the fraction-free state assumes: every basis column is an exact unit column, the
+// objective row zero on it
+bool x_start_ok(int64_t rows, int64_t cols, const int64_t *num, const int64_t *den, const int64_t *basis)
+{
+    const int64_t m = rows - 1;
+    for (int64_t i = 0; i < m; ++i) {
+        const int64_t b = basis[i];
+        if (b < 0 || b >= cols - 1) return false;
+        for (int64_t r = 0; r <= m; ++r)
+            if (num[r * cols + b] != (r == i ? den[r * cols + b] : 0)) return false;
+    }
+    return true;
+}
+
+// multipliers of the hand-over's re-elimination from the main tableau's original objective row cn / cd
+// (Cm entries): L_c (the LCM of its denominators) and cl_j = L_c * c_j; w_i of basic column b is cl[b].
+// false on overflow of 128 bits.
+bool x_objective_multipliers(int64_t Cm, const int64_t *cn, const int64_t *cd, i128_t *lc, std::vector<i128_t> &cl)
+{
+    i128_t l = 1;
+    for (int64_t j = 0; j < Cm; ++j)
+        if (!x_lcm(l, cd[j], &l)) return false;
+    cl.assign((size_t)Cm, 0);
+    for (int64_t j = 0; j < Cm; ++j)
+        if (!x_mul(l / cd[j], cn[j], &cl[j])) return false;
+    *lc = l;
+    return true;
 }
 
 // (re)load the start state at `bits`: device buffers of that width, T0, basis, a fresh control block
@@ -108,7 +138,7 @@ int x_reset(mi355x_xtab *t, int bits)
 {
     std::vector<i128_t> T0;
     i128_t D0 = 0;
-    if (x_start_state(t, bits, T0, &D0) != MI_OK) return kXOverflow;
+    if (x_start_state(t->rows, t->cols, t->num.data(), t->den.data(), bits, T0, &D0) != MI_OK) return kXOverflow;
     HIP_TRY(hipSetDevice(t->device));
     HIP_TRY(hipStreamSynchronize(t->stream));
     const size_t w = bits / 8, R = (size_t)t->rows, C = (size_t)t->cols;
@@ -203,15 +233,12 @@ int x_handover(mi355x_xtab *a, mi355x_xtab *mt)
     // multipliers of the re-elimination: L_c (LCM of the original objective row's denominators),
     // w_i = L_c * c[b_i], cl_j = L_c * c_j
     const int64_t Cm = mt->cols;
-    const int64_t *cn = &mt->num[m * Cm], *cd = &mt->den[m * Cm];
     i128_t lc = 1;
-    for (int64_t j = 0; j < Cm; ++j)
-        if (!x_lcm(lc, cd[j], &lc)) return kXOverflow;
+    std::vector<i128_t> cl;
+    if (!x_objective_multipliers(Cm, &mt->num[m * Cm], &mt->den[m * Cm], &lc, cl)) return kXOverflow;
     std::vector<i128_t> mult((size_t)(m + Cm));
-    for (int64_t i = 0; i < m; ++i)
-        if (!x_mul(lc / cd[basis[i]], cn[basis[i]], &mult[i])) return kXOverflow;
-    for (int64_t j = 0; j < Cm; ++j)
-        if (!x_mul(lc / cd[j], cn[j], &mult[m + j])) return kXOverflow;
+    for (int64_t i = 0; i < m; ++i) mult[i] = cl[basis[i]];
+    for (int64_t j = 0; j < Cm; ++j) mult[m + j] = cl[j];
     if (!x_fits(lc, mt->bits)) return kXOverflow;
     for (auto x : mult)
         if (!x_fits(x, mt->bits)) return kXOverflow;
@@ -287,16 +314,8 @@ int mi355x_xtab_create(mi355x_xtab **out, int64_t rows, int64_t cols, const int6
     t->num.assign(num, num + rows * cols);
     t->den.assign(den, den + rows * cols);
     t->basis0.assign(basis ? basis : num, basis ? basis + (rows - 1) : num);
-    // the start the fraction-free state assumes: every basis column is an exact unit column, the
-    // objective row zero on it
     const int64_t m = rows - 1;
-    bool ok = true;
-    for (int64_t i = 0; i < m && ok; ++i) {
-        const int64_t b = t->basis0[i];
-        if (b < 0 || b >= cols - 1) { ok = false; break; }
-        for (int64_t r = 0; r <= m && ok; ++r) ok = t->num[r * cols + b] == (r == i ? t->den[r * cols + b] : 0);
-    }
-    t->start_ok = ok;
+    t->start_ok = x_start_ok(rows, cols, t->num.data(), t->den.data(), t->basis0.data());
     auto undo = [&](int code) { mi355x_xtab_destroy(t); return code; };
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess)
         return undo(fail(MI_HIP_ERROR, "stream creation failed"));

@@ -195,6 +195,7 @@ struct mi355x_multibatch {
 #include "capi_batch.inc"      // mi355x_batch_*, mi355x_multibatch_*
 #include "capi_bb.inc"         // branch-and-bound node batches assembled on the devices (internal)
 #include "capi_exact.inc"      // mi355x_xtab_*: exact rational solves on fraction-free integer tableaux
+#include "capi_exact_batch.inc"  // mi355x_xbatch_*: batches of exact LPs, one workgroup per member
 #include "capi_shard.inc"      // mi355x_shard_*
 #include "capi_colpart.inc"    // mi355x_colpart_*, mi355x_rccl_unique_id
 #include "capi_tune.inc"       // mi355x_tune_*, mi355x_debug_*

@@ -367,6 +367,36 @@ void launch_x_update(const XView &v, hipStream_t s);
 // main[r][j] = lc * art[r][src(j)] (r < m); main[m][j] = D_art * cl[j] - sum_r w[r] * art[r][src(j)];
 // main D = lc * D_art.  w (m) and cl (main cols) hold values of the handles' width.
 void launch_x_handover(const XView &art, const XView &mt, const void *w, const void *cl, __int128 lc, hipStream_t s);
+// Batches of exact tableaux of one shape, one workgroup per member (kernels_exact_batch.inc,
+// capi_exact_batch.inc).  One XbView per width of a handle: member q's tableau at T + q * rows * cols,
+// its basis at basis + q * (rows - 1), its trace at trace_* + q * trace_cap, its hand-over multipliers
+// (main batches) at aux + q * (cols + 1).  A workgroup whose member is not kRunning does nothing.
+constexpr int32_t kXbIdle = 112;       // a slot no member runs in (another width, declined, not yet handed over)
+constexpr size_t  kXbSnapshotLimit = 48 * 1024;   // LDS bytes of the two snapshots at 128 bits a shape may need
+struct XbCtl {
+    int32_t  status;      // kRunning, kXbIdle, or MI_OPTIMAL / MI_UNBOUNDED / MI_MAX_PIVOTS / kXOverflow / kXInexact
+    int32_t  tp;          // artificial member: 0 phase 1, 1 handed over (phase 2 on the main member), 2 ended between
+    int32_t  tp_status;   // tp == 2: MI_INFEASIBLE / MI_ART_NONZERO / MI_ART_STUCK
+    int32_t  pad_;
+    int64_t  n_pivots;    // pivots chosen by k_xb_solve since the member's start (cumulative)
+    int64_t  cap_at;      // k_xb_solve stops with MI_MAX_PIVOTS once n_pivots reaches it (0: no cap); on an
+                          // artificial member of a two-phase job: the target of both phases and the drive-outs
+    int64_t  trace_n;     // pivots recorded (the member's trace buffers hold the first trace_cap)
+    int64_t  driveouts;   // forced pivots of k_xb_between
+    __int128 D;           // the common denominator, > 0
+};
+struct XbView {
+    void       *T;
+    int64_t    *basis;
+    XbCtl      *ctl;
+    int64_t    *trace_ec, *trace_cr;
+    const void *aux;
+    int64_t     n, rows, cols, trace_cap;
+    int         bits;     // 64 or 128
+};
+// at most launch_cap pivots per member (a bounded launch: mi355x_xbatch_cancel)
+void launch_xb_solve(const XbView &v, int is_max, int64_t launch_cap, hipStream_t s);
+void launch_xb_between(const XbView &art, const XbView &mt, hipStream_t s);
 #ifdef MI355X_TEST_HOOKS
 // test build: one arithmetic primitive of kernels_exact.inc applied element-wise (k_x_arith_probe; the
 // opcodes and the limb layout are mi355x_test_xarith's, include/mi355x_simplex_tune.h).  Device pointers.

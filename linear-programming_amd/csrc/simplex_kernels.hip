@@ -70,6 +70,7 @@
 //     kernels_layout.inc          dense <-> compact, control block, two-phase hand-over, synthetic LPs
 //     kernels_bb.inc              branch-and-bound node tableaux assembled in HBM (k_bb_assemble)
 //     kernels_exact.inc           exact rational solves on fraction-free integer tableaux (k_x_*)
+//     kernels_exact_batch.inc     batches of exact LPs, one workgroup per LP (k_xb_solve, k_xb_between)
 //     kernels_launch.inc          host-side launchers, tuning state
 #include "simplex_kernels.h"
 #include <type_traits>
@@ -88,6 +89,7 @@ namespace mi355x {
 #include "kernels_layout.inc"
 #include "kernels_bb.inc"
 #include "kernels_exact.inc"
+#include "kernels_exact_batch.inc"
 #include "kernels_launch.inc"
 
 }  // namespace mi355x

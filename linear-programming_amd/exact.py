@@ -8,6 +8,11 @@ integer tableau T with one common denominator D (kernels_exact.inc); every pivot
 hand-over and the read-back are exact, so the pivot sequence, the basis and every entry are the
 reference's own.  Values are 64-bit integers, or 128-bit ones once 64 bits overflow; a problem
 whose entries outgrow 128 bits is declined with unsupported-constraint-error.
+
+A list of problems (``mi355x_solve_problems(problems, exact=True)``) is grouped by tableau shape and
+sense; a group of two or more is one batch of exact tableaux (mi355x_xbatch_*, one workgroup per
+member: kernels_exact_batch.inc), and every member comes back as the solved ExactTableau the
+one-problem route returns.
 """
 import ctypes
 from fractions import Fraction
@@ -42,6 +47,17 @@ def _int128(lo, hi):
     return (int(hi) << 64) | (int(lo) & 0xFFFFFFFFFFFFFFFF)
 
 
+def _num_den(matrix):
+    """An object matrix of Fractions as the int64 numerators and denominators that cross the boundary."""
+    flat = list(matrix.flat)
+    for x in flat:
+        if abs(x.numerator) > _I64_MAX or x.denominator > _I64_MAX:
+            raise _declined(("coefficient", str(x)))
+    num = np.array([x.numerator for x in flat], dtype=np.int64).reshape(matrix.shape)
+    den = np.array([x.denominator for x in flat], dtype=np.int64).reshape(matrix.shape)
+    return num, den
+
+
 class ExactTableau:
     """The `tableau` struct (src/simplex.lisp:48-58) with rational entries, behind an exact device
     handle.  `.matrix` is an object array of Fractions (downloaded T / D), `.basis_columns` an int64
@@ -60,8 +76,9 @@ class ExactTableau:
         self.n_pivots = 0
         self.phase1 = None                 # the artificial tableau of a two-phase solve
         self._handle = None
+        self._batch = None                 # (XBatch, member index): a member solved in a batch
         M = np.empty((self.constraint_count + 1, self.var_count + 1), dtype=object)
-        M[:, :] = [[Fraction(x) for x in row] for row in matrix]
+        M[:, :] = [[x if type(x) is Fraction else Fraction(x) for x in row] for row in matrix]
         self._matrix = M
         self._basis = np.ascontiguousarray(basis_columns, dtype=np.int64)
         self._stale = False
@@ -69,12 +86,7 @@ class ExactTableau:
     @property
     def _h(self):
         if self._handle is None:
-            num = np.empty(self._matrix.shape, dtype=np.int64)
-            den = np.empty(self._matrix.shape, dtype=np.int64)
-            for (i, j), x in np.ndenumerate(self._matrix):
-                if abs(x.numerator) > _I64_MAX or x.denominator > _I64_MAX:
-                    raise _declined(("coefficient", str(x)))
-                num[i, j], den[i, j] = x.numerator, x.denominator
+            num, den = _num_den(self._matrix)
             h = ctypes.c_void_p()
             check(capi.lib().mi355x_xtab_create(ctypes.byref(h), num.shape[0], num.shape[1], _ptr(num), _ptr(den),
                                                 _ptr(self._basis) if self._basis.size else None, self.device,
@@ -91,8 +103,13 @@ class ExactTableau:
         T = np.empty(R * C * 2, dtype=np.int64)
         D = np.empty(2, dtype=np.int64)
         b = np.empty(max(R - 1, 0), dtype=np.int64)
-        check(capi.lib().mi355x_xtab_download(self._h, _ptr(T), _ptr(D), _ptr(b) if b.size else None),
-              "mi355x_xtab_download")
+        if self._batch:
+            xb, q = self._batch
+            check(capi.lib().mi355x_xbatch_download(xb.handle, q, _ptr(T), _ptr(D), _ptr(b) if b.size else None),
+                  "mi355x_xbatch_download")
+        else:
+            check(capi.lib().mi355x_xtab_download(self._h, _ptr(T), _ptr(D), _ptr(b) if b.size else None),
+                  "mi355x_xtab_download")
         vals = [_int128(T[2 * k], T[2 * k + 1]) for k in range(R * C)]
         return np.array(vals, dtype=object).reshape(R, C), _int128(D[0], D[1]), b
 
@@ -128,15 +145,25 @@ class ExactTableau:
     def bits(self):
         """The width the device uses for this tableau: 64 or 128."""
         b = ctypes.c_int(0)
+        if self._batch:
+            check(capi.lib().mi355x_xbatch_bits(self._batch[0].handle, self._batch[1], ctypes.byref(b)), "mi355x_xbatch_bits")
+            return int(b.value)
         check(capi.lib().mi355x_xtab_bits(self._h, ctypes.byref(b)), "mi355x_xtab_bits")
         return int(b.value)
 
     def pivot_trace(self, cap=1 << 18):
-        """(entering column, row) of every pivot the solve loops made on this tableau."""
+        """(entering column, row) of every pivot the solve loops made on this tableau (a member solved in
+        a batch: the first capi.XBATCH_TRACE_CAP of them)."""
         n = ctypes.c_int64(0)
+        if self._batch:
+            cap = min(cap, capi.XBATCH_TRACE_CAP)
         ec = np.empty(cap, dtype=np.int64)
         cr = np.empty(cap, dtype=np.int64)
-        check(capi.lib().mi355x_xtab_trace(self._h, _ptr(ec), _ptr(cr), cap, ctypes.byref(n)), "mi355x_xtab_trace")
+        if self._batch:
+            check(capi.lib().mi355x_xbatch_trace(self._batch[0].handle, self._batch[1], _ptr(ec), _ptr(cr), cap,
+                                                 ctypes.byref(n)), "mi355x_xbatch_trace")
+        else:
+            check(capi.lib().mi355x_xtab_trace(self._h, _ptr(ec), _ptr(cr), cap, ctypes.byref(n)), "mi355x_xtab_trace")
         k = min(n.value, cap)
         return np.stack([ec[:k], cr[:k]], axis=1)
 
@@ -214,3 +241,183 @@ def solve_exact(problem, device=0, max_pivots=0, min_bits=0, chunk=None):
     from .simplex import build_tableau
     tabs = build_tableau(problem, problem, device=device, exact=True, min_bits=min_bits)
     return n_solve_exact(tabs, max_pivots=max_pivots, chunk=chunk)
+
+
+# ------------------------------------------------------------------ many problems at once
+class XBatch:
+    """A mi355x_xbatch handle: the start tableaux of `tabs` (ExactTableaus of one shape) back to back.
+    Members solved in it keep it alive; the last one to go destroys it."""
+
+    def __init__(self, tabs, device=0, min_bits=0):
+        self.handle = None
+        self.n_lps = len(tabs)
+        self.rows, self.cols = tabs[0]._matrix.shape
+        pairs = [_num_den(t._matrix) for t in tabs]
+        num = np.ascontiguousarray(np.stack([p[0] for p in pairs]))
+        den = np.ascontiguousarray(np.stack([p[1] for p in pairs]))
+        basis = np.ascontiguousarray(np.stack([t._basis for t in tabs]), dtype=np.int64)
+        h = ctypes.c_void_p()
+        rc = capi.lib().mi355x_xbatch_create(ctypes.byref(h), self.n_lps, self.rows, self.cols, _ptr(num), _ptr(den),
+                                             _ptr(basis) if basis.size else None, device, int(min_bits))
+        if rc == capi.MI_UNSUPPORTED:
+            raise _declined(("batch", "shape", self.rows, self.cols))
+        capi.check(rc, "mi355x_xbatch_create")
+        self.handle = h
+
+    def solve(self, is_max, max_pivots=0):
+        """mi355x_xbatch_solve: (call status, per-member statuses, pivots of this call)."""
+        st = np.empty(self.n_lps, dtype=np.int32)
+        npv = np.zeros(self.n_lps, dtype=np.int64)
+        rc = capi.check(capi.lib().mi355x_xbatch_solve(self.handle, int(is_max), int(max_pivots), _ptr(st), _ptr(npv)),
+                        "mi355x_xbatch_solve")
+        return rc, st, npv
+
+    def solve_two_phase(self, main, main_is_max, max_pivots=0):
+        """mi355x_xbatch_solve_two_phase with self as the artificial batch: (call status, statuses,
+        pivots of this call as an (n, 2) array)."""
+        st = np.empty(self.n_lps, dtype=np.int32)
+        npv = np.zeros((self.n_lps, 2), dtype=np.int64)
+        rc = capi.check(capi.lib().mi355x_xbatch_solve_two_phase(self.handle, main.handle, int(main_is_max),
+                                                                 int(max_pivots), _ptr(st), _ptr(npv)),
+                        "mi355x_xbatch_solve_two_phase")
+        return rc, st, npv
+
+    def cancel(self):
+        capi.check(capi.lib().mi355x_xbatch_cancel(self.handle), "mi355x_xbatch_cancel")
+
+    def close(self):
+        h, self.handle = self.handle, None
+        if h:
+            capi.lib().mi355x_xbatch_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def group_exact_problems(problems, device=0, min_bits=0):
+    """The grouping of mi355x_solve_problems(exact=True), host only.  Returns (alone, groups, groups2,
+    failed): `alone` the indices that go through mi355x_simplex_solver one by one (integer members,
+    members with a float anywhere, members alone in their group), `groups` {(shape, is_max): [(k, tab)]}
+    the single-phase groups of two or more, `groups2` {(art shape, main shape, is_max): [(k, art, main)]}
+    the two-phase ones, `failed` {k: the SolverError build-tableau raised}."""
+    from .conditions import SolverError
+    from .simplex import build_tableau
+    alone, groups, groups2, failed = [], {}, {}, {}
+    for k, p in enumerate(problems):
+        if p.integer_vars or not rational_problem(p):
+            alone.append(k)
+            continue
+        try:
+            tabs = build_tableau(p, p, device=device, exact=True, min_bits=min_bits)
+        except SolverError as e:                       # e.g. the unbounded no-constraint special case
+            failed[k] = e
+            continue
+        if isinstance(tabs, list):                     # two-phase: (art main), src/simplex.lisp:326-328
+            art, main = tabs
+            groups2.setdefault((art._matrix.shape, main._matrix.shape, main.is_max), []).append((k, art, main))
+        else:
+            groups.setdefault((tabs._matrix.shape, tabs.is_max), []).append((k, tabs))
+    for g in (groups, groups2):
+        for key in [key for key, members in g.items() if len(members) == 1]:
+            alone.append(g.pop(key)[0][0])
+    return sorted(alone), groups, groups2, failed
+
+
+def _member_error(st):
+    """The exception of a member's final status (None: it has a solution)."""
+    from .conditions import SolverError
+    from .simplex import _raise_for
+    try:
+        check(int(st), "mi355x_xbatch_solve")
+        _raise_for(int(st))
+    except SolverError as e:
+        return e
+    return None
+
+
+def solve_exact_batch(members, is_max, device=0, max_pivots=0, min_bits=0, chunk=None):
+    """One group of mi355x_solve_problems(exact=True) in bounded calls (the glue's solve-in-chunks):
+    members are ExactTableaus (single phase) or (art, main) pairs of one shape.  Returns per member the
+    solved (main) tableau or the exception of its outcome; raises the declined condition when the shape
+    does not fit a batch."""
+    from .simplex import chunk_pivots
+    two = isinstance(members[0], (list, tuple))
+    first = [m[0] for m in members] if two else list(members)
+    xa = XBatch(first, device=device, min_bits=min_bits)
+    try:
+        xm = XBatch([m[1] for m in members], device=device, min_bits=min_bits) if two else None
+    except Exception:
+        xa.close()                                     # (its device memory goes at once)
+        raise
+    chunk = chunk or chunk_pivots(xa.rows, xa.cols)
+    total = np.zeros((len(members), 2) if two else len(members), dtype=np.int64)
+    done = 0
+    while True:
+        cap = min(chunk, max_pivots - done) if max_pivots > 0 else chunk
+        rc, st, npv = xa.solve_two_phase(xm, is_max, cap) if two else xa.solve(is_max, cap)
+        total += npv
+        done += cap
+        if rc == capi.MI_CANCELLED or (max_pivots > 0 and done >= max_pivots) or not (st == capi.MI_MAX_PIVOTS).any():
+            break
+    out = []
+    for q, m in enumerate(members):
+        e = _member_error(capi.MI_CANCELLED if st[q] == capi.MI_RUNNING else st[q])
+        if e is not None:
+            out.append(e)
+            continue
+        t = m[1] if two else m
+        t._batch, t._stale = (xm if two else xa, q), True
+        if two:
+            m[0]._batch, m[0]._stale = (xa, q), True
+            t.phase1 = m[0]
+            t.n_pivots = (int(total[q, 0]), int(total[q, 1]))
+        else:
+            t.n_pivots = int(total[q])
+        out.append(t)
+    return out
+
+
+def solve_problems_exact(problems, fp_tolerance=1024, device=0, max_pivots=0, errorp=True, native=False, min_bits=0,
+                         chunk=None):
+    """mi355x_solve_problems(exact=True): see there."""
+    from .conditions import SolverError
+    from .simplex import mi355x_simplex_solver
+    results = [None] * len(problems)
+    alone, groups, groups2, failed = group_exact_problems(problems, device=device, min_bits=min_bits)
+
+    def results_of(ks, rs):
+        for k, r in zip(ks, rs):
+            results[k] = r
+
+    def one_by_one(ks):
+        for k in ks:
+            try:
+                results[k] = mi355x_simplex_solver(problems[k], fp_tolerance=fp_tolerance, device=device,
+                                                   max_pivots=max_pivots, native=native, exact=True,
+                                                   exact_bits=min_bits, chunk=chunk)
+            except SolverError as e:
+                results[k] = e
+
+    for k, e in failed.items():
+        results[k] = e
+    one_by_one(alone)
+    for (_, is_max), members in groups.items():
+        try:
+            results_of([k for k, _ in members],
+                       solve_exact_batch([t for _, t in members], is_max, device, max_pivots, min_bits, chunk))
+        except UnsupportedConstraintError:              # a shape the batch declines
+            one_by_one([k for k, _ in members])
+    for (_, _, is_max), members in groups2.items():
+        try:
+            results_of([k for k, _, _ in members],
+                       solve_exact_batch([(a, t) for _, a, t in members], is_max, device, max_pivots, min_bits, chunk))
+        except UnsupportedConstraintError:
+            one_by_one([k for k, _, _ in members])
+    if errorp:
+        for r in results:
+            if isinstance(r, Exception):
+                raise r
+    return results

@@ -80,6 +80,7 @@
 (defconstant +mi-nonfinite+ 6)   ; column shards only: the tableau overflowed (see solve-column-partitioned)
 (defconstant +mi-cancelled+ 7)   ; mi355x_*_cancel from another thread (never from this single-threaded glue)
 (defconstant +mi-running+ 100)
+(defconstant +mi-unsupported+ -6)      ; a member of an exact batch whose start is not unit basis columns; a shape the batch declines
 (defconstant +mi-exact-overflow+ -7)   ; an exact tableau outgrew 128 bits   ; per-LP status of a batch member a capped / cancelled solve left unfinished
 
 (cffi:defcfun ("mi355x_device_count" device-count) :int)
@@ -190,6 +191,16 @@
 (cffi:defcfun ("mi355x_xtab_download" %xtab-download) :int
   (tab :pointer) (num-lo-hi :pointer) (den-lo-hi :pointer) (basis :pointer))
 (cffi:defcfun ("mi355x_xtab_destroy" %xtab-destroy) :void (tab :pointer))
+(cffi:defcfun ("mi355x_xbatch_create" %xbatch-create) :int
+  (out :pointer) (n-lps :int64) (rows :int64) (cols :int64) (num :pointer) (den :pointer) (basis :pointer)
+  (device :int) (min-bits :int))
+(cffi:defcfun ("mi355x_xbatch_solve" %xbatch-solve) :int
+  (batch :pointer) (is-max :int) (max-pivots :int64) (status :pointer) (n-pivots :pointer))
+(cffi:defcfun ("mi355x_xbatch_solve_two_phase" %xbatch-solve-two-phase) :int
+  (art :pointer) (main :pointer) (main-is-max :int) (max-pivots :int64) (status :pointer) (n-pivots :pointer))
+(cffi:defcfun ("mi355x_xbatch_download" %xbatch-download) :int
+  (batch :pointer) (lp-index :int64) (num-lo-hi :pointer) (den-lo-hi :pointer) (basis :pointer))
+(cffi:defcfun ("mi355x_xbatch_destroy" %xbatch-destroy) :void (batch :pointer))
 
 (define-condition mi355x-error (solver-error)
   ((code :initarg :code :reader mi355x-error-code)
@@ -535,8 +546,9 @@ Leaves the total in N-PIVOTS[0] and returns the last status."
         (check status)
         (cffi:mem-ref out :pointer)))))
 
-(defun download-exact-tableau (handle tableau)
-  "(/ T D) into the tableau's matrix, T and D rebuilt from their two 64-bit limbs; the basis."
+(defun download-exact-tableau (handle tableau &optional member)
+  "(/ T D) into the tableau's matrix, T and D rebuilt from their two 64-bit limbs; the basis.
+MEMBER: HANDLE is a batch (mi355x_xbatch_*) and the tableau its member of that index."
   (let* ((matrix (tableau-matrix tableau))
          (rows (array-dimension matrix 0))
          (cols (array-dimension matrix 1)))
@@ -544,7 +556,9 @@ Leaves the total in N-PIVOTS[0] and returns the last status."
              (+ (logand (cffi:mem-aref ptr :int64 (* 2 k)) (1- (ash 1 64)))
                 (ash (cffi:mem-aref ptr :int64 (1+ (* 2 k))) 64))))
       (cffi:with-foreign-objects ((num :int64 (* 2 rows cols)) (den :int64 2) (basis :int64 (max 1 (1- rows))))
-        (check (%xtab-download handle num den basis))
+        (check (if member
+                   (%xbatch-download handle member num den basis)
+                   (%xtab-download handle num den basis)))
         (let ((d (limbs den 0)))
           (dotimes (r rows)
             (dotimes (c cols)
@@ -588,6 +602,134 @@ Leaves the total in N-PIVOTS[0] and returns the last status."
                    (signal-outcome status)
                    (download-exact-tableau handle tableaus))
               (%xtab-destroy handle)))))))
+
+;;; Many exact problems of one shape: one batch of exact tableaux (mi355x_xbatch_*), one workgroup per
+;;; member, everything between the phases on the device.  Statuses are per member; a member that needs
+;;; more than 128 bits or whose start the library declines gets its condition object, the others
+;;; their solved tableau.
+(defun upload-exact-batch (tableaus device)
+  "mi355x_xbatch_create from same-shape tableaus' rational matrices, member after member.  NIL when
+the batch cannot take them (an entry beyond (signed-byte 64), a shape whose snapshots do not fit a
+workgroup's LDS): the caller then solves the members one by one."
+  (let* ((n (length tableaus))
+         (matrix (tableau-matrix (first tableaus)))
+         (rows (array-dimension matrix 0))
+         (cols (array-dimension matrix 1))
+         (m (1- rows))
+         (size (* n rows cols)))
+    (when (notevery (lambda (tab)
+                      (let ((mat (tableau-matrix tab)))
+                        (dotimes (k (array-total-size mat) t)
+                          (let ((x (row-major-aref mat k)))
+                            (unless (and (typep (numerator x) '(signed-byte 64))
+                                         (typep (denominator x) '(signed-byte 64)))
+                              (return nil))))))
+                    tableaus)
+      (return-from upload-exact-batch nil))
+    (let ((num (cffi:foreign-alloc :int64 :count size))
+          (den (cffi:foreign-alloc :int64 :count size))
+          (basis (cffi:foreign-alloc :int64 :count (max 1 (* n m)))))
+      (unwind-protect
+           (cffi:with-foreign-object (out :pointer)
+             (loop for tab in tableaus for k from 0
+                   do (let ((mat (tableau-matrix tab))
+                            (base (* k rows cols)))
+                        (dotimes (e (* rows cols))
+                          (let ((x (row-major-aref mat e)))
+                            (setf (cffi:mem-aref num :int64 (+ base e)) (numerator x)
+                                  (cffi:mem-aref den :int64 (+ base e)) (denominator x))))
+                        (dotimes (r m)
+                          (setf (cffi:mem-aref basis :int64 (+ (* k m) r))
+                                (aref (tableau-basis-columns tab) r)))))
+             (let ((status (%xbatch-create out n rows cols num den basis device 0)))
+               (unless (= status +mi-unsupported+)
+                 (check status)
+                 (cffi:mem-ref out :pointer))))
+        (cffi:foreign-free num)
+        (cffi:foreign-free den)
+        (cffi:foreign-free basis)))))
+
+(defun exact-member-condition (status)
+  "The condition object of a batch member's final status (NIL: it has a solution)."
+  (cond
+    ((= status +mi-exact-overflow+)
+     (make-condition 'unsupported-constraint-error :constraint '(exact overflow 128) :solver-name "mi355x-simplex"))
+    ((= status +mi-unsupported+)
+     (make-condition 'unsupported-constraint-error :constraint '(exact start) :solver-name "mi355x-simplex"))
+    (t (outcome-condition status))))
+
+(defun solve-exact-batch (members device max-pivots)
+  "MEMBERS: build-tableau's results for all-rational problems of ONE shape and sense -- tableaus, or
+lists (art main).  One batch (or a pair) of exact tableaux solved side by side in bounded foreign
+calls; MAX-PIVOTS (0 = none) caps each member, both phases together.  Returns a list parallel to
+MEMBERS: the solved (main) tableau or a condition object, or :DECLINED when the batch cannot take
+the group."
+  (let* ((two-phase (listp (first members)))
+         (n (length members))
+         (firsts (if two-phase (mapcar #'first members) members))
+         (mains (if two-phase (mapcar #'second members) members))
+         (matrix (tableau-matrix (first firsts)))
+         (is-max (max-problem-p (first mains)))
+         (first-handle (upload-exact-batch firsts device))
+         (main-handle nil))
+    (unless first-handle (return-from solve-exact-batch :declined))
+    (unwind-protect
+         (progn
+           (when two-phase
+             (setf main-handle (upload-exact-batch mains device))
+             (unless main-handle (return-from solve-exact-batch :declined)))
+           (cffi:with-foreign-objects ((status :int32 n) (pivots :int64 (* 2 n)) (budget :int64 1))
+             ;; a call's status for solve-in-chunks: MI_MAX_PIVOTS while some member is left at its cap
+             (solve-in-chunks
+              (lambda (cap)
+                (check (if two-phase
+                           (%xbatch-solve-two-phase first-handle main-handle is-max cap status pivots)
+                           (%xbatch-solve first-handle is-max cap status pivots)))
+                (setf (cffi:mem-aref budget :int64 0) cap)
+                (if (loop for k below n thereis (= (cffi:mem-aref status :int32 k) +mi-max-pivots+))
+                    +mi-max-pivots+
+                    +mi-optimal+))
+              (array-dimension matrix 0) (array-dimension matrix 1) max-pivots budget)
+             (loop for tab in mains for k from 0
+                   collect (or (exact-member-condition (cffi:mem-aref status :int32 k))
+                               (download-exact-tableau (or main-handle first-handle) tab k)))))
+      (when main-handle (%xbatch-destroy main-handle))
+      (%xbatch-destroy first-handle))))
+
+(defun solve-problems-exactly (problems device max-pivots solve-alone)
+  "The :exact t route of MI355X-SOLVE-PROBLEMS: a vector of results.  (funcall SOLVE-ALONE k problem)
+returns member K's result through MI355X-SIMPLEX-SOLVER."
+  (let ((results (make-array (length problems) :initial-element nil))
+        (groups (make-hash-table :test #'equal)))
+    (loop for problem in problems for k from 0
+          do (if (or (problem-integer-vars problem) (not (rational-numbers-p problem)))
+                 (setf (aref results k) (funcall solve-alone k problem))
+                 (let ((tableaus (handler-case (build-tableau problem problem)
+                                   (error (c) c))))
+                   (if (typep tableaus 'condition)
+                       (setf (aref results k) tableaus)
+                       (let* ((two-phase (listp tableaus))
+                              (art (tableau-matrix (if two-phase (first tableaus) tableaus)))
+                              (main (if two-phase (second tableaus) tableaus)))
+                         (push (cons k tableaus)
+                               (gethash (list two-phase (array-dimension art 0) (array-dimension art 1)
+                                              (array-dimension (tableau-matrix main) 1) (max-problem-p main))
+                                        groups)))))))
+    (maphash
+     (lambda (shape members)
+       (declare (ignore shape))
+       (setf members (reverse members))
+       (let ((outcomes (if (rest members)
+                           (solve-exact-batch (mapcar #'cdr members) device max-pivots)
+                           :declined)))
+         (if (eq outcomes :declined)
+             (loop for (k . nil) in members
+                   do (setf (aref results k) (funcall solve-alone k (nth k problems))))
+             (loop for (k . nil) in members
+                   for outcome in outcomes
+                   do (setf (aref results k) outcome)))))
+     groups)
+    results))
 
 ;;; ------------------------------------------------------------------ the native route
 ;;; SURVEY 8(f) rows 2-3: at 8192 x 4096 the reference's build-tableau conses a boxed 4097 x 12289
@@ -1173,7 +1315,7 @@ solution (unbounded-problem-error ...)."
 
 (defun mi355x-solve-problems (problems &rest args
                               &key (fp-tolerance 1024) (device 0) (devices 1) (max-pivots 0)
-                                full-tableau (errorp t) native
+                                full-tableau (errorp t) native exact
                               &allow-other-keys)
   "Solves a LIST of problems and returns the list of their solved tableaus, in order -- what
   (mapcar #'solve-problem problems) returns, with the independent LPs running side by side on
@@ -1195,6 +1337,15 @@ the GPU(s) instead of one after the other.
     problems marshalled as they are, tableaux assembled, grouped and batched in C++): the result list
     then holds MI355X-SOLUTION objects -- the way to solve BASELINE config 4's 1 024 LPs from Lisp
     without 1 024 boxed tableaux.  (:NATIVE NIL, the default, keeps every member a `tableau`.)
+  * :EXACT T (opt-in) solves the members whose numbers are all rational (and that have no integer
+    variables) with the reference's rational semantics (src/utils.lisp:84-124): they are grouped by
+    tableau shape and sense in the same way, and a group of two or more is ONE batch of exact
+    tableaux (mi355x_xbatch_*: one workgroup per member, both phases and everything between them on
+    the device, in bounded foreign calls) -- every member comes back as the solved `tableau` that
+    (mi355x-simplex-solver p :exact t) returns, its matrix holding the exact ratios.  Members alone
+    in their group, shapes the batch declines and members with a float anywhere go through
+    (mi355x-simplex-solver p :exact t) one by one; :MAX-PIVOTS caps each member, both phases
+    together.  :EXACT NIL (default): nothing changes.
   * The other keywords are MI355X-SIMPLEX-SOLVER's, applied to every member: :FP-TOLERANCE (the
     tolerance factor, src/simplex.lisp:506-511), :DEVICE (the GPU of members solved alone), :DEVICES
     (a count or a list of device ids: the sub-batches' GPUs), :MAX-PIVOTS (a cap per member; 0 = none,
@@ -1211,6 +1362,20 @@ Every returned solution object's results are bit-identical to the single-problem
         (let ((failed (find-if (lambda (r) (typep r 'condition)) results)))
           (when failed (error failed))))
       (return-from mi355x-solve-problems results)))
+  (when exact
+    (let ((results (solve-problems-exactly
+                    problems device max-pivots
+                    (lambda (k problem)
+                      (declare (ignore k))
+                      (handler-case (mi355x-simplex-solver problem :fp-tolerance fp-tolerance
+                                                                   :device device :max-pivots max-pivots
+                                                                   :full-tableau full-tableau
+                                                                   :native native :exact t)
+                        (error (c) c))))))
+      (when errorp
+        (let ((failed (find-if (lambda (r) (typep r 'condition)) results)))
+          (when failed (error failed))))
+      (return-from mi355x-solve-problems (coerce results 'list))))
   (let* ((n (length problems))
          (results (make-array n :initial-element nil))
          (groups (make-hash-table :test #'equal))

@@ -662,7 +662,8 @@ def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_p
 simplex_solver = mi355x_simplex_solver
 
 
-def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_pivots=0, errorp=True, native=False):
+def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_pivots=0, errorp=True, native=False,
+                          exact=False, exact_bits=0):
     """The glue's `mi355x-solve-problems`: a LIST of problems -> the list of their solved tableaus,
     what [solve_problem(p) for p in problems] returns, with the independent LPs side by side on the
     GPU(s).  Single-phase problems are grouped by tableau shape and sense; a group of two or more
@@ -674,7 +675,19 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
     mi355x_multibatch_two_phase_handover.  Integer problems (declined) and problems alone in their
     group go through mi355x_simplex_solver one by one; max_pivots caps every phase.  A member without a solution does not abort the
     others: errorp False leaves the exception object in its place, errorp True raises the first
-    one after every member has been attempted."""
+    one after every member has been attempted.
+    exact=True (opt-in): the members whose numbers are all rational (and that have no integer variables)
+    are built with build_tableau(exact=True) and grouped in the same way; a group of two or more is ONE
+    batch of exact tableaux (mi355x_xbatch_create / _solve or _solve_two_phase in bounded chunks, one
+    workgroup per member, exact.py), and every member comes back as the solved ExactTableau that
+    mi355x_simplex_solver(p, exact=True) returns (exact_bits as there).  Members alone in their group,
+    shapes the batch declines and members with a float anywhere go through
+    mi355x_simplex_solver(..., exact=True) one by one; max_pivots caps each member (both phases
+    together, as there).  exact=False: nothing changes."""
+    if exact:
+        from .exact import solve_problems_exact
+        return solve_problems_exact(problems, fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots,
+                                    errorp=errorp, native=native, min_bits=exact_bits)
     from .batch import MultiDeviceBatch
     if native == "many":
         # the whole list behind ONE job of the library (mi355x_simplex_solver_many_*): members come
