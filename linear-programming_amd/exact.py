@@ -256,6 +256,21 @@ class XBatch:
         num = np.ascontiguousarray(np.stack([p[0] for p in pairs]))
         den = np.ascontiguousarray(np.stack([p[1] for p in pairs]))
         basis = np.ascontiguousarray(np.stack([t._basis for t in tabs]), dtype=np.int64)
+        self._create(num, den, basis, device, min_bits)
+
+    @classmethod
+    def from_states(cls, num, den, basis, device=0, min_bits=0):
+        """A batch of start states given as arrays: numerators and denominators (n x rows x cols, int64)
+        and the bases (n x (rows - 1))."""
+        xb = cls.__new__(cls)
+        xb.handle = None
+        num = np.ascontiguousarray(num, dtype=np.int64)
+        xb.n_lps, xb.rows, xb.cols = num.shape
+        xb._create(num, np.ascontiguousarray(den, dtype=np.int64), np.ascontiguousarray(basis, dtype=np.int64),
+                   device, min_bits)
+        return xb
+
+    def _create(self, num, den, basis, device, min_bits):
         h = ctypes.c_void_p()
         rc = capi.lib().mi355x_xbatch_create(ctypes.byref(h), self.n_lps, self.rows, self.cols, _ptr(num), _ptr(den),
                                              _ptr(basis) if basis.size else None, device, int(min_bits))

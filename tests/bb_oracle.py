@@ -208,3 +208,293 @@ def random_cases(count=40, max_nodes=80, first_seed=1000):
             out.append((seed, p, res))
         seed += 1
     return out
+
+
+# ---- base problems and node lists for the node-assembly tests (test_bb_host.py, test_gpu_bb_assembly.py) ----
+# Shapes at which k_bb_rows / k_bb_assemble / k_bb_art_objective (linear-programming_amd/csrc/kernels_bb.inc)
+# make more than one trip of their strided loops, and numbers whose sums and differences round.
+_KINDS = [("v1", (2.5, None)), ("v2", (-1.0, 3.25)), ("v3", (None, 4.5)), ("v4", (None, None)), ("v5", (1.0, 2.0))]
+_OFFSET = {"v0": 0.0, "v1": 2.5, "v2": -1.0, "v3": 4.5, "v4": 0.0, "v5": 1.0}      # what a row's rhs is shifted by
+
+
+def _random_nodes(rng, names, depth, count, fractions=(0.0, 0.1, 0.5, 1.0 / 3.0)):
+    """`count` entries of `depth` rows (newest first) on random variables, both senses, bounds around the
+    offsets so that some shifted right-hand sides are negative."""
+    return [tuple((names[int(rng.integers(0, len(names)))], int(rng.integers(0, 2)),
+                   float(rng.integers(-4, 6)) + float(fractions[int(rng.integers(0, len(fractions)))]))
+                  for _ in range(depth)) for _ in range(count)]
+
+
+def tall_base(m, seed):
+    """m sparse rows on six variables of every mapping kind: plain `<=`, `>=`, `=`, and `<=` / `>=` rows
+    whose shifted right-hand side is negative (negated, sense flipped), mixed through the whole range."""
+    rng = np.random.default_rng(seed)
+    names = ["v%d" % i for i in range(6)]
+    cons = []
+    for _ in range(m):
+        k = int(rng.choice(5, p=[0.35, 0.1, 0.4, 0.1, 0.05]))
+        coef = lambda: round(float(rng.uniform(0.1, 3.0)), 3)
+        if k < 3:
+            vs = rng.choice(6, size=int(rng.integers(1, 4)), replace=False)
+            expr = [(names[int(i)], coef()) for i in vs]
+            shift = sum(c * _OFFSET[v] for v, c in expr)
+            cons.append((["<=", ">=", "="][k], expr, max(shift, 0.0) + round(float(rng.uniform(0.5, 9.0)), 2)))
+        else:                                       # 2.5 * coef(v1) >= 5 > rhs: negated
+            expr = [("v1", 2.0 + coef()), (("v0", "v4")[int(rng.integers(0, 2))], coef())]
+            cons.append((["<=", ">="][k - 3], expr, round(float(rng.uniform(0.0, 4.0)), 2)))
+    return lp.Problem(type="max" if seed % 2 else "min", vars=names, integer_vars=list(names),
+                      objective_func=[(v, round(float(rng.uniform(-3.0, 5.0)), 2)) for v in names],
+                      var_bounds=list(_KINDS), constraints=cons)
+
+
+def wide_base(n, n_eq, seed):
+    """n variables (the first six of every mapping kind) under one `<=` row over all of them, a `>=` row, a
+    negated `<=` row and n_eq sparse `=` rows."""
+    rng = np.random.default_rng(seed)
+    names = ["v%d" % i for i in range(n)]
+    cons = [("<=", [(v, float(rng.integers(1, 5))) for v in names], 10.0 * n + 0.5),
+            (">=", [("v0", 1.0), ("v1", 0.7), (names[n - 1], 0.1)], 1.5),
+            ("<=", [("v1", 2.0), (names[n - 2], 1.0 / 3.0)], 0.5)]
+    for _ in range(n_eq):
+        vs = rng.choice(n, size=3, replace=False)
+        cons.append(("=", [(names[int(i)], round(float(rng.uniform(0.1, 3.0)), 3)) for i in vs],
+                     20.0 + round(float(rng.uniform(0.0, 9.0)), 2)))
+    return lp.Problem(type="max", vars=names, integer_vars=names[:8],
+                      objective_func=[(v, float(rng.integers(-3, 5)) + 0.5) for v in names[:64]],
+                      var_bounds=list(_KINDS), constraints=cons)
+
+
+def inexact_base(seed):
+    """Nine dense rows, seven of them artificial, whose columns hold 1e16-scale entries next to 0.1, 0.7 and
+    1/3: the artificial objective row depends on the order of its additions."""
+    rng = np.random.default_rng(seed)
+    names = ["v%d" % i for i in range(6)]
+    small = [0.1, 0.7, 1.0 / 3.0, 1.7, 2.9e-3]
+
+    def coef():
+        x = small[int(rng.integers(0, len(small)))] * float(rng.integers(1, 4))
+        if rng.random() < 0.3:
+            x = float(rng.integers(1, 9)) * 1.1e16
+        return x if rng.random() < 0.6 else -x
+    cons = [(op, [(v, coef()) for v in names], float(rng.integers(1, 9)) * 3.3e16 + 0.1)
+            for op in ("=", ">=", "<=", "=", ">=", "=", "<=", ">=", "=")]
+    return lp.Problem(type="min", vars=names, integer_vars=list(names),
+                      objective_func=[(v, 0.1 * float(rng.integers(1, 9))) for v in names],
+                      var_bounds=list(_KINDS), constraints=cons)
+
+
+_SHIFTED_BOUNDS = [("v1", (0.1, None)), ("v2", (0.3, 7.7)), ("v3", (None, 0.7)), ("v4", (None, None)),
+                   ("v5", (1.0 / 3.0, None))]
+
+
+def shifted_base():
+    """Variables with non-dyadic offsets (v0: none, v1: 0.1, v2: 0.3 and a bound row, v3: upper bound 0.7,
+    v4: free, v5: 1/3) under a few rows with non-dyadic coefficients, one of them negated."""
+    names = ["v%d" % i for i in range(6)]
+    cons = [("<=", [(v, 0.1 * (i + 1)) for i, v in enumerate(names)], 30.7),
+            (">=", [("v0", 1.0), ("v1", 0.7), ("v3", -1.0 / 3.0)], 1.1),
+            ("<=", [("v1", 3.0), ("v5", 1.0)], 0.3),                   # 0.3 - 3 * 0.1 - 1/3 < 0: negated
+            ("=", [("v4", 1.0), ("v5", 0.7), ("v2", -0.1)], 0.9)]
+    return lp.Problem(type="max", vars=names, integer_vars=list(names),
+                      objective_func=[(v, 0.3 * (i + 1)) for i, v in enumerate(names)],
+                      var_bounds=list(_SHIFTED_BOUNDS), constraints=cons)
+
+
+def shifted_nodes():
+    """Depth-3 entries over node rows whose `bound - offset` rounds, is +0.0 (bound = offset: no flip), or
+    starts from a bound of -0.0 -- on a variable of every mapping kind, the free one included --, each in
+    both senses.  -> (entries, the rows they are made of)."""
+    rounds = [("v1", 1.0), ("v5", 2.0), ("v2", 3.0), ("v3", 1.0), ("v1", -0.7), ("v5", 0.1)]
+    equal = [("v1", 0.1), ("v5", 1.0 / 3.0), ("v2", 0.3), ("v3", 0.7), ("v0", 0.0), ("v4", 0.0)]
+    zeros = [("v0", -0.0), ("v1", -0.0), ("v2", -0.0), ("v3", -0.0), ("v4", -0.0), ("v5", -0.0)]
+    rows = [(v, s, b) for v, b in rounds + equal + zeros for s in (0, 1)]
+    order = np.random.default_rng(7).permutation(len(rows)).tolist()
+    rows = [rows[i] for i in order]
+    return [tuple(rows[(i + k) % len(rows)] for k in range(3)) for i in range(len(rows))], rows
+
+
+def deep_base(seed):
+    """Seven variables of every mapping kind, rows of all three senses, two of them negated."""
+    rng = np.random.default_rng(seed)
+    names = ["v%d" % i for i in range(7)]
+    cons = [("<=", [(v, float(rng.integers(1, 5))) for v in names], 30.5),
+            (">=", [("v0", 1.0), ("v1", 2.0), ("v3", -1.0)], 1.5),
+            ("=", [("v4", 1.0), ("v5", 1.5), ("v6", -0.5)], 0.75),
+            ("<=", [("v1", 1.0), ("v2", 1.0)], 0.5),                   # 0.5 - 2.5 + 1 < 0: negated
+            (">=", [("v1", 1.0), ("v6", 0.7)], 0.1),                   # negated too: becomes a `<=` row
+            (">=", [("v6", 1.0), ("v0", 0.5)], 0.0)]
+    return lp.Problem(type="max" if seed % 2 else "min", vars=names, integer_vars=list(names),
+                      objective_func=[(v, float(rng.integers(-3, 5)) + 0.5) for v in names],
+                      var_bounds=list(_KINDS) + [("v6", (-2.5, None))], constraints=cons)
+
+
+ASSEMBLY_CASES = ("tall_300", "tall_1030", "wide_main", "wide_art", "inexact", "shifted", "deep")
+_assembly = {}
+
+
+def assembly_case(name):
+    """(base problem, node entries of one depth) of a named case, made once."""
+    if name not in _assembly:
+        rng = np.random.default_rng(sum(name.encode()))
+        if name == "tall_300":
+            p = tall_base(300, 3)
+            nodes = _random_nodes(rng, p.vars, 2, 4)
+        elif name == "tall_1030":
+            p = tall_base(1030, 4)
+            nodes = _random_nodes(rng, p.vars, 3, 3)
+        elif name == "wide_main":
+            p = wide_base(4200, 2, 5)
+            nodes = _random_nodes(rng, p.vars[:8], 2, 4)
+        elif name == "wide_art":
+            p = wide_base(3800, 300, 6)
+            nodes = _random_nodes(rng, p.vars[:8], 2, 3)
+        elif name == "inexact":
+            p = inexact_base(INEXACT_SEED)
+            nodes = _random_nodes(rng, p.vars, 2, 12)
+        elif name == "shifted":
+            p, nodes = shifted_base(), shifted_nodes()[0]
+        elif name == "deep":
+            p = deep_base(1)
+            nodes = _random_nodes(rng, p.vars, 40, 6)
+        else:
+            raise KeyError(name)
+        _assembly[name] = (p, nodes)
+    return _assembly[name]
+
+
+# chosen on the CPU: the first seeds' sums happen to agree in some order for some node; with this one the
+# decreasing-order and the pairwise sum each differ from the increasing-order one at every node (pinned by
+# tests/test_bb_host.py)
+INEXACT_SEED = 19
+_host_nodes = {}
+
+
+def host_node_tableaux(name):
+    """Per node of the case: (main, main basis, art or None, art basis or None) from the host
+    build-tableau (mi355x_build_tableau) of the node problem; made once, never written to."""
+    if name not in _host_nodes:
+        p, nodes = assembly_case(name)
+        out = []
+        for entry in nodes:
+            tabs = lp.native.NativeProblem(node_problem(p, entry)).build_tableau()
+            (main, mb), art = (tabs[1], tabs[0]) if len(tabs) == 2 else (tabs[0], None)
+            out.append((main, mb, None, None) if art is None else (main, mb, art[0], art[1]))
+        for t in out:
+            for a in t:
+                if a is not None:
+                    a.setflags(write=False)
+        _host_nodes[name] = out
+    return _host_nodes[name]
+
+
+def sum_orders(art, art_basis, num_cols):
+    """The artificial objective row of a host-built artificial tableau recomputed in Python floats three
+    ways over the artificial rows (those whose basic column is an artificial one, >= num_cols - 1):
+    increasing row order from 0.0, decreasing row order from 0.0, and pairwise.  Artificial columns hold 0."""
+    m, nac = art.shape[0] - 1, art.shape[1]
+    rows = [r for r in range(m) if art_basis[r] >= num_cols - 1]
+
+    def pairwise(xs):
+        return xs[0] if len(xs) == 1 else pairwise(xs[:len(xs) // 2]) + pairwise(xs[len(xs) // 2:])
+    inc, dec, pair = [0.0] * nac, [0.0] * nac, [0.0] * nac
+    for c in list(range(num_cols - 1)) + [nac - 1]:
+        xs = [float(art[r, c]) for r in rows]
+        s = 0.0
+        for x in xs:
+            s = s + x
+        inc[c] = s
+        s = 0.0
+        for x in reversed(xs):
+            s = s + x
+        dec[c] = s
+        pair[c] = pairwise(xs)
+    return inc, dec, pair, rows
+
+
+def assert_sum_order_sensitive(name):
+    """The precondition of the artificial-objective check, on the host-built tableaux of the case: at every
+    node at least five artificial rows, the increasing-order sum from 0.0 IS the host's artificial objective
+    row bit for bit, and the decreasing-order sum and the pairwise sum each differ from it in at least one
+    column -- a kernel that summed differently cannot pass."""
+    bits = lambda a: np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+    for hm, hb, ha, hab in host_node_tableaux(name):
+        inc, dec, pair, rows = sum_orders(ha, hab, hm.shape[1])
+        assert len(rows) >= 5
+        assert np.array_equal(bits(inc), bits(ha[-1]))
+        assert (bits(dec) != bits(ha[-1])).any() and (bits(pair) != bits(ha[-1])).any()
+
+
+def restated_node_tableaux(problem, entry):
+    """What the header comment of linear-programming_amd/csrc/kernels_bb.inc lists, restated on plain Python
+    floats and lists without any library code: (main rows, main basis, artificial rows or None, artificial basis or None).
+
+    Columns: one per variable (two for a free one), then one slack column per row that is not `=`, in row
+    order, then the right-hand side.  Rows: the `x <= ub` rows of doubly-bounded variables (the last
+    variable's first), the entry's rows newest first, the problem's rows, the objective row.  A row is
+    shifted by coef * offset per bounded variable (product rounded, then the difference), negated whole when
+    its right-hand side ends up negative (sense flipped; -0.0 is not negative), and then gets slack +1
+    (`<=`, basic) or -1 (`>=`); `>=` and `=` rows are artificial: their main-basis entry is the number of
+    columns.  Artificial columns are dealt in decreasing row order; the artificial objective row is the sum of
+    the artificial rows in increasing row order from 0.0."""
+    bounds = dict(problem.var_bounds)
+    kind, col, off, ncv, pushed = {}, {}, {}, 0, []
+    for v in problem.vars:
+        lb, ub = bounds.get(v, (0.0, None))                      # no entry: the default x >= 0
+        col[v] = ncv
+        if lb is None and ub is None:
+            kind[v], off[v], ncv = "free", 0.0, ncv + 2
+            continue
+        if lb is not None and ub is not None:
+            assert 0.0 <= ub                                     # (no case here has a negative upper bound)
+            pushed.insert(0, ("<=", [(v, 1.0)], ub))
+        kind[v], off[v] = ("upper", ub) if lb is None else ("lower", lb)
+        ncv += 1
+    rows = pushed + [("<=" if s == 0 else ">=", [(v, 1.0)], b) for v, s, b in entry] + list(problem.constraints)
+    m = len(rows)
+    num_cols = ncv + sum(op != "=" for op, _, _ in rows) + 1
+    M, basis, art_rows, slack = [], [], [], ncv
+    for op, expr, rhs in rows:
+        row = [0.0] * num_cols
+        for v, c in expr:
+            c = float(c)
+            if kind[v] == "free":
+                row[col[v]], row[col[v] + 1] = c, -c
+            else:
+                row[col[v]] = c if kind[v] == "lower" else -c
+                rhs = rhs - c * off[v]
+        row[-1] = rhs
+        if rhs < 0.0:
+            row = [-x for x in row]
+            op = {"<=": ">=", ">=": "<=", "=": "="}[op]
+        if op != "=":
+            row[slack] = 1.0 if op == "<=" else -1.0
+        basis.append(slack if op == "<=" else num_cols)
+        if op != "<=":
+            art_rows.append(len(M))
+        slack += op != "="
+        M.append(row)
+    obj = [0.0] * num_cols
+    for v, c in problem.objective_func:
+        c = float(c)
+        if kind[v] == "free":
+            obj[col[v]], obj[col[v] + 1] = -c, c
+        else:
+            obj[col[v]] = -c if kind[v] == "lower" else c
+            obj[-1] = obj[-1] + c * off[v]
+    M.append(obj)
+    if not art_rows:
+        return M, basis, None, None
+    n_art = len(art_rows)
+    A = [row[:-1] + [0.0] * n_art + row[-1:] for row in M[:m]]
+    abasis = list(basis)
+    for k, r in enumerate(reversed(art_rows)):
+        A[r][num_cols - 1 + k] = 1.0
+        abasis[r] = num_cols - 1 + k
+    last = [0.0] * (num_cols + n_art)
+    for c in list(range(num_cols - 1)) + [num_cols + n_art - 1]:
+        s = 0.0
+        for r in art_rows:
+            s = s + A[r][c]
+        last[c] = s
+    A.append(last)
+    return M, basis, A, abasis

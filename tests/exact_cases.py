@@ -220,11 +220,14 @@ class Model:
             self.pivot(e, r)
 
 
-def model_solve(tabs, cls=None, keep=None, phase2_pivots=0):
+def model_solve(tabs, cls=None, keep=None, phase2_pivots=0, total_pivots=0):
     """(status, trace, final model or None, stats) of the fraction-free model (cls: Model or VecModel) on
     rational_ref's build_tableau result (a Tableau or an (art, main) pair).  keep: a dict that receives
     the artificial model ("art") and the trace's length at the end of phase 1 ("n1").  phase2_pivots > 0
-    caps phase 2 of a two-phase solve: status "max_pivots", the main model as it stands."""
+    caps phase 2 of a two-phase solve: status "max_pivots", the main model as it stands; total_pivots > 0
+    caps it at what a call of that many pivots leaves for it after phase 1 and the drive-outs (which must
+    fit the call).  keep also receives "driveout_pivots": per drive-out (column, row, every eligible column
+    -- non-zero and non-basic -- of the row at that moment)."""
     cls = cls or Model
     trace = []
     if not isinstance(tabs, tuple):
@@ -247,9 +250,12 @@ def model_solve(tabs, cls=None, keep=None, phase2_pivots=0):
             row = a.rows()[i]
             if row[a.nv] != 0:
                 return "art_nonzero", trace, None, a.stats
-            j = next((j for j in range(nv) if row[j] != 0 and j not in a.basis), None)
-            if j is None:
+            eligible = [j for j in range(nv) if row[j] != 0 and j not in a.basis]
+            if not eligible:
                 return "art_stuck", trace, None, a.stats
+            j = eligible[0]
+            if keep is not None:
+                keep.setdefault("driveout_pivots", []).append((j, i, eligible))
             a.stats["driveouts"] += 1
             a.pivot(j, i)
     # hand-over: the constraint rows and D times L_c, the objective row D * c - sum c[b_i] T_i
@@ -267,6 +273,9 @@ def model_solve(tabs, cls=None, keep=None, phase2_pivots=0):
     T.append([a.D * cl[k] - sum(w[i] * AT[i][s] for i in range(m) if w[i]) for k, s in enumerate(src)])
     mm = cls.from_state(T, a.D * lc, a.basis, nv, stats=a.stats, stage="handover", extra=[lc] + w + cl)
     mm.stage = "phase2"
+    if total_pivots:
+        phase2_pivots = total_pivots - len(trace) - a.stats["driveouts"]
+        assert phase2_pivots > 0
     st = mm.solve(main_t.is_max, trace, phase2_pivots)
     return st, trace, (mm if st in ("optimal", "max_pivots") else None), mm.stats
 

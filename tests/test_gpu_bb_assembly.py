@@ -79,6 +79,89 @@ def test_device_assembly_is_bit_identical_to_build_tableau(seed):
     assert checked == 7 * 37 + 300
 
 
+def _assemble(npb, nodes):
+    """mi355x_bb_debug_assemble of entries of one depth and one artificial-row count:
+    (main, main bases, art or None, art bases or None, art_cols)."""
+    L = lp.capi.lib()
+    n, depth = len(nodes), len(nodes[0])
+    var = np.array([[npb.index[v] for v, _, _ in e] for e in nodes], dtype=np.int64)
+    sen = np.array([[s for _, s, _ in e] for e in nodes], dtype=np.int32)
+    bnd = np.array([[b for _, _, b in e] for e in nodes], dtype=np.float64)
+    R, C, AC = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    args = [npb._h, n, depth, ptr(var), ptr(sen), ptr(bnd), 0, ctypes.byref(R), ctypes.byref(C), ctypes.byref(AC)]
+    lp.capi.check(L.mi355x_bb_debug_assemble(*args, None, None, None, None), "mi355x_bb_debug_assemble")
+    acols = AC.value
+    M = np.empty((n, R.value, C.value)); MB = np.empty((n, R.value - 1), np.int64)
+    A = np.empty((n, R.value, max(acols, 1))); AB = np.empty((n, R.value - 1), np.int64)
+    lp.capi.check(L.mi355x_bb_debug_assemble(*args, ptr(M), ptr(MB), ptr(A) if acols else None,
+                                             ptr(AB) if acols else None), "mi355x_bb_debug_assemble")
+    return M, MB, (A if acols else None), (AB if acols else None), acols
+
+
+def _check_case(name):
+    """Every node of the case, grouped by artificial-column count, against the host build-tableau: both
+    tableaux and both bases bit for bit.  -> the groups' (main shape, artificial columns)."""
+    p, nodes = B.assembly_case(name)
+    host = B.host_node_tableaux(name)
+    npb = lp.native.NativeProblem(p)
+    groups = {}
+    for q, (hm, hb, ha, hab) in enumerate(host):
+        groups.setdefault(0 if ha is None else ha.shape[1], []).append(q)
+    shapes = []
+    for acols, qs in groups.items():
+        M, MB, A, AB, got_acols = _assemble(npb, [nodes[q] for q in qs])
+        assert got_acols == acols
+        for i, q in enumerate(qs):
+            hm, hb, ha, hab = host[q]
+            assert M[i].shape == hm.shape
+            assert np.array_equal(_bits(M[i]), _bits(hm)), (name, q, np.argwhere(_bits(M[i]) != _bits(hm))[:4])
+            assert np.array_equal(MB[i], hb), (name, q)
+            if ha is not None:
+                assert A[i].shape == ha.shape
+                assert np.array_equal(_bits(A[i]), _bits(ha)), (name, q, np.argwhere(_bits(A[i]) != _bits(ha))[:4])
+                assert np.array_equal(AB[i], hab), (name, q)
+        shapes.append((M.shape[1:], acols))
+    return shapes
+
+
+@pytest.mark.parametrize("name,rows_over", [("tall_300", 256), ("tall_1030", 1024)])
+def test_tall_nodes_past_one_workgroup_and_past_the_row_grid(name, rows_over):
+    """k_bb_rows strides over more than 256 rows and its rank scan crosses the trips; k_bb_assemble's row
+    grid (1024 blocks) wraps.  Artificial and negated rows lie in every range (tests/test_bb_host.py)."""
+    for (rows, cols), acols in _check_case(name):
+        assert rows - 1 > rows_over and acols > cols
+
+
+def test_wide_nodes_past_the_column_grid():
+    """k_bb_assemble's column loop (16 blocks of 256 threads) makes a second trip: over the main tableau's
+    row, and -- main inside one trip whatever the row padding up to 256 -- over the artificial tableau's."""
+    for (rows, cols), acols in _check_case("wide_main"):
+        assert cols > 4096 and acols > cols
+    for (rows, cols), acols in _check_case("wide_art"):
+        assert cols + 256 <= 4096 < acols
+
+
+def test_inexact_artificial_objective_is_summed_in_increasing_row_order():
+    """Non-dyadic entries over many binades: the host's artificial objective row is the increasing-order sum
+    and differs from the decreasing-order and the pairwise sum at every node of the case (checked first)."""
+    B.assert_sum_order_sensitive("inexact")
+    _check_case("inexact")
+
+
+def test_shifted_right_hand_sides_that_round_and_signed_zero_bounds():
+    """bound - offset with non-dyadic offsets, bound = offset (+0.0, no flip) and bounds of -0.0 on every
+    mapping kind (what the rows hold on the host: tests/test_bb_host.py)."""
+    assert len(_check_case("shifted")) >= 3
+
+
+def test_deep_nodes():
+    """Depth 40: variables met several times in both senses, the -0.0 fill of negated base rows over forty
+    inserted slack columns."""
+    for (rows, cols), acols in _check_case("deep"):
+        assert rows == 1 + 2 + 40 + 6
+
+
 def test_debug_assemble_validates_its_arguments():
     L = lp.capi.lib()
     npb = lp.native.NativeProblem(_base(0))

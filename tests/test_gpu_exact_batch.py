@@ -186,13 +186,13 @@ def _one_pivot_per_call(xa, xm, refs):
     return total
 
 
-def _check_two_phase_batch(xa, xm, refs, total):
+def _check_two_phase_batch(xa, xm, refs, total, min_bits=0):
     for q, (p, st, trace, t, stats, n1) in enumerate(refs):
         assert tuple(total[q]) == (n1 + stats["driveouts"], len(trace) - n1)
         _, _, _, abits, atrace, an = _download(xa, q)
         lohi, D, basis, bits, mtrace, mn = _download(xm, q)
         assert atrace + mtrace == trace and an == n1
-        assert abits == bits == (64 if stats["max_bits"] <= 64 else 128)
+        assert abits == bits == (64 if stats["max_bits"] <= 64 and min_bits != 128 else 128)
         assert basis == t.basis
         lo, hi = lohi
         got = [[Fraction(lp.exact._int128(a, b), D) for a, b in zip(rl, rh)] for rl, rh in zip(lo.tolist(), hi.tolist())]
@@ -476,3 +476,184 @@ def test_mismatched_pairs_are_refused():
     big = np.ones((2, 2, 4000), dtype=np.int64)
     assert L.mi355x_xbatch_create(ctypes.byref(h), 2, 2, 4000, _ptr(big), _ptr(big), _ptr(np.zeros(2, dtype=np.int64)),
                                   0, 0) == capi.MI_UNSUPPORTED and not h.value      # the snapshots do not fit the LDS
+
+
+# ---- 11. k_xb_between past one trip of its strided loops -------------------------------------------------------
+# The drive-out column search, the w / basis copy, the hand-over's column loop (src = nav for the last column)
+# and xb_apply on the artificial tableau with more than one workgroup's worth of rows or columns, against the
+# Fraction oracle and VecModel (tests/test_exact_host.py pins it to Model and so to the oracle) -- never
+# against the one-tableau path.
+WIDE_SEEDS = (0, 1, 2)
+
+
+def _wide_refs():
+    """Three members of one shape, artificial tableau 18 x 321 and main tableau 18 x 314: mixed_problem's 300
+    variables with fewer rows than the one-tableau test's 40 + 6 + 4, whose full solve outgrows 128 bits
+    (134 to 139 bits at seeds 5, 1, 2) -- these end optimal inside 64."""
+    refs = [_reference("mixed_problem", 300, 8, 3, 2, s) for s in WIDE_SEEDS]
+    for p, st, trace, t, stats, n1 in refs:
+        assert st == "optimal" and stats["driveouts"] >= 1 and stats["max_bits"] <= 64 and n1 >= 3
+        assert len(trace) > n1                                           # (phase 2 pivots the handed-over tableau)
+    return refs
+
+
+def test_wide_group_through_solve_problems():
+    """Wider than one workgroup in both tableaux, through the public route: grouping, the batch pair, the
+    read-back -- per member against the Fraction oracle."""
+    refs = _wide_refs()
+    got = lp.solve_problems([r[0] for r in refs], exact=True)
+    assert got[0].phase1._matrix.shape == (18, 321) and got[0]._matrix.shape == (18, 314)
+    assert all(g._batch is not None and g._batch[0] is got[0]._batch[0] for g in got)     # one batch, not one by one
+    for r, g in zip(refs, got):
+        _check_member(r, g)
+
+
+@pytest.mark.parametrize("min_bits", [0, 128])
+def test_wide_group_as_a_batch_pair_in_one_call_and_in_bounded_calls(min_bits):
+    refs = _wide_refs()
+    (xa, xm), _ = _batches([r[0] for r in refs], min_bits)
+    rc, st, npv = xa.solve_two_phase(xm, True, 0)
+    assert rc == capi.MI_OK and (st == capi.MI_OPTIMAL).all()
+    _check_two_phase_batch(xa, xm, refs, npv, min_bits)
+    if min_bits == 0:
+        (xa, xm), _ = _batches([r[0] for r in refs])
+        total = _one_pivot_per_call(xa, xm, refs)
+        _check_two_phase_batch(xa, xm, refs, total)
+
+
+@functools.lru_cache(maxsize=None)
+def _pair_reference(n, m_le, m_ge, m_eq, seed, total):
+    """(problem, art tableau, main tableau, art model after the drive-outs, main model, trace, n1, stats,
+    status, drive-out pivots) of a mixed_problem under a cap of `total` pivots (0: none)."""
+    p = ec.mixed_problem(lp, n, m_le, m_ge, m_eq, seed)
+    art_t, main_t = rr.build_tableau(ec.to_dict(p))
+    keep = {}
+    st, trace, mm, stats = ec.model_solve((art_t, main_t), cls=ec.VecModel, keep=keep, total_pivots=total)
+    assert mm is not None and not stats["inexact"] and stats["max_bits"] <= 128
+    return p, art_t, main_t, keep["art"], mm, trace, keep["n1"], stats, st, keep.get("driveout_pivots", [])
+
+
+def _check_pairs_against_models(pair, refs, calls, min_bits=0):
+    """The batch pair (art, main) of the members of refs solved in `calls` (their max_pivots: they add up to
+    the references' cap, or reach past the end of an uncapped reference): per member the status, both traces,
+    both bases, D and every entry of both tableaux."""
+    xa, xm = pair
+    try:
+        total = np.zeros((len(refs), 2), dtype=np.int64)
+        for cap in calls:
+            rc, st, npv = xa.solve_two_phase(xm, True, cap)
+            assert rc == capi.MI_OK
+            total += npv
+        for q, (_, art_t, main_t, art, mm, trace, n1, stats, mst, _) in enumerate(refs):
+            assert st[q] == CODES[mst], (q, st[q], mst)
+            assert tuple(total[q]) == (n1 + stats["driveouts"], len(trace) - n1)
+            bits = 128 if min_bits == 128 or stats["max_bits"] > 64 else 64
+            lohi, D, basis, abits, atrace, an = _download(xa, q)
+            assert atrace == trace[:n1] and an == n1 and abits == bits
+            assert basis == art.basis and D == art.D and _same_entries(lohi, art.T)
+            lohi, D, basis, mbits, mtrace, mn = _download(xm, q)
+            assert mtrace == trace[n1:] and mn == len(trace) - n1 and mbits == bits
+            assert basis == mm.basis and D == mm.D and _same_entries(lohi, mm.T)
+    finally:
+        xa.close()
+        xm.close()
+
+
+@pytest.mark.parametrize("total,calls,min_bits", [(32, (32,), 0), (32, (5,) * 6 + (2,), 0), (32, (32,), 128),
+                                                  (60, (60,), 0)])
+def test_between_phases_of_the_one_tableau_tests_wide_shape(total, calls, min_bits):
+    """mixed_problem(300, 40, 6, 4), the shape of the one-tableau hand-over test (55 x 361 and 55 x 349): a full
+    solve needs more than 128 bits, so the call is capped.  Every drive-out's column lies past the first trip
+    of the search, the hand-over's column loop makes a second trip and its last column comes from the
+    artificial tableau's last one.  In one call, in bounded calls, at 128 bits from the start, and (60
+    pivots) escalating to 128 bits on the way, which replays the step."""
+    refs = [_pair_reference(300, 40, 6, 4, seed, total) for seed in (5, 1, 2)]
+    for _, art_t, main_t, _, _, _, n1, stats, st, drive in refs:
+        assert len(art_t.matrix[0]) > len(main_t.matrix[0]) > WG and n1 >= 3
+        assert st == "max_pivots" and stats["driveouts"] >= 1 and len(drive) == stats["driveouts"]
+        assert (stats["max_bits"] > 64) == (total == 60)
+        assert all(j >= WG and eligible[0] == j for j, _, eligible in drive)
+    _check_pairs_against_models(_batches([r[0] for r in refs], min_bits)[0], refs, calls, min_bits)
+
+
+def _planted(seed, row3, total=12):
+    """A start that is phase-1 optimal at once (no positive entry in the artificial objective row) with two
+    artificial variables basic at zero over the planted row row3 and a random one: both are driven out.
+    300 structural columns, three slack rows; -> the tuple of _pair_reference with the integer starts
+    ((art, basis), (main, basis)) in the problem's place."""
+    rng = np.random.default_rng(seed)
+    n, ms = 300, 3
+    nv = n + ms                                                          # main: nv columns and the right-hand side
+    main = np.zeros((ms + 3, nv + 1), dtype=np.int64)
+    main[:ms, :n] = rng.integers(1, 4, size=(ms, n))
+    main[np.arange(ms), n + np.arange(ms)] = 1
+    main[:ms, -1] = rng.integers(5, 40, size=ms)
+    main[ms, :n] = row3
+    main[ms + 1, :n] = -rng.integers(0, 3, size=n)
+    main[-1, :n] = -rng.integers(1, 4, size=n)
+    art = np.zeros((ms + 3, nv + 3), dtype=np.int64)
+    art[:, :nv] = main[:, :nv]
+    art[:, -1] = main[:, -1]
+    art[ms, nv + 1], art[ms + 1, nv] = 1, 1                              # dealt in decreasing row order
+    art[-1] = 0
+    art[-1, :nv] = main[ms, :nv] + main[ms + 1, :nv]
+    mbasis = list(range(n, n + ms)) + [nv + 1, nv + 1]
+    abasis = list(range(n, n + ms)) + [nv + 1, nv]
+    art_t = rr.Tableau(art.tolist(), abasis, nv + 2, ms + 2, {}, False)
+    main_t = rr.Tableau(main.tolist(), mbasis, nv, ms + 2, {}, True)
+    keep = {}
+    st, trace, mm, stats = ec.model_solve((art_t, main_t), cls=ec.VecModel, keep=keep, total_pivots=total)
+    assert mm is not None and not stats["inexact"] and stats["max_bits"] <= 64 and keep["n1"] == 0, (st, stats)
+    starts = ((art, np.array(abasis, dtype=np.int64)), (main, np.array(mbasis, dtype=np.int64)))
+    return starts, art_t, main_t, keep["art"], mm, trace, 0, stats, st, keep["driveout_pivots"]
+
+
+def _planted_pair(refs, min_bits=0):
+    """The planted integer starts as a batch pair; creation must succeed."""
+    pair = []
+    for w in (0, 1):
+        num = np.stack([r[0][w][0] for r in refs])
+        pair.append(lp.exact.XBatch.from_states(num, np.ones_like(num), np.stack([r[0][w][1] for r in refs]),
+                                                min_bits=min_bits))
+    return tuple(pair)
+
+
+def test_planted_drive_out_columns_beyond_and_across_the_first_trip():
+    """Members whose first drive-out row has its first eligible (non-zero, non-basic) column at an index past
+    the workgroup size, and members with eligible columns on both sides of it, held by different threads:
+    the lowest wins.  Both facts are read from the model's drive-out pivots."""
+    refs = []
+    for seed in range(3):
+        row = np.zeros(300, dtype=np.int64)
+        row[WG + 14 + seed:] = -np.random.default_rng(seed).integers(0, 3, size=300 - WG - 14 - seed)
+        row[WG + 14 + seed] = -2
+        refs.append(_planted(seed, row))
+    for seed in range(3, 6):
+        row = -np.random.default_rng(seed).integers(1, 4, size=300)
+        row[:3 + seed] = 0
+        refs.append(_planted(seed, row))
+    for r in refs[:3]:
+        j, i, eligible = r[9][0]
+        assert j >= WG and eligible[0] == j and len(r[9]) == 2
+    for r in refs[3:]:
+        j, i, eligible = r[9][0]
+        assert j < WG and j == min(eligible) and sum(e < WG for e in eligible) > 100
+        assert sum(e >= WG for e in eligible) > 40 and len({e % WG for e in eligible}) > 200
+    _check_pairs_against_models(_planted_pair(refs), refs, (12,))
+    _check_pairs_against_models(_planted_pair(refs, 128), refs, (12,), min_bits=128)
+
+
+@pytest.mark.parametrize("calls,min_bits", [((0,), 0), ((9,) * 4, 0), ((0,), 128)])
+def test_between_phases_of_a_group_taller_than_one_workgroup(calls, min_bits):
+    """264 constraint rows, artificial rows on both sides of row 256, drive-outs in rows past it, phase 2
+    pivoting the handed-over tableau: the w / basis copy, the snapshots of xb_apply on the artificial tableau
+    and the basic-column scan run past one trip, at 64 and at 128 bits."""
+    refs = [_pair_reference(10, 250, 6, 4, seed, 0) for seed in (0, 2, 3)]
+    for _, art_t, main_t, art, mm, trace, n1, stats, st, drive in refs:
+        m = len(art_t.matrix) - 1
+        arts = [i for i in range(m) if art_t.basis[i] >= main_t.var_count]
+        assert m > WG and min(arts) < WG < max(arts) and (m + 1 + len(art_t.matrix[0])) * 16 <= 48 * 1024
+        assert st == "optimal" and stats["driveouts"] >= 1 and all(i > WG for _, i, _ in drive)
+        assert len(trace) > n1 and stats["max_bits"] <= 64
+        assert any(b < 10 for b in art.basis[WG:])             # a structural column basic in a row past 256
+    _check_pairs_against_models(_batches([r[0] for r in refs], min_bits)[0], refs, calls, min_bits)
