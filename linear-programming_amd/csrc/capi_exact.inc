@@ -51,6 +51,26 @@ bool x_fits(i128_t x, int bits)
     return x != INT128_MIN_;
 }
 
+// a value of the device's width (64: the low half) at dst / src, and the ABI's low and high 64-bit limbs
+void x_put(unsigned char *dst, i128_t x, int bits)
+{
+    if (bits == 64) { const int64_t y = (int64_t)x; memcpy(dst, &y, 8); }
+    else            memcpy(dst, &x, 16);
+}
+i128_t x_get(const unsigned char *src, int bits)
+{
+    int64_t y;
+    i128_t x;
+    if (bits == 64) { memcpy(&y, src, 8); return y; }
+    memcpy(&x, src, 16);
+    return x;
+}
+void x_lo_hi(i128_t x, int64_t out[2])
+{
+    out[0] = (int64_t)(uint64_t)(u128_t)x;
+    out[1] = (int64_t)(x >> 64);
+}
+
 int x_take_cancel(mi355x_xtab *a, mi355x_xtab *b = nullptr)
 {
     int c = a->cancel.exchange(0, std::memory_order_acq_rel);
@@ -151,10 +171,7 @@ int x_reset(mi355x_xtab *t, int bits)
         t->bits = t->v.bits = bits;
     }
     std::vector<unsigned char> stage(R * C * w);
-    for (size_t k = 0; k < R * C; ++k) {
-        if (bits == 64) { const int64_t x = (int64_t)T0[k]; memcpy(&stage[k * w], &x, w); }
-        else            memcpy(&stage[k * w], &T0[k], w);
-    }
+    for (size_t k = 0; k < R * C; ++k) x_put(&stage[k * w], T0[k], bits);
     HIP_TRY(hipMemcpyAsync(t->v.T, stage.data(), stage.size(), hipMemcpyHostToDevice, t->stream));
     if (R > 1) HIP_TRY(hipMemcpyAsync(t->v.basis, t->basis0.data(), (R - 1) * sizeof(int64_t), hipMemcpyHostToDevice, t->stream));
     t->h = XCtl{};
@@ -186,19 +203,41 @@ int x_run(mi355x_xtab *t, int is_max, int64_t cap_at, mi355x_xtab *peer)
     }
 }
 
-int x_download_values(mi355x_xtab *t, int64_t r0, int64_t n, std::vector<i128_t> &out)
+// n values of the width from k0 on of the device array T (stream s, synchronised)
+int x_download_values(const void *T, int bits, hipStream_t s, int64_t k0, int64_t n, std::vector<i128_t> &out)
 {
-    const size_t w = t->bits / 8;
+    const size_t w = bits / 8;
     std::vector<unsigned char> buf((size_t)n * w);
     if (n > 0)
-        HIP_TRY(hipMemcpyAsync(buf.data(), (const unsigned char *)t->v.T + (size_t)r0 * w, buf.size(),
-                               hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
+        HIP_TRY(hipMemcpyAsync(buf.data(), (const unsigned char *)T + (size_t)k0 * w, buf.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     out.resize((size_t)n);
-    for (int64_t k = 0; k < n; ++k) {
-        if (t->bits == 64) { int64_t x; memcpy(&x, &buf[k * w], w); out[k] = x; }
-        else               memcpy(&out[k], &buf[k * w], w);
+    for (int64_t k = 0; k < n; ++k) out[k] = x_get(&buf[k * w], bits);
+    return MI_OK;
+}
+
+// what both download entry points return: the entries (n of them) and D as limb pairs
+int x_download_lo_hi(const void *T, int bits, hipStream_t s, int64_t k0, int64_t n, i128_t D, int64_t *num_lo_hi, int64_t *den_lo_hi)
+{
+    if (num_lo_hi) {
+        std::vector<i128_t> vals;
+        const int rc = x_download_values(T, bits, s, k0, n, vals);
+        if (rc != MI_OK) return rc;
+        for (int64_t k = 0; k < n; ++k) x_lo_hi(vals[k], num_lo_hi + 2 * k);
     }
+    if (den_lo_hi) x_lo_hi(D, den_lo_hi);
+    return MI_OK;
+}
+
+// the first min(total, cap, trace_cap) pivots of a trace (total: how many there were)
+int x_download_trace(const int64_t *trace_ec, const int64_t *trace_cr, int64_t total, int64_t trace_cap, hipStream_t s,
+                     int64_t *ecs, int64_t *crs, int64_t cap, int64_t *n)
+{
+    if (n) *n = total;
+    const int64_t k = std::min<int64_t>(std::min<int64_t>(total, cap), trace_cap);
+    if (k > 0 && ecs) HIP_TRY(hipMemcpyAsync(ecs, trace_ec, k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (k > 0 && crs) HIP_TRY(hipMemcpyAsync(crs, trace_cr, k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return MI_OK;
 }
 
@@ -208,14 +247,14 @@ int x_handover(mi355x_xtab *a, mi355x_xtab *mt)
 {
     const int64_t m = a->rows - 1, C = a->cols, nav = C - 1, nv = mt->cols - 1;
     std::vector<i128_t> row;
-    int rc = x_download_values(a, m * C + nav, 1, row);                  // the artificial objective value
+    int rc = x_download_values(a->v.T, a->bits, a->stream, m * C + nav, 1, row);    // the artificial objective value
     if (rc != MI_OK) return rc;
     if (row[0] != 0) return MI_INFEASIBLE;
     std::vector<int64_t> basis((size_t)m);
     if (m > 0) HIP_TRY(hipMemcpy(basis.data(), a->v.basis, m * sizeof(int64_t), hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < m; ++i) {
         if (basis[i] < nv) continue;
-        rc = x_download_values(a, i * C, C, row);
+        rc = x_download_values(a->v.T, a->bits, a->stream, i * C, C, row);
         if (rc != MI_OK) return rc;
         if (row[nav] != 0) return MI_ART_NONZERO;
         int64_t j = 0;
@@ -244,10 +283,7 @@ int x_handover(mi355x_xtab *a, mi355x_xtab *mt)
         if (!x_fits(x, mt->bits)) return kXOverflow;
     const size_t w = mt->bits / 8;
     std::vector<unsigned char> stage(mult.size() * w);
-    for (size_t k = 0; k < mult.size(); ++k) {
-        if (mt->bits == 64) { const int64_t x = (int64_t)mult[k]; memcpy(&stage[k * w], &x, w); }
-        else                memcpy(&stage[k * w], &mult[k], w);
-    }
+    for (size_t k = 0; k < mult.size(); ++k) x_put(&stage[k * w], mult[k], mt->bits);
     HIP_TRY(hipMemcpyAsync(mt->aux, stage.data(), stage.size(), hipMemcpyHostToDevice, mt->stream));
     if (m > 0) HIP_TRY(hipMemcpyAsync(mt->v.basis, basis.data(), m * sizeof(int64_t), hipMemcpyHostToDevice, mt->stream));
     mt->h = XCtl{};
@@ -285,11 +321,17 @@ int x_check_device(int device)
     return MI_OK;
 }
 
-int x_status(mi355x_xtab *t, int st)
+// a kernel's kXInexact / kXOverflow as the ABI's error, any other status as it is
+int x_exact_status(int st)
 {
     if (st == kXInexact) return fail(MI_EXACT_INEXACT, "a fraction-free division left a remainder (internal error)");
-    if (st == kXOverflow) { t->dead = true; return fail(MI_EXACT_OVERFLOW, "an entry of the exact tableau needs more than 128 bits"); }
+    if (st == kXOverflow) return fail(MI_EXACT_OVERFLOW, "an entry of the exact tableau needs more than 128 bits");
     return st;
+}
+int x_status(mi355x_xtab *t, int st)
+{
+    if (st == kXOverflow) t->dead = true;
+    return x_exact_status(st);
 }
 
 }  // namespace
@@ -417,19 +459,8 @@ int mi355x_xtab_download(mi355x_xtab *t, int64_t *num_lo_hi, int64_t *den_lo_hi,
     if (t->dead) return fail(MI_EXACT_OVERFLOW, "the tableau overflowed 128 bits");
     int rc = use_device_id(t->device);
     if (rc != MI_OK) return rc;
-    if (num_lo_hi) {
-        std::vector<i128_t> vals;
-        rc = x_download_values(t, 0, t->rows * t->cols, vals);
-        if (rc != MI_OK) return rc;
-        for (size_t k = 0; k < vals.size(); ++k) {
-            num_lo_hi[2 * k] = (int64_t)(uint64_t)(u128_t)vals[k];
-            num_lo_hi[2 * k + 1] = (int64_t)(vals[k] >> 64);
-        }
-    }
-    if (den_lo_hi) {
-        den_lo_hi[0] = (int64_t)(uint64_t)(u128_t)t->h.D;
-        den_lo_hi[1] = (int64_t)(t->h.D >> 64);
-    }
+    rc = x_download_lo_hi(t->v.T, t->bits, t->stream, 0, t->rows * t->cols, t->h.D, num_lo_hi, den_lo_hi);
+    if (rc != MI_OK) return rc;
     if (basis && t->rows > 1)
         HIP_TRY(hipMemcpy(basis, t->v.basis, (t->rows - 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
     return MI_OK;
@@ -440,13 +471,7 @@ int mi355x_xtab_trace(mi355x_xtab *t, int64_t *ecs, int64_t *crs, int64_t cap, i
     if (!t) return fail(MI_BAD_ARG, "handle is NULL");
     int rc = use_device_id(t->device);
     if (rc != MI_OK) return rc;
-    const int64_t total = t->h.trace_n;
-    if (n) *n = total;
-    const int64_t k = std::min<int64_t>(std::min<int64_t>(total, cap), kXTraceCap);
-    if (k > 0 && ecs) HIP_TRY(hipMemcpyAsync(ecs, t->v.trace_ec, k * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
-    if (k > 0 && crs) HIP_TRY(hipMemcpyAsync(crs, t->v.trace_cr, k * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
-    HIP_TRY(hipStreamSynchronize(t->stream));
-    return MI_OK;
+    return x_download_trace(t->v.trace_ec, t->v.trace_cr, t->h.trace_n, kXTraceCap, t->stream, ecs, crs, cap, n);
 }
 
 int mi355x_xtab_bits(const mi355x_xtab *t, int *bits)

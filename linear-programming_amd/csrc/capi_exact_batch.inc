@@ -1,7 +1,7 @@
 // capi_exact_batch.inc -- mi355x_xbatch_*: many exact rational LPs of one shape side by side, one
 // workgroup per member (kernels_exact_batch.inc).  Part of simplex_capi.hip (ONE translation unit:
 // included there after capi_exact.inc, whose host helpers -- x_start_state, x_start_ok,
-// x_objective_multipliers -- it shares).
+// x_objective_multipliers, x_put, x_download_lo_hi, x_download_trace, x_exact_status -- it shares).
 //
 // A handle keeps the callers' rationals of every member on the host and up to two sub-batches on the
 // device, one per width.  Every member has a slot in each: it runs in the slot of its current width,
@@ -33,7 +33,7 @@ struct mi355x_xbatch {
 namespace {
 
 constexpr int64_t kXbTraceCap = MI355X_XBATCH_TRACE_CAP;
-static_assert(MI355X_XBATCH_WORKGROUP == 256, "the header states k_xb_solve's workgroup size");
+static_assert(MI355X_XBATCH_WORKGROUP == kXThreads, "the header states k_xb_solve's workgroup size");
 
 int xb_wi(int bits) { return bits == 128 ? 1 : 0; }
 XbCtl &xb_ctl(mi355x_xbatch *b, int64_t q) { return b->w[xb_wi(b->width[q])].h[q]; }
@@ -45,19 +45,13 @@ int64_t xb_launch_cap(const mi355x_xbatch *b)
     return std::max<int64_t>(8, std::min<int64_t>(4096, ((int64_t)1 << 22) / (b->rows * b->cols)));
 }
 
-void xb_put(unsigned char *dst, i128_t x, int bits)
-{
-    if (bits == 64) { const int64_t y = (int64_t)x; memcpy(dst, &y, 8); }
-    else            memcpy(dst, &x, 16);
-}
-
 // member q's start state at `bits` into dst (rows * cols values of the width): MI_OK or kXOverflow
 int xb_stage_member(const mi355x_xbatch *b, int64_t q, int bits, unsigned char *dst, i128_t *D0)
 {
     const int64_t RC = b->rows * b->cols;
     std::vector<i128_t> T0;
     if (x_start_state(b->rows, b->cols, &b->num[q * RC], &b->den[q * RC], bits, T0, D0) != MI_OK) return kXOverflow;
-    for (int64_t k = 0; k < RC; ++k) xb_put(dst + k * (bits / 8), T0[k], bits);
+    for (int64_t k = 0; k < RC; ++k) x_put(dst + k * (bits / 8), T0[k], bits);
     return MI_OK;
 }
 
@@ -101,7 +95,7 @@ int xb_alloc(mi355x_xbatch *b, int wi)
         bool ok = mq[C] != 0;
         for (size_t j = 0; j <= C && ok; ++j) ok = x_fits(mq[j], bits);
         if (!ok) continue;                                                  // (L_c stays 0)
-        for (size_t j = 0; j <= C; ++j) xb_put(&stage[(q * (C + 1) + j) * wb], mq[j], bits);
+        for (size_t j = 0; j <= C; ++j) x_put(&stage[(q * (C + 1) + j) * wb], mq[j], bits);
     }
     HIP_TRY(hipMemcpyAsync(s.aux, stage.data(), stage.size(), hipMemcpyHostToDevice, b->stream));
     if (n * m > 0)
@@ -165,8 +159,6 @@ int32_t xb_member_status(int32_t st)
 {
     return st == kRunning ? MI_RUNNING : st;
 }
-
-int xb_inexact() { return fail(MI_EXACT_INEXACT, "a fraction-free division left a remainder (internal error)"); }
 
 }  // namespace
 
@@ -263,7 +255,7 @@ int mi355x_xbatch_solve(mi355x_xbatch *b, int is_max, int64_t max_pivots, int32_
         for (int64_t q = 0; q < n; ++q) {
             if (!xb_live(b, q)) continue;
             const int32_t st = xb_ctl(b, q).status;
-            if (st == kXInexact) return xb_inexact();
+            if (st == kXInexact) return x_exact_status(kXInexact);
             if (st == kXOverflow) {
                 // the member again from its start at 128 bits: the same pivots, up to the same count
                 if (b->width[q] == 128) { b->width[q] = 0; continue; }
@@ -359,7 +351,7 @@ int mi355x_xbatch_solve_two_phase(mi355x_xbatch *art, mi355x_xbatch *mt, int mai
             if (!xb_live(art, q)) continue;
             const XbCtl &ca = xb_ctl(art, q), &cm = xb_ctl(mt, q);
             const int32_t sa = ca.status, sm = ca.tp == 1 ? cm.status : kXbIdle;
-            if (sa == kXInexact || sm == kXInexact) return xb_inexact();
+            if (sa == kXInexact || sm == kXInexact) return x_exact_status(kXInexact);
             if (sa == kXOverflow || sm == kXOverflow) {
                 // both phases again from the start at 128 bits, up to the same pivot count
                 if (art->width[q] == 128) { art->width[q] = mt->width[q] = 0; continue; }
@@ -403,24 +395,9 @@ int mi355x_xbatch_download(mi355x_xbatch *b, int64_t q, int64_t *num_lo_hi, int6
     int rc = use_device_id(b->device);
     if (rc != MI_OK) return rc;
     const XbWidth &w = b->w[xb_wi(b->width[q])];
-    const size_t wb = b->width[q] / 8, RC = (size_t)(b->rows * b->cols), m = (size_t)b->rows - 1;
-    if (num_lo_hi) {
-        std::vector<unsigned char> buf(RC * wb);
-        HIP_TRY(hipMemcpyAsync(buf.data(), (const unsigned char *)w.v.T + (size_t)q * RC * wb, buf.size(), hipMemcpyDeviceToHost, b->stream));
-        HIP_TRY(hipStreamSynchronize(b->stream));
-        for (size_t k = 0; k < RC; ++k) {
-            i128_t x;
-            if (wb == 8) { int64_t y; memcpy(&y, &buf[k * wb], wb); x = y; }
-            else         memcpy(&x, &buf[k * wb], wb);
-            num_lo_hi[2 * k] = (int64_t)(uint64_t)(u128_t)x;
-            num_lo_hi[2 * k + 1] = (int64_t)(x >> 64);
-        }
-    }
-    if (den_lo_hi) {
-        const i128_t D = w.h[q].D;
-        den_lo_hi[0] = (int64_t)(uint64_t)(u128_t)D;
-        den_lo_hi[1] = (int64_t)(D >> 64);
-    }
+    const int64_t RC = b->rows * b->cols, m = b->rows - 1;
+    rc = x_download_lo_hi(w.v.T, b->width[q], b->stream, q * RC, RC, w.h[q].D, num_lo_hi, den_lo_hi);
+    if (rc != MI_OK) return rc;
     if (basis && m > 0) {
         HIP_TRY(hipMemcpyAsync(basis, w.v.basis + q * m, m * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
         HIP_TRY(hipStreamSynchronize(b->stream));
@@ -437,13 +414,8 @@ int mi355x_xbatch_trace(mi355x_xbatch *b, int64_t q, int64_t *ecs, int64_t *crs,
     int rc = use_device_id(b->device);
     if (rc != MI_OK) return rc;
     const XbWidth &w = b->w[xb_wi(b->width[q])];
-    const int64_t total = w.h[q].trace_n;
-    if (n) *n = total;
-    const int64_t k = std::min<int64_t>(std::min<int64_t>(total, cap), kXbTraceCap);
-    if (k > 0 && ecs) HIP_TRY(hipMemcpyAsync(ecs, w.v.trace_ec + q * kXbTraceCap, k * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-    if (k > 0 && crs) HIP_TRY(hipMemcpyAsync(crs, w.v.trace_cr + q * kXbTraceCap, k * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return MI_OK;
+    return x_download_trace(w.v.trace_ec + q * kXbTraceCap, w.v.trace_cr + q * kXbTraceCap, w.h[q].trace_n, kXbTraceCap,
+                            b->stream, ecs, crs, cap, n);
 }
 
 int mi355x_xbatch_bits(const mi355x_xbatch *b, int64_t q, int *bits)

@@ -23,6 +23,8 @@
 //   k_x_update<T>    the rank-1 update with the exact division (every element once)
 //   k_x_handover<T>  main tableau of the two-phase hand-over: constraint rows scaled by L_c and the
 //                    objective row re-eliminated, D_main = L_c * D_art
+// The rules themselves -- x_price, x_ratio, x_record, x_snapshot, x_update_elem, x_handover_column -- stand
+// here once; the kernels above and the batch kernels (kernels_exact_batch.inc) are loops around them.
 
 typedef unsigned __int128 xu128;
 
@@ -162,66 +164,32 @@ template <class T> __device__ inline void x_div_setup(__int128 D, int32_t *shift
     *inv = (__int128)xinv_odd<U>((U)(D >> sh));
 }
 
-// the pivot record of (ec, cr) -- thread 0 only; the snapshots follow in x_snapshot
-template <class T> __device__ inline void x_record(XCtl *c, const T *M, int64_t cols, int64_t ec, int64_t cr)
+// ---- what the single tableau and the batches (kernels_exact_batch.inc) share: one copy of each rule ----
+// the power of two the reduction trees start from: slots at and above it hold no candidate and are never read
+__device__ inline int x_tree_top(int64_t n)
 {
-    const T p = M[cr * cols + ec];
-    c->ec = ec;
-    c->cr = cr;
-    c->sgn = p < 0 ? -1 : 1;
-    c->pa = (__int128)(p < 0 ? -p : p);
-    c->dold = c->D;
-    x_div_setup<T>(c->dold, &c->shift, &c->inv);
-    c->D = c->pa;
-    c->apply = 1;
-}
-template <class T> __device__ inline void x_snapshot(const XView &v, const XCtl *c)
-{
-    const T *M = (const T *)v.T;
-    T *col = (T *)v.col, *prow = (T *)v.prow;
-    const int64_t ec = c->ec, cr = c->cr;
-    const int sgn = c->sgn;
-    for (int64_t i = threadIdx.x; i < v.rows; i += blockDim.x) {
-        const T a = M[i * v.cols + ec];
-        col[i] = sgn < 0 ? -a : a;
-    }
-    for (int64_t j = threadIdx.x; j < v.cols; j += blockDim.x) prow[j] = M[cr * v.cols + j];
+    int top = 1;
+    while (top < kXThreads && top < n) top <<= 1;
+    return top;
 }
 
-constexpr int kXSelectThreads = 256;
-
-template <class T> __global__ __launch_bounds__(kXSelectThreads) void k_x_select(XView v, int is_max)
+// x_price and x_ratio: every thread of the workgroup calls them, with the same arguments.  sv, sa, si:
+// kXThreads slots of LDS each, free again on return (both end on a barrier, after the read of slot 0).
+//
+// find-entering-column (src/simplex.lisp:362-379), rational dispatch: the lowest index of the strict
+// minimum (max) / maximum (min) of obj[0, nv) if that value is < 0 (> 0), -1 otherwise (optimal).
+template <class T> __device__ __forceinline__ int64_t x_price(const T *obj, int64_t nv, int is_max, T *sv, int64_t *si)
 {
-    XCtl *c = v.ctl;
-    const T *M = (const T *)v.T;
     const int tid = threadIdx.x;
-    const int64_t m = v.rows - 1, nv = v.cols - 1, C = v.cols;
-    __shared__ int go;
-    __shared__ T sv[kXSelectThreads], sa[kXSelectThreads];
-    __shared__ int64_t si[kXSelectThreads];
-    if (tid == 0) {
-        int g = 0;
-        c->apply = 0;
-        if (c->status == kRunning) {
-            if (c->err) c->status = c->err;
-            else if (c->cap_at > 0 && c->n_pivots >= c->cap_at) c->status = 3;           // MI_MAX_PIVOTS
-            else g = 1;
-        }
-        go = g;
-    }
-    __syncthreads();
-    if (!go) return;
-    // find-entering-column (src/simplex.lisp:362-379), rational dispatch
-    const T *obj = M + m * C;
     int64_t bi = -1;
     T bv = 0;
-    for (int64_t j = tid; j < nv; j += kXSelectThreads) {
+    for (int64_t j = tid; j < nv; j += kXThreads) {
         const T x = obj[j];
         if (bi < 0 || (is_max ? x < bv : x > bv)) { bv = x; bi = j; }
     }
     sv[tid] = bv; si[tid] = bi;
     __syncthreads();
-    for (int s = kXSelectThreads / 2; s > 0; s >>= 1) {
+    for (int s = x_tree_top(nv) / 2; s > 0; s >>= 1) {
         if (tid < s) {
             const int o = tid + s;
             if (si[o] >= 0 && (si[tid] < 0 || (is_max ? sv[o] < sv[tid] : sv[o] > sv[tid]) ||
@@ -230,15 +198,20 @@ template <class T> __global__ __launch_bounds__(kXSelectThreads) void k_x_select
         __syncthreads();
     }
     const int64_t ec = si[0];
-    if (ec < 0 || !(is_max ? sv[0] < 0 : sv[0] > 0)) {
-        if (tid == 0) c->status = 0;                                                        // MI_OPTIMAL
-        return;
-    }
+    const T best = sv[0];
     __syncthreads();
-    // find-pivoting-row (src/simplex.lisp:382-389), cross-multiplied
-    bi = -1;
+    return ec >= 0 && (is_max ? best < 0 : best > 0) ? ec : -1;
+}
+
+// find-pivoting-row (src/simplex.lisp:382-389), cross-multiplied: the lowest row of the strict minimum of
+// M[i][nv] / M[i][ec] over the rows i < m with M[i][ec] > 0, -1 if there is none (unbounded).  C: M's columns.
+template <class T> __device__ __forceinline__ int64_t x_ratio(const T *M, int64_t m, int64_t C, int64_t nv, int64_t ec,
+                                                              T *sv, T *sa, int64_t *si)
+{
+    const int tid = threadIdx.x;
+    int64_t bi = -1;
     T br = 0, ba = 0;
-    for (int64_t i = tid; i < m; i += kXSelectThreads) {
+    for (int64_t i = tid; i < m; i += kXThreads) {
         const T a = M[i * C + ec];
         if (a > 0) {
             const T r = M[i * C + nv];
@@ -247,7 +220,7 @@ template <class T> __global__ __launch_bounds__(kXSelectThreads) void k_x_select
     }
     sv[tid] = br; sa[tid] = ba; si[tid] = bi;
     __syncthreads();
-    for (int s = kXSelectThreads / 2; s > 0; s >>= 1) {
+    for (int s = x_tree_top(m) / 2; s > 0; s >>= 1) {
         if (tid < s) {
             const int o = tid + s;
             if (si[o] >= 0) {
@@ -262,81 +235,159 @@ template <class T> __global__ __launch_bounds__(kXSelectThreads) void k_x_select
         __syncthreads();
     }
     const int64_t cr = si[0];
+    __syncthreads();
+    return cr;
+}
+
+// the pivot record of (ec, cr) on a tableau with denominator D -- one thread; D' is r->pa
+template <class T> __device__ inline void x_record(XPivot *r, const T *M, int64_t C, int64_t ec, int64_t cr, __int128 D)
+{
+    const T p = M[cr * C + ec];
+    r->ec = ec;
+    r->cr = cr;
+    r->sgn = p < 0 ? -1 : 1;
+    r->pa = (__int128)(p < 0 ? -p : p);
+    r->dold = D;
+    x_div_setup<T>(D, &r->shift, &r->inv);
+}
+
+// the record at the width, in registers: what the snapshots and the update of one pivot take
+template <class T> struct XPivotT {
+    typedef typename XUnsigned<T>::type U;
+    int64_t ec, cr;
+    int     sgn, shift;
+    T       pa, dold;
+    U       inv;
+    __device__ explicit XPivotT(const XPivot &r)
+        : ec(r.ec), cr(r.cr), sgn(r.sgn), shift(r.shift), pa((T)r.pa), dold((T)r.dold), inv((U)r.inv) {}
+};
+
+// the entering column times sgn into col (R values) and the pivot row into prow (C values), global or LDS:
+// every thread of the workgroup calls this
+template <class T> __device__ __forceinline__ void x_snapshot(const T *M, int64_t R, int64_t C, const XPivotT<T> &p, T *col, T *prow)
+{
+    for (int64_t i = threadIdx.x; i < R; i += kXThreads) {
+        const T a = M[i * C + p.ec];
+        col[i] = p.sgn < 0 ? -a : a;
+    }
+    for (int64_t j = threadIdx.x; j < C; j += kXThreads) prow[j] = M[p.cr * C + j];
+}
+
+// the update of *x = T[r][j] from the snapshots' cv = col[r] and pv = prow[j].  0, kXOverflow or kXInexact
+// (*x is left as it was then)
+template <class T> __device__ __forceinline__ int x_update_elem(T *x, int64_t r, T cv, T pv, const XPivotT<T> &p)
+{
+    if (r == p.cr) { *x = p.sgn < 0 ? -pv : pv; return 0; }
+    T q;
+    const int e = xdiv(xsub(xmul(*x, p.pa), xmul(cv, pv)), p.dold, p.shift, p.inv, &q);
+    if (!e) *x = q;
+    return e;
+}
+
+// Column j of the hand-over's main tableau M (Cm columns) from the artificial one A (Ca columns, denominator
+// D), m constraint rows: M[r][j] = lc * A[r][src] and M[m][j] = D * cl[j] - sum_r w[r] * A[r][src], src = j but
+// the artificial right-hand side for the last column.  false: a value left the width (0 is stored for it).
+template <class T> __device__ __forceinline__ bool x_handover_column(const T *A, int64_t Ca, T *M, int64_t Cm, int64_t m,
+                                                                     int64_t j, T D, const T *w, const T *cl, T lc)
+{
+    const int64_t src = j < Cm - 1 ? j : Ca - 1;
+    auto acc = xmul(D, cl[j]);
+    bool ok = true;
+    for (int64_t r = 0; r < m; ++r) {
+        const T x = A[r * Ca + src];
+        T y = 0;
+        if (!xfit(xmul(lc, x), &y)) ok = false;
+        M[r * Cm + j] = y;
+        if (!xsub_ovf(acc, xmul(w[r], x))) ok = false;
+    }
+    T o = 0;
+    if (!xfit(acc, &o)) ok = false;
+    M[m * Cm + j] = o;
+    return ok;
+}
+
+template <class T> __global__ __launch_bounds__(kXThreads) void k_x_select(XView v, int is_max)
+{
+    XCtl *c = v.ctl;
+    const T *M = (const T *)v.T;
+    const int tid = threadIdx.x;
+    const int64_t m = v.rows - 1, nv = v.cols - 1, C = v.cols;
+    __shared__ int go;
+    __shared__ T sv[kXThreads], sa[kXThreads];
+    __shared__ int64_t si[kXThreads];
+    if (tid == 0) {
+        int g = 0;
+        c->apply = 0;
+        if (c->status == kRunning) {
+            if (c->err) c->status = c->err;
+            else if (c->cap_at > 0 && c->n_pivots >= c->cap_at) c->status = 3;           // MI_MAX_PIVOTS
+            else g = 1;
+        }
+        go = g;
+    }
+    __syncthreads();
+    if (!go) return;
+    const int64_t ec = x_price<T>(M + m * C, nv, is_max, sv, si);
+    if (ec < 0) {
+        if (tid == 0) c->status = 0;                                                        // MI_OPTIMAL
+        return;
+    }
+    const int64_t cr = x_ratio<T>(M, m, C, nv, ec, sv, sa, si);
     if (cr < 0) {
         if (tid == 0) c->status = 1;                                                        // MI_UNBOUNDED
         return;
     }
     if (tid == 0) {
-        x_record<T>(c, M, C, ec, cr);
+        x_record<T>(&c->piv, M, C, ec, cr, c->D);
+        c->D = c->piv.pa;
+        c->apply = 1;
         v.basis[cr] = ec;
         if (c->trace_n < v.trace_cap) { v.trace_ec[c->trace_n] = ec; v.trace_cr[c->trace_n] = cr; }
         c->trace_n += 1;
         c->n_pivots += 1;
     }
     __syncthreads();
-    x_snapshot<T>(v, c);
+    x_snapshot<T>(M, v.rows, C, XPivotT<T>(c->piv), (T *)v.col, (T *)v.prow);
 }
 
 // a pivot given by the host (the drive-out of src/simplex.lisp:418-436): not counted, not traced
-template <class T> __global__ __launch_bounds__(kXSelectThreads) void k_x_force(XView v, int64_t ec, int64_t cr)
+template <class T> __global__ __launch_bounds__(kXThreads) void k_x_force(XView v, int64_t ec, int64_t cr)
 {
     XCtl *c = v.ctl;
+    const T *M = (const T *)v.T;
     if (threadIdx.x == 0) {
-        x_record<T>(c, (const T *)v.T, v.cols, ec, cr);
+        x_record<T>(&c->piv, M, v.cols, ec, cr, c->D);
+        c->D = c->piv.pa;
+        c->apply = 1;
         v.basis[cr] = ec;
     }
     __syncthreads();
-    x_snapshot<T>(v, c);
+    x_snapshot<T>(M, v.rows, v.cols, XPivotT<T>(c->piv), (T *)v.col, (T *)v.prow);
 }
 
 template <class T> __global__ __launch_bounds__(256) void k_x_update(XView v)
 {
-    typedef typename XUnsigned<T>::type U;
     XCtl *c = v.ctl;
     if (!c->apply) return;
     T *M = (T *)v.T;
     const T *col = (const T *)v.col, *prow = (const T *)v.prow;
-    const int64_t cr = c->cr, C = v.cols;
-    const int sgn = c->sgn, sh = c->shift;
-    const T pa = (T)c->pa, dold = (T)c->dold;
-    const U inv = (U)c->inv;
+    const int64_t C = v.cols;
+    const XPivotT<T> p(c->piv);
     int err = 0;
     for (int64_t r = blockIdx.y; r < v.rows; r += gridDim.y) {
         const T cv = col[r];
-        for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < C; j += (int64_t)gridDim.x * blockDim.x) {
-            if (r == cr) { M[r * C + j] = sgn < 0 ? -prow[j] : prow[j]; continue; }
-            T q;
-            const int e = xdiv(xsub(xmul(M[r * C + j], pa), xmul(cv, prow[j])), dold, sh, inv, &q);
-            if (e) err = e > err ? e : err;
-            else M[r * C + j] = q;
-        }
+        for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < C; j += (int64_t)gridDim.x * blockDim.x)
+            err = max(err, x_update_elem<T>(M + r * C + j, r, cv, prow[j], p));
     }
     if (err) atomicMax(&c->err, err);
 }
 
 template <class T> __global__ __launch_bounds__(256) void k_x_handover(XView a, XView mt, const T *w, const T *cl, T lc)
 {
-    const int64_t m = a.rows - 1, nv = mt.cols - 1, nav = a.cols - 1;
-    const T *A = (const T *)a.T;
-    T *M = (T *)mt.T;
     const T D = (T)a.ctl->D;
     int err = 0;
-    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < mt.cols; j += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t src = j < nv ? j : nav;
-        auto acc = xmul(D, cl[j]);
-        bool ok = true;
-        for (int64_t r = 0; r < m; ++r) {
-            const T x = A[r * a.cols + src];
-            T y = 0;
-            if (!xfit(xmul(lc, x), &y)) ok = false;
-            M[r * mt.cols + j] = y;
-            if (!xsub_ovf(acc, xmul(w[r], x))) ok = false;
-        }
-        T o = 0;
-        if (!xfit(acc, &o)) ok = false;
-        M[m * mt.cols + j] = o;
-        if (!ok) err = kXOverflow;
-    }
+    for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < mt.cols; j += (int64_t)gridDim.x * blockDim.x)
+        if (!x_handover_column<T>((const T *)a.T, a.cols, (T *)mt.T, mt.cols, a.rows - 1, j, D, w, cl, lc)) err = kXOverflow;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         T d = 0;
         if (!xfit(xmul(lc, D), &d)) err = kXOverflow;
@@ -348,31 +399,33 @@ template <class T> __global__ __launch_bounds__(256) void k_x_handover(XView a, 
 static unsigned x_grid_x(int64_t cols) { const int64_t g = (cols + 255) / 256; return (unsigned)(g < 64 ? g : 64); }
 static unsigned x_grid_y(int64_t rows) { return (unsigned)(rows < 4096 ? rows : 4096); }
 
+// f(T()) with T the storage type of `bits`: the launchers' int64_t / __int128 pair
+template <class F> static void x_with_width(int bits, F f)
+{
+    if (bits == 64) f((int64_t)0);
+    else            f((__int128)0);
+}
+
 void launch_x_select(const XView &v, int is_max, hipStream_t s)
 {
-    if (v.bits == 64) hipLaunchKernelGGL(k_x_select<int64_t>, dim3(1), dim3(kXSelectThreads), 0, s, v, is_max);
-    else              hipLaunchKernelGGL(k_x_select<__int128>, dim3(1), dim3(kXSelectThreads), 0, s, v, is_max);
+    x_with_width(v.bits, [&](auto t) { hipLaunchKernelGGL(k_x_select<decltype(t)>, dim3(1), dim3(kXThreads), 0, s, v, is_max); });
 }
 void launch_x_force(const XView &v, int64_t ec, int64_t cr, hipStream_t s)
 {
-    if (v.bits == 64) hipLaunchKernelGGL(k_x_force<int64_t>, dim3(1), dim3(kXSelectThreads), 0, s, v, ec, cr);
-    else              hipLaunchKernelGGL(k_x_force<__int128>, dim3(1), dim3(kXSelectThreads), 0, s, v, ec, cr);
+    x_with_width(v.bits, [&](auto t) { hipLaunchKernelGGL(k_x_force<decltype(t)>, dim3(1), dim3(kXThreads), 0, s, v, ec, cr); });
 }
 void launch_x_update(const XView &v, hipStream_t s)
 {
     const dim3 grid(x_grid_x(v.cols), x_grid_y(v.rows));
-    if (v.bits == 64) hipLaunchKernelGGL(k_x_update<int64_t>, grid, dim3(256), 0, s, v);
-    else              hipLaunchKernelGGL(k_x_update<__int128>, grid, dim3(256), 0, s, v);
+    x_with_width(v.bits, [&](auto t) { hipLaunchKernelGGL(k_x_update<decltype(t)>, grid, dim3(256), 0, s, v); });
 }
 void launch_x_handover(const XView &art, const XView &mt, const void *w, const void *cl, __int128 lc, hipStream_t s)
 {
     const dim3 grid((unsigned)((mt.cols + 255) / 256));
-    if (mt.bits == 64)
-        hipLaunchKernelGGL(k_x_handover<int64_t>, grid, dim3(256), 0, s, art, mt, (const int64_t *)w,
-                           (const int64_t *)cl, (int64_t)lc);
-    else
-        hipLaunchKernelGGL(k_x_handover<__int128>, grid, dim3(256), 0, s, art, mt, (const __int128 *)w,
-                           (const __int128 *)cl, lc);
+    x_with_width(mt.bits, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_x_handover<T>, grid, dim3(256), 0, s, art, mt, (const T *)w, (const T *)cl, (T)lc);
+    });
 }
 
 #ifdef MI355X_TEST_HOOKS

@@ -1,6 +1,6 @@
 // kernels_exact_batch.inc -- many exact rational LPs of one shape side by side, one workgroup per LP.
-// Part of simplex_kernels.hip (ONE translation unit: included there after kernels_exact.inc, whose
-// arithmetic -- xmul / xsub / xdiv / x_div_setup / xfit / S256 -- and rules it uses unchanged).
+// Part of simplex_kernels.hip (ONE translation unit: included there after kernels_exact.inc, whose rules
+// -- x_price, x_ratio, x_record, x_snapshot, x_update_elem, x_handover_column -- it only loops around).
 //
 //   k_xb_solve<T>    the whole n-solve-tableau loop (src/simplex.lisp:453-461, rational dispatch) of one
 //                    member inside one launch: pricing, ratio test, pivot record, snapshots of the
@@ -19,57 +19,21 @@
 // residency.  The snapshots are dynamic LDS, (rows + cols) values of the width; a shape whose
 // snapshots at 128 bits exceed kXbSnapshotLimit is declined at creation (capi_exact_batch.inc).
 
-constexpr int kXbThreads = 256;
-
-// the pivot being applied (x_record's fields), per member, in LDS
-struct XbRec {
-    int64_t  ec, cr;
-    int32_t  sgn, shift;
-    __int128 pa, dold, inv;
-};
-
-template <class T> __device__ inline void xb_record(XbRec *r, const T *M, int64_t C, int64_t ec, int64_t cr, __int128 D)
-{
-    const T p = M[cr * C + ec];
-    r->ec = ec;
-    r->cr = cr;
-    r->sgn = p < 0 ? -1 : 1;
-    r->pa = (__int128)(p < 0 ? -p : p);
-    r->dold = D;
-    x_div_setup<T>(D, &r->shift, &r->inv);
-}
-
 // Snapshots and the update of the pivot in *rec (written by thread 0, *s_err zeroed with it): every
 // thread of the workgroup calls this.  0, kXOverflow or kXInexact (the tableau is garbage then).
-template <class T> __device__ inline int xb_apply(T *M, int R, int C, T *col, T *prow, const XbRec *rec, int *s_err)
+template <class T> __device__ inline int xb_apply(T *M, int R, int C, T *col, T *prow, const XPivot *rec, int *s_err)
 {
-    typedef typename XUnsigned<T>::type U;
     const int tid = threadIdx.x;
     __syncthreads();
-    const int64_t ec = rec->ec, cr = rec->cr;
-    const int sgn = rec->sgn, sh = rec->shift;
-    const T pa = (T)rec->pa, dold = (T)rec->dold;
-    const U inv = (U)rec->inv;
-    for (int i = tid; i < R; i += kXbThreads) {
-        const T a = M[(int64_t)i * C + ec];
-        col[i] = sgn < 0 ? -a : a;
-    }
-    for (int j = tid; j < C; j += kXbThreads) prow[j] = M[cr * C + j];
+    const XPivotT<T> p(*rec);
+    x_snapshot<T>(M, R, C, p, col, prow);
     __syncthreads();
     // element k = r * C + j of this thread: k = tid, tid + 256, ... walked as (r, j) without a division per element
-    const int dr = kXbThreads / C, dj = kXbThreads % C;
+    const int dr = kXThreads / C, dj = kXThreads % C;
     int r = tid / C, j = tid % C;
     int err = 0;
     while (r < R) {
-        T *x = M + (int64_t)r * C + j;
-        if (r == cr) {
-            *x = sgn < 0 ? -prow[j] : prow[j];
-        } else {
-            T q;
-            const int e = xdiv(xsub(xmul(*x, pa), xmul(col[r], prow[j])), dold, sh, inv, &q);
-            if (e) err = e > err ? e : err;
-            else *x = q;
-        }
+        err = max(err, x_update_elem<T>(M + (int64_t)r * C + j, r, col[r], prow[j], p));
         r += dr;
         j += dj;
         if (j >= C) { j -= C; r += 1; }
@@ -79,20 +43,12 @@ template <class T> __device__ inline int xb_apply(T *M, int R, int C, T *col, T 
     return *s_err;
 }
 
-// the power of two the reduction trees start from: slots at and above it hold no candidate
-__device__ inline int xb_tree_top(int64_t n)
-{
-    int top = 1;
-    while (top < kXbThreads && top < n) top <<= 1;
-    return top;
-}
-
-template <class T> __global__ __launch_bounds__(kXbThreads) void k_xb_solve(XbView v, int is_max, int64_t launch_cap)
+template <class T> __global__ __launch_bounds__(kXThreads) void k_xb_solve(XbView v, int is_max, int64_t launch_cap)
 {
     extern __shared__ __int128 xb_lds[];
-    __shared__ T sv[kXbThreads], sa[kXbThreads];
-    __shared__ int64_t si[kXbThreads];
-    __shared__ XbRec rec;
+    __shared__ T sv[kXThreads], sa[kXThreads];
+    __shared__ int64_t si[kXThreads];
+    __shared__ XPivot rec;
     __shared__ int s_err, s_go;
     const int tid = threadIdx.x;
     const int64_t q = blockIdx.x;
@@ -111,61 +67,14 @@ template <class T> __global__ __launch_bounds__(kXbThreads) void k_xb_solve(XbVi
     const int64_t cap_at = c->cap_at;
     __int128 D = c->D;
     int status = kRunning;
-    const int top_p = xb_tree_top(nv), top_r = xb_tree_top(m);
-    const T *obj = M + m * C;
     for (int64_t it = 0; it < launch_cap; ++it) {
         if (cap_at > 0 && n_pivots >= cap_at) { status = 3; break; }                       // MI_MAX_PIVOTS
-        // find-entering-column (src/simplex.lisp:362-379), rational dispatch: k_x_select's rule
-        int64_t bi = -1;
-        T bv = 0;
-        for (int64_t j = tid; j < nv; j += kXbThreads) {
-            const T x = obj[j];
-            if (bi < 0 || (is_max ? x < bv : x > bv)) { bv = x; bi = j; }
-        }
-        sv[tid] = bv; si[tid] = bi;
-        __syncthreads();
-        for (int s = top_p / 2; s > 0; s >>= 1) {
-            if (tid < s) {
-                const int o = tid + s;
-                if (si[o] >= 0 && (si[tid] < 0 || (is_max ? sv[o] < sv[tid] : sv[o] > sv[tid]) ||
-                                   (sv[o] == sv[tid] && si[o] < si[tid]))) { sv[tid] = sv[o]; si[tid] = si[o]; }
-            }
-            __syncthreads();
-        }
-        const int64_t ec = si[0];
-        const T best = sv[0];
-        __syncthreads();
-        if (ec < 0 || !(is_max ? best < 0 : best > 0)) { status = 0; break; }              // MI_OPTIMAL
-        // find-pivoting-row (src/simplex.lisp:382-389), cross-multiplied
-        bi = -1;
-        T br = 0, ba = 0;
-        for (int64_t i = tid; i < m; i += kXbThreads) {
-            const T a = M[i * C + ec];
-            if (a > 0) {
-                const T r = M[i * C + nv];
-                if (bi < 0 || xlt(xmul(r, ba), xmul(br, a))) { br = r; ba = a; bi = i; }
-            }
-        }
-        sv[tid] = br; sa[tid] = ba; si[tid] = bi;
-        __syncthreads();
-        for (int s = top_r / 2; s > 0; s >>= 1) {
-            if (tid < s) {
-                const int o = tid + s;
-                if (si[o] >= 0) {
-                    bool better = si[tid] < 0;
-                    if (!better) {
-                        const auto lhs = xmul(sv[o], sa[tid]), rhs = xmul(sv[tid], sa[o]);
-                        better = xlt(lhs, rhs) || (xeq(lhs, rhs) && si[o] < si[tid]);
-                    }
-                    if (better) { sv[tid] = sv[o]; sa[tid] = sa[o]; si[tid] = si[o]; }
-                }
-            }
-            __syncthreads();
-        }
-        const int64_t cr = si[0];
+        const int64_t ec = x_price<T>(M + m * C, nv, is_max, sv, si);
+        if (ec < 0) { status = 0; break; }                                                  // MI_OPTIMAL
+        const int64_t cr = x_ratio<T>(M, m, C, nv, ec, sv, sa, si);
         if (cr < 0) { status = 1; break; }                                                  // MI_UNBOUNDED
         if (tid == 0) {
-            xb_record<T>(&rec, M, C, ec, cr, D);
+            x_record<T>(&rec, M, C, ec, cr, D);
             s_err = 0;
             basis[cr] = ec;
             if (trace_n < v.trace_cap) { tec[trace_n] = ec; tcr[trace_n] = cr; }
@@ -189,10 +98,10 @@ template <class T> __global__ __launch_bounds__(kXbThreads) void k_xb_solve(XbVi
 // MI_MAX_PIVOTS when the drive-outs used the call's pivots up), tp = 2 with tp_status MI_INFEASIBLE /
 // MI_ART_NONZERO / MI_ART_STUCK, or status kXOverflow / kXInexact.  Main's aux holds, per member, cl_j =
 // L_c * c_j (cols values) and then L_c, 0 where they do not fit the width.
-template <class T> __global__ __launch_bounds__(kXbThreads) void k_xb_between(XbView a, XbView mt)
+template <class T> __global__ __launch_bounds__(kXThreads) void k_xb_between(XbView a, XbView mt)
 {
     extern __shared__ __int128 xb_lds[];
-    __shared__ XbRec rec;
+    __shared__ XPivot rec;
     __shared__ int s_err, s_go, s_j;
     const int tid = threadIdx.x;
     const int64_t q = blockIdx.x;
@@ -220,7 +129,7 @@ template <class T> __global__ __launch_bounds__(kXbThreads) void k_xb_between(Xb
         if (!end) {
             if (tid == 0) s_j = (int)nv;
             __syncthreads();
-            for (int64_t j = tid; j < nv; j += kXbThreads) {
+            for (int64_t j = tid; j < nv; j += kXThreads) {
                 if (A[i * C + j] == 0) continue;
                 bool basic = false;
                 for (int64_t k = 0; k < m && !basic; ++k) basic = basis[k] == j;
@@ -235,7 +144,7 @@ template <class T> __global__ __launch_bounds__(kXbThreads) void k_xb_between(Xb
         }
         const int64_t j = s_j;
         if (tid == 0) {
-            xb_record<T>(&rec, A, C, j, i, D);
+            x_record<T>(&rec, A, C, j, i, D);
             s_err = 0;
             basis[i] = j;
         }
@@ -247,7 +156,7 @@ template <class T> __global__ __launch_bounds__(kXbThreads) void k_xb_between(Xb
             return;
         }
     }
-    // the hand-over (src/simplex.lisp:437-451), k_x_handover's arithmetic with w_i = cl[basis[i]]
+    // the hand-over (src/simplex.lisp:437-451): x_handover_column with w_i = cl[basis[i]]
     T *Mm = (T *)mt.T + q * (int64_t)R * Cm;
     const T *cl = (const T *)mt.aux + q * (int64_t)(Cm + 1);
     const T lc = cl[Cm];
@@ -255,26 +164,12 @@ template <class T> __global__ __launch_bounds__(kXbThreads) void k_xb_between(Xb
     T *w = col;
     int64_t *mbasis = mt.basis + q * m;
     if (tid == 0) s_err = lc == 0 ? kXOverflow : 0;
-    for (int64_t i = tid; i < m; i += kXbThreads) { w[i] = cl[basis[i]]; mbasis[i] = basis[i]; }
+    for (int64_t i = tid; i < m; i += kXThreads) { w[i] = cl[basis[i]]; mbasis[i] = basis[i]; }
     __syncthreads();
     int err = 0;
     if (s_err == 0)
-        for (int j = tid; j < Cm; j += kXbThreads) {
-            const int64_t src = j < nv ? j : nav;
-            auto acc = xmul(Da, cl[j]);
-            bool ok = true;
-            for (int64_t r = 0; r < m; ++r) {
-                const T x = A[r * C + src];
-                T y = 0;
-                if (!xfit(xmul(lc, x), &y)) ok = false;
-                Mm[r * Cm + j] = y;
-                if (!xsub_ovf(acc, xmul(w[r], x))) ok = false;
-            }
-            T o = 0;
-            if (!xfit(acc, &o)) ok = false;
-            Mm[m * Cm + j] = o;
-            if (!ok) err = kXOverflow;
-        }
+        for (int j = tid; j < Cm; j += kXThreads)
+            if (!x_handover_column<T>(A, C, Mm, Cm, m, j, Da, w, cl, lc)) err = kXOverflow;
     if (err) atomicMax(&s_err, err);
     __syncthreads();
     if (tid == 0) {
@@ -301,12 +196,14 @@ size_t xb_snapshot_bytes(const XbView &v) { return (size_t)(v.rows + v.cols) * (
 void launch_xb_solve(const XbView &v, int is_max, int64_t launch_cap, hipStream_t s)
 {
     const size_t lds = xb_snapshot_bytes(v);
-    if (v.bits == 64) hipLaunchKernelGGL(k_xb_solve<int64_t>, dim3((unsigned)v.n), dim3(kXbThreads), lds, s, v, is_max, launch_cap);
-    else              hipLaunchKernelGGL(k_xb_solve<__int128>, dim3((unsigned)v.n), dim3(kXbThreads), lds, s, v, is_max, launch_cap);
+    x_with_width(v.bits, [&](auto t) {
+        hipLaunchKernelGGL(k_xb_solve<decltype(t)>, dim3((unsigned)v.n), dim3(kXThreads), lds, s, v, is_max, launch_cap);
+    });
 }
 void launch_xb_between(const XbView &art, const XbView &mt, hipStream_t s)
 {
     const size_t lds = xb_snapshot_bytes(art);
-    if (art.bits == 64) hipLaunchKernelGGL(k_xb_between<int64_t>, dim3((unsigned)art.n), dim3(kXbThreads), lds, s, art, mt);
-    else                hipLaunchKernelGGL(k_xb_between<__int128>, dim3((unsigned)art.n), dim3(kXbThreads), lds, s, art, mt);
+    x_with_width(art.bits, [&](auto t) {
+        hipLaunchKernelGGL(k_xb_between<decltype(t)>, dim3((unsigned)art.n), dim3(kXThreads), lds, s, art, mt);
+    });
 }

@@ -335,21 +335,25 @@ void   set_resident_poll(int mode);     // tuning hook: who polls the exchange r
 // double-width intermediates.
 constexpr int32_t kXOverflow = 110;    // a value left the width in use: restart wider or MI_EXACT_OVERFLOW
 constexpr int32_t kXInexact  = 111;    // a Bareiss division left a remainder: a bug (MI_EXACT_INEXACT)
+constexpr int     kXThreads  = 256;    // workgroup size of every exact kernel that prices, tests ratios or snapshots
+// the pivot being applied (x_record): in XCtl for the single tableau, in LDS for a batch member
+struct XPivot {
+    int64_t  ec, cr;      // the pivot
+    int32_t  sgn, shift;  // its sign; trailing zero bits of dold
+    __int128 pa;          // |pivot|
+    __int128 dold;        // D before the pivot
+    __int128 inv;         // inverse of the odd part of dold modulo 2^W
+};
 struct XCtl {
     int32_t  status;      // kRunning, or MI_OPTIMAL / MI_UNBOUNDED / MI_MAX_PIVOTS / kXOverflow / kXInexact
     int32_t  err;         // 0, or kXOverflow / kXInexact raised by an update (the larger one wins)
     int32_t  apply;       // the last select / force chose a pivot for the update that follows it
-    int32_t  sgn;         // sign of that pivot
-    int32_t  shift;       // trailing zero bits of dold
     int32_t  pad_;
-    int64_t  ec, cr;      // the pivot
     int64_t  n_pivots;    // pivots chosen by k_x_select since the tableau's start (cumulative)
     int64_t  cap_at;      // k_x_select stops with MI_MAX_PIVOTS once n_pivots reaches it (0: no cap)
     int64_t  trace_n;     // pivots recorded (trace buffers hold the first trace_cap)
     __int128 D;           // the common denominator, > 0
-    __int128 dold;        // D before the pivot being applied
-    __int128 pa;          // |pivot|
-    __int128 inv;         // inverse of the odd part of dold modulo 2^W
+    XPivot   piv;         // that pivot (device only)
 };
 struct XView {
     void    *T;           // rows x cols, row-major, no padding

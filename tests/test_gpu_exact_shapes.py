@@ -10,6 +10,7 @@ tests/test_exact_host.py): every case is compared pivot for pivot (trace), then 
 entry of T.  What a case must reach -- pivot counts, ties, widths -- is asserted from the model before
 the GPU runs, so a changed generator cannot quietly drop the coverage."""
 import ctypes
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -213,6 +214,37 @@ def test_planted_ties_lowest_index_wins(is_max, place):
     assert trace[0] == (cols[0], rows[0])
     _later_duplicates_differ(T, basis, nv, is_max, cols, rows, model, trace, k)
     _run(T, basis, is_max, model, st, trace, max_pivots=k)
+
+
+def test_planted_ties_in_a_tableau_below_half_a_workgroup():
+    """90 variables, 40 constraints: both reduction trees of k_x_select start below the workgroup size (at
+    128 and at 64), and the tie clause decides ("odd": see TIE_PLACES).  Trace and entries against the
+    Fraction oracle, at 64 bits and at 128."""
+    m, n, k = 40, 50, 8
+    cols, rows = [21, 22, 49], [11, 12, 39]
+    T, basis = ec.slack_tableau(m, n, 11, rhs=(2, 9))
+    nv = n + m
+    plant_price_tie(T, cols, True)
+    plant_ratio_tie(T, cols[0], rows)
+    _assert_ties(T, nv, True, cols, rows)
+    _assert_tie_clause_decides(T, nv, True, cols, rows)
+    t = rr.Tableau([[Fraction(int(x)) for x in row] for row in T], basis.tolist(), nv, m, {}, True)
+    trace = []
+    for _ in range(k):
+        e = rr.price(t)
+        trace.append((e, rr.ratio(t, e)))
+        rr.pivot(t, *trace[-1])
+    assert trace[0] == (cols[0], rows[0])
+    for min_bits, bits in ((0, 64), (128, 128)):
+        x = XTab(T, basis, min_bits)
+        try:
+            assert x.solve(True, k) == (lp.capi.MI_MAX_PIVOTS, k), lp.capi.lib().mi355x_last_error()
+            assert x.trace() == trace and x.bits == bits
+            Tx, D, b = x.state()
+            assert b == t.basis
+            assert [[Fraction(int(v), D) for v in row] for row in Tx.tolist()] == t.matrix
+        finally:
+            x.close()
 
 
 # ---- tall: ratio-test strides, gridDim.y capped at 4 096 with a y-stride
