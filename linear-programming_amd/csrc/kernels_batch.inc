@@ -142,7 +142,8 @@ __global__ __launch_bounds__(kLpThreads) void k_batch_solve(TabView t, double sg
 
 // ---- the same with blocked pivoting (compact representation) --------------------------------
 // One workgroup streams its LP at (bytes in flight) / (memory latency) ~ 30 GB/s, so a pivot of a
-// 1 MB tableau costs ~70 us however the loop is written.  Blocked as in k_la_block / k_sweep, but
+// 1 MB tableau costs ~70 us however the loop is written.  Blocked as in k_la_block / k_sweep (every
+// chain link in its general form: la_link / la_link2, kernels_la_common.inc), but
 // with everything inside the one workgroup: the look-ahead state of up to KB pending pivots
 // (col_i, prow_i), the running objective row, RHS column and column map live in LDS, a look-ahead
 // step is two memory round trips (one strided column, one row) and two workgroup reductions, and
@@ -276,12 +277,8 @@ __global__ __launch_bounds__(kBbThreads) void k_batch_block(TabView t, double sg
                             prod[kk] = ci * pa[kk];                    // rounded product
                         }
 #pragma unroll
-                        for (int kk = 0; kk < 4; ++kk) {
-                            const bool is_cr = (rmb >> (i0 + kk)) & 1u;
-                            if ((slmask >> (i0 + kk)) & 1u) a = is_cr ? 1.0 : 0.0;
-                            const double d = a - prod[kk];             // rounded difference
-                            a = is_cr ? pa[kk] : d;
-                        }
+                        for (int kk = 0; kk < 4; ++kk)                     // every link in the general form
+                            a = la_link(a, (slmask >> (i0 + kk)) & 1u, (rmb >> (i0 + kk)) & 1u, prod[kk], pa[kk]);
                     }
                 }
                 s_col[(int64_t)J * rp + r] = a;
@@ -326,14 +323,9 @@ __global__ __launch_bounds__(kBbThreads) void k_batch_block(TabView t, double sg
                             prod[kk].y = ccr * pii[kk].y;
                         }
 #pragma unroll
-                        for (int kk = 0; kk < 4; ++kk) {
-                            const bool is_cr = (crmask >> (i0 + kk)) & 1u;
-                            if ((smb >> (i0 + kk)) & 1u)      y.x = is_cr ? 1.0 : 0.0;
-                            if ((smb >> (16 + i0 + kk)) & 1u) y.y = is_cr ? 1.0 : 0.0;
-                            const double dx = y.x - prod[kk].x, dy = y.y - prod[kk].y;
-                            y.x = is_cr ? pii[kk].x : dx;
-                            y.y = is_cr ? pii[kk].y : dy;
-                        }
+                        for (int kk = 0; kk < 4; ++kk)
+                            y = la_link2(y, (smb >> (i0 + kk)) & 1u, (smb >> (16 + i0 + kk)) & 1u,
+                                         (crmask >> (i0 + kk)) & 1u, prod[kk], pii[kk]);
                     }
                 }
                 const double2 pr = scale_pair(t, p, y, piv, slot);

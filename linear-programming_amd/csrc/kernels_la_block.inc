@@ -1,5 +1,6 @@
 // kernels_la_block.inc -- the look-ahead of a whole block as ONE persistent launch (k_la_block)
-// and its hand-off protocol.
+// and its hand-off protocol.  The chains, the record format, the workgroup record's front half and
+// the bookkeeping it shares with k_shard_la_block: kernels_la_common.inc.
 // Part of simplex_kernels.hip (ONE translation unit: included there, in this order, inside namespace mi355x).
 
 // ---- the look-ahead of a whole block as ONE launch ------------------------------------------
@@ -40,16 +41,6 @@
 //     HW_REG_XCC_ID, and only if they all agree do the later stores become plain stores that stay
 //     in the one shared L2 (where the sc1 loads find them a fabric round trip sooner).
 struct LaMsg { ValIdx c; unsigned flag, same; double u, w; };
-struct LaWaveRec { double v; int i; unsigned f; int64_t s; double u, x2; };   // a wave's winner on its way into the workgroup's record
-
-__device__ __forceinline__ double lane_value_dyn(double v, int lane)    // lane: uniform, run-time
-{
-    return lane_value(v, __builtin_amdgcn_readfirstlane(lane));
-}
-__device__ __forceinline__ int64_t lane_value_dyn(int64_t v, int lane)
-{
-    return lane_value(v, __builtin_amdgcn_readfirstlane(lane));
-}
 
 template <class T> __device__ __forceinline__ void st_wt(T *p, T v)
 {
@@ -75,9 +66,6 @@ __device__ __forceinline__ unsigned xcc_id()
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
     return v & 0xfu;
 }
-
-constexpr int kLaThreads = 256;
-constexpr unsigned kEmptyIdx = 0x7fffffffu;
 
 // a 16-byte aligned pair of granules as ONE 16-byte access (every granule is validated on its own,
 // and a naturally aligned 16-byte access never tears an aligned 8-byte half)
@@ -169,118 +157,6 @@ __device__ __forceinline__ void load_granules2(unsigned long long (&g)[8], unsig
                  : "v"(b0), "v"(b1) : "memory");
 }
 
-__device__ __forceinline__ unsigned long long dbits(double x) { return (unsigned long long)__double_as_longlong(x); }
-__device__ __forceinline__ double join_bits(unsigned long long lo, unsigned long long hi)
-{
-    return __longlong_as_double((long long)(((hi & 0xffffffffull) << 32) | (lo & 0xffffffffull)));
-}
-
-// The reductions of the look-ahead move (value, 32-bit index) pairs only -- half the DPP /
-// ds_bpermute traffic of a ValIdx -- and fetch the winner's payload from the lane that holds it
-// afterwards (indices are unique, so that lane is).  Same decision rule, same tree as
-// vi_min / wave_reduce_min.
-struct Cand { double v; int i; };                                // i < 0: empty
-__device__ __forceinline__ Cand cand_min(Cand a, Cand b)
-{
-    const bool a_empty = a.i < 0, b_empty = b.i < 0;
-    const bool better  = (b.v < a.v) | ((b.v == a.v) & (b.i < a.i));
-    const bool take_b  = a_empty | (!b_empty & better);
-    Cand r;
-    r.v = take_b ? b.v : a.v;
-    r.i = take_b ? b.i : a.i;
-    return r;
-}
-template <int CTRL> __device__ __forceinline__ Cand dpp_cand(Cand x)
-{
-    Cand y;
-    y.v = __longlong_as_double(dpp64<CTRL>(__double_as_longlong(x.v)));
-    y.i = __builtin_amdgcn_update_dpp(x.i, x.i, CTRL, 0xf, 0xf, false);
-    return y;
-}
-__device__ __forceinline__ Cand shfl_down_cand(Cand x, int off)
-{
-    Cand y;
-    y.v = __shfl_down(x.v, off, 64);
-    y.i = __shfl_down(x.i, off, 64);
-    return y;
-}
-// winner of the wave in EVERY lane, plus the lane that holds it (-1: all empty)
-__device__ __forceinline__ Cand wave_reduce_cand(Cand x, int &src)
-{
-    const int mine = x.i;
-    x = cand_min(x, shfl_down_cand(x, 32));
-    x = cand_min(x, shfl_down_cand(x, 16));
-    x = cand_min(x, dpp_cand<0x108>(x));
-    x = cand_min(x, dpp_cand<0x104>(x));
-    x = cand_min(x, dpp_cand<0x102>(x));
-    x = cand_min(x, dpp_cand<0x101>(x));
-    x.v = lane_value(x.v, 0);
-    x.i = __builtin_amdgcn_readfirstlane(x.i);
-    const unsigned long long m = __ballot((mine == x.i) & (x.i >= 0));
-    src = m ? (int)__ffsll((long long)m) - 1 : -1;
-    return x;
-}
-__device__ __forceinline__ int64_t lane_pick(int64_t v, int src) { return lane_value_dyn(v, src < 0 ? 0 : src); }
-__device__ __forceinline__ double  lane_pick(double v, int src)  { return lane_value_dyn(v, src < 0 ? 0 : src); }
-__device__ __forceinline__ int     lane_pick(int v, int src)
-{
-    return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(src < 0 ? 0 : src));
-}
-
-// The same arg-min in ~30 instead of ~140 instructions for the common case -- no NaN among the
-// wave's candidates and a unique minimum: the minimum VALUE by a butterfly of v_min_f64 (gfx950's
-// v_permlane32_swap / v_permlane16_swap across the rows of 16 lanes, DPP row rotations inside
-// them; every lane ends up with it), then the lane that holds it by a ballot.  Without NaNs the
-// lexicographic (value, index) minimum is unique and independent of the reduction order, so this
-// IS the tree's winner; with a NaN candidate (vi_min is then order dependent) or an exact tie
-// (lowest index decides) the tree itself runs.
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double min_f64(double a, double b)     // operands are never NaN here
-{
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ double wave_allmin_f64(double x)
-{
-    {   // lanes l and l ^ 32: whichever half a swap puts where, {r.x, r.y} is the pair in every lane
-        const long long b = __double_as_longlong(x);
-        const unsigned lo = (unsigned)b, hi = (unsigned)((unsigned long long)b >> 32);
-        const v2u l2 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const v2u h2 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        x = min_f64(__longlong_as_double((long long)(((unsigned long long)h2.x << 32) | l2.x)),
-                    __longlong_as_double((long long)(((unsigned long long)h2.y << 32) | l2.y)));
-    }
-    {   // rows 0 <-> 1, 2 <-> 3
-        const long long b = __double_as_longlong(x);
-        const unsigned lo = (unsigned)b, hi = (unsigned)((unsigned long long)b >> 32);
-        const v2u l2 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-        const v2u h2 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        x = min_f64(__longlong_as_double((long long)(((unsigned long long)h2.x << 32) | l2.x)),
-                    __longlong_as_double((long long)(((unsigned long long)h2.y << 32) | l2.y)));
-    }
-    x = min_f64(x, __longlong_as_double(dpp64<0x128>(__double_as_longlong(x))));   // row_ror:8
-    x = min_f64(x, __longlong_as_double(dpp64<0x124>(__double_as_longlong(x))));   // row_ror:4
-    x = min_f64(x, __longlong_as_double(dpp64<0x122>(__double_as_longlong(x))));   // row_ror:2
-    x = min_f64(x, __longlong_as_double(dpp64<0x121>(__double_as_longlong(x))));   // row_ror:1
-    return x;
-}
-__device__ __forceinline__ Cand wave_argmin(Cand x, int &src)
-{
-    const bool valid = x.i >= 0;
-    if (__any(valid & (x.v != x.v))) return wave_reduce_cand(x, src);
-    const double key = valid ? x.v : __builtin_huge_val();
-    const double vmin = wave_allmin_f64(key);
-    const unsigned long long mask = __ballot(valid & (key == vmin));
-    if (__popcll(mask) > 1) return wave_reduce_cand(x, src);
-    src = mask ? (int)__ffsll((long long)mask) - 1 : -1;
-    Cand r;
-    r.v = lane_pick(x.v, src);
-    r.i = mask ? lane_pick(x.i, src) : -1;
-    if (!mask) r.v = 0.0;
-    return r;
-}
-
 // Exchange of one reduction between the workgroups.  `mine` is this thread's candidate.  Every
 // WAVE reduces its 64 candidates (tree of wave_reduce_min) and publishes its winner at once as
 // record 4 w + wave -- together with two doubles it picks out of its lanes' registers
@@ -289,9 +165,8 @@ __device__ __forceinline__ Cand wave_argmin(Cand x, int &src)
 // reduces them (tree again) and hands the winner to the other waves through LDS, with the first
 // double of the winner's own record and the second double (PRICE) / first double (RATIO) of
 // record rec_from.
-// PRICE: granules v v i s u u w w   (s = slot: 32 bits)      RATIO: v v i|flag s s u u -
+// The record's format: pack_rec / decode_rec (kernels_la_common.inc); granule 7 of a RATIO record is 0 here.
 // false: a record did not arrive within max_spins polls.
-constexpr int kLaWaves = kLaThreads / 64;
 // true: every wave collects the records itself (no LDS hop, no workgroup barrier left in the
 // kernel; four times the poll traffic on the one L2).  With a record per 64-byte line that lost
 // (rounds 2 - 4: 149 us per block of 16 at config 3 against 122 us with the first wave of a workgroup
@@ -300,27 +175,10 @@ constexpr int kLaWaves = kLaThreads / 64;
 // pivots/s against 81.9 k.
 constexpr bool kLaEveryWavePolls = true;
 
-template <bool PRICE>
-__device__ __forceinline__ void decode_rec(const unsigned long long (&g)[8], bool valid, Cand &x, int64_t &xs,
-                                           unsigned &fl, double &ru, double &rw)
-{
-    const unsigned iw = (unsigned)g[2];
-    x.v = 0.0; x.i = -1; xs = 0; fl = 0u;
-    if (valid) {
-        x.v = join_bits(g[0], g[1]);
-        x.i = (iw & kEmptyIdx) == kEmptyIdx ? -1 : (int)(iw & kEmptyIdx);
-        xs = PRICE ? (int64_t)(g[3] & 0xffffffffull) : (int64_t)(((g[4] & 0xffffffffull) << 32) | (g[3] & 0xffffffffull));
-        fl = iw >> 31;
-    }
-    ru = PRICE ? join_bits(g[4], g[5]) : join_bits(g[5], g[6]);
-    rw = PRICE ? join_bits(g[6], g[7]) : 0.0;
-}
-
 // WGR (more than kLaWaveRecordsMaxNw workgroups): ONE record per workgroup -- the four waves' winners meet in
-// LDS (s_wv), the first wave reduces them (same rule; the minimum does not depend on the shape of the
-// tree), publishes record w, collects the nw records and hands the result on through s_res.  The two
-// doubles that ride along: the winner's own one from the winning wave, the "from" one (record rec_from)
-// from wave wave_from of workgroup rec_from.
+// LDS and the first wave reduces them (wg_record), publishes record w, collects the nw records and
+// hands the result on through s_res.  The two doubles that ride along: the winner's own one from the
+// winning wave, the "from" one (record rec_from) from wave wave_from of workgroup rec_from.
 template <bool PRICE, bool WGR = false, class Extra>
 __device__ __forceinline__ bool la_exchange(ValIdx mine, unsigned myflag, ExchRec *recs, int nw, int w,
                                             unsigned tag, unsigned max_spins, bool mute, bool local,
@@ -342,37 +200,11 @@ __device__ __forceinline__ bool la_exchange(ValIdx mine, unsigned myflag, ExchRe
         extra(win, src, u, x2);
         bool pub = !mute;
         if (WGR) {
-            if (lane == 0) { LaWaveRec r; r.v = c.v; r.i = c.i; r.f = wf; r.s = cs; r.u = u; r.x2 = x2; s_wv[wave] = r; }
-            __syncthreads();
+            wg_record<PRICE>(s_wv, c, wf, cs, u, x2, w == rec_from, wave_from);   // (one barrier)
             pub = pub && wave == 0;
-            if (wave == 0) {
-                int ww = 0;
-                c.v = s_wv[0].v; c.i = s_wv[0].i; wf = s_wv[0].f;
-#pragma unroll
-                for (int k = 1; k < kLaWaves; ++k) {
-                    Cand o; o.v = s_wv[k].v; o.i = s_wv[k].i;
-                    const Cand r = cand_min(c, o);
-                    ww = (r.i != c.i) ? k : ww;                       // (indices are unique; two empty candidates: either)
-                    c = r;
-                    wf |= s_wv[k].f;
-                }
-                cs = s_wv[ww].s;
-                const bool from_here = w == rec_from;
-                if (PRICE) { u = s_wv[ww].u; x2 = from_here ? s_wv[wave_from].x2 : 0.0; }
-                else       { u = from_here ? s_wv[wave_from].u : 0.0; x2 = 0.0; }
-            }
         }
         if (pub) {
-            const unsigned long long vb = dbits(c.v), sb = (unsigned long long)cs, ub = dbits(u), wb = dbits(x2);
-            const unsigned iw = (c.i < 0 ? kEmptyIdx : (unsigned)c.i) | (wf ? 0x80000000u : 0u);
-            const unsigned word[8] = { (unsigned)vb, (unsigned)(vb >> 32), iw, (unsigned)sb,
-                                       PRICE ? (unsigned)ub : (unsigned)(sb >> 32),
-                                       PRICE ? (unsigned)(ub >> 32) : (unsigned)ub,
-                                       PRICE ? (unsigned)wb : (unsigned)(ub >> 32),
-                                       PRICE ? (unsigned)(wb >> 32) : 0u };
-            unsigned val = word[0];                              // lane k stores granule k
-#pragma unroll
-            for (int k = 1; k < 8; ++k) val = lane == k ? word[k] : val;
+            const unsigned val = pack_rec<PRICE>(c, wf, cs, u, x2, lane);
             // granule `lane` of record w * 4 + wave: G[lane][record] (transposed layout, see load_granules)
             if (lane < 8) st_x(reinterpret_cast<unsigned long long *>(recs) + lane * kMaxLaRecords + (WGR ? w : w * kLaWaves + wave),
                                ((unsigned long long)tag << 32) | val, local);
@@ -447,15 +279,7 @@ __device__ __forceinline__ bool la_exchange(ValIdx mine, unsigned myflag, ExchRe
 // The steps are a run-time loop (fully unrolled the kernel was 300 KB of straight-line code and
 // ran at the speed of instruction-cache misses): per-thread col_i[row] / prow_i[pair] of the
 // pending pivots live in LDS ([pivot][thread]: conflict-free), everything else in registers.
-//
-// With ONE wave per SIMD every instruction of the critical wave costs its full issue + latency,
-// so the chains through the pending pivots are written for instruction count: the product of a
-// link does not depend on the chained value (J independent multiplications, then J dependent
-// subtractions), the two rare exceptions of a link -- the element lies on pending pivot i's row /
-// in the slot it gave up -- are bit tests on masks the thread keeps anyway (my_rm, my_sm) plus a
-// wave-uniform mask over the pending pivots, and a wave none of whose lanes is an exception runs
-// the bare chain.  Links i >= J of a group of four are exact identities (operands 0.0:
-// x - (+0.0) == x bit for bit).
+// The chains through the pending pivots: la_chain_col / la_chain_row (kernels_la_common.inc).
 // one_xcd: see above.  fault > 0 (test hook): the last workgroup stops publishing from step
 // `fault - 1` on, as a workgroup that is not resident would.
 // WGR: the form for more than kLaWaveRecordsMaxNw workgroups (records per workgroup, one polling wave; never one XCD).
@@ -493,17 +317,9 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
     const int wave_vc = (g_vc / 64) % kLaWaves, wave_m = (g_m / 64) % kLaWaves;
     const bool wave_has_vc = (int)(g / 64) == g_vc / 64, wave_has_m = (int)(g / 64) == g_m / 64;
 
-    // a new block starts (whatever the status): pending list, stamp (the sweep applies the list
-    // only under this launch's stamp -- had the leader's workgroup never run, the list would be
-    // the previous block's) and this thread's OWN mask words, which only it ever writes
-    // (not behind a launch that lost an exchange: the host's recovery reads that launch's list)
-    if (leader && c0.status != kSyncLost) { blk->n_pending = 0; blk->stamp = epoch_base; }
     unsigned my_rm = 0u;                 // bit i: my row is pivot row i
     unsigned long long my_sm = 0ull;     // bits i, 32 + i: my pair's even / odd column is the slot pivot i gave up
-    if (g < t.bk_stride) t.bk_rmask[g] = 0u;
-    // (both slot masks whatever KMAX: a wide sweep ORs the second one in, and a block of <= 16 pivots
-    // behind an earlier block of 24 on the same handle must not see that block's bits 16 .. 23)
-    if (g < ldv)         { t.bk_smask[g] = 0u; if (t.bk_smask2) t.bk_smask2[g] = 0u; }
+    la_block_begin(t, c0, leader, g, epoch_base);
     // every way out of the launch records how many steps this workgroup COMPLETED (its col_i /
     // prow_i entries stored): the sweep applies no pivot that some workgroup did not finish
     // Where every WAVE polls for itself (up to kLaWaveRecordsMaxNw workgroups) a wave can time out on its own:
@@ -518,12 +334,7 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
     };
     if (c0.status != kRunning) return;       // (nothing pending; behind a lost exchange `done` belongs to that launch)
     if (tid == 0) s_left = 0x7fffffff;
-    // my entries of the pending columns / rows start out as +0.0: a group of four links that reaches past
-    // the last pending pivot then multiplies (+0.0) x (+0.0) for the missing ones -- x - (+0.0) == x bit for
-    // bit -- without a compare and two to four selects per LINK to zero stale operands (48 LDS stores per
-    // thread and launch against ~3 of ~9 instructions per link of both chains of every step)
-#pragma unroll
-    for (int i = 0; i < KMAX; ++i) { s_ci[i][tid] = 0.0; s_pi[i][tid] = make_double2(0.0, 0.0); }
+    la_zero_pending(s_ci, s_pi);
     __syncthreads();                                             // (s_left: the launch's only barrier outside leave / the WGR exchanges)
 
     double  b = (has_row && r < m) ? t.M[r * ld + vc] : 0.0;     // RHS entry of my row
@@ -596,55 +407,13 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
         // ---- entering column through the pending chain; RHS entry brought up to date
         double a = has_row ? t.M[r * ld + slot] : 0.0;
         double v_pa = (lane < J - 1) ? ld_l2(&t.bk_prow[(int64_t)lane * ld + slot]) : 0.0;
-        // my row's entries of the pending columns: requested from LDS NOW, so that they travel with
-        // the loads above instead of group by group inside the chain (round 4: at 24 pending pivots
-        // six dependent LDS round trips per chain)
-        double ci_all[KMAX];
-#pragma unroll
-        for (int i0 = 0; i0 < KMAX; i0 += 4) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) ci_all[i0 + k] = 0.0;
-            if (i0 < J) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) ci_all[i0 + k] = s_ci[i0 + k][tid];   // (i0 + k >= J: still the launch's +0.0)
-            }
-        }
+        double ci_all[KMAX];           // my row's entries of the pending columns: they travel with the loads above
+        la_prefetch(ci_all, s_ci, J);
         drain_vmem();                  // the loads -- and what this wave stored in the previous half-step
         if (lane == J - 1) v_pa = e.u;
         if (J > 0) b = pend(b, false, (my_rm >> (J - 1)) & 1u, s_ci[J - 1][tid], e.w);
-        {
-            // pending pivots whose given-up slot is the entering column's slot (uniform); lanes on a pending pivot row
-            const unsigned slmask = (unsigned)__ballot((lane < J) & (v_sl == slot));
-            const unsigned gen = slmask | wave_rm;                         // links that need the general form
-#pragma unroll
-            for (int i0 = 0; i0 < KMAX; i0 += 4) {
-                if (i0 < J) {
-                    double prod[4], pa[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const double ci = ci_all[i0 + k];              // (+0.0 from i0 + k == J on: zeroed at the launch's start)
-                        pa[k] = lane_value(v_pa, i0 + k);
-                        prod[k] = ci * pa[k];                          // rounded product
-                    }
-                    if (((gen >> i0) & 0xfu) == 0u) {                  // (uniform) the bare chain: ONE branch per four links
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) a = a - prod[k];   // rounded differences
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if ((gen >> (i0 + k)) & 1u) {              // (uniform; rare)
-                                const bool is_cr = (my_rm >> (i0 + k)) & 1u;
-                                if ((slmask >> (i0 + k)) & 1u) a = is_cr ? 1.0 : 0.0;
-                                const double d = a - prod[k];
-                                a = is_cr ? pa[k] : d;
-                            } else {
-                                a = a - prod[k];                       // rounded difference
-                            }
-                        }
-                    }
-                }
-            }
-        }
+        // pending pivots whose given-up slot is the entering column's slot (uniform)
+        a = la_chain_col<KMAX>(a, ci_all, v_pa, J, my_rm, (unsigned)__ballot((lane < J) & (v_sl == slot)), wave_rm);
         s_ci[J][tid] = a;
         ValIdx q; q.v = 0.0; q.i = -1; q.s = 0;
         unsigned bad = 0u;
@@ -691,56 +460,10 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
         const bool own = has_pair && (p == (slot >> 1));
         const int64_t leaving = own ? ld_l2(&t.basis[cr]) : -1;
         double2 pi_all[KMAX];          // my pair's entries of the pending rows: as ci_all above
-#pragma unroll
-        for (int i0 = 0; i0 < KMAX; i0 += 4) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) pi_all[i0 + k] = make_double2(0.0, 0.0);
-            if (i0 < J) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) pi_all[i0 + k] = s_pi[i0 + k][tid];
-            }
-        }
+        la_prefetch(pi_all, s_pi, J);
         drain_vmem();                  // the loads -- and the col_J entry stored above
-        {
-            // pending pivots whose pivot row is the new pivot row (uniform); lanes holding a given-up slot
-            const unsigned crmask = (unsigned)__ballot((lane < J) & (v_cr == cr));
-            const unsigned gen = crmask | wave_sm;                         // links that need the general form
-#pragma unroll
-            for (int i0 = 0; i0 < KMAX; i0 += 4) {
-                if (i0 < J) {
-                    double2 pii[4], prod[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        pii[k] = pi_all[i0 + k];                       // (+0.0 pairs from i0 + k == J on, as ci_all)
-                        const double ccr = lane_value(v_ccr, i0 + k);
-                        prod[k].x = ccr * pii[k].x;                    // rounded products
-                        prod[k].y = ccr * pii[k].y;
-                    }
-                    if (((gen >> i0) & 0xfu) == 0u) {                  // (uniform) the bare chain: ONE branch per four links
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            y.x = y.x - prod[k].x;
-                            y.y = y.y - prod[k].y;
-                        }
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if ((gen >> (i0 + k)) & 1u) {              // (uniform; rare)
-                                const bool is_cr = (crmask >> (i0 + k)) & 1u;
-                                if ((my_sm >> (i0 + k)) & 1ull)      y.x = is_cr ? 1.0 : 0.0;
-                                if ((my_sm >> (32 + i0 + k)) & 1ull) y.y = is_cr ? 1.0 : 0.0;
-                                const double dx = y.x - prod[k].x, dy = y.y - prod[k].y;
-                                y.x = is_cr ? pii[k].x : dx;
-                                y.y = is_cr ? pii[k].y : dy;
-                            } else {
-                                y.x = y.x - prod[k].x;
-                                y.y = y.y - prod[k].y;
-                            }
-                        }
-                    }
-                }
-            }
-        }
+        // pending pivots whose pivot row is the new pivot row (uniform)
+        y = la_chain_row<KMAX>(y, pi_all, v_ccr, J, my_sm, (unsigned)__ballot((lane < J) & (v_cr == cr)), wave_sm);
         pr = make_double2(0.0, 0.0);
         if (has_pair) {
             pr = scale_pair(t, p, y, piv, slot);
@@ -757,9 +480,7 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
             st_x(&t.l2p[ec], (int64_t)-1, local);
             st_x(&t.basis[cr], ec, local);                       // src/simplex.lisp:358
             my_sm |= 1ull << (J + 32 * (int)(slot & 1));
-            // (the sweeps' layout, slot_mask_set: pivots 0 .. 15 in bk_smask, 16 .. 31 in bk_smask2)
-            if (J < 16) t.bk_smask[p]  = (unsigned)(my_sm & 0xffffull) | ((unsigned)((my_sm >> 32) & 0xffffull) << 16);
-            else        t.bk_smask2[p] = (unsigned)((my_sm >> 16) & 0xffffull) | ((unsigned)((my_sm >> 48) & 0xffffull) << 16);
+            la_store_slot_mask(t, p, my_sm, J);
         }
         if (has_row && r == cr) {
             my_rm |= 1u << J;
@@ -767,19 +488,7 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
         }
         if (__any(has_row && r == cr)) wave_rm |= 1u << J;
         if (__any(own))                wave_sm |= 1u << J;
-        if (leader) {                                            // the one writer of these words
-            const int64_t tn = c0.trace_n + J;
-            ctl->ec = ec;
-            ctl->cr = cr;
-            ctl->slot = slot;
-            if (t.trace_ec && tn < t.trace_cap) { t.trace_ec[tn] = ec; t.trace_cr[tn] = cr; }
-            ctl->trace_n  = tn + 1;
-            ctl->n_pivots = c0.n_pivots + J + 1;
-            blk->cr[J] = cr;
-            blk->slot[J] = slot;
-            blk->ec[J] = ec;
-            blk->n_pending = J + 1;
-        }
+        if (leader) la_commit(t, c0, J, ec, cr, slot);           // the one writer of these words
         if (lane == J) { v_cr = cr; v_sl = slot; }
 #if defined(MI355X_LA_TIMING) && MI355X_LA_TIMING != 2       // (2: publish stamps only, the leader is not slowed down)
         T6 = wall_clock64();

@@ -482,7 +482,7 @@ int shard_la_block_workgroups(const TabView &t)
         t.n_lps != 1 || !t.M)
         return 0;
     const int64_t need = t.rows > (t.ld >> 1) ? t.rows : (t.ld >> 1);
-    const int64_t nw = (need + kShThreads - 1) / kShThreads;
+    const int64_t nw = (need + kLaThreads - 1) / kLaThreads;
     return nw < kMaxShardLaWorkgroups ? (int)nw : 0;         // (the last record line carries the ratio exchange's decision)
 }
 void launch_shard_la_block(const ShardLaunch *dev_shards, int n_local, int nw_max, const P2pLayout &lay, int ksteps,
@@ -492,10 +492,10 @@ void launch_shard_la_block(const ShardLaunch *dev_shards, int n_local, int nw_ma
     const dim3 grid((unsigned)nw_max, (unsigned)n_local);
     const double price_tol = (f / 8.0) * kClEpsilon, ratio_thr = 0.0 + (f / 2.0) * kClEpsilon;
     if (ksteps <= kMaxBlock)
-        hipLaunchKernelGGL(k_shard_la_block<kMaxBlock>, grid, dim3(kShThreads), 0, s, dev_shards, lay, ksteps, sgn_of(is_max),
+        hipLaunchKernelGGL(k_shard_la_block<kMaxBlock>, grid, dim3(kLaThreads), 0, s, dev_shards, lay, ksteps, sgn_of(is_max),
                            price_tol, ratio_thr, epoch_base, xepoch_base, g_la_max_spins, p2p_spins, hop, g_shard_la_fault);
     else
-        hipLaunchKernelGGL(k_shard_la_block<kLaBlockMax>, grid, dim3(kShThreads), 0, s, dev_shards, lay, ksteps, sgn_of(is_max),
+        hipLaunchKernelGGL(k_shard_la_block<kLaBlockMax>, grid, dim3(kLaThreads), 0, s, dev_shards, lay, ksteps, sgn_of(is_max),
                            price_tol, ratio_thr, epoch_base, xepoch_base, g_la_max_spins, p2p_spins, hop, g_shard_la_fault);
 }
 void launch_shard_la_rollback(const TabView &t, int la_nw, hipStream_t s)

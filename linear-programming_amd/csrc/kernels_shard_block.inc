@@ -1,5 +1,7 @@
 // kernels_shard_block.inc -- a column shard's look-ahead of a whole block as ONE persistent launch
-// (k_shard_la_block) and the roll-back of its bookkeeping after a lost exchange.
+// (k_shard_la_block) and the roll-back of its bookkeeping after a lost exchange.  What it has in common
+// with k_la_block -- chains, record format, workgroup record, bookkeeping, thread / wave constants -- is
+// kernels_la_common.inc's; its stores are write-through (st_wt) where k_la_block's are st_x(.., local).
 // Part of simplex_kernels.hip (ONE translation unit: included there, in this order, inside namespace mi355x).
 
 // ---- what a shard's step was, and what it is here ------------------------------------------------
@@ -41,8 +43,6 @@
 // workgroups (later ones only by those that hold pairs): it is the co-residency check, and it precedes
 // the shard's first push -- a shard whose workgroups are not all resident never sends anything, so that
 // every shard then ends the launch with nothing committed.
-constexpr int kShThreads = 256, kShWaves = kShThreads / 64;
-
 struct ShMsg { double v; int i; unsigned flag; int64_t s; double u, w; };   // flag: 1 non-finite, 2 a peer's column lost, 8 timed out
 
 // records l, l + 64, ... of a 64-byte-per-record buffer: four 16-byte loads per record, all in flight, L1
@@ -109,23 +109,6 @@ __device__ __forceinline__ void sh_load4(unsigned long long (&g)[4][8], const Ex
     sh_split(g[0], a0, a1, a2, a3); sh_split(g[1], b0, b1, b2, b3); sh_split(g[2], c0, c1, c2, c3); sh_split(g[3], d0, d1, d2, d3);
 }
 
-// PRICE: granules v v i s u u w w   (s = slot: 32 bits)      RATIO: v v i|bad s s u u lost
-template <bool PRICE>
-__device__ __forceinline__ void sh_decode(const unsigned long long (&g)[8], bool valid, Cand &x, int64_t &xs,
-                                          unsigned &fl, double &ru, double &rw)
-{
-    const unsigned iw = (unsigned)g[2];
-    x.v = 0.0; x.i = -1; xs = 0; fl = 0u;
-    if (valid) {
-        x.v = join_bits(g[0], g[1]);
-        x.i = (iw & kEmptyIdx) == kEmptyIdx ? -1 : (int)(iw & kEmptyIdx);
-        xs = PRICE ? (int64_t)(g[3] & 0xffffffffull) : (int64_t)(((g[4] & 0xffffffffull) << 32) | (g[3] & 0xffffffffull));
-        fl = (iw >> 31) | (PRICE ? 0u : (((unsigned)g[7] & 1u) << 1));
-    }
-    ru = PRICE ? join_bits(g[4], g[5]) : join_bits(g[5], g[6]);
-    rw = PRICE ? join_bits(g[6], g[7]) : 0.0;
-}
-
 // The polling wave: records [0, nrec) until every one carries `tag` (or max_spins polls went by), then the
 // winner (same rule, same result as any other tree: the minimum is unique), its slot / payload, the first
 // double of its own record, and the "from" double (PRICE: second, RATIO: first) of record rec_from.
@@ -165,7 +148,7 @@ __device__ __forceinline__ void sh_poll(const ExchRec *recs, int nrec, unsigned 
     for (int a = 0; a < 4; ++a) {
         if (a < ng) {                                            // (uniform)
             Cand x; int64_t xs; unsigned f; double u, w;
-            sh_decode<PRICE>(g[a], lane + 64 * a < nrec, x, xs, f, u, w);
+            decode_rec<PRICE>(g[a], lane + 64 * a < nrec, x, xs, f, u, w);
             const Cand r = cand_min(best, x);
             const bool took = r.i != best.i;                      // (indices are unique; two empty candidates: either)
             bs = took ? xs : bs;
@@ -188,12 +171,12 @@ __device__ __forceinline__ void sh_poll(const ExchRec *recs, int nrec, unsigned 
 // The same exchange read by ALL FOUR waves of a workgroup, a quarter of the records each (wave k: records
 // k Q .. k Q + Q - 1, Q = ceil(nrec / 4) <= 64: one record per lane, ONE group of four loads), the four partial
 // winners meeting in LDS: the decode of three record groups by one wave was 0.5 us of the ratio exchange's 3.4.
-struct ShPart { double v; int i; unsigned flag; int64_t s; double u, from; };
+// A partial winner is a LaWaveRec whose x2 is the "from" double and whose f also carries 8: timed out.
 template <bool PRICE>
-__device__ __forceinline__ ShPart sh_poll_quarter(const ExchRec *recs, int nrec, unsigned tag, unsigned max_spins, int rec_from, int wave)
+__device__ __forceinline__ LaWaveRec sh_poll_quarter(const ExchRec *recs, int nrec, unsigned tag, unsigned max_spins, int rec_from, int wave)
 {
     const int lane = (int)(threadIdx.x & 63u);
-    const int Q = (nrec + kShWaves - 1) / kShWaves;
+    const int Q = (nrec + kLaWaves - 1) / kLaWaves;
     const int first = wave * Q;
     const int count = nrec - first < Q ? (nrec - first < 0 ? 0 : nrec - first) : Q;
     const bool have = lane < count;
@@ -213,16 +196,16 @@ __device__ __forceinline__ ShPart sh_poll_quarter(const ExchRec *recs, int nrec,
         }
     }
     Cand x; int64_t xs; unsigned f; double u, w;
-    sh_decode<PRICE>(g, have && fine, x, xs, f, u, w);
+    decode_rec<PRICE>(g, have && fine, x, xs, f, u, w);
     int src;
     const Cand b = wave_argmin(x, src);
-    ShPart p;
+    LaWaveRec p;
     p.v = b.v; p.i = b.i;
     p.s = lane_pick(xs, src);
     p.u = lane_pick(u, src);
     const int fl = rec_from - first;                              // the "from" record's lane in this quarter (if it is here)
-    p.from = (fl >= 0 && fl < count) ? lane_value_dyn(PRICE ? w : u, fl) : 0.0;
-    p.flag = (__any((f & 1u) != 0u) ? 1u : 0u) | (__any((f & 2u) != 0u) ? 2u : 0u) | (fine ? 0u : 8u);
+    p.x2 = (fl >= 0 && fl < count) ? lane_value_dyn(PRICE ? w : u, fl) : 0.0;
+    p.f = (__any((f & 1u) != 0u) ? 1u : 0u) | (__any((f & 2u) != 0u) ? 2u : 0u) | (fine ? 0u : 8u);
     return p;
 }
 
@@ -238,7 +221,7 @@ __device__ __forceinline__ void sh_exchange(ValIdx mine, unsigned myflag, ExchRe
                                             unsigned tag, unsigned max_spins, int rec_from, int wave_from,
                                             LaWaveRec *s_wv, Extra extra, bool give_up, ShMsg &out, bool polls = true)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     Cand c; c.v = mine.v; c.i = (int)mine.i;
     int src;
     c = wave_argmin(c, src);
@@ -247,34 +230,10 @@ __device__ __forceinline__ void sh_exchange(ValIdx mine, unsigned myflag, ExchRe
     double u = 0.0, x2 = 0.0;
     ValIdx win; win.v = c.v; win.i = c.i; win.s = cs;
     extra(win, src, u, x2);
-    if (lane == 0) { LaWaveRec r; r.v = c.v; r.i = c.i; r.f = wf; r.s = cs; r.u = u; r.x2 = x2; s_wv[wave] = r; }
-    __syncthreads();
+    wg_record<PRICE>(s_wv, c, wf, cs, u, x2, w == rec_from, wave_from);   // (one barrier)
     if (wave != 0) return;
-    int ww = 0;
-    c.v = s_wv[0].v; c.i = s_wv[0].i; wf = s_wv[0].f;
-#pragma unroll
-    for (int k = 1; k < kShWaves; ++k) {
-        Cand o; o.v = s_wv[k].v; o.i = s_wv[k].i;
-        const Cand r = cand_min(c, o);
-        ww = (r.i != c.i) ? k : ww;
-        c = r;
-        wf |= s_wv[k].f;
-    }
-    cs = s_wv[ww].s;
-    const bool from_here = w == rec_from;
-    if (PRICE) { u = s_wv[ww].u; x2 = from_here ? s_wv[wave_from].x2 : 0.0; }
-    else       { u = from_here ? s_wv[wave_from].u : 0.0; x2 = 0.0; }
     if (publishes) {
-        const unsigned long long vb = dbits(c.v), sb = (unsigned long long)cs, ub = dbits(u), wb = dbits(x2);
-        const unsigned iw = (c.i < 0 ? kEmptyIdx : (unsigned)c.i) | ((wf & 1u) ? 0x80000000u : 0u);
-        const unsigned word[8] = { (unsigned)vb, (unsigned)(vb >> 32), iw, (unsigned)sb,
-                                   PRICE ? (unsigned)ub : (unsigned)(sb >> 32),
-                                   PRICE ? (unsigned)(ub >> 32) : (unsigned)ub,
-                                   PRICE ? (unsigned)wb : (unsigned)(ub >> 32),
-                                   PRICE ? (unsigned)(wb >> 32) : ((wf >> 1) & 1u) };
-        unsigned val = word[0];                                  // lane k stores granule k of record w: ONE 64-byte line
-#pragma unroll
-        for (int k = 1; k < 8; ++k) val = lane == k ? word[k] : val;
+        const unsigned val = pack_rec<PRICE>(c, wf, cs, u, x2, lane);   // lane k stores granule k of record w: ONE 64-byte line
         if (lane < 8) st_wt(&recs[w].g[lane], ((unsigned long long)tag << 32) | val);
     }
     out.v = 0.0; out.i = -1; out.s = 0; out.u = out.w = 0.0; out.flag = 0u;
@@ -317,24 +276,24 @@ __device__ __forceinline__ void sh_decision_poll(const ExchRec *line, unsigned t
 // its own buffer, which is what a shard of a real partition pays minus the wire).  fault: as k_la_block's,
 // applied to the last workgroup of the LAST shard of the launch.
 template <int KMAX>
-__global__ __launch_bounds__(kShThreads) void k_shard_la_block(const ShardLaunch *__restrict__ shards, P2pLayout lay,
+__global__ __launch_bounds__(kLaThreads) void k_shard_la_block(const ShardLaunch *__restrict__ shards, P2pLayout lay,
                                                               int ksteps, double sgn, double price_tol, double ratio_thr,
                                                               unsigned epoch_base, unsigned xepoch_base, unsigned max_spins,
                                                               unsigned p2p_spins, int hop, int fault)
 {
     static_assert(KMAX % 4 == 0 && KMAX <= 24, "groups of four links; 32 + 32 bits of my_sm; 6 KB of LDS per pending pivot");
-    __shared__ double    s_ci[KMAX][kShThreads];
-    __shared__ double2   s_pi[KMAX][kShThreads];
+    __shared__ double    s_ci[KMAX][kLaThreads];
+    __shared__ double2   s_pi[KMAX][kLaThreads];
     __shared__ ShMsg     s_res, s_res2;
-    __shared__ LaWaveRec s_wv[kShWaves];
-    __shared__ ShPart    s_part[kShWaves];
+    __shared__ LaWaveRec s_wv[kLaWaves];
+    __shared__ LaWaveRec s_part[kLaWaves];
     const ShardLaunch &S = shards[blockIdx.y];
     const TabView t = S.t;
     const int w = blockIdx.x;
     const int64_t m = t.rows - 1, vcl = t.cols - 1, ld = t.ld, ldv = ld >> 1;
     const int64_t need = t.rows > ldv ? t.rows : ldv;
-    const int nw = (int)((need + kShThreads - 1) / kShThreads);  // this shard's workgroups (the grid is the widest shard's)
-    const int nwp = (int)((ldv + kShThreads - 1) / kShThreads);  // ... of which these hold column pairs
+    const int nw = (int)((need + kLaThreads - 1) / kLaThreads);  // this shard's workgroups (the grid is the widest shard's)
+    const int nwp = (int)((ldv + kLaThreads - 1) / kLaThreads);  // ... of which these hold column pairs
     if (w >= nw) return;
     Ctl *ctl = t.ctl;
     const Ctl c0 = *ctl;
@@ -344,28 +303,24 @@ __global__ __launch_bounds__(kShThreads) void k_shard_la_block(const ShardLaunch
     const bool compact = t.p2l != nullptr;
     const int64_t bias = compact ? 0 : S.col_offset;             // dense shard: global index of local column 0
     const int rank = S.rank, world = lay.world;
-    const int64_t g = (int64_t)w * kShThreads + tid;
+    const int64_t g = (int64_t)w * kLaThreads + tid;
     const bool has_row = g < t.rows, has_pair = g < ldv;
     const int64_t r = g, p = g;
     const double2 *M2 = reinterpret_cast<const double2 *>(t.M);
     // thread that owns the RHS pair / the objective row: workgroup (= record), wave, lane
     const int g_vc = (int)(vcl >> 1), g_m = (int)m;
-    const int rec_vc = g_vc / kShThreads, rec_m = g_m / kShThreads;
-    const int wave_vc = (g_vc / 64) % kShWaves, wave_m = (g_m / 64) % kShWaves;
+    const int rec_vc = g_vc / kLaThreads, rec_m = g_m / kLaThreads;
+    const int wave_vc = (g_vc / 64) % kLaWaves, wave_m = (g_m / 64) % kLaWaves;
     const bool wave_has_vc = (int)(g / 64) == g_vc / 64, wave_has_m = (int)(g / 64) == g_m / 64;
 
-    // a new block starts (whatever the status): see k_la_block
-    if (leader && c0.status != kSyncLost) { blk->n_pending = 0; blk->stamp = epoch_base; }
     unsigned my_rm = 0u;
     unsigned long long my_sm = 0ull;
-    if (g < t.bk_stride) t.bk_rmask[g] = 0u;
-    if (g < ldv)         { t.bk_smask[g] = 0u; if (t.bk_smask2) t.bk_smask2[g] = 0u; }
+    la_block_begin(t, c0, leader, g, epoch_base);
     auto leave = [&](int steps) {
         if (tid == 0) st_wt(&blk->done[w], (int64_t)(((unsigned long long)epoch_base << 8) | (unsigned)steps));
     };
     if (c0.status != kRunning) return;
-#pragma unroll
-    for (int i = 0; i < KMAX; ++i) { s_ci[i][tid] = 0.0; s_pi[i][tid] = make_double2(0.0, 0.0); }
+    la_zero_pending(s_ci, s_pi);
 
     double  b = (has_row && r < m) ? t.M[r * ld + vcl] : 0.0;    // my row's entry of the shard's RHS copy
     double2 z = has_pair ? M2[m * ldv + p] : make_double2(0.0, 0.0);
@@ -525,15 +480,7 @@ __global__ __launch_bounds__(kShThreads) void k_shard_la_block(const ShardLaunch
         // ---- entering column: the owner chains its entry through the pending pivots and pushes it; the
         // others wait for their row's granules.  My RHS entry through pivot J-1 meanwhile.
         double ci_all[KMAX];
-#pragma unroll
-        for (int i0 = 0; i0 < KMAX; i0 += 4) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) ci_all[i0 + k] = 0.0;
-            if (i0 < J) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) ci_all[i0 + k] = s_ci[i0 + k][tid];
-            }
-        }
+        la_prefetch(ci_all, s_ci, J);
         unsigned lost = 0u;
         if (!mine) {
             // exchange B, consumer: my row's two granules of this pivot's column, in my own buffer
@@ -554,35 +501,7 @@ __global__ __launch_bounds__(kShThreads) void k_shard_la_block(const ShardLaunch
         if (J > 0) b = pend(b, false, (my_rm >> (J - 1)) & 1u, s_ci[J - 1][tid], e.w);
         if (mine) {
             if (lane == J - 1) v_pa = e.u;
-            const unsigned slmask = (unsigned)__ballot((lane < J) & (v_sl == lc) & (slot >= 0));
-            const unsigned gen = slmask | wave_rm;
-#pragma unroll
-            for (int i0 = 0; i0 < KMAX; i0 += 4) {
-                if (i0 < J) {
-                    double prod[4], pa[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        pa[k] = lane_value(v_pa, i0 + k);
-                        prod[k] = ci_all[i0 + k] * pa[k];              // rounded product
-                    }
-                    if (((gen >> i0) & 0xfu) == 0u) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) a = a - prod[k];   // rounded differences
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if ((gen >> (i0 + k)) & 1u) {
-                                const bool is_cr = (my_rm >> (i0 + k)) & 1u;
-                                if ((slmask >> (i0 + k)) & 1u) a = is_cr ? 1.0 : 0.0;
-                                const double d = a - prod[k];
-                                a = is_cr ? pa[k] : d;
-                            } else {
-                                a = a - prod[k];
-                            }
-                        }
-                    }
-                }
-            }
+            a = la_chain_col<KMAX>(a, ci_all, v_pa, J, my_rm, (unsigned)__ballot((lane < J) & (v_sl == lc) & (slot >= 0)), wave_rm);
             if (has_row && world > 1) {
                 // exchange B, producer: my row's entry straight into the OTHER shards' buffers
                 const unsigned long long vb = dbits(a);
@@ -620,22 +539,14 @@ __global__ __launch_bounds__(kShThreads) void k_shard_la_block(const ShardLaunch
                            quit, qq, false);
         ExchRec *line = t.la_rx + (kMaxShardLaWorkgroups - 1);    // (the last record: nw < kMaxShardLaWorkgroups)
         if (shared_poll) {
-            const ShPart mp = sh_poll_quarter<false>(t.la_rx, nw, e_ratio, max_spins, rec_m, wave);
+            const LaWaveRec mp = sh_poll_quarter<false>(t.la_rx, nw, e_ratio, max_spins, rec_m, wave);
             if (lane == 0) s_part[wave] = mp;
             __syncthreads();
-            Cand c; c.v = s_part[0].v; c.i = s_part[0].i;
-            int ww = 0;
-            unsigned fl = s_part[0].flag;
-#pragma unroll
-            for (int k = 1; k < kShWaves; ++k) {
-                Cand o; o.v = s_part[k].v; o.i = s_part[k].i;
-                const Cand r2 = cand_min(c, o);
-                ww = (r2.i != c.i) ? k : ww;
-                c = r2;
-                fl |= s_part[k].flag;
-            }
-            const int Qr = (nw + kShWaves - 1) / kShWaves;
-            qq.v = c.v; qq.i = c.i; qq.s = s_part[ww].s; qq.u = s_part[ww].u; qq.w = s_part[rec_m / Qr].from; qq.flag = fl;
+            Cand c;
+            unsigned fl;
+            const int ww = fold_waves(s_part, c, fl);
+            const int Qr = (nw + kLaWaves - 1) / kLaWaves;
+            qq.v = c.v; qq.i = c.i; qq.s = s_part[ww].s; qq.u = s_part[ww].u; qq.w = s_part[rec_m / Qr].x2; qq.flag = fl;
             if (w == 0 && wave == 0 && !mute) sh_decision_publish(line, e_ratio, qq);
         } else {
             if (wave == 0) {
@@ -675,55 +586,9 @@ __global__ __launch_bounds__(kShThreads) void k_shard_la_block(const ShardLaunch
         const bool keeper = slot >= 0 ? own : leader;
         const int64_t leaving = keeper ? ld_l2(&t.basis[cr]) : -1;
         double2 pi_all[KMAX];
-#pragma unroll
-        for (int i0 = 0; i0 < KMAX; i0 += 4) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) pi_all[i0 + k] = make_double2(0.0, 0.0);
-            if (i0 < J) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) pi_all[i0 + k] = s_pi[i0 + k][tid];
-            }
-        }
+        la_prefetch(pi_all, s_pi, J);
         drain_vmem();                  // the loads -- and the col_J entry / granules stored above
-        {
-            const unsigned crmask = (unsigned)__ballot((lane < J) & (v_cr == cr));
-            const unsigned gen = crmask | wave_sm;
-#pragma unroll
-            for (int i0 = 0; i0 < KMAX; i0 += 4) {
-                if (i0 < J) {
-                    double2 pii[4], prod[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        pii[k] = pi_all[i0 + k];
-                        const double ccr = lane_value(v_ccr, i0 + k);
-                        prod[k].x = ccr * pii[k].x;
-                        prod[k].y = ccr * pii[k].y;
-                    }
-                    if (((gen >> i0) & 0xfu) == 0u) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            y.x = y.x - prod[k].x;
-                            y.y = y.y - prod[k].y;
-                        }
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            if ((gen >> (i0 + k)) & 1u) {
-                                const bool is_cr = (crmask >> (i0 + k)) & 1u;
-                                if ((my_sm >> (i0 + k)) & 1ull)      y.x = is_cr ? 1.0 : 0.0;
-                                if ((my_sm >> (32 + i0 + k)) & 1ull) y.y = is_cr ? 1.0 : 0.0;
-                                const double dx = y.x - prod[k].x, dy = y.y - prod[k].y;
-                                y.x = is_cr ? pii[k].x : dx;
-                                y.y = is_cr ? pii[k].y : dy;
-                            } else {
-                                y.x = y.x - prod[k].x;
-                                y.y = y.y - prod[k].y;
-                            }
-                        }
-                    }
-                }
-            }
-        }
+        y = la_chain_row<KMAX>(y, pi_all, v_ccr, J, my_sm, (unsigned)__ballot((lane < J) & (v_cr == cr)), wave_sm);
         pr = make_double2(0.0, 0.0);
         if (has_pair) {
             pr = scale_pair(t, p, y, piv, slot);
@@ -739,8 +604,7 @@ __global__ __launch_bounds__(kShThreads) void k_shard_la_block(const ShardLaunch
             st_wt(&t.l2p[leaving], slot);
             st_wt(&t.l2p[ec], (int64_t)-1);
             my_sm |= 1ull << (J + 32 * (int)(slot & 1));
-            if (J < 16) t.bk_smask[p]  = (unsigned)(my_sm & 0xffffull) | ((unsigned)((my_sm >> 32) & 0xffffull) << 16);
-            else        t.bk_smask2[p] = (unsigned)((my_sm >> 16) & 0xffffull) | ((unsigned)((my_sm >> 48) & 0xffffull) << 16);
+            la_store_slot_mask(t, p, my_sm, J);
         }
         if (keeper) {
             st_wt(&t.basis[cr], ec);                             // src/simplex.lisp:358 (GLOBAL column indices on every shard)
@@ -752,19 +616,7 @@ __global__ __launch_bounds__(kShThreads) void k_shard_la_block(const ShardLaunch
         }
         if (__any(has_row && r == cr)) wave_rm |= 1u << J;
         if (__any(own))                wave_sm |= 1u << J;
-        if (leader) {                                            // the one writer of these words
-            const int64_t tn = c0.trace_n + J;
-            ctl->ec = ec;
-            ctl->cr = cr;
-            ctl->slot = slot;
-            if (t.trace_ec && tn < t.trace_cap) { t.trace_ec[tn] = ec; t.trace_cr[tn] = cr; }
-            ctl->trace_n  = tn + 1;
-            ctl->n_pivots = c0.n_pivots + J + 1;
-            blk->cr[J] = cr;
-            blk->slot[J] = slot;
-            blk->ec[J] = ec;
-            blk->n_pending = J + 1;
-        }
+        if (leader) la_commit(t, c0, J, ec, cr, slot);           // the one writer of these words
         if (lane == J) { v_cr = cr; v_sl = slot; }
 #ifdef MI355X_LA_TIMING
         T5 = wall_clock64();

@@ -62,6 +62,7 @@
 //     kernels_select_update.inc   per-pivot path: k_select*, step-wise pieces, per-pivot shard steps, k_update
 //     kernels_lookahead.inc       pending-pivot chain, k_la_gather / k_la_scale
 //     kernels_shard.inc           look-ahead step of a column shard (k_shard_la_*, k_shard_p2p_step)
+//     kernels_la_common.inc       what the block look-aheads share: chains, record format, workgroup record, bookkeeping
 //     kernels_la_block.inc        persistent look-ahead k_la_block + hand-off protocol, k_la_rollback
 //     kernels_shard_block.inc     a column shard's look-ahead of a whole block as one persistent launch (k_shard_la_block)
 //     kernels_sweep.inc           k_sweep, k_sweep16
@@ -81,6 +82,7 @@ namespace mi355x {
 #include "kernels_select_update.inc"
 #include "kernels_lookahead.inc"
 #include "kernels_shard.inc"
+#include "kernels_la_common.inc"
 #include "kernels_la_block.inc"
 #include "kernels_shard_block.inc"
 #include "kernels_sweep.inc"
