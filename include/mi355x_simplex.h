@@ -76,6 +76,7 @@ typedef struct mi355x_solve    mi355x_solve;     /* a problem on its way to a so
 typedef struct mi355x_solve_many mi355x_solve_many; /* a LIST of problems on their way to solutions   */
 typedef struct mi355x_xtab     mi355x_xtab;      /* one exact (fraction-free integer) tableau in HBM */
 typedef struct mi355x_xbatch   mi355x_xbatch;    /* many exact tableaux of one shape, one workgroup per member */
+typedef struct mi355x_xbb_base mi355x_xbb_base;  /* a base problem's general form, for exact branch-and-bound nodes */
 
 /* ---- library / device ------------------------------------------------------------- */
 int         mi355x_abi_version(void);
@@ -401,6 +402,40 @@ int  mi355x_xbatch_bits(const mi355x_xbatch *b, int64_t lp_index, int *bits);
 /* any thread: the call running on the batch returns MI_CANCELLED after its current launches (whole pivots) */
 int  mi355x_xbatch_cancel(mi355x_xbatch *b);
 void mi355x_xbatch_destroy(mi355x_xbatch *b);
+/* ---- exact branch-and-bound  (simplex-solver with integer variables on rationals, src/simplex.lisp:462-542,
+ * where violated-integer-constraint's integerp, :475-480, is meaningful) ------------------------------------
+ * The search, build-tableau of the base problem and the reading of solutions stay in the host language,
+ * which has bignums.  The library turns a base problem and lists of node rows into batches of exact start
+ * states on the device, and gathers what tableau-objective-value / -variable / -reduced-cost read. */
+/* The base problem's general-form tableau -- build-tableau's main tableau (src/simplex.lisp:189-283) with
+ * basis[i] == cols for a row that needs an artificial variable -- as rationals num / den, plus what places
+ * a node row: ncv structural columns, nb rows pushed for doubly-bounded variables (:198-202; node rows go
+ * after them, :146), and per variable its var-mapping (:189-212): kind 0 positive / 1 negative / 2 signed,
+ * its column, its offset off_num / off_den.  MI_EXACT_OVERFLOW when the problem at one integer scale needs
+ * more than 128 bits.  A base may be destroyed while batches made from it live. */
+int  mi355x_xbb_base_create(mi355x_xbb_base **out, int64_t rows, int64_t cols, const int64_t *num,
+                            const int64_t *den, const int64_t *basis, int64_t ncv, int64_t nb,
+                            int64_t n_vars, const int32_t *kind, const int64_t *col,
+                            const int64_t *off_num, const int64_t *off_den, int device);
+void mi355x_xbb_base_destroy(mi355x_xbb_base *base);
+/* build-and-solve's tableaux (src/simplex.lisp:489-500 through build-tableau, :142-328) of n_nodes nodes of
+ * one depth and one number of artificial rows, written on the device: node q is the base problem with the
+ * rows var <= bound (sense 0) / var >= bound (sense 1) at [q * depth, (q + 1) * depth), newest first, in
+ * front of its constraints.  *out_main is a batch of (rows + depth) x (cols + depth) members; *out_art is
+ * NULL when no row is artificial (solve *out_main with mi355x_xbatch_solve), else the batch of artificial
+ * tableaux (solve the pair with mi355x_xbatch_solve_two_phase).  Both are ordinary mi355x_xbatch handles;
+ * a member whose start state needs more than 128 bits reports MI_EXACT_OVERFLOW when solved.  MI_BAD_ARG
+ * when the nodes differ in their number of artificial rows; MI_UNSUPPORTED for a shape
+ * mi355x_xbatch_create declines.  min_bits as for mi355x_xbatch_create. */
+int  mi355x_xbatch_create_nodes(mi355x_xbatch **out_main, mi355x_xbatch **out_art,
+                                const mi355x_xbb_base *base, int64_t n_nodes, int64_t depth,
+                                const int64_t *var, const int32_t *sense, const int64_t *bound,
+                                int min_bits);
+/* All that tableau-objective-value, tableau-variable and tableau-reduced-cost read (src/simplex.lisp:74-120)
+ * of every member, in one copy: values_lo_hi holds per member 1 + rows + cols limb pairs -- D, the last
+ * column (rows values), the last row (cols values) --, basis (may be NULL) rows - 1 entries per member.
+ * status (n_lps entries, may be NULL): MI_OK, or MI_EXACT_OVERFLOW for a member past 128 bits (zeros). */
+int  mi355x_xbatch_readback(mi355x_xbatch *b, int64_t *values_lo_hi, int64_t *basis, int32_t *status);
 /* Branch-and-bound (simplex-solver with integer variables, src/simplex.lisp:462-542) as a resumable job.
  * Opt-in: every other entry point still declines integer problems with MI_UNSUPPORTED.  The search is the
  * reference's node for node -- a depth-first walk over an explicit stack of entries, each node the problem

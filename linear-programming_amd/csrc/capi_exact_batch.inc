@@ -9,6 +9,12 @@
 // into its 128-bit slot and replays, with the other restarted members, up to the same cumulative pivot
 // count.  The host reads the control blocks once per round of launches; nothing between the phases
 // comes back to the host per member.
+//
+// A member's start state has one of two sources: the caller's rationals (mi355x_xbatch_create), or a node
+// spec -- a base problem and the member's node rows -- from which k_xbb_assemble writes it on the device
+// (mi355x_xbatch_create_nodes, capi_exact_bb.inc).  Everything after the start is the same for both.
+
+struct XbbNodes;                         // capi_exact_bb.inc: the node spec of a handle made by create_nodes
 
 struct XbWidth {
     XbView             v{};              // v.T == nullptr: this width is not allocated
@@ -20,7 +26,10 @@ struct mi355x_xbatch {
     int         device = 0;
     hipStream_t stream = nullptr;
     int64_t     n = 0, rows = 0, cols = 0;
-    std::vector<int64_t> num, den, basis0;      // the callers' tableaux, member after member
+    std::vector<int64_t> num, den, basis0;      // the callers' tableaux, member after member (none: see nodes)
+    std::shared_ptr<XbbNodes> nodes;            // the other source of the start states: the members' node rows
+    int64_t    *rb = nullptr;                   // mi355x_xbatch_readback's device buffer, made at its first call
+    int32_t    *rb_width = nullptr;
     std::vector<char>    start_ok;              // per member: unit basis columns over a zero objective entry
     std::vector<int>     width;                 // per member: 64, 128, or 0 once it needs more than 128 bits
     std::vector<i128_t>  mult;                  // per member: cl_j (cols values), then L_c (0: overflowed 128 bits)
@@ -34,6 +43,10 @@ namespace {
 
 constexpr int64_t kXbTraceCap = MI355X_XBATCH_TRACE_CAP;
 static_assert(MI355X_XBATCH_WORKGROUP == kXThreads, "the header states k_xb_solve's workgroup size");
+
+// member q of a handle made from node specs assembled again at 128 bits (capi_exact_bb.inc): MI_OK and its
+// D, kXOverflow, or an error
+int xbb_reassemble_128(mi355x_xbatch *b, int64_t q, hipStream_t s, __int128 *D0);
 
 int xb_wi(int bits) { return bits == 128 ? 1 : 0; }
 XbCtl &xb_ctl(mi355x_xbatch *b, int64_t q) { return b->w[xb_wi(b->width[q])].h[q]; }
@@ -98,7 +111,7 @@ int xb_alloc(mi355x_xbatch *b, int wi)
         for (size_t j = 0; j <= C; ++j) x_put(&stage[(q * (C + 1) + j) * wb], mq[j], bits);
     }
     HIP_TRY(hipMemcpyAsync(s.aux, stage.data(), stage.size(), hipMemcpyHostToDevice, b->stream));
-    if (n * m > 0)
+    if (n * m > 0 && !b->nodes)                                             // (node specs: k_xbb_assemble writes the bases)
         HIP_TRY(hipMemcpyAsync(s.v.basis, b->basis0.data(), n * m * sizeof(int64_t), hipMemcpyHostToDevice, b->stream));
     s.h.assign(n, xb_fresh(0));
     HIP_TRY(hipMemcpyAsync(s.v.ctl, s.h.data(), n * sizeof(XbCtl), hipMemcpyHostToDevice, b->stream));
@@ -128,13 +141,20 @@ int xb_restart_128(mi355x_xbatch *b, int64_t q, int32_t status, int64_t cap_at, 
     int rc = xb_alloc(b, 1);
     if (rc != MI_OK) return rc;
     const size_t RC = (size_t)(b->rows * b->cols), m = (size_t)b->rows - 1;
-    std::vector<unsigned char> stage(RC * 16);
+    std::vector<unsigned char> stage;
     i128_t D0 = 0;
-    if (xb_stage_member(b, q, 128, stage.data(), &D0) != MI_OK) { b->width[q] = 0; return kXOverflow; }
     XbWidth &w = b->w[1];
-    HIP_TRY(hipMemcpyAsync((unsigned char *)w.v.T + (size_t)q * RC * 16, stage.data(), stage.size(), hipMemcpyHostToDevice, s));
-    if (m > 0)
-        HIP_TRY(hipMemcpyAsync(w.v.basis + q * m, &b->basis0[q * m], m * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    if (b->nodes) {
+        rc = xbb_reassemble_128(b, q, s, &D0);
+        if (rc == kXOverflow) { b->width[q] = 0; return kXOverflow; }
+        if (rc != MI_OK) return rc;
+    } else {
+        stage.resize(RC * 16);
+        if (xb_stage_member(b, q, 128, stage.data(), &D0) != MI_OK) { b->width[q] = 0; return kXOverflow; }
+        HIP_TRY(hipMemcpyAsync((unsigned char *)w.v.T + (size_t)q * RC * 16, stage.data(), stage.size(), hipMemcpyHostToDevice, s));
+        if (m > 0)
+            HIP_TRY(hipMemcpyAsync(w.v.basis + q * m, &b->basis0[q * m], m * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    }
     w.h[q] = xb_fresh(D0);
     w.h[q].status = status;
     w.h[q].cap_at = cap_at;
@@ -440,6 +460,8 @@ void mi355x_xbatch_destroy(mi355x_xbatch *b)
     if (b->stream) (void)hipStreamSynchronize(b->stream);
     xb_free(b, 0);
     xb_free(b, 1);
+    (void)hipFree(b->rb);
+    (void)hipFree(b->rb_width);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }

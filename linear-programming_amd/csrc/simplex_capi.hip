@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -196,6 +197,7 @@ struct mi355x_multibatch {
 #include "capi_bb.inc"         // branch-and-bound node batches assembled on the devices (internal)
 #include "capi_exact.inc"      // mi355x_xtab_*: exact rational solves on fraction-free integer tableaux
 #include "capi_exact_batch.inc"  // mi355x_xbatch_*: batches of exact LPs, one workgroup per member
+#include "capi_exact_bb.inc"   // mi355x_xbb_base_*, mi355x_xbatch_create_nodes / _readback: exact branch-and-bound
 #include "capi_shard.inc"      // mi355x_shard_*
 #include "capi_colpart.inc"    // mi355x_colpart_*, mi355x_rccl_unique_id
 #include "capi_tune.inc"       // mi355x_tune_*, mi355x_debug_*

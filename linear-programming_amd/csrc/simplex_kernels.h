@@ -401,6 +401,28 @@ struct XbView {
 // at most launch_cap pivots per member (a bounded launch: mi355x_xbatch_cancel)
 void launch_xb_solve(const XbView &v, int is_max, int64_t launch_cap, hipStream_t s);
 void launch_xb_between(const XbView &art, const XbView &mt, hipStream_t s);
+// Exact branch-and-bound (kernels_exact_bb.inc, capi_exact_bb.inc): the base problem's general-form tableau
+// at integer scale Db, and the node rows of the members of a batch.
+struct XbbBaseView {
+    const void    *B;                 // rows x cols values of the width, tight: Db * (base entry)
+    const void    *voff;              // per variable, of the width: Db * offset
+    int64_t        rows, cols, ncv, nb;
+    const int64_t *basis;             // rows - 1; an entry == cols: an artificial row
+    const int32_t *kind;              // per variable: 0 positive, 1 negative, 2 signed
+    const int64_t *vcol;
+    __int128       Db;                // > 0, fits the width
+};
+struct XbbNodeRows {
+    const int64_t *var;               // (member, k) at member * d + k, newest row first
+    const int32_t *sense;             // 0 `<=`, 1 `>=`
+    const int64_t *bound;
+    int64_t        d;
+};
+// members q0 .. q0 + count - 1 into their slots of mt and / or at (a view whose T is NULL is left out)
+void launch_xbb_assemble(const XbView &mt, const XbView &at, const XbbBaseView &b, const XbbNodeRows &nr, int64_t q0,
+                         int64_t count, hipStream_t s);
+// every member whose width[q] is the view's: D, right-hand sides, objective row (limb pairs) and basis
+void launch_xbb_readback(const XbView &v, const int32_t *width, int64_t *values, int64_t *basis, hipStream_t s);
 #ifdef MI355X_TEST_HOOKS
 // test build: one arithmetic primitive of kernels_exact.inc applied element-wise (k_x_arith_probe; the
 // opcodes and the limb layout are mi355x_test_xarith's, include/mi355x_simplex_tune.h).  Device pointers.

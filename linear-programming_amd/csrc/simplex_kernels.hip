@@ -72,6 +72,7 @@
 //     kernels_bb.inc              branch-and-bound node tableaux assembled in HBM (k_bb_assemble)
 //     kernels_exact.inc           exact rational solves on fraction-free integer tableaux (k_x_*)
 //     kernels_exact_batch.inc     batches of exact LPs, one workgroup per LP (k_xb_solve, k_xb_between)
+//     kernels_exact_bb.inc        exact branch-and-bound: integer node tableaux, light read-back (k_xbb_*)
 //     kernels_launch.inc          host-side launchers, tuning state
 #include "simplex_kernels.h"
 #include <type_traits>
@@ -92,6 +93,7 @@ namespace mi355x {
 #include "kernels_bb.inc"
 #include "kernels_exact.inc"
 #include "kernels_exact_batch.inc"
+#include "kernels_exact_bb.inc"
 #include "kernels_launch.inc"
 
 }  // namespace mi355x

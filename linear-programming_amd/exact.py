@@ -270,6 +270,13 @@ class XBatch:
                    device, min_bits)
         return xb
 
+    @classmethod
+    def from_handle(cls, handle, n_lps, rows, cols):
+        """A batch the library made itself (mi355x_xbatch_create_nodes)."""
+        xb = cls.__new__(cls)
+        xb.handle, xb.n_lps, xb.rows, xb.cols = handle, int(n_lps), int(rows), int(cols)
+        return xb
+
     def _create(self, num, den, basis, device, min_bits):
         h = ctypes.c_void_p()
         rc = capi.lib().mi355x_xbatch_create(ctypes.byref(h), self.n_lps, self.rows, self.cols, _ptr(num), _ptr(den),
@@ -353,12 +360,27 @@ def _member_error(st):
     return None
 
 
+def batch_in_chunks(xa, xm, is_max, max_pivots=0, chunk=None):
+    """A batch (xm None) or a two-phase pair of batches in bounded calls (the glue's solve-in-chunks):
+    -> (final member statuses, pivots per member -- (n, 2) for a pair)."""
+    from .simplex import chunk_pivots
+    chunk = chunk or chunk_pivots(xa.rows, xa.cols)
+    total = np.zeros((xa.n_lps, 2) if xm else xa.n_lps, dtype=np.int64)
+    done = 0
+    while True:
+        cap = min(chunk, max_pivots - done) if max_pivots > 0 else chunk
+        rc, st, npv = xa.solve_two_phase(xm, is_max, cap) if xm else xa.solve(is_max, cap)
+        total += npv
+        done += cap
+        if rc == capi.MI_CANCELLED or (max_pivots > 0 and done >= max_pivots) or not (st == capi.MI_MAX_PIVOTS).any():
+            return st, total
+
+
 def solve_exact_batch(members, is_max, device=0, max_pivots=0, min_bits=0, chunk=None):
     """One group of mi355x_solve_problems(exact=True) in bounded calls (the glue's solve-in-chunks):
     members are ExactTableaus (single phase) or (art, main) pairs of one shape.  Returns per member the
     solved (main) tableau or the exception of its outcome; raises the declined condition when the shape
     does not fit a batch."""
-    from .simplex import chunk_pivots
     two = isinstance(members[0], (list, tuple))
     first = [m[0] for m in members] if two else list(members)
     xa = XBatch(first, device=device, min_bits=min_bits)
@@ -367,16 +389,7 @@ def solve_exact_batch(members, is_max, device=0, max_pivots=0, min_bits=0, chunk
     except Exception:
         xa.close()                                     # (its device memory goes at once)
         raise
-    chunk = chunk or chunk_pivots(xa.rows, xa.cols)
-    total = np.zeros((len(members), 2) if two else len(members), dtype=np.int64)
-    done = 0
-    while True:
-        cap = min(chunk, max_pivots - done) if max_pivots > 0 else chunk
-        rc, st, npv = xa.solve_two_phase(xm, is_max, cap) if two else xa.solve(is_max, cap)
-        total += npv
-        done += cap
-        if rc == capi.MI_CANCELLED or (max_pivots > 0 and done >= max_pivots) or not (st == capi.MI_MAX_PIVOTS).any():
-            break
+    st, total = batch_in_chunks(xa, xm, is_max, max_pivots, chunk)
     out = []
     for q, m in enumerate(members):
         e = _member_error(capi.MI_CANCELLED if st[q] == capi.MI_RUNNING else st[q])

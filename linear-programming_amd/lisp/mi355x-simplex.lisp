@@ -42,7 +42,8 @@
   (:use :cl)
   (:import-from :linear-programming/simplex
                 #:build-tableau #:tableau-matrix #:tableau-basis-columns
-                #:tableau-var-count #:tableau-constraint-count #:tableau-instance-problem)
+                #:tableau-var-count #:tableau-constraint-count #:tableau-instance-problem
+                #:tableau-variable #:tableau-objective-value)
   (:import-from :linear-programming/problem
                 #:problem-type #:problem-vars #:problem-objective-var #:problem-objective-func
                 #:problem-integer-vars #:problem-var-bounds #:problem-constraints)
@@ -201,6 +202,15 @@
 (cffi:defcfun ("mi355x_xbatch_download" %xbatch-download) :int
   (batch :pointer) (lp-index :int64) (num-lo-hi :pointer) (den-lo-hi :pointer) (basis :pointer))
 (cffi:defcfun ("mi355x_xbatch_destroy" %xbatch-destroy) :void (batch :pointer))
+(cffi:defcfun ("mi355x_xbb_base_create" %xbb-base-create) :int
+  (out :pointer) (rows :int64) (cols :int64) (num :pointer) (den :pointer) (basis :pointer) (ncv :int64)
+  (nb :int64) (n-vars :int64) (kind :pointer) (col :pointer) (off-num :pointer) (off-den :pointer) (device :int))
+(cffi:defcfun ("mi355x_xbb_base_destroy" %xbb-base-destroy) :void (base :pointer))
+(cffi:defcfun ("mi355x_xbatch_create_nodes" %xbatch-create-nodes) :int
+  (out-main :pointer) (out-art :pointer) (base :pointer) (n-nodes :int64) (depth :int64) (var :pointer)
+  (sense :pointer) (bound :pointer) (min-bits :int))
+(cffi:defcfun ("mi355x_xbatch_readback" %xbatch-readback) :int
+  (batch :pointer) (values-lo-hi :pointer) (basis :pointer) (status :pointer))
 
 (define-condition mi355x-error (solver-error)
   ((code :initarg :code :reader mi355x-error-code)
@@ -571,9 +581,10 @@ MEMBER: HANDLE is a batch (mi355x_xbatch_*) and the tableau its member of that i
   (when (= status +mi-exact-overflow+) (exact-declined '(overflow 128)))
   status)
 
-(defun solve-exactly (problem device max-pivots)
-  "build-tableau, then n-solve-tableau on exact tableaux in bounded calls; returns the tableau."
-  (let ((tableaus (build-tableau problem problem)))
+(defun solve-exactly (problem device max-pivots &optional (instance-problem problem))
+  "build-tableau, then n-solve-tableau on exact tableaux in bounded calls; returns the tableau.
+INSTANCE-PROBLEM: a branch-and-bound node of PROBLEM (src/simplex.lisp:488-501)."
+  (let ((tableaus (build-tableau problem instance-problem)))
     (cffi:with-foreign-object (n-pivots :int64 2)
       (if (listp tableaus)
           (destructuring-bind (art-tab main-tab) tableaus
@@ -730,6 +741,230 @@ returns member K's result through MI355X-SIMPLEX-SOLVER."
                    do (setf (aref results k) outcome)))))
      groups)
     results))
+
+;;; :exact t with :branch-and-bound t: simplex-solver with integer variables (src/simplex.lisp:462-542) on
+;;; rationals, where violated-integer-constraint's INTEGERP (:475-480) is meaningful.  The loop below is
+;;; the reference's, entry for entry; only WHEN a node LP is solved differs: the top :bb-width unsolved
+;;; entries of the stack are solved in one round, grouped by (depth, artificial rows) into batches of
+;;; exact tableaux that the library assembles on the device from the base problem's general form and the
+;;; entries' rows (mi355x_xbatch_create_nodes), and read back light (mi355x_xbatch_readback).  Every
+;;; stack entry is popped sooner or later and a node's result depends on its own rows only, so the
+;;; results do not depend on :bb-width.  An entry here is a list of rows (var sense bound), newest
+;;; first, sense 0 for <= and 1 for >=.
+(defun exact-node-problem (problem entry)
+  "PROBLEM with the entry's rows in front of its constraints (src/simplex.lisp:489-500)."
+  (let ((node (copy-structure problem)))
+    (setf (slot-value node 'linear-programming/problem::constraints)
+          (append (mapcar (lambda (row)
+                            (destructuring-bind (var sense bound) row
+                              (list (if (zerop sense) '<= '>=) (list (cons var 1)) bound)))
+                          entry)
+                  (problem-constraints problem)))
+    node))
+
+(defun exact-mapping-offset (mapping)
+  (if (eq (first mapping) 'linear-programming/simplex::signed) 0 (third mapping)))
+
+(defun exact-row-artificial-p (mapping sense bound)
+  "Does the node row need an artificial variable?  (a negative bound - offset flips its sense, :243-252)"
+  (= 1 (if (minusp (- bound (exact-mapping-offset mapping))) (- 1 sense) sense)))
+
+(defun upload-exact-bb-base (problem main-tab device)
+  "mi355x_xbb_base_create from the general form MAIN-TAB (build-tableau's main tableau) of PROBLEM."
+  (let* ((matrix (tableau-matrix main-tab))
+         (rows (array-dimension matrix 0))
+         (cols (array-dimension matrix 1))
+         (vars (coerce (problem-vars problem) 'list))
+         (n-vars (length vars))
+         (mappings (mapcar (lambda (var) (gethash var (linear-programming/simplex::tableau-var-mapping main-tab))) vars))
+         (ncv (loop for mapping in mappings
+                    sum (if (eq (first mapping) 'linear-programming/simplex::signed) 2 1)))
+         (nb (count-if (lambda (entry) (and (cadr entry) (cddr entry))) (problem-var-bounds problem))))
+    (cffi:with-foreign-objects ((num :int64 (* rows cols)) (den :int64 (* rows cols))
+                                (basis :int64 (max 1 (1- rows))) (kind :int32 n-vars) (col :int64 n-vars)
+                                (off-num :int64 n-vars) (off-den :int64 n-vars) (out :pointer))
+      (flet ((int64 (x)
+               (unless (typep x '(signed-byte 64)) (exact-declined (list 'coefficient x)))
+               x))
+        (dotimes (e (* rows cols))
+          (let ((x (row-major-aref matrix e)))
+            (setf (cffi:mem-aref num :int64 e) (int64 (numerator x))
+                  (cffi:mem-aref den :int64 e) (int64 (denominator x)))))
+        (dotimes (r (1- rows))
+          (setf (cffi:mem-aref basis :int64 r) (aref (tableau-basis-columns main-tab) r)))
+        (loop for mapping in mappings for v from 0
+              do (let ((offset (exact-mapping-offset mapping)))
+                   (setf (cffi:mem-aref kind :int32 v)
+                         (position (first mapping) '(linear-programming/simplex::positive
+                                                     linear-programming/simplex::negative
+                                                     linear-programming/simplex::signed))
+                         (cffi:mem-aref col :int64 v) (second mapping)
+                         (cffi:mem-aref off-num :int64 v) (int64 (numerator offset))
+                         (cffi:mem-aref off-den :int64 v) (int64 (denominator offset))))))
+      (let ((status (%xbb-base-create out rows cols num den basis ncv nb n-vars kind col off-num off-den device)))
+        (when (= status +mi-exact-overflow+) (exact-declined '(overflow 128)))
+        (check status)
+        (cffi:mem-ref out :pointer)))))
+
+(defun exact-light-values (problem main-tab ptr basis rows cols)
+  "(objective . alist of (var . value)) of one member from mi355x_xbatch_readback's values at PTR -- D, the
+right-hand sides, the objective row as limb pairs -- and its basis: tableau-objective-value and
+tableau-variable (src/simplex.lisp:74-107) on ratios."
+  (flet ((limbs (k)
+           (+ (logand (cffi:mem-aref ptr :int64 (* 2 k)) (1- (ash 1 64)))
+              (ash (cffi:mem-aref ptr :int64 (1+ (* 2 k))) 64))))
+    (let ((d (limbs 0)))
+      (flet ((basic (column)
+               (let ((idx (loop for r below (1- rows)
+                                when (= column (cffi:mem-aref basis :int64 r)) return r)))
+                 (if idx (/ (limbs (+ 1 idx)) d) 0))))
+        (cons (/ (limbs (+ 1 rows (1- cols))) d)
+              (loop for var across (problem-vars problem)
+                    collect (let ((mapping (gethash var (linear-programming/simplex::tableau-var-mapping main-tab))))
+                              (cons var
+                                    (ecase (first mapping)
+                                      (linear-programming/simplex::positive
+                                       (+ (third mapping) (basic (second mapping))))
+                                      (linear-programming/simplex::negative
+                                       (- (third mapping) (basic (second mapping))))
+                                      (linear-programming/simplex::signed
+                                       (- (basic (second mapping)) (basic (1+ (second mapping))))))))))))))
+
+(defun solve-exact-bb-group (problem main-tab base entries n-art max-pivots)
+  "ENTRIES: nodes of one depth and one number of artificial rows (N-ART, the base's included).  One batch (or
+pair) assembled by the library, solved in bounded calls, read back light.  A list parallel to ENTRIES:
+(objective . values), :INFEASIBLE, or the condition object of the node's outcome."
+  (let* ((n (length entries))
+         (depth (length (first entries)))
+         (rows (+ depth (array-dimension (tableau-matrix main-tab) 0)))
+         (cols (+ depth (array-dimension (tableau-matrix main-tab) 1)))
+         (per (+ 1 rows cols))
+         (vars (problem-vars problem))
+         (is-max (max-problem-p main-tab))
+         (main-handle nil)
+         (art-handle nil)
+         (values-lo-hi (cffi:foreign-alloc :int64 :count (* 2 n per)))
+         (basis (cffi:foreign-alloc :int64 :count (max 1 (* n (1- rows))))))
+    (unwind-protect
+         (cffi:with-foreign-objects ((var :int64 (* n depth)) (sense :int32 (* n depth)) (bound :int64 (* n depth))
+                                     (out-main :pointer) (out-art :pointer) (status :int32 n)
+                                     (member-status :int32 n) (pivots :int64 (* 2 n)) (budget :int64 1))
+           (loop for entry in entries for q from 0
+                 do (loop for (name row-sense row-bound) in entry for k from 0
+                          do (unless (typep row-bound '(signed-byte 64)) (exact-declined (list 'bound row-bound)))
+                             (setf (cffi:mem-aref var :int64 (+ (* q depth) k)) (position name vars)
+                                   (cffi:mem-aref sense :int32 (+ (* q depth) k)) row-sense
+                                   (cffi:mem-aref bound :int64 (+ (* q depth) k)) row-bound)))
+           (let ((created (%xbatch-create-nodes out-main out-art base n depth var sense bound 0)))
+             (when (= created +mi-unsupported+) (exact-declined (list 'batch 'shape rows cols)))
+             (check created))
+           (setf main-handle (cffi:mem-ref out-main :pointer)
+                 art-handle (if (zerop n-art) nil (cffi:mem-ref out-art :pointer)))
+           (solve-in-chunks
+            (lambda (cap)
+              (check (if art-handle
+                         (%xbatch-solve-two-phase art-handle main-handle is-max cap status pivots)
+                         (%xbatch-solve main-handle is-max cap status pivots)))
+              (setf (cffi:mem-aref budget :int64 0) cap)
+              (if (loop for k below n thereis (= (cffi:mem-aref status :int32 k) +mi-max-pivots+))
+                  +mi-max-pivots+
+                  +mi-optimal+))
+            rows (+ cols n-art) max-pivots budget)
+           (check (%xbatch-readback main-handle values-lo-hi basis member-status))
+           (loop for q below n
+                 collect (let ((st (cffi:mem-aref status :int32 q)))
+                           (cond
+                             ((= st +mi-infeasible+) :infeasible)
+                             ((or (/= st +mi-optimal+) (/= 0 (cffi:mem-aref member-status :int32 q)))
+                              (exact-member-condition (if (= st +mi-optimal+) +mi-exact-overflow+ st)))
+                             (t (exact-light-values problem main-tab
+                                                    (cffi:inc-pointer values-lo-hi (* 16 q per))
+                                                    (cffi:inc-pointer basis (* 8 q (1- rows)))
+                                                    rows cols))))))
+      (when art-handle (%xbatch-destroy art-handle))
+      (when main-handle (%xbatch-destroy main-handle))
+      (cffi:foreign-free values-lo-hi)
+      (cffi:foreign-free basis))))
+
+(defun solve-exact-branch-and-bound (problem device max-pivots bb-width max-nodes)
+  "simplex-solver (src/simplex.lisp:506-542) on an integer problem whose numbers are all rational.  Returns
+the incumbent's solved `tableau` (its node solved once more on its own, so that the reference's methods
+serve it), or signals as the reference does."
+  (when (null (problem-constraints problem))
+    (exact-declined '(branch-and-bound no-constraints)))       ; (build-tableau's special case has no general form)
+  (let* ((tableaus (build-tableau problem problem))
+         (main-tab (if (listp tableaus) (second tableaus) tableaus))
+         (base-art (count (array-dimension (tableau-matrix main-tab) 1) (tableau-basis-columns main-tab)))
+         (base (upload-exact-bb-base problem main-tab device))
+         (results (make-hash-table :test #'equal))
+         (comparator (if (eq (problem-type problem) 'max) #'< #'>))
+         (stack (list '()))
+         (processed 0)
+         (current-best nil)
+         (current-entry nil))
+    (flet ((solve-round ()
+             ;; the top BB-WIDTH unsolved entries of the stack, in one round
+             (let ((groups (make-hash-table :test #'equal)))
+               (loop for entry in stack
+                     with taken = 0
+                     while (< taken bb-width)
+                     unless (nth-value 1 (gethash entry results))
+                       do (incf taken)
+                          (if (null entry)
+                              (setf (gethash entry results)
+                                    (handler-case
+                                        (let ((tab (solve-exactly problem device max-pivots)))
+                                          (cons (tableau-objective-value tab)
+                                                (loop for var across (problem-vars problem)
+                                                      collect (cons var (tableau-variable tab var)))))
+                                      (infeasible-problem-error () :infeasible)))
+                              (push entry
+                                    (gethash (list (length entry)
+                                                   (+ base-art
+                                                      (loop for (var sense bound) in entry
+                                                            count (exact-row-artificial-p
+                                                                   (gethash var (linear-programming/simplex::tableau-var-mapping main-tab))
+                                                                   sense bound))))
+                                             groups))))
+               (maphash (lambda (shape entries)
+                          (loop for entry in entries
+                                for result in (solve-exact-bb-group problem main-tab base entries (second shape)
+                                                                    max-pivots)
+                                do (setf (gethash entry results) result)))
+                        groups)))
+           (violated (values-alist)                               ; violated-integer-constraint, :475-480
+             (find-if (lambda (var) (not (integerp (cdr (assoc var values-alist)))))
+                      (problem-integer-vars problem))))
+      (unwind-protect
+           (loop while stack
+                 do (when (and (plusp max-nodes) (>= processed max-nodes))
+                      (error 'mi355x-error :code +mi-max-pivots+ :message "node cap reached"))
+                    (unless (nth-value 1 (gethash (first stack) results))
+                      (solve-round))
+                    (let* ((entry (pop stack))
+                           (result (gethash entry results)))
+                      (incf processed)
+                      (remhash entry results)
+                      (cond
+                        ((eq result :infeasible))
+                        ((typep result 'condition) (error result))
+                        (t
+                         (destructuring-bind (objective . values-alist) result
+                           (let ((split-var (violated values-alist)))
+                             (cond
+                               ((and split-var current-best (not (funcall comparator current-best objective))))
+                               (split-var                          ; gen-entries, :466-473
+                                (let ((value (cdr (assoc split-var values-alist))))
+                                  (setf stack (list* (cons (list split-var 0 (floor value)) entry)
+                                                     (cons (list split-var 1 (ceiling value)) entry)
+                                                     stack))))
+                               ((or (not current-best) (funcall comparator current-best objective))
+                                (setf current-best objective
+                                      current-entry entry)))))))))
+        (%xbb-base-destroy base))
+      (if current-best
+          (solve-exactly problem device max-pivots (exact-node-problem problem current-entry))
+          (error 'infeasible-problem-error)))))
 
 ;;; ------------------------------------------------------------------ the native route
 ;;; SURVEY 8(f) rows 2-3: at 8192 x 4096 the reference's build-tableau conses a boxed 4097 x 12289
@@ -1084,10 +1319,19 @@ double-float-epsilons of an integer), :max-nodes (0 = no cap).
 :exact T (opt-in) solves a problem whose numbers are all rational with the reference's rational
 semantics (src/utils.lisp:84-124) on exact integer tableaux and returns the solved `tableau`, its
 matrix holding the exact ratios; any float in the problem means the double-float routes above,
-unchanged.  Not together with :branch-and-bound (declined)."
+unchanged.
+:exact T together with :branch-and-bound T, on a problem with integer variables whose numbers are all
+rational: the reference's branch-and-bound in rational arithmetic, where its integrality test is INTEGERP
+of a ratio (src/simplex.lisp:475-480); :bb-width node LPs per round as batches of exact tableaux assembled
+on the device, :max-nodes as above; returns the incumbent's solved `tableau`.  (Without integer variables
+the combination is declined; with a float anywhere it is the double-float branch-and-bound above.)"
   (declare (ignore args))
   (when (and exact branch-and-bound)
-    (exact-declined '(branch-and-bound)))
+    (unless (problem-integer-vars problem)
+      (exact-declined '(branch-and-bound)))
+    (when (rational-numbers-p problem)
+      (return-from mi355x-simplex-solver
+        (solve-exact-branch-and-bound problem device max-pivots bb-width max-nodes))))
   ;; :branch-and-bound T (opt-in): integer problems through the library's branch-and-bound job
   ;; (:bb-width node LPs side by side, :int-tolerance 0 = exact integrality, :max-nodes 0 = no cap)
   (when (and branch-and-bound (problem-integer-vars problem))

@@ -199,7 +199,8 @@ def with_tableau_variables(var_list, tableau):
 
 
 # ------------------------------------------------------------------ build-tableau (host)
-def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, device=0, exact=False, min_bits=0):
+def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, device=0, exact=False, min_bits=0,
+                  general=False):
     """build-tableau (src/simplex.lisp:142-328) in double-float: returns a Tableau, or
     [art_tableau, main_tableau] when the trivial basis is infeasible.
 
@@ -207,7 +208,10 @@ def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, devi
     own build-tableau does this job and the glue converts the result to double-float.
     exact=True: the same steps in exact rationals (Fraction object matrices, Fraction mapping
     offsets), the reference's own build-tableau on rational input; the result is an ExactTableau
-    (exact.py, min_bits: its starting width) or a list of two."""
+    (exact.py, min_bits: its starting width) or a list of two.
+    general=True: the general form only -- the main tableau of :189-283 (basis entry = the number of
+    columns on a row that needs an artificial variable), also for a problem without constraints: what
+    branch-and-bound nodes are assembled from (exact_bb.py; host_problem.cpp's build(general=true))."""
     if instance_problem is None:
         instance_problem = problem
     if exact:
@@ -231,7 +235,7 @@ def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, devi
         return Tableau(problem, inst, matrix, basis, var_count, ccount, mappings,
                        fp_tolerance_factor, device)
 
-    if not constraints:                                                  # :153-186
+    if not constraints and not general:                                  # :153-186
         M = zeros((n + 1, n + 1))
         basis = np.arange(n, dtype=np.int64)
         objd = dict(problem.objective_func)
@@ -326,7 +330,7 @@ def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, devi
             M[m, mp[1]] = -f(coef)
             M[m, mp[1] + 1] = f(coef)
     main = mk(M, basis, num_cols - 1, m, instance_problem)
-    if not art_rows:
+    if not art_rows or general:
         return main
     num_art = len(art_rows)                                              # :292-325
     nac = num_cols + num_art
@@ -631,10 +635,21 @@ def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_p
     exact=True (opt-in): a problem whose numbers are all rational (int or Fraction) is solved with the
     reference's rational semantics (src/utils.lisp:84-124) on exact integer tableaux (exact.py) and the
     solved ExactTableau is returned, its read-back in Fractions; exact_bits 128 starts at 128 bits
-    instead of 64.  Any float in the problem means the double path, unchanged.  Not together with
-    branch_and_bound (declined)."""
+    instead of 64.  Any float in the problem means the double path, unchanged.
+    exact=True together with branch_and_bound=True, on a problem with integer variables whose numbers are
+    all rational: the reference's branch-and-bound in rational arithmetic, where its integrality test is
+    `integerp` of a ratio (src/simplex.lisp:475-480) -- exact_bb.py: up to bb_width node LPs side by side
+    as batches of exact tableaux assembled on the device; returns the incumbent's solved ExactTableau.
+    (With a float anywhere: the f64 branch-and-bound above, unchanged.  Without integer variables the
+    combination is declined.)"""
     if exact and branch_and_bound:
-        raise UnsupportedConstraintError(("exact", "branch-and-bound"), "mi355x-simplex")
+        from .exact import rational_problem
+        if not problem.integer_vars:
+            raise UnsupportedConstraintError(("exact", "branch-and-bound"), "mi355x-simplex")
+        if rational_problem(problem):
+            from .exact_bb import solve_branch_and_bound_exact
+            return solve_branch_and_bound_exact(problem, width=bb_width, device=device, max_pivots=max_pivots,
+                                                max_nodes=max_nodes, min_bits=exact_bits, chunk=chunk)
     if problem.integer_vars and branch_and_bound:
         from .native import solve_branch_and_bound
         return solve_branch_and_bound(problem, fp_tolerance=fp_tolerance, int_tolerance=int_tolerance,

@@ -371,7 +371,7 @@ CL_FUNCTIONS = {
     "caddr": _sig(1, 1), "cdddr": _sig(1, 1), "first": _sig(1, 1), "second": _sig(1, 1), "third": _sig(1, 1), "fourth": _sig(1, 1),
     "rest": _sig(1, 1), "last": _sig(1, 2), "nth": _sig(2, 2), "nthcdr": _sig(2, 2), "cons": _sig(2, 2), "list": _sig(0), "list*": _sig(1),
     "append": _sig(0), "nconc": _sig(0), "reverse": _sig(1, 1), "nreverse": _sig(1, 1), "length": _sig(1, 1), "elt": _sig(2, 2),
-    "copy-list": _sig(1, 1), "copy-seq": _sig(1, 1), "subseq": _sig(2, 3), "member": _sig(2, None, [":key", ":test", ":test-not"]),
+    "copy-list": _sig(1, 1), "copy-seq": _sig(1, 1), "copy-structure": _sig(1, 1), "subseq": _sig(2, 3), "member": _sig(2, None, [":key", ":test", ":test-not"]),
     "assoc": _sig(2, None, [":key", ":test", ":test-not"]), "mapcar": _sig(2), "mapc": _sig(2), "mapcan": _sig(2), "map": _sig(3),
     "maphash": _sig(2, 2), "reduce": _sig(2, None, _SEQ_KEYS), "find": _sig(2, None, _SEQ_KEYS), "find-if": _sig(2, None, _SEQ_KEYS),
     "position": _sig(2, None, _SEQ_KEYS), "position-if": _sig(2, None, _SEQ_KEYS), "count": _sig(2, None, _SEQ_KEYS),
