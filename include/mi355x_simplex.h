@@ -320,7 +320,9 @@ void mi355x_simplex_solver_many_abandon(mi355x_solve_many *job);
  * src/simplex.lisp:337-461 under the rational dispatch.  Values are stored as 64-bit integers (128-bit
  * products) or 128-bit integers (256-bit products); a solve that overflows 64 bits restarts from the
  * initial tableau(s) at 128 bits (results do not depend on the width), one that overflows 128 bits ends
- * with MI_EXACT_OVERFLOW and the handle can only be destroyed.
+ * with MI_EXACT_OVERFLOW and the handle can only be destroyed -- unless the handle was created with
+ * mi355x_xtab_create_wide and max_bits 256: then the solve restarts once more at 256 bits (four 64-bit limbs
+ * per value, 512-bit products), and only what outgrows those ends with MI_EXACT_OVERFLOW.
  * Start state: with L_i the LCM of row i's denominators and the objective row's LCM multiplied into the
  * first constraint row's, D0 = prod L_i and T0 = D0 * t0 -- the state after the slack identity has been
  * pivoted, which needs the basis columns to be exact unit columns and the objective row zero on them
@@ -331,9 +333,17 @@ void mi355x_simplex_solver_many_abandon(mi355x_solve_many *job);
  * 64 bits when T0 fits, 128: start at 128.  MI_EXACT_OVERFLOW when T0 needs more than 128 bits. */
 int  mi355x_xtab_create(mi355x_xtab **out, int64_t rows, int64_t cols, const int64_t *num,
                         const int64_t *den, const int64_t *basis, int device, int min_bits);
+/* mi355x_xtab_create with the widest width the handle's solves may escalate to: max_bits 128 (exactly
+ * mi355x_xtab_create) or 256.  min_bits 0, 64, 128 or 256, at most max_bits: the width to start at when T0
+ * fits it (a T0 that does not starts at the next one that holds it).  Any other value of either is MI_BAD_ARG,
+ * before a device is looked at.  MI_EXACT_OVERFLOW when T0 needs more than max_bits. */
+int  mi355x_xtab_create_wide(mi355x_xtab **out, int64_t rows, int64_t cols, const int64_t *num,
+                             const int64_t *den, const int64_t *basis, int device, int min_bits, int max_bits);
 /* n-solve-tableau, single phase (src/simplex.lisp:453-461): at most max_pivots pivots (0 = no cap),
  * *n_pivots = pivots made by this call.  MI_OPTIMAL / MI_UNBOUNDED / MI_MAX_PIVOTS (a further call
- * carries on exactly) / MI_CANCELLED (mi355x_xtab_cancel from another thread; whole pivots only). */
+ * carries on exactly) / MI_CANCELLED (mi355x_xtab_cancel from another thread; whole pivots only).
+ * MI_EXACT_OVERFLOW once the widest width the handle allows is exceeded (the message names it); the handle
+ * is dead from then on and every further call on it says the same. */
 int  mi355x_xtab_solve(mi355x_xtab *t, int is_max, int64_t max_pivots, int64_t *n_pivots);
 /* n-solve-tableau, two-phase branch (src/simplex.lisp:402-452): phase 1 on `art` (a min problem), the
  * exact feasibility test, the drive-out pivots (first non-basic column with a non-zero entry, negative
@@ -342,17 +352,23 @@ int  mi355x_xtab_solve(mi355x_xtab *t, int is_max, int64_t max_pivots, int64_t *
  * denominators) and phase 2.  max_pivots caps both phases together (0 = no cap); a call after
  * MI_MAX_PIVOTS or MI_CANCELLED carries on where the job stopped.  n_pivots[0] = phase-1 pivots made by
  * this call (drive-out pivots included; they are not in the trace, as in the reference's loop),
- * n_pivots[1] = phase-2 pivots.  Outcomes as mi355x_solve_two_phase. */
+ * n_pivots[1] = phase-2 pivots.  Outcomes as mi355x_solve_two_phase.  The job runs at one width, both
+ * tableaux restarting together; handles created with different max_bits are MI_BAD_ARG. */
 int  mi355x_xtab_solve_two_phase(mi355x_xtab *art, mi355x_xtab *main_tab, int main_is_max,
                                  int64_t max_pivots, int64_t *n_pivots);
 /* tableau-matrix / tableau-basis-columns (src/simplex.lisp:48-58): the raw T as (low, high) 64-bit
  * limbs of a two's complement 128-bit integer per entry (rows*cols*2), D likewise (2), the basis
  * (rows-1).  t_ij = T_ij / D.  Any pointer may be NULL. */
 int  mi355x_xtab_download(mi355x_xtab *t, int64_t *num_lo_hi, int64_t *den_lo_hi, int64_t *basis);
+/* The same with `limbs` little-endian 64-bit limbs per value (two's complement, sign-extended): entries
+ * rows*cols*limbs, D limbs values.  limbs 2 or 4, and the handle's width at most 64 * limbs; anything else
+ * is MI_BAD_ARG.  On a handle at 256 bits mi355x_xtab_download itself fails with MI_BAD_ARG (its message
+ * names this form) and writes nothing: a value is never truncated. */
+int  mi355x_xtab_download_limbs(mi355x_xtab *t, int limbs, int64_t *num_limbs, int64_t *den_limbs, int64_t *basis);
 /* the (entering column, row) of every pivot chosen by the solve loops since the start, in order (the
  * drive-out pivots are not in it); at most cap, *n = all. */
 int  mi355x_xtab_trace(mi355x_xtab *t, int64_t *entering_cols, int64_t *pivot_rows, int64_t cap, int64_t *n);
-/* the width in use: 64 or 128 */
+/* the width in use: 64, 128 or 256 */
 int  mi355x_xtab_bits(const mi355x_xtab *t, int *bits);
 /* mi355x_tab_cancel for the exact solves (any thread) */
 int  mi355x_xtab_cancel(mi355x_xtab *t);

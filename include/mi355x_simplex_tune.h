@@ -221,9 +221,20 @@ int         mi355x_tune_set_la_fault(int step_plus_1);       /* > 0: the last wo
  *                                                                     110 (quotient too wide) or 111 (remainder)
  *   12 xrem: |256-bit a| mod 128-bit b (0 < b < 2^127)
  *   13 xinv_odd modulo 2^64 (a)    14 xinv_odd modulo 2^128 (a)       a odd
- *   15 xctz of the 128-bit a (non-zero) -> out limb 0 */
+ *   15 xctz of the 128-bit a (non-zero) -> out limb 0
+ *   16 xinv_odd modulo 2^256 (a odd, all four limbs)               17 xctz of the 256-bit a (non-zero) -> out limb 0 */
 int         mi355x_test_xarith(int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out,
                                int32_t *rc, int device);
+/* The same for the primitives of the 256-bit width (xwide.h) that take or return 512-bit values: element i of a,
+ * b and out is EIGHT limbs at [8 i, 8 i + 8); a 256-bit value takes limbs 0 .. 3.  op:
+ *    0 xmul 256 x 256 -> 512
+ *    1 add   2 xsub   3 negate (a)   4 xlt -> out limb 0   5 xeq -> out limb 0   (512-bit a, b; wrapping)
+ *    6 xsub_ovf: 512-bit a - b                                        rc 1: the difference left the width
+ *    7 xfit 512 -> 256 (a)                                            rc 1: outside the symmetric range
+ *    8 xdiv: 512-bit a / 256-bit b                                    b > 0; rc 0, 110 or 111 as above
+ *    9 xrem: |512-bit a| mod 256-bit b (0 < b < 2^255) */
+int         mi355x_test_xarith8(int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out,
+                                int32_t *rc, int device);
 #endif
 
 #ifdef __cplusplus

@@ -31,9 +31,11 @@ SIGNATURES = {
     "mi355x_init": (_int, [_int]),
     "mi355x_tab_create": (_int, [_pp, _i64, _i64, _p, _p, _int]),
     "mi355x_xtab_create": (_int, [_pp, _i64, _i64, _p, _p, _p, _int, _int]),
+    "mi355x_xtab_create_wide": (_int, [_pp, _i64, _i64, _p, _p, _p, _int, _int, _int]),
     "mi355x_xtab_solve": (_int, [_p, _int, _i64, _p]),
     "mi355x_xtab_solve_two_phase": (_int, [_p, _p, _int, _i64, _p]),
     "mi355x_xtab_download": (_int, [_p, _p, _p, _p]),
+    "mi355x_xtab_download_limbs": (_int, [_p, _int, _p, _p, _p]),
     "mi355x_xtab_trace": (_int, [_p, _p, _p, _i64, _p]),
     "mi355x_xtab_bits": (_int, [_p, _p]),
     "mi355x_xtab_cancel": (_int, [_p]),
@@ -214,6 +216,7 @@ _TEST_HOOKS = {
     "mi355x_tune_set_shard_la_fault": (_int, [_int]),
     # one primitive of the exact kernels' wide integer arithmetic over arrays of operands
     "mi355x_test_xarith": (_int, [_int, _i64, _p, _p, _p, _p, _int]),
+    "mi355x_test_xarith8": (_int, [_int, _i64, _p, _p, _p, _p, _int]),
 }
 TEST_LIB_PATH = os.path.join(HERE, "libmi355x_simplex_test.so")
 

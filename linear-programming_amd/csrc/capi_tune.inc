@@ -102,13 +102,15 @@ int         mi355x_tab_path_counts(const mi355x_tab *t, int64_t *out8)
 }
 #ifdef MI355X_TEST_HOOKS
 // one arithmetic primitive of the exact kernels (kernels_exact.inc) over n operand tuples, one launch
-int         mi355x_test_xarith(int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out, int32_t *rc, int device)
+// (limbs per element: 4 for mi355x_test_xarith, 8 for mi355x_test_xarith8)
+static int  x_arith_probe(int limbs, int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out, int32_t *rc, int device)
 {
-    if (op < 0 || op >= kXProbeOps || n < 1 || n > (1 << 24) || !a || !b || !out || !rc) return fail(MI_BAD_ARG, "bad opcode, count or NULL array");
+    if (op < 0 || op >= (limbs == 4 ? (int)kXProbeOps : (int)kXProbe8Ops) || n < 1 || n > (1 << 24) || !a || !b || !out || !rc)
+        return fail(MI_BAD_ARG, "bad opcode, count or NULL array");
     int st = x_check_device(device);
     if (st != MI_OK) return st;
     if (hipSetDevice(device) != hipSuccess) return fail(MI_HIP_ERROR, "hipSetDevice failed");
-    const size_t bytes = (size_t)n * 4 * sizeof(int64_t);
+    const size_t bytes = (size_t)n * limbs * sizeof(int64_t);
     int64_t *da = nullptr, *db = nullptr, *dout = nullptr;
     int32_t *drc = nullptr;
     hipError_t e = hipMalloc(&da, bytes);
@@ -118,7 +120,8 @@ int         mi355x_test_xarith(int op, int64_t n, const int64_t *a, const int64_
     if (e == hipSuccess) e = hipMemcpy(da, a, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(db, b, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        launch_x_arith_probe(op, n, da, db, dout, drc, nullptr);
+        if (limbs == 4) launch_x_arith_probe(op, n, da, db, dout, drc, nullptr);
+        else            launch_x_arith_probe8(op, n, da, db, dout, drc, nullptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
@@ -126,6 +129,15 @@ int         mi355x_test_xarith(int op, int64_t n, const int64_t *a, const int64_
     (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout); (void)hipFree(drc);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "mi355x_test_xarith: %s", hipGetErrorString(e));
     return MI_OK;
+}
+int         mi355x_test_xarith(int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out, int32_t *rc, int device)
+{
+    return x_arith_probe(4, op, n, a, b, out, rc, device);
+}
+// the primitives of the 256-bit width whose operands or results are 512 bits: elements of eight limbs
+int         mi355x_test_xarith8(int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out, int32_t *rc, int device)
+{
+    return x_arith_probe(8, op, n, a, b, out, rc, device);
 }
 #endif
 

@@ -16,7 +16,8 @@
 // slow bitwise remainder, which only ever runs on that path.
 //
 // W = 64: int64_t storage, __int128 products.  W = 128: __int128 storage, 256-bit products as two
-// 128-bit limbs (S256 below).  Plain C++ throughout.
+// 128-bit limbs (S256 below).  W = 256 (the single tableau only): X256 storage, X512 products, both from
+// xwide.h -- the overloads below hand the rules its functions.  Plain C++ throughout.
 //
 //   k_x_select<T>    one workgroup: pricing, ratio test, pivot record, snapshots col / prow
 //   k_x_force<T>     one workgroup: the same record and snapshots for a given pivot (drive-out)
@@ -151,9 +152,46 @@ __device__ inline int xctz(xu128 d)
     return lo ? __builtin_ctzll(lo) : 64 + __builtin_ctzll((uint64_t)(d >> 64));
 }
 
+// ---- the same overload set at W = 256: X256 -> X512 products (xwide.h) ---------------------------------
+__device__ inline X512 xmul(const X256 &a, const X256 &b) { return xw_mul(a, b); }
+__device__ inline X512 xsub(const X512 &a, const X512 &b) { return a - b; }   // operands below 2^510 in magnitude
+__device__ inline bool xlt(const X512 &a, const X512 &b) { return xw_lt(a, b); }
+__device__ inline bool xeq(const X512 &a, const X512 &b) { return xw_eq(a, b); }
+__device__ inline bool xsub_ovf(X512 &acc, const X512 &b) { return xw_sub_ovf(acc, b); }
+__device__ inline bool xfit(const X512 &x, X256 *out) { return xw_fit<4>(x, out); }
+__device__ inline bool xsym(const X256 &x) { return !xw_is_min(x); }
+__device__ inline XU256 xrem(const X512 &N, const XU256 &d) { return xw_rem<4>(N, d); }   // N below 2^511 in magnitude, 0 < d < 2^255
+__device__ inline int xctz(const XU256 &d) { return xw_ctz(d); }
+// xinv_odd<XU256> is the template above: 3 * 2^7 = 384 correct bits after its seven steps, 256 needed (128 bits
+// need six of them, 64 five)
+__device__ inline int xdiv(const X512 &N, const X256 &D, int shift, const XU256 &inv, X256 *q)
+{
+    if (shift && xw_ctz_limbs<8>(N.l) < shift) return kXInexact;
+    const X256 qs = (XUWide<4>(X256(xw_sar(N, shift))) * inv).as_signed();
+    if (xsym(qs) && xeq(xmul(qs, D), N)) { *q = qs; return 0; }
+    const XU256 r = xrem(N, XU256(D));
+    return xw_ctz(r) == 256 ? kXOverflow : kXInexact;
+}
+
 template <class T> struct XUnsigned;
 template <> struct XUnsigned<int64_t>  { typedef uint64_t type; };
 template <> struct XUnsigned<__int128> { typedef xu128 type; };
+template <> struct XUnsigned<X256>     { typedef XU256 type; };
+
+// the pivot record and the denominator of a width: XPivot and __int128 up to 128 bits, their twins at 256
+// (XCtl, simplex_kernels.h)
+template <class T> struct XRec {
+    typedef XPivot Pivot;
+    typedef __int128 Wide;
+    __device__ static Wide  &D(XCtl *c) { return c->D; }
+    __device__ static Pivot &piv(XCtl *c) { return c->piv; }
+};
+template <> struct XRec<X256> {
+    typedef XPivotW Pivot;
+    typedef X256 Wide;
+    __device__ static Wide  &D(XCtl *c) { return c->Dw; }
+    __device__ static Pivot &piv(XCtl *c) { return c->pivw; }
+};
 
 // what xdiv takes besides D = 2^shift * odd, D > 0: the shift and the inverse of the odd part modulo 2^W
 template <class T> __device__ inline void x_div_setup(__int128 D, int32_t *shift, __int128 *inv)
@@ -162,6 +200,12 @@ template <class T> __device__ inline void x_div_setup(__int128 D, int32_t *shift
     const int sh = xctz((xu128)D);
     *shift = sh;
     *inv = (__int128)xinv_odd<U>((U)(D >> sh));
+}
+template <class T> __device__ inline void x_div_setup(const X256 &D, int32_t *shift, X256 *inv)
+{
+    const int sh = xctz(XU256(D));
+    *shift = sh;
+    *inv = xinv_odd<XU256>(xw_shr(XU256(D), sh)).as_signed();
 }
 
 // ---- what the single tableau and the batches (kernels_exact_batch.inc) share: one copy of each rule ----
@@ -240,13 +284,14 @@ template <class T> __device__ __forceinline__ int64_t x_ratio(const T *M, int64_
 }
 
 // the pivot record of (ec, cr) on a tableau with denominator D -- one thread; D' is r->pa
-template <class T> __device__ inline void x_record(XPivot *r, const T *M, int64_t C, int64_t ec, int64_t cr, __int128 D)
+template <class T> __device__ inline void x_record(typename XRec<T>::Pivot *r, const T *M, int64_t C, int64_t ec, int64_t cr,
+                                                   typename XRec<T>::Wide D)
 {
     const T p = M[cr * C + ec];
     r->ec = ec;
     r->cr = cr;
     r->sgn = p < 0 ? -1 : 1;
-    r->pa = (__int128)(p < 0 ? -p : p);
+    r->pa = (typename XRec<T>::Wide)(p < 0 ? -p : p);
     r->dold = D;
     x_div_setup<T>(D, &r->shift, &r->inv);
 }
@@ -258,7 +303,7 @@ template <class T> struct XPivotT {
     int     sgn, shift;
     T       pa, dold;
     U       inv;
-    __device__ explicit XPivotT(const XPivot &r)
+    __device__ explicit XPivotT(const typename XRec<T>::Pivot &r)
         : ec(r.ec), cr(r.cr), sgn(r.sgn), shift(r.shift), pa((T)r.pa), dold((T)r.dold), inv((U)r.inv) {}
 };
 
@@ -338,8 +383,8 @@ template <class T> __global__ __launch_bounds__(kXThreads) void k_x_select(XView
         return;
     }
     if (tid == 0) {
-        x_record<T>(&c->piv, M, C, ec, cr, c->D);
-        c->D = c->piv.pa;
+        x_record<T>(&XRec<T>::piv(c), M, C, ec, cr, XRec<T>::D(c));
+        XRec<T>::D(c) = XRec<T>::piv(c).pa;
         c->apply = 1;
         v.basis[cr] = ec;
         if (c->trace_n < v.trace_cap) { v.trace_ec[c->trace_n] = ec; v.trace_cr[c->trace_n] = cr; }
@@ -347,7 +392,7 @@ template <class T> __global__ __launch_bounds__(kXThreads) void k_x_select(XView
         c->n_pivots += 1;
     }
     __syncthreads();
-    x_snapshot<T>(M, v.rows, C, XPivotT<T>(c->piv), (T *)v.col, (T *)v.prow);
+    x_snapshot<T>(M, v.rows, C, XPivotT<T>(XRec<T>::piv(c)), (T *)v.col, (T *)v.prow);
 }
 
 // a pivot given by the host (the drive-out of src/simplex.lisp:418-436): not counted, not traced
@@ -356,13 +401,13 @@ template <class T> __global__ __launch_bounds__(kXThreads) void k_x_force(XView 
     XCtl *c = v.ctl;
     const T *M = (const T *)v.T;
     if (threadIdx.x == 0) {
-        x_record<T>(&c->piv, M, v.cols, ec, cr, c->D);
-        c->D = c->piv.pa;
+        x_record<T>(&XRec<T>::piv(c), M, v.cols, ec, cr, XRec<T>::D(c));
+        XRec<T>::D(c) = XRec<T>::piv(c).pa;
         c->apply = 1;
         v.basis[cr] = ec;
     }
     __syncthreads();
-    x_snapshot<T>(M, v.rows, v.cols, XPivotT<T>(c->piv), (T *)v.col, (T *)v.prow);
+    x_snapshot<T>(M, v.rows, v.cols, XPivotT<T>(XRec<T>::piv(c)), (T *)v.col, (T *)v.prow);
 }
 
 template <class T> __global__ __launch_bounds__(256) void k_x_update(XView v)
@@ -372,7 +417,7 @@ template <class T> __global__ __launch_bounds__(256) void k_x_update(XView v)
     T *M = (T *)v.T;
     const T *col = (const T *)v.col, *prow = (const T *)v.prow;
     const int64_t C = v.cols;
-    const XPivotT<T> p(c->piv);
+    const XPivotT<T> p(XRec<T>::piv(c));
     int err = 0;
     for (int64_t r = blockIdx.y; r < v.rows; r += gridDim.y) {
         const T cv = col[r];
@@ -384,14 +429,14 @@ template <class T> __global__ __launch_bounds__(256) void k_x_update(XView v)
 
 template <class T> __global__ __launch_bounds__(256) void k_x_handover(XView a, XView mt, const T *w, const T *cl, T lc)
 {
-    const T D = (T)a.ctl->D;
+    const T D = (T)XRec<T>::D(a.ctl);
     int err = 0;
     for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < mt.cols; j += (int64_t)gridDim.x * blockDim.x)
         if (!x_handover_column<T>((const T *)a.T, a.cols, (T *)mt.T, mt.cols, a.rows - 1, j, D, w, cl, lc)) err = kXOverflow;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         T d = 0;
         if (!xfit(xmul(lc, D), &d)) err = kXOverflow;
-        mt.ctl->D = (__int128)d;
+        XRec<T>::D(mt.ctl) = (typename XRec<T>::Wide)d;
     }
     if (err) atomicMax(&mt.ctl->err, err);
 }
@@ -399,32 +444,41 @@ template <class T> __global__ __launch_bounds__(256) void k_x_handover(XView a, 
 static unsigned x_grid_x(int64_t cols) { const int64_t g = (cols + 255) / 256; return (unsigned)(g < 64 ? g : 64); }
 static unsigned x_grid_y(int64_t rows) { return (unsigned)(rows < 4096 ? rows : 4096); }
 
-// f(T()) with T the storage type of `bits`: the launchers' int64_t / __int128 pair
+// f(T()) with T the storage type of `bits`: the int64_t / __int128 pair of every exact launcher (the batches'
+// and branch-and-bound's too, which stop at 128 bits) ...
 template <class F> static void x_with_width(int bits, F f)
 {
     if (bits == 64) f((int64_t)0);
     else            f((__int128)0);
 }
+// ... and its third case, for the launchers of the single tableau alone
+template <class F> static void x_with_tab_width(int bits, F f)
+{
+    if (bits == 256) f(X256());
+    else             x_with_width(bits, f);
+}
 
 void launch_x_select(const XView &v, int is_max, hipStream_t s)
 {
-    x_with_width(v.bits, [&](auto t) { hipLaunchKernelGGL(k_x_select<decltype(t)>, dim3(1), dim3(kXThreads), 0, s, v, is_max); });
+    x_with_tab_width(v.bits, [&](auto t) { hipLaunchKernelGGL(k_x_select<decltype(t)>, dim3(1), dim3(kXThreads), 0, s, v, is_max); });
 }
 void launch_x_force(const XView &v, int64_t ec, int64_t cr, hipStream_t s)
 {
-    x_with_width(v.bits, [&](auto t) { hipLaunchKernelGGL(k_x_force<decltype(t)>, dim3(1), dim3(kXThreads), 0, s, v, ec, cr); });
+    x_with_tab_width(v.bits, [&](auto t) { hipLaunchKernelGGL(k_x_force<decltype(t)>, dim3(1), dim3(kXThreads), 0, s, v, ec, cr); });
 }
 void launch_x_update(const XView &v, hipStream_t s)
 {
     const dim3 grid(x_grid_x(v.cols), x_grid_y(v.rows));
-    x_with_width(v.bits, [&](auto t) { hipLaunchKernelGGL(k_x_update<decltype(t)>, grid, dim3(256), 0, s, v); });
+    x_with_tab_width(v.bits, [&](auto t) { hipLaunchKernelGGL(k_x_update<decltype(t)>, grid, dim3(256), 0, s, v); });
 }
-void launch_x_handover(const XView &art, const XView &mt, const void *w, const void *cl, __int128 lc, hipStream_t s)
+void launch_x_handover(const XView &art, const XView &mt, const void *w, const void *cl, const void *lc, hipStream_t s)
 {
     const dim3 grid((unsigned)((mt.cols + 255) / 256));
-    x_with_width(mt.bits, [&](auto t) {
+    x_with_tab_width(mt.bits, [&](auto t) {
         typedef decltype(t) T;
-        hipLaunchKernelGGL(k_x_handover<T>, grid, dim3(256), 0, s, art, mt, (const T *)w, (const T *)cl, (T)lc);
+        T lcv;
+        __builtin_memcpy(&lcv, lc, sizeof(T));
+        hipLaunchKernelGGL(k_x_handover<T>, grid, dim3(256), 0, s, art, mt, (const T *)w, (const T *)cl, lcv);
     });
 }
 
@@ -437,6 +491,14 @@ __device__ inline __int128 xp_i128(const int64_t *p) { return (__int128)(((xu128
 __device__ inline S256 xp_s256(const int64_t *p) { S256 r; r.lo = (xu128)xp_i128(p); r.hi = xp_i128(p + 2); return r; }
 __device__ inline void xp_put(int64_t *o, __int128 x) { o[0] = (int64_t)(uint64_t)(xu128)x; o[1] = (int64_t)(x >> 64); }
 __device__ inline void xp_put(int64_t *o, S256 x) { xp_put(o, (__int128)x.lo); xp_put(o + 2, x.hi); }
+
+template <int N> __device__ inline XWide<N> xp_wide(const int64_t *p)
+{
+    XWide<N> r;
+    for (int i = 0; i < N; ++i) r.l[i] = (uint64_t)p[i];
+    return r;
+}
+template <int N> __device__ inline void xp_put(int64_t *o, const XWide<N> &x) { for (int i = 0; i < N; ++i) o[i] = (int64_t)x.l[i]; }
 
 __global__ __launch_bounds__(256) void k_x_arith_probe(int op, int64_t n, const int64_t *a, const int64_t *b,
                                                        int64_t *out, int32_t *rc)
@@ -483,6 +545,11 @@ __global__ __launch_bounds__(256) void k_x_arith_probe(int op, int64_t n, const 
             if (xp_i128(pa) == 0) { st = -1; break; }
             o[0] = xctz((xu128)xp_i128(pa));
             break;
+        case kXProbeInv256: xp_put(o, xinv_odd<XU256>(XU256(xp_wide<4>(pa))).as_signed()); break;
+        case kXProbeCtz256:
+            if (xp_wide<4>(pa) == 0) { st = -1; break; }
+            o[0] = xctz(XU256(xp_wide<4>(pa)));
+            break;
         default: st = -1;
         }
         rc[i] = st;
@@ -493,5 +560,51 @@ void launch_x_arith_probe(int op, int64_t n, const int64_t *a, const int64_t *b,
 {
     const int64_t g = (n + 255) / 256;
     hipLaunchKernelGGL(k_x_arith_probe, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, s, op, n, a, b, out, rc);
+}
+
+// Element i of a, b and out is eight limbs at [8 i, 8 i + 8): a 512-bit value takes all of them, a 256-bit one
+// the low four (out: the rest is zero).  rc as above.
+__global__ __launch_bounds__(256) void k_x_arith_probe8(int op, int64_t n, const int64_t *a, const int64_t *b,
+                                                        int64_t *out, int32_t *rc)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t *pa = a + 8 * i, *pb = b + 8 * i;
+        int64_t *o = out + 8 * i;
+        int32_t st = 0;
+        for (int k = 0; k < 8; ++k) o[k] = 0;
+        switch (op) {
+        case kXProbe8Mul256: xp_put(o, xmul(xp_wide<4>(pa), xp_wide<4>(pb))); break;
+        case kXProbe8Add512: xp_put(o, xp_wide<8>(pa) + xp_wide<8>(pb)); break;
+        case kXProbe8Sub512: xp_put(o, xsub(xp_wide<8>(pa), xp_wide<8>(pb))); break;
+        case kXProbe8Neg512: xp_put(o, -xp_wide<8>(pa)); break;
+        case kXProbe8Lt512:  o[0] = xlt(xp_wide<8>(pa), xp_wide<8>(pb)) ? 1 : 0; break;
+        case kXProbe8Eq512:  o[0] = xeq(xp_wide<8>(pa), xp_wide<8>(pb)) ? 1 : 0; break;
+        case kXProbe8SubOvf256: { X512 acc = xp_wide<8>(pa); st = xsub_ovf(acc, xp_wide<8>(pb)) ? 0 : 1; xp_put(o, acc); break; }
+        case kXProbe8Fit256: { X256 y = 0; st = xfit(xp_wide<8>(pa), &y) ? 0 : 1; xp_put(o, y); break; }
+        case kXProbe8Div256: {
+            int32_t sh; X256 inv, q = 0;
+            const X256 d = xp_wide<4>(pb);
+            if (!(d > 0)) { st = -1; break; }
+            x_div_setup<X256>(d, &sh, &inv);
+            st = xdiv(xp_wide<8>(pa), d, sh, XU256(inv), &q);
+            xp_put(o, q);
+            break;
+        }
+        case kXProbe8Rem256: {
+            const X256 d = xp_wide<4>(pb);
+            if (!(d > 0)) { st = -1; break; }
+            xp_put(o, xrem(xp_wide<8>(pa), XU256(d)).as_signed());
+            break;
+        }
+        default: st = -1;
+        }
+        rc[i] = st;
+    }
+}
+
+void launch_x_arith_probe8(int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out, int32_t *rc, hipStream_t s)
+{
+    const int64_t g = (n + 255) / 256;
+    hipLaunchKernelGGL(k_x_arith_probe8, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, s, op, n, a, b, out, rc);
 }
 #endif

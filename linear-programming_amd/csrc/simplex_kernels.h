@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "xwide.h"
 
 namespace mi355x {
 
@@ -330,7 +331,8 @@ void   set_resident_poll(int mode);     // tuning hook: who polls the exchange r
 
 // Exact (fraction-free, Bareiss) tableaux: kernels_exact.inc, capi_exact.inc.  The tableau is an
 // integer matrix T and one positive integer D with t_ij = T_ij / D (objective row included),
-// stored as int64_t (bits 64) or __int128 (bits 128).  Every stored value stays inside the
+// stored as int64_t (bits 64), __int128 (bits 128) or X256 (bits 256: four 64-bit limbs, xwide.h; the
+// single tableau only, and only on a handle that allows it).  Every stored value stays inside the
 // symmetric range (-2^(W-1), 2^(W-1)), so products and their differences never overflow the
 // double-width intermediates.
 constexpr int32_t kXOverflow = 110;    // a value left the width in use: restart wider or MI_EXACT_OVERFLOW
@@ -344,6 +346,17 @@ struct XPivot {
     __int128 dold;        // D before the pivot
     __int128 inv;         // inverse of the odd part of dold modulo 2^W
 };
+// the 256-bit storage type, its products, and the unsigned twin the inverses live in
+typedef XWide<4>  X256;
+typedef XWide<8>  X512;
+typedef XUWide<4> XU256;
+// XPivot's twin at 256 bits.  XPivot itself is also the record a batch member keeps in LDS, and the batches
+// stay at 64 / 128 bits: it keeps its layout, and the single tableau's control block carries this one beside it.
+struct XPivotW {
+    int64_t  ec, cr;
+    int32_t  sgn, shift;
+    X256     pa, dold, inv;
+};
 struct XCtl {
     int32_t  status;      // kRunning, or MI_OPTIMAL / MI_UNBOUNDED / MI_MAX_PIVOTS / kXOverflow / kXInexact
     int32_t  err;         // 0, or kXOverflow / kXInexact raised by an update (the larger one wins)
@@ -354,6 +367,8 @@ struct XCtl {
     int64_t  trace_n;     // pivots recorded (trace buffers hold the first trace_cap)
     __int128 D;           // the common denominator, > 0
     XPivot   piv;         // that pivot (device only)
+    X256     Dw;          // bits == 256: the common denominator (D is unused then) ...
+    XPivotW  pivw;        // ... and the pivot
 };
 struct XView {
     void    *T;           // rows x cols, row-major, no padding
@@ -363,14 +378,15 @@ struct XView {
     XCtl    *ctl;
     int64_t *trace_ec, *trace_cr;
     int64_t  rows, cols, trace_cap;
-    int      bits;        // 64 or 128
+    int      bits;        // 64, 128 or 256
 };
 void launch_x_select(const XView &v, int is_max, hipStream_t s);
 void launch_x_force(const XView &v, int64_t ec, int64_t cr, hipStream_t s);
 void launch_x_update(const XView &v, hipStream_t s);
 // main[r][j] = lc * art[r][src(j)] (r < m); main[m][j] = D_art * cl[j] - sum_r w[r] * art[r][src(j)];
-// main D = lc * D_art.  w (m) and cl (main cols) hold values of the handles' width.
-void launch_x_handover(const XView &art, const XView &mt, const void *w, const void *cl, __int128 lc, hipStream_t s);
+// main D = lc * D_art.  w (m) and cl (main cols) hold values of the handles' width (device memory), lc points
+// at one such value on the host.
+void launch_x_handover(const XView &art, const XView &mt, const void *w, const void *cl, const void *lc, hipStream_t s);
 // Batches of exact tableaux of one shape, one workgroup per member (kernels_exact_batch.inc,
 // capi_exact_batch.inc).  One XbView per width of a handle: member q's tableau at T + q * rows * cols,
 // its basis at basis + q * (rows - 1), its trace at trace_* + q * trace_cap, its hand-over multipliers
@@ -428,8 +444,13 @@ void launch_xbb_readback(const XbView &v, const int32_t *width, int64_t *values,
 // opcodes and the limb layout are mi355x_test_xarith's, include/mi355x_simplex_tune.h).  Device pointers.
 enum XProbeOp { kXProbeMul64 = 0, kXProbeMul128, kXProbeAdd256, kXProbeSub256, kXProbeNeg256, kXProbeLt256,
                 kXProbeSubOvf64, kXProbeSubOvf128, kXProbeFit64, kXProbeFit128, kXProbeDiv64, kXProbeDiv128,
-                kXProbeRem, kXProbeInv64, kXProbeInv128, kXProbeCtz, kXProbeOps };
+                kXProbeRem, kXProbeInv64, kXProbeInv128, kXProbeCtz, kXProbeInv256, kXProbeCtz256, kXProbeOps };
 void launch_x_arith_probe(int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out, int32_t *rc, hipStream_t s);
+// the same for the 256-bit width's primitives with 512-bit operands or results: elements of eight limbs
+// (k_x_arith_probe8, mi355x_test_xarith8)
+enum XProbe8Op { kXProbe8Mul256 = 0, kXProbe8Add512, kXProbe8Sub512, kXProbe8Neg512, kXProbe8Lt512, kXProbe8Eq512,
+                 kXProbe8SubOvf256, kXProbe8Fit256, kXProbe8Div256, kXProbe8Rem256, kXProbe8Ops };
+void launch_x_arith_probe8(int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out, int32_t *rc, hipStream_t s);
 #endif
 
 int         update_variant_count();

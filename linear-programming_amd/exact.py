@@ -7,7 +7,9 @@ boundary as numerators and denominators (mi355x_xtab_create).  On the GPU it is 
 integer tableau T with one common denominator D (kernels_exact.inc); every pivot, the two-phase
 hand-over and the read-back are exact, so the pivot sequence, the basis and every entry are the
 reference's own.  Values are 64-bit integers, or 128-bit ones once 64 bits overflow; a problem
-whose entries outgrow 128 bits is declined with unsupported-constraint-error.
+whose entries outgrow 128 bits is declined with unsupported-constraint-error -- or, with
+``exact_max_bits=256`` (opt-in), solved again at 256 bits on the single-tableau path and declined
+only past those.
 
 A list of problems (``mi355x_solve_problems(problems, exact=True)``) is grouped by tableau shape and
 sense; a group of two or more is one batch of exact tableaux (mi355x_xbatch_*, one workgroup per
@@ -33,11 +35,18 @@ def _declined(what):
     return UnsupportedConstraintError(("exact",) + tuple(what), "mi355x-simplex")
 
 
-def check(rc, where):
+def _check_widths(min_bits, max_bits):
+    """The (min_bits, max_bits) pairs mi355x_xtab_create_wide takes."""
+    if max_bits not in (128, 256) or min_bits not in (0, 64, 128, 256) or min_bits > max_bits:
+        raise ValueError("exact widths: min_bits %r must be 0, 64, 128 or 256 and at most max_bits %r (128 or 256)"
+                         % (min_bits, max_bits))
+
+
+def check(rc, where, max_bits=128):
     """capi.check, with MI_EXACT_OVERFLOW as the condition a caller can act on (fall back to the
-    reference's solver)."""
+    reference's solver); max_bits: the limit of the handle that overflowed."""
     if rc == capi.MI_EXACT_OVERFLOW:
-        raise _declined(("overflow", "128 bits"))
+        raise _declined(("overflow", "%d bits" % max_bits))
     if rc == capi.MI_UNSUPPORTED:
         raise _declined(("start", "basis columns are not unit columns"))
     return capi.check(rc, where)
@@ -45,6 +54,14 @@ def check(rc, where):
 
 def _int128(lo, hi):
     return (int(hi) << 64) | (int(lo) & 0xFFFFFFFFFFFFFFFF)
+
+
+def _int_of_limbs(limbs):
+    """Little-endian 64-bit limbs, two's complement: the top limb carries the sign."""
+    v = int(limbs[-1])
+    for x in reversed(limbs[:-1]):
+        v = (v << 64) | (int(x) & 0xFFFFFFFFFFFFFFFF)
+    return v
 
 
 def _num_den(matrix):
@@ -65,7 +82,7 @@ class ExactTableau:
     exact = True
 
     def __init__(self, problem, instance_problem, matrix, basis_columns, var_count, constraint_count,
-                 var_mapping, device=0, min_bits=0):
+                 var_mapping, device=0, min_bits=0, max_bits=128):
         self.problem = problem
         self.instance_problem = instance_problem
         self.var_count = int(var_count)
@@ -73,6 +90,8 @@ class ExactTableau:
         self.var_mapping = var_mapping
         self.device = device
         self.min_bits = int(min_bits)
+        self.max_bits = int(max_bits)            # the widest width its solves may escalate to: 128 or 256
+        _check_widths(self.min_bits, self.max_bits)
         self.n_pivots = 0
         self.phase1 = None                 # the artificial tableau of a two-phase solve
         self._handle = None
@@ -88,9 +107,14 @@ class ExactTableau:
         if self._handle is None:
             num, den = _num_den(self._matrix)
             h = ctypes.c_void_p()
-            check(capi.lib().mi355x_xtab_create(ctypes.byref(h), num.shape[0], num.shape[1], _ptr(num), _ptr(den),
-                                                _ptr(self._basis) if self._basis.size else None, self.device,
-                                                self.min_bits), "mi355x_xtab_create")
+            basis = _ptr(self._basis) if self._basis.size else None
+            if self.max_bits == 128:
+                rc = capi.lib().mi355x_xtab_create(ctypes.byref(h), num.shape[0], num.shape[1], _ptr(num), _ptr(den),
+                                                   basis, self.device, self.min_bits)
+            else:
+                rc = capi.lib().mi355x_xtab_create_wide(ctypes.byref(h), num.shape[0], num.shape[1], _ptr(num),
+                                                        _ptr(den), basis, self.device, self.min_bits, self.max_bits)
+            check(rc, "mi355x_xtab_create", self.max_bits)
             self._handle = h
         return self._handle
 
@@ -100,16 +124,23 @@ class ExactTableau:
     def raw(self):
         """(T as Python ints, D, basis) as the device holds them."""
         R, C = self._matrix.shape
+        b = np.empty(max(R - 1, 0), dtype=np.int64)
+        if not self._batch and self.bits == 256:
+            T = np.empty(R * C * 4, dtype=np.int64)
+            D = np.empty(4, dtype=np.int64)
+            check(capi.lib().mi355x_xtab_download_limbs(self._h, 4, _ptr(T), _ptr(D), _ptr(b) if b.size else None),
+                  "mi355x_xtab_download_limbs", self.max_bits)
+            vals = [_int_of_limbs(T[4 * k:4 * k + 4]) for k in range(R * C)]
+            return np.array(vals, dtype=object).reshape(R, C), _int_of_limbs(D), b
         T = np.empty(R * C * 2, dtype=np.int64)
         D = np.empty(2, dtype=np.int64)
-        b = np.empty(max(R - 1, 0), dtype=np.int64)
         if self._batch:
             xb, q = self._batch
             check(capi.lib().mi355x_xbatch_download(xb.handle, q, _ptr(T), _ptr(D), _ptr(b) if b.size else None),
                   "mi355x_xbatch_download")
         else:
             check(capi.lib().mi355x_xtab_download(self._h, _ptr(T), _ptr(D), _ptr(b) if b.size else None),
-                  "mi355x_xtab_download")
+                  "mi355x_xtab_download", self.max_bits)
         vals = [_int128(T[2 * k], T[2 * k + 1]) for k in range(R * C)]
         return np.array(vals, dtype=object).reshape(R, C), _int128(D[0], D[1]), b
 
@@ -143,7 +174,7 @@ class ExactTableau:
 
     @property
     def bits(self):
-        """The width the device uses for this tableau: 64 or 128."""
+        """The width the device uses for this tableau: 64, 128 or 256."""
         b = ctypes.c_int(0)
         if self._batch:
             check(capi.lib().mi355x_xbatch_bits(self._batch[0].handle, self._batch[1], ctypes.byref(b)), "mi355x_xbatch_bits")
@@ -196,7 +227,7 @@ def n_solve_exact(tabs, max_pivots=0, chunk=None):
 
         def call(cap):
             rc = check(L.mi355x_xtab_solve_two_phase(art._h, main._h, int(main.is_max), int(cap), npv),
-                       "mi355x_xtab_solve_two_phase")
+                       "mi355x_xtab_solve_two_phase", art.max_bits)
             done[0] += int(npv[0])
             done[1] += int(npv[1])
             return rc, int(npv[0]) + int(npv[1])
@@ -211,7 +242,8 @@ def n_solve_exact(tabs, max_pivots=0, chunk=None):
         return main
 
     def call(cap):
-        rc = check(L.mi355x_xtab_solve(tabs._h, int(tabs.is_max), int(cap), ctypes.byref(n)), "mi355x_xtab_solve")
+        rc = check(L.mi355x_xtab_solve(tabs._h, int(tabs.is_max), int(cap), ctypes.byref(n)), "mi355x_xtab_solve",
+                   tabs.max_bits)
         return rc, int(n.value)
     try:
         rc, total = _solve_in_chunks(call, tabs.constraint_count + 1, tabs.var_count + 1, int(max_pivots), chunk=chunk)
@@ -236,10 +268,11 @@ def rational_problem(problem):
                       for _, e, rhs in problem.constraints)
 
 
-def solve_exact(problem, device=0, max_pivots=0, min_bits=0, chunk=None):
-    """The exact route of mi355x_simplex_solver: build-tableau in Fractions, then the exact solve."""
+def solve_exact(problem, device=0, max_pivots=0, min_bits=0, chunk=None, exact_max_bits=128):
+    """The exact route of mi355x_simplex_solver: build-tableau in Fractions, then the exact solve
+    (exact_max_bits: 128, or 256 to let it escalate to 256-bit tableaux)."""
     from .simplex import build_tableau
-    tabs = build_tableau(problem, problem, device=device, exact=True, min_bits=min_bits)
+    tabs = build_tableau(problem, problem, device=device, exact=True, min_bits=min_bits, max_bits=exact_max_bits)
     return n_solve_exact(tabs, max_pivots=max_pivots, chunk=chunk)
 
 
@@ -317,6 +350,11 @@ class XBatch:
             self.close()
         except Exception:
             pass
+
+
+def overflowed_128(result):
+    """A member's result is the condition a batch (or a 128-bit handle) declines an overflow with."""
+    return isinstance(result, UnsupportedConstraintError) and tuple(result.constraint) == ("exact", "overflow", "128 bits")
 
 
 def group_exact_problems(problems, device=0, min_bits=0):
@@ -409,12 +447,16 @@ def solve_exact_batch(members, is_max, device=0, max_pivots=0, min_bits=0, chunk
 
 
 def solve_problems_exact(problems, fp_tolerance=1024, device=0, max_pivots=0, errorp=True, native=False, min_bits=0,
-                         chunk=None):
-    """mi355x_solve_problems(exact=True): see there."""
+                         chunk=None, exact_max_bits=128):
+    """mi355x_solve_problems(exact=True): see there.  exact_max_bits=256: the batches stay at their 64 / 128
+    bits, and a member a batch declines for overflowing them is solved again, alone, on the single-tableau
+    path with 256 bits allowed; its result (or its condition) takes its slot, the other members are untouched."""
     from .conditions import SolverError
     from .simplex import mi355x_simplex_solver
+    _check_widths(min_bits, exact_max_bits)
     results = [None] * len(problems)
-    alone, groups, groups2, failed = group_exact_problems(problems, device=device, min_bits=min_bits)
+    batch_bits = min(min_bits, 128)                    # (a batch member is at most 128 bits wide)
+    alone, groups, groups2, failed = group_exact_problems(problems, device=device, min_bits=batch_bits)
 
     def results_of(ks, rs):
         for k, r in zip(ks, rs):
@@ -425,25 +467,26 @@ def solve_problems_exact(problems, fp_tolerance=1024, device=0, max_pivots=0, er
             try:
                 results[k] = mi355x_simplex_solver(problems[k], fp_tolerance=fp_tolerance, device=device,
                                                    max_pivots=max_pivots, native=native, exact=True,
-                                                   exact_bits=min_bits, chunk=chunk)
+                                                   exact_bits=min_bits, exact_max_bits=exact_max_bits, chunk=chunk)
             except SolverError as e:
                 results[k] = e
+
+    def batch(ks, members, is_max):
+        try:
+            results_of(ks, solve_exact_batch(members, is_max, device, max_pivots, batch_bits, chunk))
+        except UnsupportedConstraintError:              # a shape the batch declines
+            one_by_one(ks)
+            return
+        if exact_max_bits > 128:
+            one_by_one([k for k in ks if overflowed_128(results[k])])
 
     for k, e in failed.items():
         results[k] = e
     one_by_one(alone)
     for (_, is_max), members in groups.items():
-        try:
-            results_of([k for k, _ in members],
-                       solve_exact_batch([t for _, t in members], is_max, device, max_pivots, min_bits, chunk))
-        except UnsupportedConstraintError:              # a shape the batch declines
-            one_by_one([k for k, _ in members])
+        batch([k for k, _ in members], [t for _, t in members], is_max)
     for (_, _, is_max), members in groups2.items():
-        try:
-            results_of([k for k, _, _ in members],
-                       solve_exact_batch([(a, t) for _, a, t in members], is_max, device, max_pivots, min_bits, chunk))
-        except UnsupportedConstraintError:
-            one_by_one([k for k, _, _ in members])
+        batch([k for k, _, _ in members], [(a, t) for _, a, t in members], is_max)
     if errorp:
         for r in results:
             if isinstance(r, Exception):

@@ -33,7 +33,7 @@
 ;;;; for the reference's rational semantics: a problem whose numbers are all rational is then
 ;;;; solved on exact fraction-free integer tableaux (mi355x_xtab_*) and the tableau's matrix holds
 ;;;; the exact ratios afterwards.  Entries beyond (signed-byte 64), or values that outgrow 128 bits
-;;;; during the solve, are declined with unsupported-constraint-error.
+;;;; (256 bits with :exact-max-bits 256) during the solve, are declined with unsupported-constraint-error.
 ;;;;
 ;;;; NOTE: could not be executed in the build image (no Lisp there); reviewed against
 ;;;; include/mi355x_simplex.h and the reference sources cited inline.
@@ -185,12 +185,17 @@
 (cffi:defcfun ("mi355x_xtab_create" %xtab-create) :int
   (out :pointer) (rows :int64) (cols :int64) (num :pointer) (den :pointer) (basis :pointer)
   (device :int) (min-bits :int))
+(cffi:defcfun ("mi355x_xtab_create_wide" %xtab-create-wide) :int
+  (out :pointer) (rows :int64) (cols :int64) (num :pointer) (den :pointer) (basis :pointer)
+  (device :int) (min-bits :int) (max-bits :int))
 (cffi:defcfun ("mi355x_xtab_solve" %xtab-solve) :int
   (tab :pointer) (is-max :int) (max-pivots :int64) (n-pivots :pointer))
 (cffi:defcfun ("mi355x_xtab_solve_two_phase" %xtab-solve-two-phase) :int
   (art :pointer) (main :pointer) (main-is-max :int) (max-pivots :int64) (n-pivots :pointer))
 (cffi:defcfun ("mi355x_xtab_download" %xtab-download) :int
   (tab :pointer) (num-lo-hi :pointer) (den-lo-hi :pointer) (basis :pointer))
+(cffi:defcfun ("mi355x_xtab_download_limbs" %xtab-download-limbs) :int
+  (tab :pointer) (limbs :int) (num-limbs :pointer) (den-limbs :pointer) (basis :pointer))
 (cffi:defcfun ("mi355x_xtab_destroy" %xtab-destroy) :void (tab :pointer))
 (cffi:defcfun ("mi355x_xbatch_create" %xbatch-create) :int
   (out :pointer) (n-lps :int64) (rows :int64) (cols :int64) (num :pointer) (den :pointer) (basis :pointer)
@@ -535,8 +540,9 @@ Leaves the total in N-PIVOTS[0] and returns the last status."
 (defun exact-declined (what)
   (error 'unsupported-constraint-error :constraint (cons 'exact what) :solver-name "mi355x-simplex"))
 
-(defun upload-exact-tableau (tableau device)
-  "mi355x_xtab_create from the tableau's rational matrix; declines entries beyond (signed-byte 64)."
+(defun upload-exact-tableau (tableau device &optional (max-bits 128))
+  "mi355x_xtab_create (MAX-BITS 256: mi355x_xtab_create_wide, a handle whose solves may go on to 256
+bits) from the tableau's rational matrix; declines entries beyond (signed-byte 64)."
   (let* ((matrix (tableau-matrix tableau))
          (rows (array-dimension matrix 0))
          (cols (array-dimension matrix 1)))
@@ -551,24 +557,33 @@ Leaves the total in N-PIVOTS[0] and returns the last status."
                   (cffi:mem-aref den :int64 (+ (* r cols) c)) (denominator x)))))
       (dotimes (r (1- rows))
         (setf (cffi:mem-aref basis :int64 r) (aref (tableau-basis-columns tableau) r)))
-      (let ((status (%xtab-create out rows cols num den basis device 0)))
-        (when (= status +mi-exact-overflow+) (exact-declined '(overflow 128)))
+      (let ((status (if (= max-bits 128)
+                        (%xtab-create out rows cols num den basis device 0)
+                        (%xtab-create-wide out rows cols num den basis device 0 max-bits))))
+        (when (= status +mi-exact-overflow+) (exact-declined (list 'overflow max-bits)))
         (check status)
         (cffi:mem-ref out :pointer)))))
 
-(defun download-exact-tableau (handle tableau &optional member)
-  "(/ T D) into the tableau's matrix, T and D rebuilt from their two 64-bit limbs; the basis.
+(defun download-exact-tableau (handle tableau &optional member (max-bits 128))
+  "(/ T D) into the tableau's matrix, T and D rebuilt from their 64-bit limbs (two, or four from a handle
+that may be at 256 bits: MAX-BITS 256); the basis.
 MEMBER: HANDLE is a batch (mi355x_xbatch_*) and the tableau its member of that index."
   (let* ((matrix (tableau-matrix tableau))
          (rows (array-dimension matrix 0))
-         (cols (array-dimension matrix 1)))
+         (cols (array-dimension matrix 1))
+         (n-limbs (if (and (null member) (> max-bits 128)) 4 2)))
     (flet ((limbs (ptr k)
-             (+ (logand (cffi:mem-aref ptr :int64 (* 2 k)) (1- (ash 1 64)))
-                (ash (cffi:mem-aref ptr :int64 (1+ (* 2 k))) 64))))
-      (cffi:with-foreign-objects ((num :int64 (* 2 rows cols)) (den :int64 2) (basis :int64 (max 1 (1- rows))))
-        (check (if member
-                   (%xbatch-download handle member num den basis)
-                   (%xtab-download handle num den basis)))
+             ;; little-endian, two's complement: the top limb carries the sign
+             (let ((value (cffi:mem-aref ptr :int64 (+ (* n-limbs k) (1- n-limbs)))))
+               (loop for i from (- n-limbs 2) downto 0
+                     do (setf value (+ (ash value 64)
+                                       (logand (cffi:mem-aref ptr :int64 (+ (* n-limbs k) i)) (1- (ash 1 64))))))
+               value)))
+      (cffi:with-foreign-objects ((num :int64 (* n-limbs rows cols)) (den :int64 n-limbs)
+                                  (basis :int64 (max 1 (1- rows))))
+        (check (cond (member (%xbatch-download handle member num den basis))
+                     ((= n-limbs 4) (%xtab-download-limbs handle 4 num den basis))
+                     (t (%xtab-download handle num den basis))))
         (let ((d (limbs den 0)))
           (dotimes (r rows)
             (dotimes (c cols)
@@ -577,41 +592,45 @@ MEMBER: HANDLE is a batch (mi355x_xbatch_*) and the tableau its member of that i
           (setf (aref (tableau-basis-columns tableau) r) (cffi:mem-aref basis :int64 r)))
         tableau))))
 
-(defun exact-status (status)
-  (when (= status +mi-exact-overflow+) (exact-declined '(overflow 128)))
+(defun exact-status (status &optional (max-bits 128))
+  "STATUS, or the declined condition that carries the width that was the limit."
+  (when (= status +mi-exact-overflow+) (exact-declined (list 'overflow max-bits)))
   status)
 
-(defun solve-exactly (problem device max-pivots &optional (instance-problem problem))
+(defun solve-exactly (problem device max-pivots &optional (instance-problem problem) (max-bits 128))
   "build-tableau, then n-solve-tableau on exact tableaux in bounded calls; returns the tableau.
-INSTANCE-PROBLEM: a branch-and-bound node of PROBLEM (src/simplex.lisp:488-501)."
+INSTANCE-PROBLEM: a branch-and-bound node of PROBLEM (src/simplex.lisp:488-501).  MAX-BITS: 128, or 256
+to let the solve start again at 256 bits where 128 overflow."
   (let ((tableaus (build-tableau problem instance-problem)))
     (cffi:with-foreign-object (n-pivots :int64 2)
       (if (listp tableaus)
           (destructuring-bind (art-tab main-tab) tableaus
-            (let ((art (upload-exact-tableau art-tab device)))
+            (let ((art (upload-exact-tableau art-tab device max-bits)))
               (unwind-protect
-                   (let ((main (upload-exact-tableau main-tab device)))
+                   (let ((main (upload-exact-tableau main-tab device max-bits)))
                      (unwind-protect
                           (let* ((matrix (tableau-matrix art-tab))
                                  (status (solve-in-chunks
                                           (lambda (cap)
                                             (prog1 (exact-status (%xtab-solve-two-phase art main (max-problem-p main-tab)
-                                                                                        cap n-pivots))
+                                                                                        cap n-pivots)
+                                                                 max-bits)
                                               (incf (cffi:mem-aref n-pivots :int64 0) (cffi:mem-aref n-pivots :int64 1))))
                                           (array-dimension matrix 0) (array-dimension matrix 1)
                                           max-pivots n-pivots)))
                             (signal-outcome status)
-                            (download-exact-tableau main main-tab))
+                            (download-exact-tableau main main-tab nil max-bits))
                        (%xtab-destroy main)))
                 (%xtab-destroy art))))
-          (let ((handle (upload-exact-tableau tableaus device)))
+          (let ((handle (upload-exact-tableau tableaus device max-bits)))
             (unwind-protect
                  (let ((status (solve-in-chunks
-                                (lambda (cap) (exact-status (%xtab-solve handle (max-problem-p tableaus) cap n-pivots)))
+                                (lambda (cap) (exact-status (%xtab-solve handle (max-problem-p tableaus) cap n-pivots)
+                                                            max-bits))
                                 (1+ (tableau-constraint-count tableaus)) (1+ (tableau-var-count tableaus))
                                 max-pivots n-pivots)))
                    (signal-outcome status)
-                   (download-exact-tableau handle tableaus))
+                   (download-exact-tableau handle tableaus nil max-bits))
               (%xtab-destroy handle)))))))
 
 ;;; Many exact problems of one shape: one batch of exact tableaux (mi355x_xbatch_*), one workgroup per
@@ -669,12 +688,13 @@ workgroup's LDS): the caller then solves the members one by one."
      (make-condition 'unsupported-constraint-error :constraint '(exact start) :solver-name "mi355x-simplex"))
     (t (outcome-condition status))))
 
-(defun solve-exact-batch (members device max-pivots)
+(defun solve-exact-batch (members device max-pivots &optional solve-wider)
   "MEMBERS: build-tableau's results for all-rational problems of ONE shape and sense -- tableaus, or
 lists (art main).  One batch (or a pair) of exact tableaux solved side by side in bounded foreign
 calls; MAX-PIVOTS (0 = none) caps each member, both phases together.  Returns a list parallel to
 MEMBERS: the solved (main) tableau or a condition object, or :DECLINED when the batch cannot take
-the group."
+the group.  SOLVE-WIDER (a function of the member's index, or NIL): what a member that outgrew the
+batch's 128 bits gets instead of its condition."
   (let* ((two-phase (listp (first members)))
          (n (length members))
          (firsts (if two-phase (mapcar #'first members) members))
@@ -702,14 +722,17 @@ the group."
                     +mi-optimal+))
               (array-dimension matrix 0) (array-dimension matrix 1) max-pivots budget)
              (loop for tab in mains for k from 0
-                   collect (or (exact-member-condition (cffi:mem-aref status :int32 k))
-                               (download-exact-tableau (or main-handle first-handle) tab k)))))
+                   collect (cond ((and solve-wider (= (cffi:mem-aref status :int32 k) +mi-exact-overflow+))
+                                  (funcall solve-wider k))
+                                 ((exact-member-condition (cffi:mem-aref status :int32 k)))
+                                 (t (download-exact-tableau (or main-handle first-handle) tab k))))))
       (when main-handle (%xbatch-destroy main-handle))
       (%xbatch-destroy first-handle))))
 
-(defun solve-problems-exactly (problems device max-pivots solve-alone)
+(defun solve-problems-exactly (problems device max-pivots solve-alone &optional (max-bits 128))
   "The :exact t route of MI355X-SOLVE-PROBLEMS: a vector of results.  (funcall SOLVE-ALONE k problem)
-returns member K's result through MI355X-SIMPLEX-SOLVER."
+returns member K's result through MI355X-SIMPLEX-SOLVER.  MAX-BITS 256: the batches stay at their 64 / 128
+bits, and a member that outgrows them is solved again through SOLVE-ALONE (which allows 256 bits)."
   (let ((results (make-array (length problems) :initial-element nil))
         (groups (make-hash-table :test #'equal)))
     (loop for problem in problems for k from 0
@@ -731,7 +754,11 @@ returns member K's result through MI355X-SIMPLEX-SOLVER."
        (declare (ignore shape))
        (setf members (reverse members))
        (let ((outcomes (if (rest members)
-                           (solve-exact-batch (mapcar #'cdr members) device max-pivots)
+                           (solve-exact-batch (mapcar #'cdr members) device max-pivots
+                                              (when (> max-bits 128)
+                                                (lambda (q)
+                                                  (let ((k (car (nth q members))))
+                                                    (funcall solve-alone k (nth k problems))))))
                            :declined)))
          (if (eq outcomes :declined)
              (loop for (k . nil) in members
@@ -1294,7 +1321,7 @@ phases together.  Returns the final status."
 (defun mi355x-simplex-solver (problem &rest args
                               &key (fp-tolerance 1024) (device 0) (devices 1) (max-pivots 0)
                                 full-tableau (native :auto) branch-and-bound (bb-width 1)
-                                (int-tolerance 0) (max-nodes 0) exact
+                                (int-tolerance 0) (max-nodes 0) exact (exact-max-bits 128)
                               &allow-other-keys)
   "Solver interface function for the MI355X backend (the value of
 linear-programming:*solver*, src/solver.lisp:39-49).  Takes a problem and backend keyword
@@ -1319,13 +1346,20 @@ double-float-epsilons of an integer), :max-nodes (0 = no cap).
 :exact T (opt-in) solves a problem whose numbers are all rational with the reference's rational
 semantics (src/utils.lisp:84-124) on exact integer tableaux and returns the solved `tableau`, its
 matrix holding the exact ratios; any float in the problem means the double-float routes above,
-unchanged.
+unchanged.  :exact-max-bits (128, the default, or 256; opt-in) is the widest integer the exact tableaux
+may grow to: with 256 a solve that outgrows 128 bits starts again at 256 bits instead of being declined,
+and the declined condition past those is (exact overflow 256).
 :exact T together with :branch-and-bound T, on a problem with integer variables whose numbers are all
 rational: the reference's branch-and-bound in rational arithmetic, where its integrality test is INTEGERP
 of a ratio (src/simplex.lisp:475-480); :bb-width node LPs per round as batches of exact tableaux assembled
 on the device, :max-nodes as above; returns the incumbent's solved `tableau`.  (Without integer variables
-the combination is declined; with a float anywhere it is the double-float branch-and-bound above.)"
+the combination is declined; with a float anywhere it is the double-float branch-and-bound above.  Exact
+branch-and-bound rides on batches, which stop at 128 bits: with :exact-max-bits 256 it is an error.)"
   (declare (ignore args))
+  (unless (member exact-max-bits '(128 256))
+    (error "MI355X-SIMPLEX-SOLVER: :exact-max-bits must be 128 or 256, not ~S" exact-max-bits))
+  (when (and exact branch-and-bound (/= exact-max-bits 128))
+    (error "MI355X-SIMPLEX-SOLVER: :exact t :branch-and-bound t does not take :exact-max-bits ~S" exact-max-bits))
   (when (and exact branch-and-bound)
     (unless (problem-integer-vars problem)
       (exact-declined '(branch-and-bound)))
@@ -1340,7 +1374,7 @@ the combination is declined; with a float anywhere it is the double-float branch
                               max-nodes)))
   ;; :exact T (opt-in): all-rational problems on exact tableaux (integer problems are declined below)
   (when (and exact (null (problem-integer-vars problem)) (rational-numbers-p problem))
-    (return-from mi355x-simplex-solver (solve-exactly problem device max-pivots)))
+    (return-from mi355x-simplex-solver (solve-exactly problem device max-pivots problem exact-max-bits)))
   (when (problem-integer-vars problem)
     (error 'unsupported-constraint-error
            :constraint (cons 'integer (problem-integer-vars problem))
@@ -1559,7 +1593,7 @@ solution (unbounded-problem-error ...)."
 
 (defun mi355x-solve-problems (problems &rest args
                               &key (fp-tolerance 1024) (device 0) (devices 1) (max-pivots 0)
-                                full-tableau (errorp t) native exact
+                                full-tableau (errorp t) native exact (exact-max-bits 128)
                               &allow-other-keys)
   "Solves a LIST of problems and returns the list of their solved tableaus, in order -- what
   (mapcar #'solve-problem problems) returns, with the independent LPs running side by side on
@@ -1589,7 +1623,9 @@ the GPU(s) instead of one after the other.
     (mi355x-simplex-solver p :exact t) returns, its matrix holding the exact ratios.  Members alone
     in their group, shapes the batch declines and members with a float anywhere go through
     (mi355x-simplex-solver p :exact t) one by one; :MAX-PIVOTS caps each member, both phases
-    together.  :EXACT NIL (default): nothing changes.
+    together.  :EXACT-MAX-BITS 256 (default 128): the batches stay at 64 / 128 bits, and a member a
+    batch declines for outgrowing them is solved again, alone, with 256 bits allowed; its result (or its
+    condition) takes its place, the other members are untouched.  :EXACT NIL (default): nothing changes.
   * The other keywords are MI355X-SIMPLEX-SOLVER's, applied to every member: :FP-TOLERANCE (the
     tolerance factor, src/simplex.lisp:506-511), :DEVICE (the GPU of members solved alone), :DEVICES
     (a count or a list of device ids: the sub-batches' GPUs), :MAX-PIVOTS (a cap per member; 0 = none,
@@ -1614,8 +1650,10 @@ Every returned solution object's results are bit-identical to the single-problem
                       (handler-case (mi355x-simplex-solver problem :fp-tolerance fp-tolerance
                                                                    :device device :max-pivots max-pivots
                                                                    :full-tableau full-tableau
-                                                                   :native native :exact t)
-                        (error (c) c))))))
+                                                                   :native native :exact t
+                                                                   :exact-max-bits exact-max-bits)
+                        (error (c) c)))
+                    exact-max-bits)))
       (when errorp
         (let ((failed (find-if (lambda (r) (typep r 'condition)) results)))
           (when failed (error failed))))

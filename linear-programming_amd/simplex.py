@@ -200,7 +200,7 @@ def with_tableau_variables(var_list, tableau):
 
 # ------------------------------------------------------------------ build-tableau (host)
 def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, device=0, exact=False, min_bits=0,
-                  general=False):
+                  general=False, max_bits=128):
     """build-tableau (src/simplex.lisp:142-328) in double-float: returns a Tableau, or
     [art_tableau, main_tableau] when the trivial basis is infeasible.
 
@@ -208,7 +208,8 @@ def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, devi
     own build-tableau does this job and the glue converts the result to double-float.
     exact=True: the same steps in exact rationals (Fraction object matrices, Fraction mapping
     offsets), the reference's own build-tableau on rational input; the result is an ExactTableau
-    (exact.py, min_bits: its starting width) or a list of two.
+    (exact.py, min_bits: its starting width, max_bits: the widest it may escalate to, 128 or 256) or a
+    list of two.
     general=True: the general form only -- the main tableau of :189-283 (basis entry = the number of
     columns on a row that needs an artificial variable), also for a problem without constraints: what
     branch-and-bound nodes are assembled from (exact_bb.py; host_problem.cpp's build(general=true))."""
@@ -231,7 +232,7 @@ def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, devi
     def mk(matrix, basis, var_count, ccount, inst):
         if exact:
             from .exact import ExactTableau
-            return ExactTableau(problem, inst, matrix, basis, var_count, ccount, mappings, device, min_bits)
+            return ExactTableau(problem, inst, matrix, basis, var_count, ccount, mappings, device, min_bits, max_bits)
         return Tableau(problem, inst, matrix, basis, var_count, ccount, mappings,
                        fp_tolerance_factor, device)
 
@@ -614,7 +615,8 @@ def _native_numbers(problem):
 
 def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_pivots=0,
                           full_tableau=False, native="auto", chunk=None, branch_and_bound=False,
-                          bb_width=1, int_tolerance=0, max_nodes=0, exact=False, exact_bits=0, **_ignored):
+                          bb_width=1, int_tolerance=0, max_nodes=0, exact=False, exact_bits=0, exact_max_bits=128,
+                          **_ignored):
     """What the Lisp glue installs as `*solver*` (src/solver.lisp:39-56): takes a problem and
     backend keyword arguments, returns a solution object answering the four solution-*
     generics -- on the NATIVE route (default whenever the problem's numbers are floats / integers
@@ -635,13 +637,22 @@ def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_p
     exact=True (opt-in): a problem whose numbers are all rational (int or Fraction) is solved with the
     reference's rational semantics (src/utils.lisp:84-124) on exact integer tableaux (exact.py) and the
     solved ExactTableau is returned, its read-back in Fractions; exact_bits 128 starts at 128 bits
-    instead of 64.  Any float in the problem means the double path, unchanged.
+    instead of 64.  Any float in the problem means the double path, unchanged.  exact_max_bits=256
+    (opt-in; default 128) lets a solve whose entries outgrow 128 bits start again at 256 bits instead of
+    being declined (exact_bits=256 then starts there); the condition past 256 bits names that limit.
     exact=True together with branch_and_bound=True, on a problem with integer variables whose numbers are
     all rational: the reference's branch-and-bound in rational arithmetic, where its integrality test is
     `integerp` of a ratio (src/simplex.lisp:475-480) -- exact_bb.py: up to bb_width node LPs side by side
     as batches of exact tableaux assembled on the device; returns the incumbent's solved ExactTableau.
     (With a float anywhere: the f64 branch-and-bound above, unchanged.  Without integer variables the
-    combination is declined.)"""
+    combination is declined.)  Exact branch-and-bound rides on batches, which stop at 128 bits: together
+    with exact_max_bits=256 it is an argument error."""
+    if exact and exact_max_bits != 128:
+        from .exact import _check_widths
+        _check_widths(exact_bits, exact_max_bits)
+        if branch_and_bound:
+            raise ValueError("exact=True, branch_and_bound=True does not take exact_max_bits=%r: exact "
+                             "branch-and-bound runs on batches of at most 128 bits" % (exact_max_bits,))
     if exact and branch_and_bound:
         from .exact import rational_problem
         if not problem.integer_vars:
@@ -660,7 +671,8 @@ def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_p
     if exact:
         from .exact import rational_problem, solve_exact
         if rational_problem(problem):
-            return solve_exact(problem, device=device, max_pivots=max_pivots, min_bits=exact_bits, chunk=chunk)
+            return solve_exact(problem, device=device, max_pivots=max_pivots, min_bits=exact_bits, chunk=chunk,
+                               exact_max_bits=exact_max_bits)
     if native and not full_tableau and devices <= 1 and len(problem.vars) > 0 and \
             (native is True or _native_numbers(problem)):
         from .native import NativeProblem
@@ -678,7 +690,7 @@ simplex_solver = mi355x_simplex_solver
 
 
 def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_pivots=0, errorp=True, native=False,
-                          exact=False, exact_bits=0):
+                          exact=False, exact_bits=0, exact_max_bits=128):
     """The glue's `mi355x-solve-problems`: a LIST of problems -> the list of their solved tableaus,
     what [solve_problem(p) for p in problems] returns, with the independent LPs side by side on the
     GPU(s).  Single-phase problems are grouped by tableau shape and sense; a group of two or more
@@ -698,11 +710,13 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
     mi355x_simplex_solver(p, exact=True) returns (exact_bits as there).  Members alone in their group,
     shapes the batch declines and members with a float anywhere go through
     mi355x_simplex_solver(..., exact=True) one by one; max_pivots caps each member (both phases
-    together, as there).  exact=False: nothing changes."""
+    together, as there).  exact_max_bits=256: batches stay at 64 / 128 bits; a member a batch declines for
+    overflowing 128 bits is solved again alone with 256 bits allowed and its result takes its slot.
+    exact=False: nothing changes."""
     if exact:
         from .exact import solve_problems_exact
         return solve_problems_exact(problems, fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots,
-                                    errorp=errorp, native=native, min_bits=exact_bits)
+                                    errorp=errorp, native=native, min_bits=exact_bits, exact_max_bits=exact_max_bits)
     from .batch import MultiDeviceBatch
     if native == "many":
         # the whole list behind ONE job of the library (mi355x_simplex_solver_many_*): members come
