@@ -372,6 +372,17 @@ int  mi355x_xtab_trace(mi355x_xtab *t, int64_t *entering_cols, int64_t *pivot_ro
 int  mi355x_xtab_bits(const mi355x_xtab *t, int *bits);
 /* mi355x_tab_cancel for the exact solves (any thread) */
 int  mi355x_xtab_cancel(mi355x_xtab *t);
+/* The pivot rule of the handle's solves: which column find-entering-column (src/simplex.lisp:362-379) and which
+ * row find-pivoting-row (src/simplex.lisp:382-389) would choose is the default, MI_RULE_DANTZIG; the reference
+ * has no anti-cycling rule, and on rationals a cycle never ends.  MI_RULE_BLAND replaces both choices: the
+ * lowest column j < var_count whose objective entry is < 0 (max) / > 0 (min), and among the rows of the strict
+ * minimum ratio the one whose basis column is lowest; it ends on every input (Bland's theorem).
+ * MI_RULE_DANTZIG_BLAND is the default rule until a chosen pivot is degenerate (its row's right-hand side 0),
+ * then Bland's until one is not; it ends on every input as well and makes far fewer pivots.  The drive-out
+ * pivots are not affected.  The rule belongs to the handle: it survives the restart at a wider width.  Set it
+ * on both handles of a two-phase pair.  MI_BAD_ARG for an unknown rule and for a handle that has made a pivot. */
+enum { MI_RULE_DANTZIG = 0, MI_RULE_BLAND = 1, MI_RULE_DANTZIG_BLAND = 2 };
+int  mi355x_xtab_set_pivot_rule(mi355x_xtab *t, int rule);
 void mi355x_xtab_destroy(mi355x_xtab *t);
 /* ---- batches of exact rational tableaux  (n-solve-tableau, src/simplex.lisp:399-461, under the rational
  * dispatch of src/utils.lisp:84-124, for many problems of one shape at once) ------------------------------
@@ -417,6 +428,11 @@ int  mi355x_xbatch_trace(mi355x_xbatch *b, int64_t lp_index, int64_t *entering_c
 int  mi355x_xbatch_bits(const mi355x_xbatch *b, int64_t lp_index, int *bits);
 /* any thread: the call running on the batch returns MI_CANCELLED after its current launches (whole pivots) */
 int  mi355x_xbatch_cancel(mi355x_xbatch *b);
+/* mi355x_xtab_set_pivot_rule for every member of the batch, at either width: what replaces find-entering-column
+ * (src/simplex.lisp:362-379) and find-pivoting-row (src/simplex.lisp:382-389) in its solves.  Set it on both
+ * batches of a two-phase pair, those of mi355x_xbatch_create_nodes included.  MI_BAD_ARG for an unknown rule
+ * and for a batch one of whose members has made a pivot. */
+int  mi355x_xbatch_set_pivot_rule(mi355x_xbatch *b, int rule);
 void mi355x_xbatch_destroy(mi355x_xbatch *b);
 /* ---- exact branch-and-bound  (simplex-solver with integer variables on rationals, src/simplex.lisp:462-542,
  * where violated-integer-constraint's integerp, :475-480, is meaningful) ------------------------------------

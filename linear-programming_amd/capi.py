@@ -18,6 +18,7 @@ MI_BB_INFEASIBLE, MI_BB_PRUNED, MI_BB_BRANCHED, MI_BB_INCUMBENT, MI_BB_NOT_BETTE
 MI_BAD_ARG, MI_HIP_ERROR, MI_RCCL_ERROR, MI_NO_DEVICE, MI_NO_MEMORY, MI_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 MI_EXACT_OVERFLOW, MI_EXACT_INEXACT = -7, -8
 XBATCH_WORKGROUP, XBATCH_TRACE_CAP = 256, 1024    # MI355X_XBATCH_WORKGROUP, MI355X_XBATCH_TRACE_CAP
+MI_RULE_DANTZIG, MI_RULE_BLAND, MI_RULE_DANTZIG_BLAND = 0, 1, 2    # mi355x_xtab_set_pivot_rule / mi355x_xbatch_set_pivot_rule
 
 _i64, _dbl, _p, _int = ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_int
 _pp = ctypes.POINTER(ctypes.c_void_p)
@@ -39,6 +40,7 @@ SIGNATURES = {
     "mi355x_xtab_trace": (_int, [_p, _p, _p, _i64, _p]),
     "mi355x_xtab_bits": (_int, [_p, _p]),
     "mi355x_xtab_cancel": (_int, [_p]),
+    "mi355x_xtab_set_pivot_rule": (_int, [_p, _int]),
     "mi355x_xtab_destroy": (None, [_p]),
     "mi355x_xbatch_create": (_int, [_pp, _i64, _i64, _i64, _p, _p, _p, _int, _int]),
     "mi355x_xbatch_solve": (_int, [_p, _int, _i64, _p, _p]),
@@ -47,6 +49,7 @@ SIGNATURES = {
     "mi355x_xbatch_trace": (_int, [_p, _i64, _p, _p, _i64, _p]),
     "mi355x_xbatch_bits": (_int, [_p, _i64, _p]),
     "mi355x_xbatch_cancel": (_int, [_p]),
+    "mi355x_xbatch_set_pivot_rule": (_int, [_p, _int]),
     "mi355x_xbatch_destroy": (None, [_p]),
     "mi355x_xbb_base_create": (_int, [_pp, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _int]),
     "mi355x_xbb_base_destroy": (None, [_p]),

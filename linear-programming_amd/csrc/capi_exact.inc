@@ -595,6 +595,18 @@ int mi355x_xtab_bits(const mi355x_xtab *t, int *bits)
     return MI_OK;
 }
 
+int mi355x_xtab_set_pivot_rule(mi355x_xtab *t, int rule)
+{
+    if (!t) return fail(MI_BAD_ARG, "handle is NULL");
+    if (rule != MI_RULE_DANTZIG && rule != MI_RULE_BLAND && rule != MI_RULE_DANTZIG_BLAND)
+        return fail(MI_BAD_ARG, "unknown pivot rule %d", rule);
+    if (t->h.n_pivots > 0 || t->tp_phase != 0 || t->tp_driveouts > 0)
+        return fail(MI_BAD_ARG, "the pivot rule is set before the handle's first pivot");
+    t->v.rule = rule;                            // (k_x_select reads it there; no reset touches it)
+    t->h.stall = 0;                              // (x_run writes the mirror to the device before its first launch)
+    return MI_OK;
+}
+
 int mi355x_xtab_cancel(mi355x_xtab *t)
 {
     if (!t) return fail(MI_BAD_ARG, "handle is NULL");

@@ -34,6 +34,7 @@ struct mi355x_xbatch {
     std::vector<int>     width;                 // per member: 64, 128, or 0 once it needs more than 128 bits
     std::vector<i128_t>  mult;                  // per member: cl_j (cols values), then L_c (0: overflowed 128 bits)
     XbWidth     w[2];                           // the 64-bit and the 128-bit sub-batch
+    int         rule = MI_RULE_DANTZIG;         // mi355x_xbatch_set_pivot_rule; each width's v.rule carries it to k_xb_solve
     bool        derived = false;                // the main batch of a two-phase job
     mi355x_xbatch *tp_main = nullptr;           // on the artificial batch: its main batch
     std::atomic<int> cancel{0};
@@ -102,6 +103,7 @@ int xb_alloc(mi355x_xbatch *b, int wi)
     HIP_TRY(hipMalloc(&s.aux, n * (C + 1) * wb));
     s.v.aux = s.aux;
     s.v.n = b->n; s.v.rows = b->rows; s.v.cols = b->cols; s.v.trace_cap = kXbTraceCap; s.v.bits = bits;
+    s.v.rule = b->rule;
     std::vector<unsigned char> stage(n * (C + 1) * wb, 0);
     for (size_t q = 0; q < n; ++q) {
         const i128_t *mq = &b->mult[q * (C + 1)];
@@ -443,6 +445,24 @@ int mi355x_xbatch_bits(const mi355x_xbatch *b, int64_t q, int *bits)
     if (!b || !bits) return fail(MI_BAD_ARG, "NULL argument");
     if (q < 0 || q >= b->n) return fail(MI_BAD_ARG, "member %lld out of range", (long long)q);
     *bits = b->width[q] ? b->width[q] : 128;
+    return MI_OK;
+}
+
+int mi355x_xbatch_set_pivot_rule(mi355x_xbatch *b, int rule)
+{
+    if (!b) return fail(MI_BAD_ARG, "handle is NULL");
+    if (rule != MI_RULE_DANTZIG && rule != MI_RULE_BLAND && rule != MI_RULE_DANTZIG_BLAND)
+        return fail(MI_BAD_ARG, "unknown pivot rule %d", rule);
+    // (a member at its start has no pivot, no drive-out and no stall flag, in either width's slot)
+    for (int wi = 0; wi < 2; ++wi)
+        for (const XbCtl &c : b->w[wi].h)
+            if (c.n_pivots > 0 || c.driveouts > 0 || c.tp != 0)
+                return fail(MI_BAD_ARG, "the pivot rule is set before the batch's first pivot");
+    b->rule = rule;
+    for (int wi = 0; wi < 2; ++wi) {
+        if (b->w[wi].v.T) b->w[wi].v.rule = rule;
+        for (XbCtl &c : b->w[wi].h) c.stall = 0;     // (the solve calls write the mirrors to the device first)
+    }
     return MI_OK;
 }
 

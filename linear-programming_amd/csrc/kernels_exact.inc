@@ -10,6 +10,8 @@
 //               width; strict, the lowest row wins a tie
 //   pivot       (r, e), p = T_re:  T'_rj = sgn(p) T_rj,
 //                                   T'_ij = (T_ij |p| - sgn(p) T_ie T_rj) / D   (i != r),   D' = |p|
+// (Both choices are the reference's, MI_RULE_DANTZIG.  The opt-in rules replace them in x_price and x_ratio:
+// Bland's lowest eligible column and lowest basis column among tied rows, always or after a degenerate pivot.)
 // Every division is exact (Sylvester's identity).  It is done as: shift out the 2^k factor of D,
 // multiply by the inverse of its odd part modulo 2^W, and verify q * D == N at double width.  A
 // failed check tells overflow (the quotient does not fit the width) from a remainder (a bug) by a
@@ -19,7 +21,8 @@
 // 128-bit limbs (S256 below).  W = 256 (the single tableau only): X256 storage, X512 products, both from
 // xwide.h -- the overloads below hand the rules its functions.  Plain C++ throughout.
 //
-//   k_x_select<T>    one workgroup: pricing, ratio test, pivot record, snapshots col / prow
+//   k_x_select<T, kRules>  one workgroup: pricing, ratio test, pivot record, snapshots col / prow (kRules: the
+//                    handle's pivot rule is not the reference's -- MI_RULE_BLAND, MI_RULE_DANTZIG_BLAND)
 //   k_x_force<T>     one workgroup: the same record and snapshots for a given pivot (drive-out)
 //   k_x_update<T>    the rank-1 update with the exact division (every element once)
 //   k_x_handover<T>  main tableau of the two-phase hand-over: constraint rows scaled by L_c and the
@@ -222,10 +225,30 @@ __device__ inline int x_tree_top(int64_t n)
 //
 // find-entering-column (src/simplex.lisp:362-379), rational dispatch: the lowest index of the strict
 // minimum (max) / maximum (min) of obj[0, nv) if that value is < 0 (> 0), -1 otherwise (optimal).
-template <class T> __device__ __forceinline__ int64_t x_price(const T *obj, int64_t nv, int is_max, T *sv, int64_t *si)
+// bland (the same in every thread): Bland's choice instead, the lowest j < nv with obj[j] < 0 (> 0); no values
+// go through LDS then, every thread stops at the first such j of its stride and the tree takes the minimum.
+template <class T> __device__ __forceinline__ int64_t x_price(const T *obj, int64_t nv, int is_max, bool bland, T *sv, int64_t *si)
 {
     const int tid = threadIdx.x;
     int64_t bi = -1;
+    if (bland) {
+        for (int64_t j = tid; j < nv; j += kXThreads) {
+            const T x = obj[j];
+            if (is_max ? x < 0 : x > 0) { bi = j; break; }
+        }
+        si[tid] = bi;
+        __syncthreads();
+        for (int s = x_tree_top(nv) / 2; s > 0; s >>= 1) {
+            if (tid < s) {
+                const int64_t o = si[tid + s];
+                if (o >= 0 && (si[tid] < 0 || o < si[tid])) si[tid] = o;
+            }
+            __syncthreads();
+        }
+        const int64_t ec = si[0];
+        __syncthreads();
+        return ec;
+    }
     T bv = 0;
     for (int64_t j = tid; j < nv; j += kXThreads) {
         const T x = obj[j];
@@ -249,20 +272,29 @@ template <class T> __device__ __forceinline__ int64_t x_price(const T *obj, int6
 
 // find-pivoting-row (src/simplex.lisp:382-389), cross-multiplied: the lowest row of the strict minimum of
 // M[i][nv] / M[i][ec] over the rows i < m with M[i][ec] > 0, -1 if there is none (unbounded).  C: M's columns.
+// bland (the same in every thread): among the rows of the minimum the one whose basis column basis[i] is lowest
+// instead; the key of each kept row then goes through sk (kXThreads slots of LDS, untouched otherwise) beside it.
 template <class T> __device__ __forceinline__ int64_t x_ratio(const T *M, int64_t m, int64_t C, int64_t nv, int64_t ec,
-                                                              T *sv, T *sa, int64_t *si)
+                                                              const int64_t *basis, bool bland, T *sv, T *sa, int64_t *si,
+                                                              int64_t *sk)
 {
     const int tid = threadIdx.x;
-    int64_t bi = -1;
+    int64_t bi = -1, bk = 0;
     T br = 0, ba = 0;
     for (int64_t i = tid; i < m; i += kXThreads) {
         const T a = M[i * C + ec];
         if (a > 0) {
             const T r = M[i * C + nv];
-            if (bi < 0 || xlt(xmul(r, ba), xmul(br, a))) { br = r; ba = a; bi = i; }
+            bool better = bi < 0;
+            if (!better) {
+                const auto lhs = xmul(r, ba), rhs = xmul(br, a);
+                better = xlt(lhs, rhs) || (bland && xeq(lhs, rhs) && basis[i] < bk);
+            }
+            if (better) { br = r; ba = a; bi = i; if (bland) bk = basis[i]; }
         }
     }
     sv[tid] = br; sa[tid] = ba; si[tid] = bi;
+    if (bland) sk[tid] = bk;
     __syncthreads();
     for (int s = x_tree_top(m) / 2; s > 0; s >>= 1) {
         if (tid < s) {
@@ -271,9 +303,9 @@ template <class T> __device__ __forceinline__ int64_t x_ratio(const T *M, int64_
                 bool better = si[tid] < 0;
                 if (!better) {
                     const auto lhs = xmul(sv[o], sa[tid]), rhs = xmul(sv[tid], sa[o]);
-                    better = xlt(lhs, rhs) || (xeq(lhs, rhs) && si[o] < si[tid]);
+                    better = xlt(lhs, rhs) || (xeq(lhs, rhs) && (bland ? sk[o] < sk[tid] : si[o] < si[tid]));
                 }
-                if (better) { sv[tid] = sv[o]; sa[tid] = sa[o]; si[tid] = si[o]; }
+                if (better) { sv[tid] = sv[o]; sa[tid] = sa[o]; si[tid] = si[o]; if (bland) sk[tid] = sk[o]; }
             }
         }
         __syncthreads();
@@ -282,6 +314,10 @@ template <class T> __device__ __forceinline__ int64_t x_ratio(const T *M, int64_
     __syncthreads();
     return cr;
 }
+
+// the rule in force at one selection (MI_RULE_*): Bland's under rule 1, and under rule 2 while the member's
+// stall flag stands (its last selected pivot was degenerate)
+__device__ inline bool x_bland(int rule, int stall) { return rule == 1 || (rule == 2 && stall != 0); }
 
 // the pivot record of (ec, cr) on a tableau with denominator D -- one thread; D' is r->pa
 template <class T> __device__ inline void x_record(typename XRec<T>::Pivot *r, const T *M, int64_t C, int64_t ec, int64_t cr,
@@ -351,15 +387,17 @@ template <class T> __device__ __forceinline__ bool x_handover_column(const T *A,
     return ok;
 }
 
-template <class T> __global__ __launch_bounds__(kXThreads) void k_x_select(XView v, int is_max)
+// kRules false: the reference's rule alone, compiled without the other two (v.rule == MI_RULE_DANTZIG is launched
+// so: its code and its LDS are what they were before the rules came); true: v.rule decides at run time
+template <class T, bool kRules> __global__ __launch_bounds__(kXThreads) void k_x_select(XView v, int is_max)
 {
     XCtl *c = v.ctl;
     const T *M = (const T *)v.T;
     const int tid = threadIdx.x;
     const int64_t m = v.rows - 1, nv = v.cols - 1, C = v.cols;
-    __shared__ int go;
+    __shared__ int go, s_bland;
     __shared__ T sv[kXThreads], sa[kXThreads];
-    __shared__ int64_t si[kXThreads];
+    __shared__ int64_t si[kXThreads], sk[kRules ? kXThreads : 1];
     if (tid == 0) {
         int g = 0;
         c->apply = 0;
@@ -369,15 +407,17 @@ template <class T> __global__ __launch_bounds__(kXThreads) void k_x_select(XView
             else g = 1;
         }
         go = g;
+        if (kRules) s_bland = x_bland(v.rule, c->stall);
     }
     __syncthreads();
     if (!go) return;
-    const int64_t ec = x_price<T>(M + m * C, nv, is_max, sv, si);
+    const bool bland = kRules && s_bland != 0;
+    const int64_t ec = x_price<T>(M + m * C, nv, is_max, bland, sv, si);
     if (ec < 0) {
         if (tid == 0) c->status = 0;                                                        // MI_OPTIMAL
         return;
     }
-    const int64_t cr = x_ratio<T>(M, m, C, nv, ec, sv, sa, si);
+    const int64_t cr = x_ratio<T>(M, m, C, nv, ec, v.basis, bland, sv, sa, si, sk);
     if (cr < 0) {
         if (tid == 0) c->status = 1;                                                        // MI_UNBOUNDED
         return;
@@ -386,6 +426,7 @@ template <class T> __global__ __launch_bounds__(kXThreads) void k_x_select(XView
         x_record<T>(&XRec<T>::piv(c), M, C, ec, cr, XRec<T>::D(c));
         XRec<T>::D(c) = XRec<T>::piv(c).pa;
         c->apply = 1;
+        if (kRules && v.rule == 2) c->stall = M[cr * C + nv] == 0;    // a degenerate pivot: rule 2 selects by Bland's rule next
         v.basis[cr] = ec;
         if (c->trace_n < v.trace_cap) { v.trace_ec[c->trace_n] = ec; v.trace_cr[c->trace_n] = cr; }
         c->trace_n += 1;
@@ -460,7 +501,11 @@ template <class F> static void x_with_tab_width(int bits, F f)
 
 void launch_x_select(const XView &v, int is_max, hipStream_t s)
 {
-    x_with_tab_width(v.bits, [&](auto t) { hipLaunchKernelGGL(k_x_select<decltype(t)>, dim3(1), dim3(kXThreads), 0, s, v, is_max); });
+    x_with_tab_width(v.bits, [&](auto t) {
+        typedef decltype(t) T;
+        if (v.rule) hipLaunchKernelGGL((k_x_select<T, true>), dim3(1), dim3(kXThreads), 0, s, v, is_max);
+        else        hipLaunchKernelGGL((k_x_select<T, false>), dim3(1), dim3(kXThreads), 0, s, v, is_max);
+    });
 }
 void launch_x_force(const XView &v, int64_t ec, int64_t cr, hipStream_t s)
 {

@@ -2,7 +2,7 @@
 // Part of simplex_kernels.hip (ONE translation unit: included there after kernels_exact.inc, whose rules
 // -- x_price, x_ratio, x_record, x_snapshot, x_update_elem, x_handover_column -- it only loops around).
 //
-//   k_xb_solve<T>    the whole n-solve-tableau loop (src/simplex.lisp:453-461, rational dispatch) of one
+//   k_xb_solve<T, kRules>  the whole n-solve-tableau loop (src/simplex.lisp:453-461, rational dispatch) of one
 //                    member inside one launch: pricing, ratio test, pivot record, snapshots of the
 //                    entering column (times sgn) and the pivot row in LDS, the update in place
 //   k_xb_between<T>  everything between the phases (src/simplex.lisp:405-451) of one member: the exact
@@ -43,11 +43,12 @@ template <class T> __device__ inline int xb_apply(T *M, int R, int C, T *col, T 
     return *s_err;
 }
 
-template <class T> __global__ __launch_bounds__(kXThreads) void k_xb_solve(XbView v, int is_max, int64_t launch_cap)
+// kRules: as for k_x_select
+template <class T, bool kRules> __global__ __launch_bounds__(kXThreads) void k_xb_solve(XbView v, int is_max, int64_t launch_cap)
 {
     extern __shared__ __int128 xb_lds[];
     __shared__ T sv[kXThreads], sa[kXThreads];
-    __shared__ int64_t si[kXThreads];
+    __shared__ int64_t si[kXThreads], sk[kRules ? kXThreads : 1];
     __shared__ XPivot rec;
     __shared__ int s_err, s_go;
     const int tid = threadIdx.x;
@@ -65,14 +66,20 @@ template <class T> __global__ __launch_bounds__(kXThreads) void k_xb_solve(XbVie
     // the member's state, the same in every thread; thread 0 stores it at the end
     int64_t n_pivots = c->n_pivots, trace_n = c->trace_n;
     const int64_t cap_at = c->cap_at;
+    const int rule = kRules ? v.rule : 0;
+    int stall = kRules ? c->stall : 0;
     __int128 D = c->D;
     int status = kRunning;
     for (int64_t it = 0; it < launch_cap; ++it) {
         if (cap_at > 0 && n_pivots >= cap_at) { status = 3; break; }                       // MI_MAX_PIVOTS
-        const int64_t ec = x_price<T>(M + m * C, nv, is_max, sv, si);
+        const bool bland = x_bland(rule, stall);
+        const int64_t ec = x_price<T>(M + m * C, nv, is_max, bland, sv, si);
         if (ec < 0) { status = 0; break; }                                                  // MI_OPTIMAL
-        const int64_t cr = x_ratio<T>(M, m, C, nv, ec, sv, sa, si);
+        const int64_t cr = x_ratio<T>(M, m, C, nv, ec, basis, bland, sv, sa, si, sk);
         if (cr < 0) { status = 1; break; }                                                  // MI_UNBOUNDED
+        // a degenerate pivot: rule 2 selects by Bland's rule next (read before xb_apply's first barrier, so
+        // before any thread updates the tableau)
+        if (rule == 2) stall = M[cr * C + nv] == 0;
         if (tid == 0) {
             x_record<T>(&rec, M, C, ec, cr, D);
             s_err = 0;
@@ -89,6 +96,7 @@ template <class T> __global__ __launch_bounds__(kXThreads) void k_xb_solve(XbVie
         c->status = status;
         c->n_pivots = n_pivots;
         c->trace_n = trace_n;
+        if (kRules) c->stall = stall;
         c->D = D;
     }
 }
@@ -185,6 +193,7 @@ template <class T> __global__ __launch_bounds__(kXThreads) void k_xb_between(XbV
         cm->D = (__int128)d;
         cm->n_pivots = 0;
         cm->trace_n = 0;
+        cm->stall = 0;
         cm->cap_at = target > 0 && target > n1 ? target - n1 : 0;
         cm->status = target > 0 && target <= n1 ? 3 : kRunning;                             // MI_MAX_PIVOTS
         ca->tp = 1;
@@ -197,7 +206,9 @@ void launch_xb_solve(const XbView &v, int is_max, int64_t launch_cap, hipStream_
 {
     const size_t lds = xb_snapshot_bytes(v);
     x_with_width(v.bits, [&](auto t) {
-        hipLaunchKernelGGL(k_xb_solve<decltype(t)>, dim3((unsigned)v.n), dim3(kXThreads), lds, s, v, is_max, launch_cap);
+        typedef decltype(t) T;
+        if (v.rule) hipLaunchKernelGGL((k_xb_solve<T, true>), dim3((unsigned)v.n), dim3(kXThreads), lds, s, v, is_max, launch_cap);
+        else        hipLaunchKernelGGL((k_xb_solve<T, false>), dim3((unsigned)v.n), dim3(kXThreads), lds, s, v, is_max, launch_cap);
     });
 }
 void launch_xb_between(const XbView &art, const XbView &mt, hipStream_t s)

@@ -361,7 +361,7 @@ struct XCtl {
     int32_t  status;      // kRunning, or MI_OPTIMAL / MI_UNBOUNDED / MI_MAX_PIVOTS / kXOverflow / kXInexact
     int32_t  err;         // 0, or kXOverflow / kXInexact raised by an update (the larger one wins)
     int32_t  apply;       // the last select / force chose a pivot for the update that follows it
-    int32_t  pad_;
+    int32_t  stall;       // the stall flag of rule 2: the last pivot k_x_select chose was degenerate (rhs 0)
     int64_t  n_pivots;    // pivots chosen by k_x_select since the tableau's start (cumulative)
     int64_t  cap_at;      // k_x_select stops with MI_MAX_PIVOTS once n_pivots reaches it (0: no cap)
     int64_t  trace_n;     // pivots recorded (trace buffers hold the first trace_cap)
@@ -379,6 +379,7 @@ struct XView {
     int64_t *trace_ec, *trace_cr;
     int64_t  rows, cols, trace_cap;
     int      bits;        // 64, 128 or 256
+    int      rule;        // MI_RULE_*: how k_x_select prices and breaks ratio ties
 };
 void launch_x_select(const XView &v, int is_max, hipStream_t s);
 void launch_x_force(const XView &v, int64_t ec, int64_t cr, hipStream_t s);
@@ -397,7 +398,7 @@ struct XbCtl {
     int32_t  status;      // kRunning, kXbIdle, or MI_OPTIMAL / MI_UNBOUNDED / MI_MAX_PIVOTS / kXOverflow / kXInexact
     int32_t  tp;          // artificial member: 0 phase 1, 1 handed over (phase 2 on the main member), 2 ended between
     int32_t  tp_status;   // tp == 2: MI_INFEASIBLE / MI_ART_NONZERO / MI_ART_STUCK
-    int32_t  pad_;
+    int32_t  stall;       // the stall flag of rule 2: the last pivot k_xb_solve chose was degenerate (rhs 0)
     int64_t  n_pivots;    // pivots chosen by k_xb_solve since the member's start (cumulative)
     int64_t  cap_at;      // k_xb_solve stops with MI_MAX_PIVOTS once n_pivots reaches it (0: no cap); on an
                           // artificial member of a two-phase job: the target of both phases and the drive-outs
@@ -413,6 +414,7 @@ struct XbView {
     const void *aux;
     int64_t     n, rows, cols, trace_cap;
     int         bits;     // 64 or 128
+    int         rule;     // MI_RULE_*: how k_xb_solve prices and breaks ratio ties
 };
 // at most launch_cap pivots per member (a bounded launch: mi355x_xbatch_cancel)
 void launch_xb_solve(const XbView &v, int is_max, int64_t launch_cap, hipStream_t s);

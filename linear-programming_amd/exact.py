@@ -15,6 +15,10 @@ A list of problems (``mi355x_solve_problems(problems, exact=True)``) is grouped 
 sense; a group of two or more is one batch of exact tableaux (mi355x_xbatch_*, one workgroup per
 member: kernels_exact_batch.inc), and every member comes back as the solved ExactTableau the
 one-problem route returns.
+
+``pivot_rule`` (opt-in, every exact solve): "dantzig" is the reference's choice of column and row, which has
+no anti-cycling rule -- on rationals a cycle never ends; "bland" and "dantzig-bland" end on every input
+(mi355x_xtab_set_pivot_rule, include/mi355x_simplex.h).
 """
 import ctypes
 from fractions import Fraction
@@ -33,6 +37,16 @@ def _ptr(a):
 
 def _declined(what):
     return UnsupportedConstraintError(("exact",) + tuple(what), "mi355x-simplex")
+
+
+PIVOT_RULES = {"dantzig": capi.MI_RULE_DANTZIG, "bland": capi.MI_RULE_BLAND, "dantzig-bland": capi.MI_RULE_DANTZIG_BLAND}
+
+
+def pivot_rule_code(name):
+    """MI_RULE_* of a rule's name; ValueError for any other."""
+    if not isinstance(name, str) or name not in PIVOT_RULES:
+        raise ValueError("pivot_rule %r: must be one of %s" % (name, ", ".join(repr(k) for k in PIVOT_RULES)))
+    return PIVOT_RULES[name]
 
 
 def _check_widths(min_bits, max_bits):
@@ -80,9 +94,10 @@ class ExactTableau:
     handle.  `.matrix` is an object array of Fractions (downloaded T / D), `.basis_columns` an int64
     array; `pivot_trace()` and `bits` as for Tableau."""
     exact = True
+    pivot_rule = "dantzig"                 # set_pivot_rule; the handle gets it when it is made
 
     def __init__(self, problem, instance_problem, matrix, basis_columns, var_count, constraint_count,
-                 var_mapping, device=0, min_bits=0, max_bits=128):
+                 var_mapping, device=0, min_bits=0, max_bits=128, pivot_rule="dantzig"):
         self.problem = problem
         self.instance_problem = instance_problem
         self.var_count = int(var_count)
@@ -92,6 +107,8 @@ class ExactTableau:
         self.min_bits = int(min_bits)
         self.max_bits = int(max_bits)            # the widest width its solves may escalate to: 128 or 256
         _check_widths(self.min_bits, self.max_bits)
+        pivot_rule_code(pivot_rule)
+        self.pivot_rule = pivot_rule
         self.n_pivots = 0
         self.phase1 = None                 # the artificial tableau of a two-phase solve
         self._handle = None
@@ -116,7 +133,17 @@ class ExactTableau:
                                                         _ptr(den), basis, self.device, self.min_bits, self.max_bits)
             check(rc, "mi355x_xtab_create", self.max_bits)
             self._handle = h
+            if self.pivot_rule != "dantzig":
+                capi.check(capi.lib().mi355x_xtab_set_pivot_rule(h, pivot_rule_code(self.pivot_rule)),
+                           "mi355x_xtab_set_pivot_rule")
         return self._handle
+
+    def set_pivot_rule(self, name):
+        """mi355x_xtab_set_pivot_rule: before the tableau's first pivot (both tableaux of a two-phase pair)."""
+        code = pivot_rule_code(name)
+        if self._handle is not None:
+            capi.check(capi.lib().mi355x_xtab_set_pivot_rule(self._handle, code), "mi355x_xtab_set_pivot_rule")
+        self.pivot_rule = name
 
     def _touch(self):
         self._stale = True
@@ -214,10 +241,14 @@ def cancel_solve(tableau):
         check(capi.lib().mi355x_xtab_cancel(t._h), "mi355x_xtab_cancel")
 
 
-def n_solve_exact(tabs, max_pivots=0, chunk=None):
+def n_solve_exact(tabs, max_pivots=0, chunk=None, pivot_rule=None):
     """n-solve-tableau (src/simplex.lisp:399-461) on an ExactTableau or a list [art, main], in bounded
-    calls (the glue's solve-in-chunks).  Returns the solved (main) tableau; raises as n_solve_tableau."""
+    calls (the glue's solve-in-chunks).  Returns the solved (main) tableau; raises as n_solve_tableau.
+    pivot_rule: set on the tableau (on both of a pair) first; None leaves them as they are."""
     from .simplex import _raise_for, _solve_in_chunks
+    if pivot_rule is not None:
+        for t in (tabs if isinstance(tabs, (list, tuple)) else [tabs]):
+            t.set_pivot_rule(pivot_rule)
     L = capi.lib()
     n = ctypes.c_int64(0)
     if isinstance(tabs, (list, tuple)):
@@ -268,12 +299,13 @@ def rational_problem(problem):
                       for _, e, rhs in problem.constraints)
 
 
-def solve_exact(problem, device=0, max_pivots=0, min_bits=0, chunk=None, exact_max_bits=128):
+def solve_exact(problem, device=0, max_pivots=0, min_bits=0, chunk=None, exact_max_bits=128, pivot_rule="dantzig"):
     """The exact route of mi355x_simplex_solver: build-tableau in Fractions, then the exact solve
-    (exact_max_bits: 128, or 256 to let it escalate to 256-bit tableaux)."""
+    (exact_max_bits: 128, or 256 to let it escalate to 256-bit tableaux; pivot_rule: the module's docstring)."""
     from .simplex import build_tableau
+    pivot_rule_code(pivot_rule)
     tabs = build_tableau(problem, problem, device=device, exact=True, min_bits=min_bits, max_bits=exact_max_bits)
-    return n_solve_exact(tabs, max_pivots=max_pivots, chunk=chunk)
+    return n_solve_exact(tabs, max_pivots=max_pivots, chunk=chunk, pivot_rule=pivot_rule)
 
 
 # ------------------------------------------------------------------ many problems at once
@@ -281,7 +313,8 @@ class XBatch:
     """A mi355x_xbatch handle: the start tableaux of `tabs` (ExactTableaus of one shape) back to back.
     Members solved in it keep it alive; the last one to go destroys it."""
 
-    def __init__(self, tabs, device=0, min_bits=0):
+    def __init__(self, tabs, device=0, min_bits=0, pivot_rule="dantzig"):
+        pivot_rule_code(pivot_rule)
         self.handle = None
         self.n_lps = len(tabs)
         self.rows, self.cols = tabs[0]._matrix.shape
@@ -290,25 +323,38 @@ class XBatch:
         den = np.ascontiguousarray(np.stack([p[1] for p in pairs]))
         basis = np.ascontiguousarray(np.stack([t._basis for t in tabs]), dtype=np.int64)
         self._create(num, den, basis, device, min_bits)
+        self.set_pivot_rule(pivot_rule)
 
     @classmethod
-    def from_states(cls, num, den, basis, device=0, min_bits=0):
+    def from_states(cls, num, den, basis, device=0, min_bits=0, pivot_rule="dantzig"):
         """A batch of start states given as arrays: numerators and denominators (n x rows x cols, int64)
         and the bases (n x (rows - 1))."""
+        pivot_rule_code(pivot_rule)
         xb = cls.__new__(cls)
         xb.handle = None
         num = np.ascontiguousarray(num, dtype=np.int64)
         xb.n_lps, xb.rows, xb.cols = num.shape
         xb._create(num, np.ascontiguousarray(den, dtype=np.int64), np.ascontiguousarray(basis, dtype=np.int64),
                    device, min_bits)
+        xb.set_pivot_rule(pivot_rule)
         return xb
 
     @classmethod
-    def from_handle(cls, handle, n_lps, rows, cols):
+    def from_handle(cls, handle, n_lps, rows, cols, pivot_rule="dantzig"):
         """A batch the library made itself (mi355x_xbatch_create_nodes)."""
         xb = cls.__new__(cls)
         xb.handle, xb.n_lps, xb.rows, xb.cols = handle, int(n_lps), int(rows), int(cols)
+        xb.set_pivot_rule(pivot_rule)
         return xb
+
+    pivot_rule = "dantzig"
+
+    def set_pivot_rule(self, name):
+        """mi355x_xbatch_set_pivot_rule: before the batch's first pivot (both batches of a two-phase pair)."""
+        code = pivot_rule_code(name)
+        if code != capi.MI_RULE_DANTZIG or self.pivot_rule != "dantzig":
+            capi.check(capi.lib().mi355x_xbatch_set_pivot_rule(self.handle, code), "mi355x_xbatch_set_pivot_rule")
+        self.pivot_rule = name
 
     def _create(self, num, den, basis, device, min_bits):
         h = ctypes.c_void_p()
@@ -414,16 +460,16 @@ def batch_in_chunks(xa, xm, is_max, max_pivots=0, chunk=None):
             return st, total
 
 
-def solve_exact_batch(members, is_max, device=0, max_pivots=0, min_bits=0, chunk=None):
+def solve_exact_batch(members, is_max, device=0, max_pivots=0, min_bits=0, chunk=None, pivot_rule="dantzig"):
     """One group of mi355x_solve_problems(exact=True) in bounded calls (the glue's solve-in-chunks):
     members are ExactTableaus (single phase) or (art, main) pairs of one shape.  Returns per member the
     solved (main) tableau or the exception of its outcome; raises the declined condition when the shape
     does not fit a batch."""
     two = isinstance(members[0], (list, tuple))
     first = [m[0] for m in members] if two else list(members)
-    xa = XBatch(first, device=device, min_bits=min_bits)
+    xa = XBatch(first, device=device, min_bits=min_bits, pivot_rule=pivot_rule)
     try:
-        xm = XBatch([m[1] for m in members], device=device, min_bits=min_bits) if two else None
+        xm = XBatch([m[1] for m in members], device=device, min_bits=min_bits, pivot_rule=pivot_rule) if two else None
     except Exception:
         xa.close()                                     # (its device memory goes at once)
         raise
@@ -447,13 +493,15 @@ def solve_exact_batch(members, is_max, device=0, max_pivots=0, min_bits=0, chunk
 
 
 def solve_problems_exact(problems, fp_tolerance=1024, device=0, max_pivots=0, errorp=True, native=False, min_bits=0,
-                         chunk=None, exact_max_bits=128):
-    """mi355x_solve_problems(exact=True): see there.  exact_max_bits=256: the batches stay at their 64 / 128
+                         chunk=None, exact_max_bits=128, pivot_rule="dantzig"):
+    """mi355x_solve_problems(exact=True): see there.  pivot_rule goes to every batch and to every member solved
+    alone, the 256-bit re-solve included; a member with a float declines a rule other than "dantzig".  exact_max_bits=256: the batches stay at their 64 / 128
     bits, and a member a batch declines for overflowing them is solved again, alone, on the single-tableau
     path with 256 bits allowed; its result (or its condition) takes its slot, the other members are untouched."""
     from .conditions import SolverError
     from .simplex import mi355x_simplex_solver
     _check_widths(min_bits, exact_max_bits)
+    rule_kw = {} if pivot_rule_code(pivot_rule) == capi.MI_RULE_DANTZIG else {"pivot_rule": pivot_rule}   # (the default: the calls as they were)
     results = [None] * len(problems)
     batch_bits = min(min_bits, 128)                    # (a batch member is at most 128 bits wide)
     alone, groups, groups2, failed = group_exact_problems(problems, device=device, min_bits=batch_bits)
@@ -467,13 +515,14 @@ def solve_problems_exact(problems, fp_tolerance=1024, device=0, max_pivots=0, er
             try:
                 results[k] = mi355x_simplex_solver(problems[k], fp_tolerance=fp_tolerance, device=device,
                                                    max_pivots=max_pivots, native=native, exact=True,
-                                                   exact_bits=min_bits, exact_max_bits=exact_max_bits, chunk=chunk)
+                                                   exact_bits=min_bits, exact_max_bits=exact_max_bits, chunk=chunk,
+                                                   **rule_kw)
             except SolverError as e:
                 results[k] = e
 
     def batch(ks, members, is_max):
         try:
-            results_of(ks, solve_exact_batch(members, is_max, device, max_pivots, batch_bits, chunk))
+            results_of(ks, solve_exact_batch(members, is_max, device, max_pivots, batch_bits, chunk, **rule_kw))
         except UnsupportedConstraintError:              # a shape the batch declines
             one_by_one(ks)
             return

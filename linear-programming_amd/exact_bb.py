@@ -21,7 +21,7 @@ import numpy as np
 
 from . import capi
 from .conditions import InfeasibleProblemError, SolverError
-from .exact import ExactTableau, XBatch, _declined, _int128, _num_den, _ptr, batch_in_chunks
+from .exact import ExactTableau, XBatch, _declined, _int128, _num_den, _ptr, batch_in_chunks, pivot_rule_code
 
 # outcomes of a trace row: the values of MI_BB_* (mi355x_simplex_solver_bb_trace)
 BB_INFEASIBLE, BB_PRUNED, BB_BRANCHED, BB_INCUMBENT, BB_NOT_BETTER, BB_FAILED = range(6)
@@ -249,9 +249,9 @@ class Base:
         capi.check(rc, "mi355x_xbb_base_create")
         self.handle = h
 
-    def create_nodes(self, entries, min_bits=0):
+    def create_nodes(self, entries, min_bits=0, pivot_rule="dantzig"):
         """mi355x_xbatch_create_nodes for entries of one depth and one number of artificial rows:
-        (main XBatch, artificial XBatch or None)."""
+        (main XBatch, artificial XBatch or None), both with pivot_rule set."""
         g, n, d = self.g, len(entries), len(entries[0])
         flat = [r for e in entries for r in e]
         if any(abs(b) > _I64_MAX for _, _, b in flat):
@@ -268,7 +268,11 @@ class Base:
         rows, cols = g.matrix.shape[0] + d, g.matrix.shape[1] + d
         n_art = g.n_art + sum(g.row_artificial(*r) for r in entries[0])
         main = XBatch.from_handle(hm, n, rows, cols)
-        return main, (XBatch.from_handle(ha, n, rows, cols + n_art) if ha else None)
+        art = XBatch.from_handle(ha, n, rows, cols + n_art) if ha else None          # (owned from here on)
+        main.set_pivot_rule(pivot_rule)
+        if art:
+            art.set_pivot_rule(pivot_rule)
+        return main, art
 
     def close(self):
         h, self.handle = self.handle, None
@@ -337,8 +341,10 @@ class LightSolution:
 class DeviceRounds:
     """The `solve_round` of the GPU (see the module's docstring)."""
 
-    def __init__(self, problem, device=0, max_pivots=0, min_bits=0, chunk=None):
+    def __init__(self, problem, device=0, max_pivots=0, min_bits=0, chunk=None, pivot_rule="dantzig"):
         self.problem, self.device, self.max_pivots, self.min_bits, self.chunk = problem, device, max_pivots, min_bits, chunk
+        pivot_rule_code(pivot_rule)
+        self.pivot_rule = pivot_rule                                  # of the root and of every node batch
         self.g = self.base = None
         self.root = None                                              # the root's solved ExactTableau
         self.declined = 0                                             # nodes that came back declined
@@ -348,7 +354,7 @@ class DeviceRounds:
         from .simplex import build_tableau, tableau_objective_value, tableau_variable
         try:
             tabs = build_tableau(self.problem, self.problem, device=self.device, exact=True, min_bits=self.min_bits)
-            t = n_solve_exact(tabs, max_pivots=self.max_pivots, chunk=self.chunk)
+            t = n_solve_exact(tabs, max_pivots=self.max_pivots, chunk=self.chunk, pivot_rule=self.pivot_rule)
         except SolverError as e:
             return _status_of(e), None, None
         self.root = t
@@ -368,7 +374,7 @@ class DeviceRounds:
         is_max = self.problem.type == "max"
         for ks in groups.values():
             try:
-                main, art = self.base.create_nodes([entries[k] for k in ks], self.min_bits)
+                main, art = self.base.create_nodes([entries[k] for k in ks], self.min_bits, self.pivot_rule)
             except SolverError as e:                                  # a shape or a bound the batch declines
                 for k in ks:
                     out[k] = (e, None, None)
@@ -402,9 +408,10 @@ class ExactBranchAndBound:
     """One exact search on the GPU: run() -> the incumbent's solved ExactTableau, or raises the reference's
     errors; trace() / stats() as native.BranchAndBound, `result.objectives` the trace's objectives as Fractions."""
 
-    def __init__(self, problem, width=1, device=0, max_pivots=0, max_nodes=0, min_bits=0, chunk=None):
+    def __init__(self, problem, width=1, device=0, max_pivots=0, max_nodes=0, min_bits=0, chunk=None, pivot_rule="dantzig"):
         self.problem, self.width, self.max_nodes = problem, int(width), int(max_nodes)
-        self.rounds = DeviceRounds(problem, device=device, max_pivots=max_pivots, min_bits=min_bits, chunk=chunk)
+        self.rounds = DeviceRounds(problem, device=device, max_pivots=max_pivots, min_bits=min_bits, chunk=chunk,
+                                   pivot_rule=pivot_rule)
         self.result = None
 
     def run(self):
@@ -426,7 +433,9 @@ class ExactBranchAndBound:
         return dict(self.result.stats(), declined=self.rounds.declined)
 
 
-def solve_branch_and_bound_exact(problem, width=1, device=0, max_pivots=0, max_nodes=0, min_bits=0, chunk=None):
+def solve_branch_and_bound_exact(problem, width=1, device=0, max_pivots=0, max_nodes=0, min_bits=0, chunk=None,
+                                 pivot_rule="dantzig"):
     """simplex-solver with integer variables (src/simplex.lisp:506-542) on a problem whose numbers are all
-    rational: the incumbent as a solved ExactTableau (its read-back in Fractions)."""
-    return ExactBranchAndBound(problem, width, device, max_pivots, max_nodes, min_bits, chunk).run()
+    rational: the incumbent as a solved ExactTableau (its read-back in Fractions).  pivot_rule: of the root's
+    solve and of every node batch (exact.py)."""
+    return ExactBranchAndBound(problem, width, device, max_pivots, max_nodes, min_bits, chunk, pivot_rule).run()

@@ -197,6 +197,7 @@
 (cffi:defcfun ("mi355x_xtab_download_limbs" %xtab-download-limbs) :int
   (tab :pointer) (limbs :int) (num-limbs :pointer) (den-limbs :pointer) (basis :pointer))
 (cffi:defcfun ("mi355x_xtab_destroy" %xtab-destroy) :void (tab :pointer))
+(cffi:defcfun ("mi355x_xtab_set_pivot_rule" %xtab-set-pivot-rule) :int (tab :pointer) (rule :int))
 (cffi:defcfun ("mi355x_xbatch_create" %xbatch-create) :int
   (out :pointer) (n-lps :int64) (rows :int64) (cols :int64) (num :pointer) (den :pointer) (basis :pointer)
   (device :int) (min-bits :int))
@@ -207,6 +208,7 @@
 (cffi:defcfun ("mi355x_xbatch_download" %xbatch-download) :int
   (batch :pointer) (lp-index :int64) (num-lo-hi :pointer) (den-lo-hi :pointer) (basis :pointer))
 (cffi:defcfun ("mi355x_xbatch_destroy" %xbatch-destroy) :void (batch :pointer))
+(cffi:defcfun ("mi355x_xbatch_set_pivot_rule" %xbatch-set-pivot-rule) :int (batch :pointer) (rule :int))
 (cffi:defcfun ("mi355x_xbb_base_create" %xbb-base-create) :int
   (out :pointer) (rows :int64) (cols :int64) (num :pointer) (den :pointer) (basis :pointer) (ncv :int64)
   (nb :int64) (n-vars :int64) (kind :pointer) (col :pointer) (off-num :pointer) (off-den :pointer) (device :int))
@@ -540,9 +542,24 @@ Leaves the total in N-PIVOTS[0] and returns the last status."
 (defun exact-declined (what)
   (error 'unsupported-constraint-error :constraint (cons 'exact what) :solver-name "mi355x-simplex"))
 
-(defun upload-exact-tableau (tableau device &optional (max-bits 128))
+(defun pivot-rule-code (pivot-rule)
+  "MI_RULE_* of :PIVOT-RULE's value (include/mi355x_simplex.h); any other value is an error."
+  (case pivot-rule
+    (:dantzig 0)
+    (:bland 1)
+    (:dantzig-bland 2)
+    (t (error "MI355X-SIMPLEX: :pivot-rule must be :dantzig, :bland or :dantzig-bland, not ~S" pivot-rule))))
+
+(defun check-pivot-rule (pivot-rule exact)
+  "The argument errors of :PIVOT-RULE: an unknown rule, and a rule other than :DANTZIG without :EXACT T (the
+double-float routes keep the reference's rule: in floating point neither of the other two is a theorem)."
+  (when (and (plusp (pivot-rule-code pivot-rule)) (not exact))
+    (error "MI355X-SIMPLEX: :pivot-rule ~S needs :exact t" pivot-rule)))
+
+(defun upload-exact-tableau (tableau device &optional (max-bits 128) (rule 0))
   "mi355x_xtab_create (MAX-BITS 256: mi355x_xtab_create_wide, a handle whose solves may go on to 256
-bits) from the tableau's rational matrix; declines entries beyond (signed-byte 64)."
+bits) from the tableau's rational matrix; declines entries beyond (signed-byte 64).  RULE: the handle's
+pivot rule (mi355x_xtab_set_pivot_rule), 0 for the reference's."
   (let* ((matrix (tableau-matrix tableau))
          (rows (array-dimension matrix 0))
          (cols (array-dimension matrix 1)))
@@ -562,7 +579,13 @@ bits) from the tableau's rational matrix; declines entries beyond (signed-byte 6
                         (%xtab-create-wide out rows cols num den basis device 0 max-bits))))
         (when (= status +mi-exact-overflow+) (exact-declined (list 'overflow max-bits)))
         (check status)
-        (cffi:mem-ref out :pointer)))))
+        (let ((handle (cffi:mem-ref out :pointer))
+              (done nil))
+          (unwind-protect
+               (progn (unless (zerop rule) (check (%xtab-set-pivot-rule handle rule)))
+                      (setf done t)
+                      handle)
+            (unless done (%xtab-destroy handle))))))))
 
 (defun download-exact-tableau (handle tableau &optional member (max-bits 128))
   "(/ T D) into the tableau's matrix, T and D rebuilt from their 64-bit limbs (two, or four from a handle
@@ -597,17 +620,17 @@ MEMBER: HANDLE is a batch (mi355x_xbatch_*) and the tableau its member of that i
   (when (= status +mi-exact-overflow+) (exact-declined (list 'overflow max-bits)))
   status)
 
-(defun solve-exactly (problem device max-pivots &optional (instance-problem problem) (max-bits 128))
+(defun solve-exactly (problem device max-pivots &optional (instance-problem problem) (max-bits 128) (rule 0))
   "build-tableau, then n-solve-tableau on exact tableaux in bounded calls; returns the tableau.
 INSTANCE-PROBLEM: a branch-and-bound node of PROBLEM (src/simplex.lisp:488-501).  MAX-BITS: 128, or 256
-to let the solve start again at 256 bits where 128 overflow."
+to let the solve start again at 256 bits where 128 overflow.  RULE: the pivot rule of every tableau."
   (let ((tableaus (build-tableau problem instance-problem)))
     (cffi:with-foreign-object (n-pivots :int64 2)
       (if (listp tableaus)
           (destructuring-bind (art-tab main-tab) tableaus
-            (let ((art (upload-exact-tableau art-tab device max-bits)))
+            (let ((art (upload-exact-tableau art-tab device max-bits rule)))
               (unwind-protect
-                   (let ((main (upload-exact-tableau main-tab device max-bits)))
+                   (let ((main (upload-exact-tableau main-tab device max-bits rule)))
                      (unwind-protect
                           (let* ((matrix (tableau-matrix art-tab))
                                  (status (solve-in-chunks
@@ -622,7 +645,7 @@ to let the solve start again at 256 bits where 128 overflow."
                             (download-exact-tableau main main-tab nil max-bits))
                        (%xtab-destroy main)))
                 (%xtab-destroy art))))
-          (let ((handle (upload-exact-tableau tableaus device max-bits)))
+          (let ((handle (upload-exact-tableau tableaus device max-bits rule)))
             (unwind-protect
                  (let ((status (solve-in-chunks
                                 (lambda (cap) (exact-status (%xtab-solve handle (max-problem-p tableaus) cap n-pivots)
@@ -637,10 +660,11 @@ to let the solve start again at 256 bits where 128 overflow."
 ;;; member, everything between the phases on the device.  Statuses are per member; a member that needs
 ;;; more than 128 bits or whose start the library declines gets its condition object, the others
 ;;; their solved tableau.
-(defun upload-exact-batch (tableaus device)
+(defun upload-exact-batch (tableaus device &optional (rule 0))
   "mi355x_xbatch_create from same-shape tableaus' rational matrices, member after member.  NIL when
 the batch cannot take them (an entry beyond (signed-byte 64), a shape whose snapshots do not fit a
-workgroup's LDS): the caller then solves the members one by one."
+workgroup's LDS): the caller then solves the members one by one.  RULE: the batch's pivot rule
+(mi355x_xbatch_set_pivot_rule), 0 for the reference's."
   (let* ((n (length tableaus))
          (matrix (tableau-matrix (first tableaus)))
          (rows (array-dimension matrix 0))
@@ -674,7 +698,13 @@ workgroup's LDS): the caller then solves the members one by one."
              (let ((status (%xbatch-create out n rows cols num den basis device 0)))
                (unless (= status +mi-unsupported+)
                  (check status)
-                 (cffi:mem-ref out :pointer))))
+                 (let ((handle (cffi:mem-ref out :pointer))
+                       (done nil))
+                   (unwind-protect
+                        (progn (unless (zerop rule) (check (%xbatch-set-pivot-rule handle rule)))
+                               (setf done t)
+                               handle)
+                     (unless done (%xbatch-destroy handle)))))))
         (cffi:foreign-free num)
         (cffi:foreign-free den)
         (cffi:foreign-free basis)))))
@@ -688,26 +718,26 @@ workgroup's LDS): the caller then solves the members one by one."
      (make-condition 'unsupported-constraint-error :constraint '(exact start) :solver-name "mi355x-simplex"))
     (t (outcome-condition status))))
 
-(defun solve-exact-batch (members device max-pivots &optional solve-wider)
+(defun solve-exact-batch (members device max-pivots &optional solve-wider (rule 0))
   "MEMBERS: build-tableau's results for all-rational problems of ONE shape and sense -- tableaus, or
 lists (art main).  One batch (or a pair) of exact tableaux solved side by side in bounded foreign
 calls; MAX-PIVOTS (0 = none) caps each member, both phases together.  Returns a list parallel to
 MEMBERS: the solved (main) tableau or a condition object, or :DECLINED when the batch cannot take
 the group.  SOLVE-WIDER (a function of the member's index, or NIL): what a member that outgrew the
-batch's 128 bits gets instead of its condition."
+batch's 128 bits gets instead of its condition.  RULE: the pivot rule of both batches."
   (let* ((two-phase (listp (first members)))
          (n (length members))
          (firsts (if two-phase (mapcar #'first members) members))
          (mains (if two-phase (mapcar #'second members) members))
          (matrix (tableau-matrix (first firsts)))
          (is-max (max-problem-p (first mains)))
-         (first-handle (upload-exact-batch firsts device))
+         (first-handle (upload-exact-batch firsts device rule))
          (main-handle nil))
     (unless first-handle (return-from solve-exact-batch :declined))
     (unwind-protect
          (progn
            (when two-phase
-             (setf main-handle (upload-exact-batch mains device))
+             (setf main-handle (upload-exact-batch mains device rule))
              (unless main-handle (return-from solve-exact-batch :declined)))
            (cffi:with-foreign-objects ((status :int32 n) (pivots :int64 (* 2 n)) (budget :int64 1))
              ;; a call's status for solve-in-chunks: MI_MAX_PIVOTS while some member is left at its cap
@@ -729,10 +759,11 @@ batch's 128 bits gets instead of its condition."
       (when main-handle (%xbatch-destroy main-handle))
       (%xbatch-destroy first-handle))))
 
-(defun solve-problems-exactly (problems device max-pivots solve-alone &optional (max-bits 128))
+(defun solve-problems-exactly (problems device max-pivots solve-alone &optional (max-bits 128) (rule 0))
   "The :exact t route of MI355X-SOLVE-PROBLEMS: a vector of results.  (funcall SOLVE-ALONE k problem)
 returns member K's result through MI355X-SIMPLEX-SOLVER.  MAX-BITS 256: the batches stay at their 64 / 128
-bits, and a member that outgrows them is solved again through SOLVE-ALONE (which allows 256 bits)."
+bits, and a member that outgrows them is solved again through SOLVE-ALONE (which allows 256 bits).  RULE: the
+pivot rule of every batch (SOLVE-ALONE carries its own)."
   (let ((results (make-array (length problems) :initial-element nil))
         (groups (make-hash-table :test #'equal)))
     (loop for problem in problems for k from 0
@@ -758,7 +789,8 @@ bits, and a member that outgrows them is solved again through SOLVE-ALONE (which
                                               (when (> max-bits 128)
                                                 (lambda (q)
                                                   (let ((k (car (nth q members))))
-                                                    (funcall solve-alone k (nth k problems))))))
+                                                    (funcall solve-alone k (nth k problems)))))
+                                              rule)
                            :declined)))
          (if (eq outcomes :declined)
              (loop for (k . nil) in members
@@ -857,10 +889,11 @@ tableau-variable (src/simplex.lisp:74-107) on ratios."
                                       (linear-programming/simplex::signed
                                        (- (basic (second mapping)) (basic (1+ (second mapping))))))))))))))
 
-(defun solve-exact-bb-group (problem main-tab base entries n-art max-pivots)
+(defun solve-exact-bb-group (problem main-tab base entries n-art max-pivots &optional (rule 0))
   "ENTRIES: nodes of one depth and one number of artificial rows (N-ART, the base's included).  One batch (or
 pair) assembled by the library, solved in bounded calls, read back light.  A list parallel to ENTRIES:
-(objective . values), :INFEASIBLE, or the condition object of the node's outcome."
+(objective . values), :INFEASIBLE, or the condition object of the node's outcome.  RULE: the pivot rule, set on
+both batches."
   (let* ((n (length entries))
          (depth (length (first entries)))
          (rows (+ depth (array-dimension (tableau-matrix main-tab) 0)))
@@ -887,6 +920,9 @@ pair) assembled by the library, solved in bounded calls, read back light.  A lis
              (check created))
            (setf main-handle (cffi:mem-ref out-main :pointer)
                  art-handle (if (zerop n-art) nil (cffi:mem-ref out-art :pointer)))
+           (unless (zerop rule)
+             (check (%xbatch-set-pivot-rule main-handle rule))
+             (when art-handle (check (%xbatch-set-pivot-rule art-handle rule))))
            (solve-in-chunks
             (lambda (cap)
               (check (if art-handle
@@ -913,10 +949,11 @@ pair) assembled by the library, solved in bounded calls, read back light.  A lis
       (cffi:foreign-free values-lo-hi)
       (cffi:foreign-free basis))))
 
-(defun solve-exact-branch-and-bound (problem device max-pivots bb-width max-nodes)
+(defun solve-exact-branch-and-bound (problem device max-pivots bb-width max-nodes &optional (rule 0))
   "simplex-solver (src/simplex.lisp:506-542) on an integer problem whose numbers are all rational.  Returns
 the incumbent's solved `tableau` (its node solved once more on its own, so that the reference's methods
-serve it), or signals as the reference does."
+serve it), or signals as the reference does.  RULE: the pivot rule of the root, of every node batch and of
+that last solve."
   (when (null (problem-constraints problem))
     (exact-declined '(branch-and-bound no-constraints)))       ; (build-tableau's special case has no general form)
   (let* ((tableaus (build-tableau problem problem))
@@ -940,7 +977,7 @@ serve it), or signals as the reference does."
                           (if (null entry)
                               (setf (gethash entry results)
                                     (handler-case
-                                        (let ((tab (solve-exactly problem device max-pivots)))
+                                        (let ((tab (solve-exactly problem device max-pivots problem 128 rule)))
                                           (cons (tableau-objective-value tab)
                                                 (loop for var across (problem-vars problem)
                                                       collect (cons var (tableau-variable tab var)))))
@@ -956,7 +993,7 @@ serve it), or signals as the reference does."
                (maphash (lambda (shape entries)
                           (loop for entry in entries
                                 for result in (solve-exact-bb-group problem main-tab base entries (second shape)
-                                                                    max-pivots)
+                                                                    max-pivots rule)
                                 do (setf (gethash entry results) result)))
                         groups)))
            (violated (values-alist)                               ; violated-integer-constraint, :475-480
@@ -990,7 +1027,7 @@ serve it), or signals as the reference does."
                                       current-entry entry)))))))))
         (%xbb-base-destroy base))
       (if current-best
-          (solve-exactly problem device max-pivots (exact-node-problem problem current-entry))
+          (solve-exactly problem device max-pivots (exact-node-problem problem current-entry) 128 rule)
           (error 'infeasible-problem-error)))))
 
 ;;; ------------------------------------------------------------------ the native route
@@ -1322,6 +1359,7 @@ phases together.  Returns the final status."
                               &key (fp-tolerance 1024) (device 0) (devices 1) (max-pivots 0)
                                 full-tableau (native :auto) branch-and-bound (bb-width 1)
                                 (int-tolerance 0) (max-nodes 0) exact (exact-max-bits 128)
+                                (pivot-rule :dantzig)
                               &allow-other-keys)
   "Solver interface function for the MI355X backend (the value of
 linear-programming:*solver*, src/solver.lisp:39-49).  Takes a problem and backend keyword
@@ -1354,8 +1392,18 @@ rational: the reference's branch-and-bound in rational arithmetic, where its int
 of a ratio (src/simplex.lisp:475-480); :bb-width node LPs per round as batches of exact tableaux assembled
 on the device, :max-nodes as above; returns the incumbent's solved `tableau`.  (Without integer variables
 the combination is declined; with a float anywhere it is the double-float branch-and-bound above.  Exact
-branch-and-bound rides on batches, which stop at 128 bits: with :exact-max-bits 256 it is an error.)"
+branch-and-bound rides on batches, which stop at 128 bits: with :exact-max-bits 256 it is an error.)
+:pivot-rule (opt-in, with :exact T only) is how the exact solves choose a pivot.  :dantzig, the default, is
+find-entering-column and find-pivoting-row (src/simplex.lisp:362-389) as they stand: no anti-cycling rule, and
+on rationals a cycle never ends.  :bland takes the lowest eligible column and, among the rows of the minimum
+ratio, the one whose basis column is lowest; :dantzig-bland does so only after a degenerate pivot and until
+the next one that is not.  Both end on every input; they reach the exact branch-and-bound's root and node
+batches too.  An unknown rule, and a rule other than :dantzig without :exact T, are errors; with :exact T on a
+problem that holds a float such a rule is declined: unsupported-constraint-error (exact pivot-rule RULE)."
   (declare (ignore args))
+  (check-pivot-rule pivot-rule exact)
+  (when (and (plusp (pivot-rule-code pivot-rule)) (not (rational-numbers-p problem)))
+    (exact-declined (list 'pivot-rule pivot-rule)))
   (unless (member exact-max-bits '(128 256))
     (error "MI355X-SIMPLEX-SOLVER: :exact-max-bits must be 128 or 256, not ~S" exact-max-bits))
   (when (and exact branch-and-bound (/= exact-max-bits 128))
@@ -1365,7 +1413,8 @@ branch-and-bound rides on batches, which stop at 128 bits: with :exact-max-bits 
       (exact-declined '(branch-and-bound)))
     (when (rational-numbers-p problem)
       (return-from mi355x-simplex-solver
-        (solve-exact-branch-and-bound problem device max-pivots bb-width max-nodes))))
+        (solve-exact-branch-and-bound problem device max-pivots bb-width max-nodes
+                                      (pivot-rule-code pivot-rule)))))
   ;; :branch-and-bound T (opt-in): integer problems through the library's branch-and-bound job
   ;; (:bb-width node LPs side by side, :int-tolerance 0 = exact integrality, :max-nodes 0 = no cap)
   (when (and branch-and-bound (problem-integer-vars problem))
@@ -1374,7 +1423,8 @@ branch-and-bound rides on batches, which stop at 128 bits: with :exact-max-bits 
                               max-nodes)))
   ;; :exact T (opt-in): all-rational problems on exact tableaux (integer problems are declined below)
   (when (and exact (null (problem-integer-vars problem)) (rational-numbers-p problem))
-    (return-from mi355x-simplex-solver (solve-exactly problem device max-pivots problem exact-max-bits)))
+    (return-from mi355x-simplex-solver
+      (solve-exactly problem device max-pivots problem exact-max-bits (pivot-rule-code pivot-rule))))
   (when (problem-integer-vars problem)
     (error 'unsupported-constraint-error
            :constraint (cons 'integer (problem-integer-vars problem))
@@ -1594,6 +1644,7 @@ solution (unbounded-problem-error ...)."
 (defun mi355x-solve-problems (problems &rest args
                               &key (fp-tolerance 1024) (device 0) (devices 1) (max-pivots 0)
                                 full-tableau (errorp t) native exact (exact-max-bits 128)
+                                (pivot-rule :dantzig)
                               &allow-other-keys)
   "Solves a LIST of problems and returns the list of their solved tableaus, in order -- what
   (mapcar #'solve-problem problems) returns, with the independent LPs running side by side on
@@ -1626,12 +1677,17 @@ the GPU(s) instead of one after the other.
     together.  :EXACT-MAX-BITS 256 (default 128): the batches stay at 64 / 128 bits, and a member a
     batch declines for outgrowing them is solved again, alone, with 256 bits allowed; its result (or its
     condition) takes its place, the other members are untouched.  :EXACT NIL (default): nothing changes.
+  * :PIVOT-RULE (:DANTZIG, the default, :BLAND or :DANTZIG-BLAND; with :EXACT T only): MI355X-SIMPLEX-SOLVER's,
+    for every batch and every member solved alone, the 256-bit re-solve included.  An unknown rule and a rule
+    other than :DANTZIG without :EXACT T are errors; a member that holds a float declines such a rule, and its
+    condition takes its place.
   * The other keywords are MI355X-SIMPLEX-SOLVER's, applied to every member: :FP-TOLERANCE (the
     tolerance factor, src/simplex.lisp:506-511), :DEVICE (the GPU of members solved alone), :DEVICES
     (a count or a list of device ids: the sub-batches' GPUs), :MAX-PIVOTS (a cap per member; 0 = none,
     as the reference), :FULL-TABLEAU (every entry of every solved tableau written back).
 Every returned solution object's results are bit-identical to the single-problem path's."
   (declare (ignore args))
+  (check-pivot-rule pivot-rule exact)
   (when (and (eq native :many) (not full-tableau) problems)
     ;; the whole list behind ONE job of the library: no build-tableau, no boxed matrices; the members
     ;; come back as MI355X-SOLUTION objects
@@ -1651,9 +1707,10 @@ Every returned solution object's results are bit-identical to the single-problem
                                                                    :device device :max-pivots max-pivots
                                                                    :full-tableau full-tableau
                                                                    :native native :exact t
-                                                                   :exact-max-bits exact-max-bits)
+                                                                   :exact-max-bits exact-max-bits
+                                                                   :pivot-rule pivot-rule)
                         (error (c) c)))
-                    exact-max-bits)))
+                    exact-max-bits (pivot-rule-code pivot-rule))))
       (when errorp
         (let ((failed (find-if (lambda (r) (typep r 'condition)) results)))
           (when failed (error failed))))

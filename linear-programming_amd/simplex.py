@@ -616,7 +616,7 @@ def _native_numbers(problem):
 def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_pivots=0,
                           full_tableau=False, native="auto", chunk=None, branch_and_bound=False,
                           bb_width=1, int_tolerance=0, max_nodes=0, exact=False, exact_bits=0, exact_max_bits=128,
-                          **_ignored):
+                          pivot_rule="dantzig", **_ignored):
     """What the Lisp glue installs as `*solver*` (src/solver.lisp:39-56): takes a problem and
     backend keyword arguments, returns a solution object answering the four solution-*
     generics -- on the NATIVE route (default whenever the problem's numbers are floats / integers
@@ -646,7 +646,23 @@ def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_p
     as batches of exact tableaux assembled on the device; returns the incumbent's solved ExactTableau.
     (With a float anywhere: the f64 branch-and-bound above, unchanged.  Without integer variables the
     combination is declined.)  Exact branch-and-bound rides on batches, which stop at 128 bits: together
-    with exact_max_bits=256 it is an argument error."""
+    with exact_max_bits=256 it is an argument error.
+    pivot_rule (opt-in, exact solves only): "dantzig" (default) is the reference's choice of entering column
+    and pivot row (find-entering-column / find-pivoting-row), which has no anti-cycling rule, so that on
+    rationals a cycle never ends; "bland" takes the lowest eligible column and breaks ratio ties by the lowest
+    basis column, "dantzig-bland" does so only after a degenerate pivot and until the next one that is not.
+    Both end on every input.  It reaches the exact branch-and-bound's root and node batches as well.  An
+    unknown name and a rule other than "dantzig" without exact=True are argument errors (in floating point
+    neither rule is a theorem); with exact=True on a problem that holds a float -- which would take the double
+    path -- such a rule is declined: unsupported-constraint-error ("exact", "pivot-rule", name)."""
+    from .exact import pivot_rule_code
+    if pivot_rule_code(pivot_rule) != 0 and not exact:
+        raise ValueError("pivot_rule=%r needs exact=True: the double-precision paths keep the reference's rule"
+                         % (pivot_rule,))
+    if pivot_rule != "dantzig":
+        from .exact import rational_problem
+        if not rational_problem(problem):
+            raise UnsupportedConstraintError(("exact", "pivot-rule", pivot_rule), "mi355x-simplex")
     if exact and exact_max_bits != 128:
         from .exact import _check_widths
         _check_widths(exact_bits, exact_max_bits)
@@ -660,7 +676,8 @@ def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_p
         if rational_problem(problem):
             from .exact_bb import solve_branch_and_bound_exact
             return solve_branch_and_bound_exact(problem, width=bb_width, device=device, max_pivots=max_pivots,
-                                                max_nodes=max_nodes, min_bits=exact_bits, chunk=chunk)
+                                                max_nodes=max_nodes, min_bits=exact_bits, chunk=chunk,
+                                                pivot_rule=pivot_rule)
     if problem.integer_vars and branch_and_bound:
         from .native import solve_branch_and_bound
         return solve_branch_and_bound(problem, fp_tolerance=fp_tolerance, int_tolerance=int_tolerance,
@@ -672,7 +689,7 @@ def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_p
         from .exact import rational_problem, solve_exact
         if rational_problem(problem):
             return solve_exact(problem, device=device, max_pivots=max_pivots, min_bits=exact_bits, chunk=chunk,
-                               exact_max_bits=exact_max_bits)
+                               exact_max_bits=exact_max_bits, pivot_rule=pivot_rule)
     if native and not full_tableau and devices <= 1 and len(problem.vars) > 0 and \
             (native is True or _native_numbers(problem)):
         from .native import NativeProblem
@@ -690,7 +707,7 @@ simplex_solver = mi355x_simplex_solver
 
 
 def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_pivots=0, errorp=True, native=False,
-                          exact=False, exact_bits=0, exact_max_bits=128):
+                          exact=False, exact_bits=0, exact_max_bits=128, pivot_rule="dantzig"):
     """The glue's `mi355x-solve-problems`: a LIST of problems -> the list of their solved tableaus,
     what [solve_problem(p) for p in problems] returns, with the independent LPs side by side on the
     GPU(s).  Single-phase problems are grouped by tableau shape and sense; a group of two or more
@@ -712,11 +729,19 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
     mi355x_simplex_solver(..., exact=True) one by one; max_pivots caps each member (both phases
     together, as there).  exact_max_bits=256: batches stay at 64 / 128 bits; a member a batch declines for
     overflowing 128 bits is solved again alone with 256 bits allowed and its result takes its slot.
-    exact=False: nothing changes."""
+    exact=False: nothing changes.
+    pivot_rule: as for mi355x_simplex_solver, for every batch and every member solved alone; an unknown name
+    and a rule other than "dantzig" with exact=False are argument errors, and a member with a float declines
+    such a rule (its condition takes its slot when errorp is False)."""
+    from .exact import pivot_rule_code
+    if pivot_rule_code(pivot_rule) != 0 and not exact:
+        raise ValueError("pivot_rule=%r needs exact=True: the double-precision paths keep the reference's rule"
+                         % (pivot_rule,))
     if exact:
         from .exact import solve_problems_exact
         return solve_problems_exact(problems, fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots,
-                                    errorp=errorp, native=native, min_bits=exact_bits, exact_max_bits=exact_max_bits)
+                                    errorp=errorp, native=native, min_bits=exact_bits, exact_max_bits=exact_max_bits,
+                                    pivot_rule=pivot_rule)
     from .batch import MultiDeviceBatch
     if native == "many":
         # the whole list behind ONE job of the library (mi355x_simplex_solver_many_*): members come
