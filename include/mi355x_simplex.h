@@ -463,6 +463,29 @@ int  mi355x_xbatch_create_nodes(mi355x_xbatch **out_main, mi355x_xbatch **out_ar
                                 const mi355x_xbb_base *base, int64_t n_nodes, int64_t depth,
                                 const int64_t *var, const int32_t *sense, const int64_t *bound,
                                 int min_bits);
+/* build-tableau (src/simplex.lisp:214-328) of n_lps problems of one shape, written on the device: a batch of
+ * exact LPs straight from the problems' rows, with no tableau built on the host.  Member q is given in column
+ * space, as build-tableau holds it after :189-241 and before :243, at q * (m + 1) * (ncv + 1): rows 0 .. m-1 are
+ * the ncv structural coefficients and, last, the right-hand side with the offsets already subtracted; row m is
+ * the objective row as :270-283 stores it, the signs applied, the constant last.  Every entry is a reduced
+ * fraction num / den (den > 0, gcd(|num|, den) == 1, zero is 0 / 1); sense (n_lps x m): 0 `<=`, 1 `>=`, 2 `=`.
+ * What the members start from is what build-tableau followed by mi355x_xbatch_create gives, entry for entry: a
+ * row whose right-hand side is < 0 negated and its sense flipped (:243-252), slack columns in row order for
+ * the rows that are not `=` (:254-265), artificial columns in decreasing row order (:257, :261, :296-300), the
+ * artificial objective row (:302-316), and the integer scale of mi355x_xtab_create.  *out_main is a batch of
+ * (m + 1) x (ncv + n_slack + 1) members; *out_art is NULL when no row is artificial (solve *out_main with
+ * mi355x_xbatch_solve), else the batch of artificial tableaux with n_art more columns (solve the pair with
+ * mi355x_xbatch_solve_two_phase).  Both are ordinary mi355x_xbatch handles; the rows stay on the device while
+ * either lives, and a member that overflows 64 bits is assembled again from them at 128 bits.  A tableau
+ * leaves a width exactly when its common denominator or one of its entries does -- no intermediate of the
+ * assembly is larger -- and a member whose start state needs more than 128 bits reports MI_EXACT_OVERFLOW
+ * when solved.  MI_BAD_ARG (the message names the member) for m < 1, ncv < 1, a fraction that is not reduced, a
+ * sense outside 0 .. 2, and members that differ in their number of `=` rows or of artificial rows;
+ * MI_UNSUPPORTED for exactly the shapes mi355x_xbatch_create declines.  min_bits as for mi355x_xbatch_create. */
+int  mi355x_xbatch_create_lps(mi355x_xbatch **out_main, mi355x_xbatch **out_art,
+                              int64_t n_lps, int64_t m, int64_t ncv,
+                              const int64_t *num, const int64_t *den, const int32_t *sense,
+                              int device, int min_bits);
 /* All that tableau-objective-value, tableau-variable and tableau-reduced-cost read (src/simplex.lisp:74-120)
  * of every member, in one copy: values_lo_hi holds per member 1 + rows + cols limb pairs -- D, the last
  * column (rows values), the last row (cols values) --, basis (may be NULL) rows - 1 entries per member.

@@ -13,7 +13,7 @@ GPU, and fails loudly otherwise.
 (The directory name contains a hyphen; import it with
 ``importlib.import_module("linear-programming_amd")``.)
 """
-from . import batch, capi, exact, exact_bb, native, simplex, solver, synth       # noqa: F401
+from . import batch, capi, exact, exact_bb, exact_lps, native, simplex, solver, synth       # noqa: F401
 from .native import NativeProblem, NativeSolution               # noqa: F401
 from .batch import TableauBatch, MultiDeviceBatch               # noqa: F401
 from .exact import ExactTableau                                  # noqa: F401

@@ -54,6 +54,7 @@ SIGNATURES = {
     "mi355x_xbb_base_create": (_int, [_pp, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _int]),
     "mi355x_xbb_base_destroy": (None, [_p]),
     "mi355x_xbatch_create_nodes": (_int, [_pp, _pp, _p, _i64, _i64, _p, _p, _p, _int]),
+    "mi355x_xbatch_create_lps": (_int, [_pp, _pp, _i64, _i64, _i64, _p, _p, _p, _int, _int]),
     "mi355x_xbatch_readback": (_int, [_p, _p, _p, _p]),
     "mi355x_tab_create_compact": (_int, [_pp, _i64, _i64, _i64, _p, _p, _p, _int]),
     "mi355x_tab_upload": (_int, [_p, _p, _p]),

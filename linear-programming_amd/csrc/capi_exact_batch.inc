@@ -12,9 +12,12 @@
 //
 // A member's start state has one of two sources: the caller's rationals (mi355x_xbatch_create), or a node
 // spec -- a base problem and the member's node rows -- from which k_xbb_assemble writes it on the device
-// (mi355x_xbatch_create_nodes, capi_exact_bb.inc).  Everything after the start is the same for both.
+// (mi355x_xbatch_create_nodes, capi_exact_bb.inc).  A third source is the members' problem rows in column
+// space, from which k_xb_assemble_lps writes it on the device (mi355x_xbatch_create_lps, capi_exact_lps.inc).
+// Everything after the start is the same for all three.
 
 struct XbbNodes;                         // capi_exact_bb.inc: the node spec of a handle made by create_nodes
+struct XbLps;                            // capi_exact_lps.inc: the problem rows of a handle made by create_lps
 
 struct XbWidth {
     XbView             v{};              // v.T == nullptr: this width is not allocated
@@ -28,6 +31,7 @@ struct mi355x_xbatch {
     int64_t     n = 0, rows = 0, cols = 0;
     std::vector<int64_t> num, den, basis0;      // the callers' tableaux, member after member (none: see nodes)
     std::shared_ptr<XbbNodes> nodes;            // the other source of the start states: the members' node rows
+    std::shared_ptr<XbLps> lps;                 // or the third: the members' problem rows, resident on the device
     int64_t    *rb = nullptr;                   // mi355x_xbatch_readback's device buffer, made at its first call
     int32_t    *rb_width = nullptr;
     std::vector<char>    start_ok;              // per member: unit basis columns over a zero objective entry
@@ -48,6 +52,8 @@ static_assert(MI355X_XBATCH_WORKGROUP == kXThreads, "the header states k_xb_solv
 // member q of a handle made from node specs assembled again at 128 bits (capi_exact_bb.inc): MI_OK and its
 // D, kXOverflow, or an error
 int xbb_reassemble_128(mi355x_xbatch *b, int64_t q, hipStream_t s, __int128 *D0);
+// the same for a handle made from problem rows (capi_exact_lps.inc)
+int xlp_reassemble_128(mi355x_xbatch *b, int64_t q, hipStream_t s, __int128 *D0);
 
 int xb_wi(int bits) { return bits == 128 ? 1 : 0; }
 XbCtl &xb_ctl(mi355x_xbatch *b, int64_t q) { return b->w[xb_wi(b->width[q])].h[q]; }
@@ -113,7 +119,7 @@ int xb_alloc(mi355x_xbatch *b, int wi)
         for (size_t j = 0; j <= C; ++j) x_put(&stage[(q * (C + 1) + j) * wb], mq[j], bits);
     }
     HIP_TRY(hipMemcpyAsync(s.aux, stage.data(), stage.size(), hipMemcpyHostToDevice, b->stream));
-    if (n * m > 0 && !b->nodes)                                             // (node specs: k_xbb_assemble writes the bases)
+    if (n * m > 0 && !b->nodes && !b->lps)                                  // (specs: the assembling kernel writes the bases)
         HIP_TRY(hipMemcpyAsync(s.v.basis, b->basis0.data(), n * m * sizeof(int64_t), hipMemcpyHostToDevice, b->stream));
     s.h.assign(n, xb_fresh(0));
     HIP_TRY(hipMemcpyAsync(s.v.ctl, s.h.data(), n * sizeof(XbCtl), hipMemcpyHostToDevice, b->stream));
@@ -146,8 +152,8 @@ int xb_restart_128(mi355x_xbatch *b, int64_t q, int32_t status, int64_t cap_at, 
     std::vector<unsigned char> stage;
     i128_t D0 = 0;
     XbWidth &w = b->w[1];
-    if (b->nodes) {
-        rc = xbb_reassemble_128(b, q, s, &D0);
+    if (b->nodes || b->lps) {
+        rc = b->nodes ? xbb_reassemble_128(b, q, s, &D0) : xlp_reassemble_128(b, q, s, &D0);
         if (rc == kXOverflow) { b->width[q] = 0; return kXOverflow; }
         if (rc != MI_OK) return rc;
     } else {

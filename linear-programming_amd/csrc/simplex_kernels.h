@@ -441,6 +441,17 @@ void launch_xbb_assemble(const XbView &mt, const XbView &at, const XbbBaseView &
                          int64_t count, hipStream_t s);
 // every member whose width[q] is the view's: D, right-hand sides, objective row (limb pairs) and basis
 void launch_xbb_readback(const XbView &v, const int32_t *width, int64_t *values, int64_t *basis, hipStream_t s);
+// Exact batches built from problem rows (kernels_exact_lps.inc, capi_exact_lps.inc): the members of a group in
+// column space, reduced fractions, member q's (m + 1) x (ncv + 1) entries at q * (m + 1) * (ncv + 1).
+struct XbLpsView {
+    const int64_t *num, *den;         // rows 0 .. m-1: ncv coefficients and the right-hand side; row m: the objective row
+    const int32_t *sense;             // (member, row) at member * m + row: 0 `<=`, 1 `>=`, 2 `=`
+    int64_t        m, ncv, n_slack, n_art;   // n_slack rows are not `=`; n_art rows end up `>=` or `=` (every member)
+};
+// members q0 .. q0 + count - 1 into their slots of mt and / or at (a view whose T is NULL is left out): tableau,
+// basis and D; status kXOverflow for a tableau that does not fit the view's width
+void launch_xb_assemble_lps(const XbView &mt, const XbView &at, const XbLpsView &sp, int64_t q0, int64_t count, hipStream_t s);
+size_t xb_assemble_lps_lds(int64_t m);                                      // its dynamic LDS in bytes
 #ifdef MI355X_TEST_HOOKS
 // test build: one arithmetic primitive of kernels_exact.inc applied element-wise (k_x_arith_probe; the
 // opcodes and the limb layout are mi355x_test_xarith's, include/mi355x_simplex_tune.h).  Device pointers.

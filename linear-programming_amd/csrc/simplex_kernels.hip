@@ -73,6 +73,7 @@
 //     kernels_exact.inc           exact rational solves on fraction-free integer tableaux (k_x_*)
 //     kernels_exact_batch.inc     batches of exact LPs, one workgroup per LP (k_xb_solve, k_xb_between)
 //     kernels_exact_bb.inc        exact branch-and-bound: integer node tableaux, light read-back (k_xbb_*)
+//     kernels_exact_lps.inc       exact batches built from problem rows on the device (k_xb_assemble_lps)
 //     kernels_launch.inc          host-side launchers, tuning state
 #include "simplex_kernels.h"
 #include <type_traits>
@@ -94,6 +95,7 @@ namespace mi355x {
 #include "kernels_exact.inc"
 #include "kernels_exact_batch.inc"
 #include "kernels_exact_bb.inc"
+#include "kernels_exact_lps.inc"
 #include "kernels_launch.inc"
 
 }  // namespace mi355x

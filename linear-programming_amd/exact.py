@@ -493,14 +493,33 @@ def solve_exact_batch(members, is_max, device=0, max_pivots=0, min_bits=0, chunk
 
 
 def solve_problems_exact(problems, fp_tolerance=1024, device=0, max_pivots=0, errorp=True, native=False, min_bits=0,
-                         chunk=None, exact_max_bits=128, pivot_rule="dantzig"):
+                         chunk=None, exact_max_bits=128, pivot_rule="dantzig", device_build=False):
     """mi355x_solve_problems(exact=True): see there.  pivot_rule goes to every batch and to every member solved
     alone, the 256-bit re-solve included; a member with a float declines a rule other than "dantzig".  exact_max_bits=256: the batches stay at their 64 / 128
     bits, and a member a batch declines for overflowing them is solved again, alone, on the single-tableau
-    path with 256 bits allowed; its result (or its condition) takes its slot, the other members are untouched."""
+    path with 256 bits allowed; its result (or its condition) takes its slot, the other members are untouched.
+    device_build=True (opt-in): the members are lowered to rows of numerators and denominators and their tableaux
+    built on the device (exact_lps.py); members alone in their group, members exact_lps.lower_problem does not
+    take, groups the batch declines and members that end past 128 bits go through the route above, whose
+    outcomes, exceptions and errorp these are."""
     from .conditions import SolverError
     from .simplex import mi355x_simplex_solver
     _check_widths(min_bits, exact_max_bits)
+    if device_build:
+        from .exact_lps import solve_problems_device_built
+        pivot_rule_code(pivot_rule)
+
+        def host_route(ps):
+            return solve_problems_exact(ps, fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots, errorp=False,
+                                        native=native, min_bits=min_bits, chunk=chunk, exact_max_bits=exact_max_bits,
+                                        pivot_rule=pivot_rule)
+        results = solve_problems_device_built(problems, host_route, device=device, max_pivots=max_pivots,
+                                              min_bits=min(min_bits, 128), chunk=chunk, pivot_rule=pivot_rule)
+        if errorp:
+            for r in results:
+                if isinstance(r, Exception):
+                    raise r
+        return results
     rule_kw = {} if pivot_rule_code(pivot_rule) == capi.MI_RULE_DANTZIG else {"pivot_rule": pivot_rule}   # (the default: the calls as they were)
     results = [None] * len(problems)
     batch_bits = min(min_bits, 128)                    # (a batch member is at most 128 bits wide)

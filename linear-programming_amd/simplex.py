@@ -707,7 +707,7 @@ simplex_solver = mi355x_simplex_solver
 
 
 def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_pivots=0, errorp=True, native=False,
-                          exact=False, exact_bits=0, exact_max_bits=128, pivot_rule="dantzig"):
+                          exact=False, exact_bits=0, exact_max_bits=128, pivot_rule="dantzig", device_build=False):
     """The glue's `mi355x-solve-problems`: a LIST of problems -> the list of their solved tableaus,
     what [solve_problem(p) for p in problems] returns, with the independent LPs side by side on the
     GPU(s).  Single-phase problems are grouped by tableau shape and sense; a group of two or more
@@ -730,6 +730,9 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
     together, as there).  exact_max_bits=256: batches stay at 64 / 128 bits; a member a batch declines for
     overflowing 128 bits is solved again alone with 256 bits allowed and its result takes its slot.
     exact=False: nothing changes.
+    device_build=True (opt-in, with exact=True only -- an argument error otherwise): the exact members' tableaux are
+    built on the device from their rows (exact_lps.py: mi355x_xbatch_create_lps) instead of on the host; the
+    results are the same, member for member.
     pivot_rule: as for mi355x_simplex_solver, for every batch and every member solved alone; an unknown name
     and a rule other than "dantzig" with exact=False are argument errors, and a member with a float declines
     such a rule (its condition takes its slot when errorp is False)."""
@@ -737,11 +740,14 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
     if pivot_rule_code(pivot_rule) != 0 and not exact:
         raise ValueError("pivot_rule=%r needs exact=True: the double-precision paths keep the reference's rule"
                          % (pivot_rule,))
+    if device_build and not exact:
+        raise ValueError("device_build=True needs exact=True: it builds the tableaux of the exact batches")
     if exact:
         from .exact import solve_problems_exact
+        kw = {"device_build": True} if device_build else {}               # (the default: the call as it was)
         return solve_problems_exact(problems, fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots,
                                     errorp=errorp, native=native, min_bits=exact_bits, exact_max_bits=exact_max_bits,
-                                    pivot_rule=pivot_rule)
+                                    pivot_rule=pivot_rule, **kw)
     from .batch import MultiDeviceBatch
     if native == "many":
         # the whole list behind ONE job of the library (mi355x_simplex_solver_many_*): members come

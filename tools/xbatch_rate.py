@@ -14,6 +14,13 @@ Both paths build every member's tableau on the host first (build_tableau(exact=T
 Python, the same work in both); the columns "after build" time what is left once the tableaux exist --
 uploads, solves and hand-overs -- which is where the two paths differ.
 
+The device-built route, mi355x_solve_problems(ps, exact=True, device_build=True), is a third path on the same
+sets in the same run: the members are lowered to rows of numerators and denominators (exact_lps.lower_problem)
+and their tableaux built on the device (mi355x_xbatch_create_lps).  "built s" is its wall time, "b/built" the
+host-built batch's wall time over it, "lower s" the time of the lowering and grouping alone
+(exact_lps.group_lowered) and "share" that time's part of "built s".  Every member's outcome is compared with
+the host-built batch's.
+
     python tools/xbatch_rate.py [--counts 64,256,1024] [--reps 5] [--out profiles/xbatch_rate.txt]
 """
 import argparse
@@ -91,10 +98,11 @@ def main():
     args = ap.parse_args()
     lines = ["# exact LPs: one batch (mi355x_solve_problems(exact=True)) against one by one "
              "(solve_problem(p, exact=True)); median of %d after a warm-up; 'after': the same without the "
-             "host's build-tableau, which both paths share" % args.reps,
-             "%-30s %6s %8s %12s %12s %14s %14s %7s %12s %12s %7s" % (
+             "host's build-tableau, which both paths share; 'built': the batch with device_build=True, 'b/built' "
+             "batch s over it, 'lower': its lowering and grouping alone, 'share' their part of 'built'" % args.reps,
+             "%-30s %6s %8s %12s %12s %14s %14s %7s %12s %12s %7s %10s %8s %10s %6s" % (
                  "set", "n", "pivots", "batch s", "one-by-one s", "batch piv/s", "1-by-1 piv/s", "ratio",
-                 "batch after", "1-by-1 after", "ratio")]
+                 "batch after", "1-by-1 after", "ratio", "built s", "b/built", "lower s", "share")]
     print("\n".join(lines), flush=True)
     sets = (("mixed 6,3,2,1", lambda s: ec.mixed_problem(lp, 6, 3, 2, 1, s)),
             ("slack 32x32", lambda s: slack_problem(32, 32, s)))
@@ -114,9 +122,19 @@ def main():
                 assert a.basis_columns.tolist() == b.basis_columns.tolist()
             ab, _ = timed(batch_after_build, args.reps, lambda: lp.exact.group_exact_problems(ps))
             a1, _ = timed(one_by_one_after_build, args.reps, lambda: [lp.build_tableau(p, exact=True) for p in ps])
+            td, built = timed(lambda: lp.solve_problems(ps, exact=True, device_build=True, errorp=False), args.reps)
+            tl, (host, _) = timed(lambda: lp.exact_lps.group_lowered(ps), args.reps)
+            assert not host and k == sum(pivots(s) for s in built)
+            for a, b in zip(built, batch):
+                if isinstance(b, Exception):
+                    assert type(a) is type(b)
+                    continue
+                assert a._batch is not None and a._handle is None
+                assert lp.solution_objective_value(a) == lp.solution_objective_value(b)
+                assert a.basis_columns.tolist() == b.basis_columns.tolist()
             name_n = "%s (%d solved)" % (name, sum(not isinstance(s, Exception) for s in batch))
-            line = "%-30s %6d %8d %12.4f %12.4f %14.0f %14.0f %7.1f %12.4f %12.4f %7.1f" % (
-                name_n, n, k, tb, t1, k / tb, k / t1, t1 / tb, ab, a1, a1 / ab)
+            line = "%-30s %6d %8d %12.4f %12.4f %14.0f %14.0f %7.1f %12.4f %12.4f %7.1f %10.4f %8.1f %10.4f %6.2f" % (
+                name_n, n, k, tb, t1, k / tb, k / t1, t1 / tb, ab, a1, a1 / ab, td, tb / td, tl, tl / td)
             lines.append(line)
             print(line, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
