@@ -133,6 +133,9 @@ int         mi355x_tune_set_la_max_spins(unsigned polls);    /* polls before a w
  * clean blocks (four times as many after each further loss).  mi355x_debug_set_la_rearm overrides the
  * number of clean blocks left (tests). */
 int         mi355x_tab_la_lost(const mi355x_tab *t);
+/* Workgroups of this handle's last persistent look-ahead launch (0: none so far): a thread per constraint
+ * row and per pair of non-RHS columns. */
+int         mi355x_tab_la_workgroups(const mi355x_tab *t);
 int         mi355x_debug_set_la_rearm(mi355x_tab *t, int64_t blocks);
 /* Which implementation the dispatcher actually enqueued on this handle so far, launches by class:
  * out8[0] per-pivot updates (k_update), [1] persistent look-ahead blocks (k_la_block), [2] two-launch

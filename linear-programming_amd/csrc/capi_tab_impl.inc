@@ -515,7 +515,7 @@ int prime_block_kernels(mi355x_tab *t, int is_max, double f)
 {
     const TabView &v = t->c;
     const int bk = block_size(t);
-    const int la_nw = la_block_workgroups(v);
+    const int la_nw = la_launch_workgroups(v);
     int forms[8], nf = 0;
     if (bk > kMaxBlock) { forms[nf++] = bk; forms[nf++] = 20; }
     forms[nf++] = kMaxBlock; forms[nf++] = kMaxBlock - 1; forms[nf++] = 8; forms[nf++] = 4; forms[nf++] = 2;
@@ -591,7 +591,7 @@ int enqueue_block(mi355x_tab *t, int is_max, double f, int k)
             t->la_epoch = 1;
         }
         stamp = t->la_epoch;
-        la_nw = la_block_workgroups(v);
+        la_nw = la_launch_workgroups(v);
         launch_la_block(v, k, is_max, f, t->la_epoch, t->stream);
         t->la_last_nw = la_nw;
         t->la_epoch += 2 * kLaBlockMax + 2;

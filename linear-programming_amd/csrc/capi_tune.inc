@@ -89,6 +89,8 @@ int         mi355x_tune_set_la_fault(int step_plus_1) { set_la_fault(step_plus_1
 // how often an exchange of the persistent look-ahead was lost on this handle (it then runs the
 // two-launch look-ahead until it is re-armed: enqueue_block)
 int         mi355x_tab_la_lost(const mi355x_tab *t) { return t ? t->la_losses : 0; }
+// workgroups of the handle's last persistent look-ahead launch (la_launch_workgroups; 0: none so far)
+int         mi355x_tab_la_workgroups(const mi355x_tab *t) { return t ? t->la_last_nw : 0; }
 // test / measurement aid: clean two-launch blocks before a demoted handle tries the persistent form again
 int         mi355x_debug_set_la_rearm(mi355x_tab *t, int64_t blocks) { if (!t) return MI_BAD_ARG; t->la_rearm_in = blocks; return MI_OK; }
 // launches enqueued on this handle so far, by class: [0] per-pivot updates, [1] persistent look-ahead

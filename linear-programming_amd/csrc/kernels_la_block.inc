@@ -5,10 +5,10 @@
 
 // ---- the look-ahead of a whole block as ONE launch ------------------------------------------
 // Two launches per look-ahead step are two kernel boundaries (2.5 us each) plus cold caches at
-// every start.  For tableaux whose rows and column pairs fit a few workgroups (config 3: 17 x 256
-// threads cover 4097 rows and 4104 pairs) the steps of a block run inside one launch instead:
-// thread g owns row g (entering-column / RHS side) AND column pair g (pivot-row / objective-row
-// side); its col_i[r], prow_i[pair], RHS entry and objective-row pair stay in registers / LDS from
+// every start.  For tableaux whose rows and column pairs fit a few workgroups (config 3: 16 x 256
+// threads cover 4096 constraint rows and 4096 pairs of non-RHS columns) the steps of a block run inside
+// one launch instead: thread g owns row g (entering-column / RHS side) AND column pair g (pivot-row /
+// objective-row side); its col_i[r], prow_i[pair], RHS entry and objective-row pair stay in registers / LDS from
 // step to step, and the two reductions of a step go through a message exchange between the
 // workgroups.  All workgroups reduce the same records with the same comparisons, so they take
 // every decision (entering column, pivot row, termination) identically without further
@@ -21,8 +21,7 @@
 //     written by ONE store and polled with L1-bypassing (sc1) loads until all tags match: no
 //     fence, no release/acquire pair, no read-modify-write;
 //   * what a step has just produced and the next half-step needs at once travels IN the records
-//     (the pivot-row entry of the winning candidate, the RHS entry of the new pivot row, the
-//     objective-row entry of the new column);
+//     (the pivot-row entry of the winning candidate, the RHS entry of the winning row);
 //   * everything else another workgroup reads inside the launch (col_i, prow_i of the older
 //     pending pivots, basis) is stored WRITE-THROUGH (sc1: relaxed agent-scope atomic stores) and
 //     read with sc1 loads, and every wave drains its stores (s_waitcnt vmcnt(0)) half a step
@@ -40,7 +39,7 @@
 //     the first exchange of a launch (write-through, valid anywhere) carries every workgroup's
 //     HW_REG_XCC_ID, and only if they all agree do the later stores become plain stores that stay
 //     in the one shared L2 (where the sc1 loads find them a fabric round trip sooner).
-struct LaMsg { ValIdx c; unsigned flag, same; double u, w; };
+struct LaMsg { ValIdx c; unsigned flag, same; double u; };
 
 template <class T> __device__ __forceinline__ void st_wt(T *p, T v)
 {
@@ -159,13 +158,14 @@ __device__ __forceinline__ void load_granules2(unsigned long long (&g)[8], unsig
 
 // Exchange of one reduction between the workgroups.  `mine` is this thread's candidate.  Every
 // WAVE reduces its 64 candidates (tree of wave_reduce_min) and publishes its winner at once as
-// record 4 w + wave -- together with two doubles it picks out of its lanes' registers
-// (extra(winner, lane that holds it, u, x2)) -- so nothing waits for a workgroup barrier on the
-// way out; the first wave of every workgroup collects all records (lane l: records l and l + 64),
-// reduces them (tree again) and hands the winner to the other waves through LDS, with the first
-// double of the winner's own record and the second double (PRICE) / first double (RATIO) of
-// record rec_from.
-// The record's format: pack_rec / decode_rec (kernels_la_common.inc); granule 7 of a RATIO record is 0 here.
+// record 4 w + wave -- together with one double it picks out of its lanes' registers
+// (extra(winner, lane that holds it, u)) -- so nothing waits for a workgroup barrier on the
+// way out; the first wave of every workgroup collects all records (lane l: record l and, beyond 64
+// records, l + 64), reduces them (tree again) and hands the winner to the other waves through LDS, with
+// the double of the winner's own record.  Nothing else rides in a record: what a step needs of the RHS
+// column and of the objective row it has on the side that decides (k_la_block below).
+// The record's format: pack_rec / decode_rec (kernels_la_common.inc); the second double of a PRICE record
+// and granule 7 of a RATIO record are 0 here.
 // false: a record did not arrive within max_spins polls.
 // true: every wave collects the records itself (no LDS hop, no workgroup barrier left in the
 // kernel; four times the poll traffic on the one L2).  With a record per 64-byte line that lost
@@ -175,16 +175,77 @@ __device__ __forceinline__ void load_granules2(unsigned long long (&g)[8], unsig
 // pivots/s against 81.9 k.
 constexpr bool kLaEveryWavePolls = true;
 
+// The collecting half: poll until every record carries `tag`, reduce, winner and its double into `out`.
+// TWO: more than 64 records -- lane l also takes record l + 64 and folds the two before the tree; without
+// it the second record's loads, tag tests, decode and fold do not exist.  want_same (uniform; the launch's
+// first exchange): do all records carry the same double?  (the XCC ids)
+template <bool PRICE, bool TWO>
+__device__ __forceinline__ void la_collect(const ExchRec *recs, int nrec, unsigned tag, unsigned max_spins,
+                                           bool want_same, LaMsg &out, unsigned long long *ts)
+{
+    const int lane = threadIdx.x & 63;
+    const bool v0 = lane < nrec, v1 = TWO && lane + 64 < nrec;
+    const unsigned long long *gl = reinterpret_cast<const unsigned long long *>(recs) + lane;   // granule 0 of record `lane`
+    unsigned long long g0[8], g1[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) g1[k] = 0ull;
+    unsigned spins = 0;
+    bool fine = true;
+    for (;;) {
+        // (records past nrec exist in the buffer -- kMaxLaRecords of them -- and are never validated)
+        if (TWO) load_granules2(g0, g1, gl);
+        else     load_granules(g0, gl);
+        bool ok0 = true, ok1 = true;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            ok0 &= (unsigned)(g0[k] >> 32) == tag;
+            if (TWO) ok1 &= (unsigned)(g1[k] >> 32) == tag;
+        }
+        if (__all((ok0 | !v0) & (ok1 | !v1))) break;
+        if (++spins > max_spins) { fine = false; break; }
+    }
+#ifdef MI355X_LA_TIMING
+    if (ts) { ts[1] = wall_clock64(); ts[3] = spins; }
+#endif
+    Cand xl;
+    int64_t sl;
+    unsigned fl_l;
+    double ul, u1 = 0.0, unused;
+    decode_rec<PRICE>(g0, v0, xl, sl, fl_l, ul, unused);
+    const double u0 = ul;
+    if (TWO) {
+        // lane-local fold of the two records (= the 64-apart level of a 128-wide tree)
+        Cand x1;
+        int64_t s1;
+        unsigned f1;
+        decode_rec<PRICE>(g1, v1, x1, s1, f1, u1, unused);
+        const Cand x01 = cand_min(xl, x1);
+        const bool hi = x01.i != xl.i;                            // record l + 64 won (indices are unique)
+        xl = x01; sl = hi ? s1 : sl; ul = hi ? u1 : ul; fl_l |= f1;
+    }
+    int src;
+    const Cand x = wave_argmin(xl, src);                          // uniform
+    const unsigned fl = __any(fl_l != 0u) ? 1u : 0u;
+    out.c.v = x.v; out.c.i = x.i;
+    out.c.s = lane_pick(sl, src);
+    out.u = lane_pick(ul, src);                                   // the winner's own record
+    out.flag = fine ? fl : 2u;
+    out.same = 0u;
+    if (want_same) {
+        const unsigned long long ref = dbits(lane_value(u0, 0));
+        out.same = __all(((dbits(u0) == ref) || !v0) && ((dbits(u1) == ref) || !v1)) ? 1u : 0u;
+    }
+}
+
 // WGR (more than kLaWaveRecordsMaxNw workgroups): ONE record per workgroup -- the four waves' winners meet in
-// LDS and the first wave reduces them (wg_record), publishes record w, collects the nw records and
-// hands the result on through s_res.  The two doubles that ride along: the winner's own one from the
-// winning wave, the "from" one (record rec_from) from wave wave_from of workgroup rec_from.
+// LDS and the first wave reduces them (wg_record), publishes record w, collects the nw (<= 64) records and
+// hands the result on through s_res.  The double that rides along is the winning wave's.
 template <bool PRICE, bool WGR = false, class Extra>
 __device__ __forceinline__ bool la_exchange(ValIdx mine, unsigned myflag, ExchRec *recs, int nw, int w,
                                             unsigned tag, unsigned max_spins, bool mute, bool local,
-                                            int rec_from, LaMsg *s_res, LaMsg &out, Extra extra,
+                                            bool want_same, LaMsg *s_res, LaMsg &out, Extra extra,
                                             unsigned long long *ts, double *dbg = nullptr,
-                                            bool give_up = false, LaWaveRec *s_wv = nullptr, int wave_from = 0)
+                                            bool give_up = false, LaWaveRec *s_wv = nullptr)
 {
     constexpr bool kEvery = kLaEveryWavePolls && !WGR;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -197,10 +258,10 @@ __device__ __forceinline__ bool la_exchange(ValIdx mine, unsigned myflag, ExchRe
         unsigned wf = __any(myflag != 0u) ? 1u : 0u;
         double u = 0.0, x2 = 0.0;
         ValIdx win; win.v = c.v; win.i = c.i; win.s = cs;
-        extra(win, src, u, x2);
+        extra(win, src, u);
         bool pub = !mute;
         if (WGR) {
-            wg_record<PRICE>(s_wv, c, wf, cs, u, x2, w == rec_from, wave_from);   // (one barrier)
+            wg_record<PRICE, true>(s_wv, c, wf, cs, u, x2, false, 0);   // (one barrier)
             pub = pub && wave == 0;
         }
         if (pub) {
@@ -217,56 +278,17 @@ __device__ __forceinline__ bool la_exchange(ValIdx mine, unsigned myflag, ExchRe
     if (ts) ts[0] = wall_clock64();
 #endif
     if (give_up) { out.flag = 2u; return false; }               // test hook (workgroup-uniform): published, then "timed out"
-    if (kEvery || tid < 64) {
-        // ---- collect: lane l <- records l and l + 64
-        const bool v0 = lane < nrec, v1 = lane + 64 < nrec;
-        const unsigned long long *gl = reinterpret_cast<const unsigned long long *>(recs) + lane;   // granule 0 of record `lane`
-        unsigned long long g0[8], g1[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) g1[k] = 0ull;
-        unsigned spins = 0;
-        bool fine = true;
-        for (;;) {
-            // (records past nrec exist in the buffer -- kMaxLaRecords of them -- and are never validated)
-            if (nrec > 64) load_granules2(g0, g1, gl);
-            else           load_granules(g0, gl);
-            bool ok0 = true, ok1 = true;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { ok0 &= (unsigned)(g0[k] >> 32) == tag; ok1 &= (unsigned)(g1[k] >> 32) == tag; }
-            if (__all((ok0 | !v0) & (ok1 | !v1))) break;
-            if (++spins > max_spins) { fine = false; break; }
+    auto collect = [&](LaMsg &o) {
+        if (!WGR && nrec > 64) la_collect<PRICE, true>(recs, nrec, tag, max_spins, want_same, o, ts);    // (uniform)
+        else                   la_collect<PRICE, false>(recs, nrec, tag, max_spins, want_same, o, ts);
+    };
+    if (kEvery) collect(out);                                   // every wave has the result in registers
+    else {
+        if (tid < 64) {
+            LaMsg res;
+            collect(res);
+            if (lane == 0) *s_res = res;
         }
-#ifdef MI355X_LA_TIMING
-        if (ts) { ts[1] = wall_clock64(); ts[3] = spins; }
-#endif
-        Cand x0, x1;
-        int64_t s0, s1;
-        unsigned f0, f1;
-        double u0, u1, w0, w1;
-        decode_rec<PRICE>(g0, v0, x0, s0, f0, u0, w0);
-        decode_rec<PRICE>(g1, v1, x1, s1, f1, u1, w1);
-        // lane-local fold of the two records (= the 64-apart level of a 128-wide tree)
-        const Cand x01 = cand_min(x0, x1);
-        const bool hi = x01.i != x0.i;                            // record l + 64 won (indices are unique)
-        int src;
-        const Cand x = wave_argmin(x01, src);                     // uniform
-        const unsigned fl = __any((f0 | f1) != 0u) ? 1u : 0u;
-        const int64_t bs = lane_pick(hi ? s1 : s0, src);
-        const double bu = lane_pick(hi ? u1 : u0, src);           // the winner's own record
-        const double fsel = PRICE ? (rec_from < 64 ? w0 : w1) : (rec_from < 64 ? u0 : u1);
-        const double bw = lane_value_dyn(fsel, rec_from & 63);
-        // do all records carry the same first double?  (the XCC ids of the first exchange)
-        const unsigned long long ref = dbits(lane_value(u0, 0));
-        const unsigned same = __all(((dbits(u0) == ref) || !v0) && ((dbits(u1) == ref) || !v1)) ? 1u : 0u;
-        if (kEvery) {                                            // every wave has the result in registers
-            out.c.v = x.v; out.c.i = x.i; out.c.s = bs;
-            out.flag = fine ? fl : 2u; out.same = same; out.u = bu; out.w = bw;
-        } else if (lane == 0) {
-            s_res->c.v = x.v; s_res->c.i = x.i; s_res->c.s = bs;
-            s_res->flag = fine ? fl : 2u; s_res->same = same; s_res->u = bu; s_res->w = bw;
-        }
-    }
-    if (!kEvery) {
         __syncthreads();
         out = *s_res;
     }
@@ -308,18 +330,30 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
     const int lane = tid & 63;
     const int64_t m = t.rows - 1, vc = t.cols - 1, ld = t.ld, ldv = ld >> 1;
     const int64_t g = (int64_t)w * kLaThreads + tid;
-    const bool has_row = g < t.rows, has_pair = g < ldv;
+    // Rows below the objective row and pairs that hold a non-RHS column have an owner (the launch is
+    // la_launch_workgroups() wide).  The objective row and the RHS column need none: their entries of a step are
+    // already in the other side's registers, bit for bit --
+    //   col_J[m] is z[slot] (the objective row goes through the same reset-or-subtract, on the same operands,
+    //   in the same order, whether it is chained as a row entry of the entering column or kept up to date as
+    //   z), and z[slot] is the pricing winner's key;
+    //   prow_J[vc] is b[cr] / pivot (the same for the RHS column and b), and b[cr] rides in the ratio record.
+    // With vc odd the last owned pair holds the RHS next to a real column; its owner chains and stores that
+    // entry as any other (the same bits once more).
+    const int64_t npair = (vc + 1) >> 1;
+    const bool has_row = g < m, has_pair = g < npair;
     const int64_t r = g, p = g;
     const double2 *M2 = reinterpret_cast<const double2 *>(t.M);
-    // thread that owns the RHS pair / the objective row: workgroup, wave, lane, record
-    const int g_vc = (int)(vc >> 1), g_m = (int)m;
-    const int rec_vc = g_vc / (WGR ? kLaThreads : 64), rec_m = g_m / (WGR ? kLaThreads : 64);   // (= 4 * workgroup + wave; WGR: workgroup)
-    const int wave_vc = (g_vc / 64) % kLaWaves, wave_m = (g_m / 64) % kLaWaves;
-    const bool wave_has_vc = (int)(g / 64) == g_vc / 64, wave_has_m = (int)(g / 64) == g_m / 64;
+    // who stores what has no owner, for the sweeps (not the leader's wave: it commits the pivot): col_J[m]; prow_J
+    // from column 2 npair on -- the RHS entry if vc is even, then ld padding (+0.0: scale_pair)
+    const bool stores_cm = w == 0 && tid == 64, stores_tail = w == 0 && (tid >> 6) == 2;
 
     unsigned my_rm = 0u;                 // bit i: my row is pivot row i
     unsigned long long my_sm = 0ull;     // bits i, 32 + i: my pair's even / odd column is the slot pivot i gave up
     la_block_begin(t, c0, leader, g, epoch_base);
+    {   // the mask words past the last owner (objective row, row padding; RHS pair, ld padding): zero as everybody's
+        const int64_t n_own = (int64_t)nw * kLaThreads, n_mask = t.bk_stride > ldv ? t.bk_stride : ldv;
+        for (int64_t g2 = g + n_own; g2 < n_mask; g2 += n_own) la_zero_masks(t, g2);
+    }
     // every way out of the launch records how many steps this workgroup COMPLETED (its col_i /
     // prow_i entries stored): the sweep applies no pivot that some workgroup did not finish
     // Where every WAVE polls for itself (up to kLaWaveRecordsMaxNw workgroups) a wave can time out on its own:
@@ -337,9 +371,9 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
     la_zero_pending(s_ci, s_pi);
     __syncthreads();                                             // (s_left: the launch's only barrier outside leave / the WGR exchanges)
 
-    double  b = (has_row && r < m) ? t.M[r * ld + vc] : 0.0;     // RHS entry of my row
+    double  b = has_row ? t.M[r * ld + vc] : 0.0;                // RHS entry of my row
     double2 z = has_pair ? M2[m * ldv + p] : make_double2(0.0, 0.0);   // objective row, my pair
-    int64_t l0 = (has_pair && 2 * p < vc) ? t.p2l[2 * p] : -1;   // logical columns of my pair
+    int64_t l0 = has_pair ? t.p2l[2 * p] : -1;                   // logical columns of my pair
     int64_t l1 = (has_pair && 2 * p + 1 < vc) ? t.p2l[2 * p + 1] : -1;
     int64_t v_cr = -1, v_sl = -1;                                // lane i: pivot row / slot of pivot i
     unsigned wave_rm = 0u, wave_sm = 0u;                         // bit i: SOME lane of my wave is on pivot row i / holds slot i
@@ -373,18 +407,17 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
         dbg_r = t.rhs + 512 + (2 * J + 1) * 72;
 #endif
         // ---- pricing: my pair's candidates -> wave winner -> record -> everybody's winner.
-        // The record also carries the winner's entry of prow_{J-1} and (from its owner) the RHS
-        // entry of prow_{J-1}: what the chain below needs of the row that was stored last.
+        // The record also carries the winner's entry of prow_{J-1}: what the chain below needs of the
+        // row that was stored last.
         ValIdx best; best.v = 0.0; best.i = -1; best.s = 0;
-        if (has_pair && 2 * p < vc)     { ValIdx c = price_cand(z.x * sgn, l0, 2 * p);     best = vi_min(best, c); }
+        if (has_pair)                   { ValIdx c = price_cand(z.x * sgn, l0, 2 * p);     best = vi_min(best, c); }
         if (has_pair && 2 * p + 1 < vc) { ValIdx c = price_cand(z.y * sgn, l1, 2 * p + 1); best = vi_min(best, c); }
         LaMsg e;
-        if (!la_exchange<true, WGR>(best, 0u, t.la_px, nw, w, e_price, max_spins, mute, local, rec_vc, &s_res, e,
-                [&](const ValIdx &c, int src, double &u, double &x2) {
+        if (!la_exchange<true, WGR>(best, 0u, t.la_px, nw, w, e_price, max_spins, mute, local, J == 0, &s_res, e,
+                [&](const ValIdx &c, int src, double &u) {
                     if (J == 0) { u = my_xcc; return; }
                     u = lane_pick((c.s & 1) ? pr.y : pr.x, src);            // prow_{J-1}[winner's slot]
-                    if (wave_has_vc) x2 = lane_value_dyn((vc & 1) ? pr.y : pr.x, g_vc & 63);
-                }, ts_p, dbg_p, false, s_wv, wave_vc)) {
+                }, ts_p, dbg_p, false, s_wv)) {
             if (lane == 0) st_wt(&ctl->status, kSyncLost);       // same word, same value from every wave that gives up
             leave(J);
             return;
@@ -404,14 +437,16 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
             return;
         }
         const int64_t ec = e.c.i, slot = uniform64(e.c.s);
-        // ---- entering column through the pending chain; RHS entry brought up to date
+        // col_J[m] = z[slot]: the winner's key with the sign taken back (sgn is +-1: exact)
+        const double cmj = e.c.v * sgn;
+        const bool bad_m = !(fabs(cmj) <= 1.7976931348623157e308);   // (uniform) as for every entry of the column below
+        // ---- entering column through the pending chain
         double a = has_row ? t.M[r * ld + slot] : 0.0;
         double v_pa = (lane < J - 1) ? ld_l2(&t.bk_prow[(int64_t)lane * ld + slot]) : 0.0;
         double ci_all[KMAX];           // my row's entries of the pending columns: they travel with the loads above
         la_prefetch(ci_all, s_ci, J);
         drain_vmem();                  // the loads -- and what this wave stored in the previous half-step
         if (lane == J - 1) v_pa = e.u;
-        if (J > 0) b = pend(b, false, (my_rm >> (J - 1)) & 1u, s_ci[J - 1][tid], e.w);
         // pending pivots whose given-up slot is the entering column's slot (uniform)
         a = la_chain_col<KMAX>(a, ci_all, v_pa, J, my_rm, (unsigned)__ballot((lane < J) & (v_sl == slot)), wave_rm);
         s_ci[J][tid] = a;
@@ -420,7 +455,7 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
         if (has_row) {
             st_x(&t.bk_col[(int64_t)J * t.bk_stride + r], a, local);
             bad = !(fabs(a) <= 1.7976931348623157e308);
-            if (r < m && ratio_thr < a) {
+            if (ratio_thr < a) {
                 const double qv = b / a;
                 if (qv != qv) bad = 1u;                        // a NaN quotient: decided on the dense path (kNeedDense)
                 else { q.v = qv; q.i = r; q.s = __double_as_longlong(a); }
@@ -429,11 +464,12 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
 #ifdef MI355X_LA_TIMING
         T3 = wall_clock64();
 #endif
-        // ---- ratio test; the record of the objective row's wave carries col_J[m]
+        if (stores_cm) st_x(&t.bk_col[(int64_t)J * t.bk_stride + m], cmj, local);
+        // ---- ratio test; a record carries the RHS entry of its candidate's row
         LaMsg qq;
-        if (!la_exchange<false, WGR>(q, bad, t.la_rx, nw, w, e_ratio, max_spins, mute, local, rec_m, &s_res, qq,
-                [&](const ValIdx &, int, double &u, double &) { if (wave_has_m) u = lane_value_dyn(a, g_m & 63); },
-                ts_r, dbg_r, quit, s_wv, wave_m)) {
+        if (!la_exchange<false, WGR>(q, bad, t.la_rx, nw, w, e_ratio, max_spins, mute, local, false, &s_res, qq,
+                [&](const ValIdx &, int src, double &u) { u = lane_pick(b, src); },
+                ts_r, dbg_r, quit, s_wv)) {
             if (lane == 0) st_wt(&ctl->status, kSyncLost);
             leave(J);
             return;
@@ -441,7 +477,7 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
 #ifdef MI355X_LA_TIMING
         T5 = wall_clock64();
 #endif
-        if (qq.flag != 0u) {                                     // inf / NaN in the column: see kNeedDense
+        if (qq.flag != 0u || bad_m) {                            // inf / NaN in the column: see kNeedDense
             if (leader) ctl->status = kNeedDense;
             leave(J);
             return;
@@ -453,7 +489,10 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
         }
         const int64_t cr = uniform64(qq.c.i);
         const double piv = __longlong_as_double(qq.c.s);
-        const double cmj = qq.w;                                 // col_J[m]
+        // prow_J[vc] = b[cr] / pivot (scale_pair's division); my RHS entry through pivot J right away -- off
+        // the pricing path, operands in registers
+        const double prj_vc = qq.u / piv;
+        b = pend(b, false, has_row && r == cr, a, prj_vc);
         // ---- pivot row through the chain -> prow_J; objective row through pivot J
         double2 y = has_pair ? M2[cr * ldv + p] : make_double2(0.0, 0.0);
         const double v_ccr = (lane < J) ? ld_l2(&t.bk_col[(int64_t)lane * t.bk_stride + cr]) : 0.0;
@@ -473,6 +512,9 @@ __global__ __launch_bounds__(kLaThreads) void k_la_block(TabView t, int ksteps, 
             z.y = pend(z.y, 2 * p + 1 == slot, false, cmj, pr.y);
         }
         s_pi[J][tid] = pr;
+        if (stores_tail)
+            for (int64_t c = 2 * npair + lane; c < ld; c += 64)
+                st_x(&t.bk_prow[(int64_t)J * ld + c], c == vc ? prj_vc : 0.0, local);
         if (own) {                                               // the slot changes hands
             if (2 * p == slot) l0 = leaving; else l1 = leaving;
             st_x(&t.p2l[slot], leaving, local);

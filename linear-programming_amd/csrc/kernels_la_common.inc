@@ -302,8 +302,9 @@ __device__ __forceinline__ int fold_waves(const LaWaveRec *s, Cand &c, unsigned 
 // thread of the workgroup); then, in the FIRST wave only, the workgroup's record: the winner of the
 // four, the winner's own double from the winning wave, the "from" double (PRICE: x2, RATIO: u) from wave
 // wave_from if this workgroup is the one that owns it (from_here).  The other waves' arguments are
-// left as they were.
-template <bool PRICE>
+// left as they were.  OWN_U (k_la_block's RATIO records): the first double is the winner's own, as a PRICE
+// record's, and nothing rides "from" anywhere.
+template <bool PRICE, bool OWN_U = false>
 __device__ __forceinline__ void wg_record(LaWaveRec *s_wv, Cand &c, unsigned &wf, int64_t &cs, double &u, double &x2,
                                           bool from_here, int wave_from)
 {
@@ -314,7 +315,7 @@ __device__ __forceinline__ void wg_record(LaWaveRec *s_wv, Cand &c, unsigned &wf
     const int ww = fold_waves(s_wv, c, wf);
     cs = s_wv[ww].s;
     if (PRICE) { u = s_wv[ww].u; x2 = from_here ? s_wv[wave_from].x2 : 0.0; }
-    else       { u = from_here ? s_wv[wave_from].u : 0.0; x2 = 0.0; }
+    else       { u = OWN_U ? s_wv[ww].u : (from_here ? s_wv[wave_from].u : 0.0); x2 = 0.0; }
 }
 
 // ---- the block's bookkeeping -------------------------------------------------------------------
@@ -328,11 +329,15 @@ __device__ __forceinline__ void wg_record(LaWaveRec *s_wv, Cand &c, unsigned &wf
 // and thread g's OWN mask words, which only it ever writes.  Both slot masks whatever KMAX: a wide
 // sweep ORs the second one in, and a block of <= 16 pivots behind an earlier block of 24 on the same
 // handle must not see that block's bits 16 .. 23.
+__device__ __forceinline__ void la_zero_masks(const TabView &t, int64_t g)
+{
+    if (g < t.bk_stride) t.bk_rmask[g] = 0u;
+    if (g < (t.ld >> 1)) { t.bk_smask[g] = 0u; if (t.bk_smask2) t.bk_smask2[g] = 0u; }
+}
 __device__ __forceinline__ void la_block_begin(const TabView &t, const Ctl &c0, bool leader, int64_t g, unsigned epoch_base)
 {
     if (leader && c0.status != kSyncLost) { t.blk->n_pending = 0; t.blk->stamp = epoch_base; }
-    if (g < t.bk_stride) t.bk_rmask[g] = 0u;
-    if (g < (t.ld >> 1)) { t.bk_smask[g] = 0u; if (t.bk_smask2) t.bk_smask2[g] = 0u; }
+    la_zero_masks(t, g);
 }
 // My entries of the pending columns / rows start out as +0.0: a group of four links that reaches past
 // the last pending pivot then multiplies (+0.0) x (+0.0) for the missing ones -- x - (+0.0) == x bit for

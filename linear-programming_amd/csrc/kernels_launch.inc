@@ -466,6 +466,17 @@ int la_block_workgroups(const TabView &t)
     return (int)((need + kLaThreads - 1) / kLaThreads);
 }
 
+// The workgroups k_la_block is LAUNCHED with: a thread per constraint row and per pair that holds a non-RHS
+// column (the objective row and the RHS column have no owner there).  What follows the launch follows this
+// count -- the sweeps' and the rollback's la_nw, BlockCtl::done, one-XCD mode, records per wave or per workgroup;
+// which tableaux take the persistent look-ahead and every block-size decision stay on la_block_workgroups().
+int la_launch_workgroups(const TabView &t)
+{
+    const int64_t m = t.rows - 1, npair = t.cols >> 1;         // (ceil(vc / 2), vc = cols - 1)
+    const int64_t need = m > npair ? m : npair;
+    return need > 0 ? (int)((need + kLaThreads - 1) / kLaThreads) : 1;
+}
+
 void launch_la_rollback(const TabView &t, int la_nw, hipStream_t s)
 {
     hipLaunchKernelGGL(k_la_rollback, dim3(1), dim3(1), 0, s, t, la_nw);
@@ -506,7 +517,7 @@ void launch_shard_la_rollback(const TabView &t, int la_nw, hipStream_t s)
 // form: the block size that picks the kernel (<= 16: the 16-step look-ahead, above: the 24-step one)
 void launch_la_block_form(const TabView &t, int form, int ksteps, int is_max, double f, unsigned epoch_base, hipStream_t s)
 {
-    const int nw = la_block_workgroups(t);
+    const int nw = la_launch_workgroups(t);
     // one-XCD mode: 8 x nw blocks, every eighth takes part (the kernel verifies where they run); more than
     // kLaWaveRecordsMaxNw workgroups: records per workgroup, spread over the chip (an XCD has 32 CUs)
     const bool wgr = nw > kLaWaveRecordsMaxNw;

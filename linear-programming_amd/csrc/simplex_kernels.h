@@ -203,6 +203,7 @@ int  sweep_kind(int kmax);                 // 2 wide pair, 1 k_sweep16, 0 k_swee
 // of the pivots the leader committed but the sweep did not apply
 void launch_la_rollback(const TabView &t, int la_nw, hipStream_t s);
 int  la_block_workgroups(const TabView &t);
+int  la_launch_workgroups(const TabView &t);
 // the whole look-ahead of a block (steps 0 .. ksteps-1) as ONE launch of a few persistent
 // workgroups that exchange their reduction candidates through la_px / la_rx; epoch_base (> 0)
 // must grow by at least 2*kMaxBlock+2 from launch to launch on the same tableau (the records

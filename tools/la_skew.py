@@ -21,7 +21,7 @@ L.mi355x_tab_sync(h, ctypes.byref(npv))
 N = 512 + 32 * 72
 buf = np.zeros(N)
 L.mi355x_debug_rhs(h, buf.ctypes.data_as(ctypes.c_void_p), N, 0)
-d = buf[512:].reshape(32, 72)[:, :68] * 0.01          # us
+d = buf[512:].reshape(32, 72)[:, :64] * 0.01          # us (config 3: 16 workgroups, 64 records)
 t0 = d.min()
 print("exchange (step, kind): first publish (us since block start) | spread last-first | median-first | 5 latest records (wave index: delay)")
 prev_last = None
