@@ -620,6 +620,38 @@ int  mi355x_multibatch_solve_two_phase(mi355x_multibatch *art, mi355x_multibatch
                                        double fp_factor, int32_t *status, int64_t *n_pivots);
 int  mi355x_multibatch_cancel(mi355x_multibatch *mb);
 void mi355x_multibatch_destroy(mi355x_multibatch *mb);
+/* build-tableau (src/simplex.lisp:243-328) of n_lps problems of one shape, written on the device(s): batches
+ * straight from the problems' rows, with no dense tableau built or uploaded by the host (opt-in; what
+ * mi355x_xbatch_create_lps is for the exact batches, in doubles).  Member q is given in column space, as
+ * build-tableau holds it after :189-241 and before :243, at lps + q * (m + 1) * (ncv + 1): rows 0 .. m-1 are the
+ * ncv structural coefficients and, last, the right-hand side with the offsets already subtracted; row m is the
+ * objective row as :270-283 stores it, the signs applied, the constant last.  sense (n_lps x m): 0 `<=`, 1 `>=`,
+ * 2 `=`.  Every entry and every basis entry the members start from is what mi355x_build_tableau produces, bit for
+ * bit, the sign of zero included: a row whose right-hand side is < 0.0 negated and its sense flipped (:243-252;
+ * not -0.0, not NaN), slack columns in row order for the rows that are not `=` (:254-265; the other slack
+ * columns of a negated row hold -0.0), artificial columns in decreasing row order (:257, :261, :296-300), the
+ * artificial objective row summed in increasing row order from 0.0 (:302-316).  *out_main is a batch of
+ * (m + 1) x (ncv + n_slack + 1) members whose basis entry is the number of columns on an artificial row;
+ * *out_art is NULL when no row is artificial (solve *out_main), else the batch of artificial tableaux with n_art
+ * more columns (phase 1 on *out_art, mi355x_multibatch_two_phase_handover, phase 2 on *out_main, or
+ * mi355x_multibatch_solve_two_phase).  Both are ordinary handles in the state mi355x_*batch_create leaves: every
+ * solve, hand-over, download, cancel and destroy entry serves them.  The multibatch form splits the members as
+ * mi355x_multibatch_create does and sends each sub-batch's rows to its device.  MI_BAD_ARG (before any device is
+ * looked for; the message names the member) for a NULL array, m < 1, ncv < 1, a sense outside 0 .. 2, and
+ * members that differ in their number of `=` rows or of artificial rows -- a row is artificial when it is `=`
+ * or, after the flip, `>=`. */
+int  mi355x_batch_create_lps(mi355x_batch **out_main, mi355x_batch **out_art,
+                             int64_t n_lps, int64_t m, int64_t ncv,
+                             const double *lps, const int32_t *sense, int device);
+int  mi355x_multibatch_create_lps(mi355x_multibatch **out_main, mi355x_multibatch **out_art,
+                                  int64_t n_lps, int64_t m, int64_t ncv,
+                                  const double *lps, const int32_t *sense,
+                                  int n_devices, const int *device_ids);
+/* All that tableau-objective-value, tableau-variable and tableau-reduced-cost read (src/simplex.lisp:74-120) of
+ * every member, gathered on the device and fetched with one copy per sub-batch: last_rows n_lps x cols, last_cols
+ * n_lps x rows, bases n_lps x (rows - 1), by the global member index; each may be NULL. */
+int  mi355x_batch_readback(mi355x_batch *b, double *last_rows, double *last_cols, int64_t *bases);
+int  mi355x_multibatch_readback(mi355x_multibatch *mb, double *last_rows, double *last_cols, int64_t *bases);
 
 /* ---- column-partitioned tableau: per-shard steps (BASELINE config 5) --------------- */
 /* One tableau whose non-RHS columns are split across shards (one shard = one handle = one

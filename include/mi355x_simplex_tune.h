@@ -181,6 +181,14 @@ int         mi355x_debug_rhs(mi355x_tab *t, double *out, int64_t n, int clear);
 int         mi355x_debug_last_wait(double *out2);            /* host microseconds of the last status read-back:
                                                                 [0] launching k_ctl_publish, [1] polling its
                                                                 sequence number (bench.py's steady-state leg)   */
+/* test aid: member lp_index of a dense batch as it is STORED, padding columns included -- one 2-D copy of
+ * rows x ld doubles; *ld (may be NULL) = the leading dimension; out NULL: only *ld.  What a create entry left
+ * in the columns [cols, ld) (mi355x_batch_create_lps writes them itself). */
+int         mi355x_batch_debug_stored(mi355x_batch *b, int64_t lp_index, double *out, int64_t *ld);
+/* measurement aid: enable != 0 brackets the assembly kernels (k_blp_rows, k_blp_assemble, k_blp_art_objective) of
+ * every sub-batch mi355x_*batch_create_lps builds from now on with HIP events; every call returns the device
+ * milliseconds and the sub-batches counted since the previous call (either may be NULL) and starts over. */
+int         mi355x_batch_lps_timing(int enable, double *sum_ms, int64_t *n_sub_batches);
 
 /* ---- branch-and-bound: device assembly of node tableaux (k_bb_assemble) ------------------------ */
 /* n_nodes nodes of one depth of problem p's search -- node q's rows (var, sense 0 `<=` / 1 `>=`, bound)

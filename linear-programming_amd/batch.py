@@ -13,6 +13,30 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _lps_arrays(lps, sense):
+    """The members of one group as create_lps takes them: lps n x (m + 1) x (ncv + 1) float64, sense n x m int32;
+    -> (lps, sense, n, m, ncv, columns of the main tableau, artificial rows)."""
+    L = np.ascontiguousarray(lps, dtype=np.float64)
+    S = np.ascontiguousarray(sense, dtype=np.int32)
+    if L.ndim != 3 or S.shape != (L.shape[0], L.shape[1] - 1):
+        raise ValueError("lps must be n x (m + 1) x (ncv + 1) and sense n x m")
+    n, m, ncv = L.shape[0], L.shape[1] - 1, L.shape[2] - 1
+    n_eq = n_art = 0
+    if n and m > 0:                                      # (from member 0; the library checks that all agree)
+        flip = L[0, :m, ncv] < 0.0
+        op = np.where(S[0] == 2, 2, np.where(flip, 1 - S[0], S[0]))
+        n_eq, n_art = int((S[0] == 2).sum()), int((op != 0).sum())
+    return L, S, n, m, ncv, ncv + (m - n_eq) + 1, n_art
+
+
+def _readback(call, h, n_lps, rows, cols, where):
+    row = np.empty((n_lps, cols), dtype=np.float64)
+    col = np.empty((n_lps, rows), dtype=np.float64)
+    bas = np.empty((n_lps, rows - 1), dtype=np.int64)
+    capi.check(call(h, _ptr(row), _ptr(col), _ptr(bas)), where)
+    return row, col, bas
+
+
 class TableauBatch:
     def __init__(self, handle, n_lps, rows, cols):
         self._h, self.n_lps, self.rows, self.cols = handle, int(n_lps), int(rows), int(cols)
@@ -38,6 +62,21 @@ class TableauBatch:
                                                             _ptr(seeds), device),
                    "mi355x_batch_create_synthetic")
         return cls(h, n_lps, n_cons + 1, n_vars + n_cons + 1)
+
+    @classmethod
+    def from_lps(cls, lps, sense, device=0):
+        """The members' tableaux built on the device from their rows (mi355x_batch_create_lps; batch_lps.py):
+        -> (main batch, batch of artificial tableaux or None)."""
+        L, S, n, m, ncv, cols, n_art = _lps_arrays(lps, sense)
+        hm, ha = ctypes.c_void_p(), ctypes.c_void_p()
+        capi.check(capi.lib().mi355x_batch_create_lps(ctypes.byref(hm), ctypes.byref(ha), n, m, ncv, _ptr(L), _ptr(S),
+                                                      device), "mi355x_batch_create_lps")
+        return cls(hm, n, m + 1, cols), (cls(ha, n, m + 1, cols + n_art) if ha else None)
+
+    def readback(self):
+        """(last rows n x cols, last columns n x rows, bases n x (rows - 1)) of all members in one copy."""
+        return _readback(capi.lib().mi355x_batch_readback, self._h, self.n_lps, self.rows, self.cols,
+                         "mi355x_batch_readback")
 
     def solve(self, is_max=True, fp_tolerance=1024, max_pivots=0):
         """Returns (status int32[n_lps], n_pivots int64[n_lps])."""
@@ -121,6 +160,24 @@ class MultiDeviceBatch:
                                                                  int(n_devices), devs),
                    "mi355x_multibatch_create_synthetic")
         return cls(h, n_lps, n_cons + 1, n_vars + n_cons + 1)
+
+    @classmethod
+    def from_lps(cls, lps, sense, n_devices, device_ids=None):
+        """The members' tableaux built on the devices from their rows (mi355x_multibatch_create_lps; batch_lps.py):
+        lps n x (m + 1) x (ncv + 1), sense n x m -> (main batch, batch of artificial tableaux or None)."""
+        L, S, n, m, ncv, cols, n_art = _lps_arrays(lps, sense)
+        keep, devs = cls._devs(device_ids)
+        hm, ha = ctypes.c_void_p(), ctypes.c_void_p()
+        capi.check(capi.lib().mi355x_multibatch_create_lps(ctypes.byref(hm), ctypes.byref(ha), n, m, ncv, _ptr(L),
+                                                           _ptr(S), int(n_devices), devs),
+                   "mi355x_multibatch_create_lps")
+        return cls(hm, n, m + 1, cols), (cls(ha, n, m + 1, cols + n_art) if ha else None)
+
+    def readback(self):
+        """(last rows n x cols, last columns n x rows, bases n x (rows - 1)) of all members: one copy per
+        sub-batch (mi355x_multibatch_readback)."""
+        return _readback(capi.lib().mi355x_multibatch_readback, self._h, self.n_lps, self.rows, self.cols,
+                         "mi355x_multibatch_readback")
 
     def info(self):
         a, b = ctypes.c_int(0), ctypes.c_int(0)

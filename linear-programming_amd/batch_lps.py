@@ -1,0 +1,212 @@
+"""Double-precision batches built on the device (opt-in: ``mi355x_solve_problems(ps, from_rows=True)``, and the
+array front end ``solve_lps``).
+
+The default list route builds every member's tableau on the host -- build_tableau, a dense [A | I | b] matrix
+per member and its artificial twin for a two-phase member -- stacks them and uploads them all.  Here a problem
+is only *lowered*: the steps of build-tableau that need the problem's names (src/simplex.lisp:189-241, :270-283:
+var-mappings, bound rows, offsets, the objective row's signs) leave one row of doubles per constraint, in column
+space, and everything after that -- the flip of a negative right-hand side, slack and artificial columns, both
+bases, the artificial objective row (:243-328) -- is k_blp_rows / k_blp_assemble / k_blp_art_objective on the
+device (mi355x_multibatch_create_lps, csrc/kernels_batch_lps.inc).  What a batch starts from is what
+build_tableau produces, bit for bit, so are the pivot sequences and every result.  The exact batches have the
+same entry in exact_lps.py.
+"""
+from collections import namedtuple
+
+import numpy as np
+
+from . import capi
+from .batch import MultiDeviceBatch
+
+SENSES = {"<=": 0, ">=": 1, "=": 2}
+
+LoweredRows = namedtuple("LoweredRows", "L sense mapping is_max")
+
+
+def host_reason(problem):
+    """Why a problem stays on the default route (None: lower_problem_rows takes it)."""
+    if problem.integer_vars:
+        return "integer variables"
+    if not problem.constraints:
+        return "no constraints"
+    if any(op not in SENSES for op, _, _ in problem.constraints):
+        return "constraint"
+    return None
+
+
+def lower_problem_rows(problem):
+    """build_tableau's steps :189-241 and :270-283 without a dense tableau: (L, sense, mapping, is_max) with L a
+    float64 array (m + 1) x (ncv + 1) -- per constraint the structural coefficients and the right-hand side less
+    the offsets, then the objective row with its signs applied and its constant -- sense an int32 array (0 `<=`,
+    1 `>=`, 2 `=`), mapping build_tableau's var_mapping.  The statements are build_tableau's, in its order:
+    float() of every number, a coefficient assigned (a later term of the same variable replaces an earlier one),
+    the right-hand side float(rhs) less float(coef) * offset per term, the constant plus the same products.  None
+    for what stays on the default route (host_reason)."""
+    if host_reason(problem) is not None:
+        return None
+    f = float
+    constraints = [(op, list(expr), rhs) for op, expr, rhs in problem.constraints]
+    bounds = dict(problem.var_bounds)
+    mappings, column = {}, 0
+    for var in problem.vars:                                              # :189-212
+        if var not in bounds:
+            mappings[var] = ("positive", column, 0.0)
+        else:
+            lb, ub = bounds[var]
+            if lb is not None and ub is not None:
+                if 0 <= ub:
+                    constraints.insert(0, ("<=", [(var, 1)], ub))
+                else:
+                    constraints.insert(0, (">=", [(var, 1)], -ub))
+                mappings[var] = ("positive", column, f(lb))
+            elif lb is not None:
+                mappings[var] = ("positive", column, f(lb))
+            elif ub is not None:
+                mappings[var] = ("negative", column, f(ub))
+            else:
+                mappings[var] = ("signed", column)
+                column += 1
+        column += 1
+    ncv, m = column, len(constraints)
+    L = np.zeros((m + 1, ncv + 1))
+    sense = np.empty(m, dtype=np.int32)
+    for row, (op, expr, rhs) in enumerate(constraints):                   # :223-241
+        sense[row] = SENSES[op]
+        L[row, ncv] = f(rhs)
+        for var, coef in expr:
+            mp = mappings[var]
+            if mp[0] == "positive":
+                L[row, mp[1]] = f(coef)
+                L[row, ncv] -= f(coef) * mp[2]
+            elif mp[0] == "negative":
+                L[row, mp[1]] = -f(coef)
+                L[row, ncv] -= f(coef) * mp[2]
+            else:
+                L[row, mp[1]] = f(coef)
+                L[row, mp[1] + 1] = -f(coef)
+    for var, coef in problem.objective_func:                              # :270-283
+        mp = mappings[var]
+        if mp[0] == "positive":
+            L[m, mp[1]] = -f(coef)
+            L[m, ncv] += f(coef) * mp[2]
+        elif mp[0] == "negative":
+            L[m, mp[1]] = f(coef)
+            L[m, ncv] += f(coef) * mp[2]
+        else:
+            L[m, mp[1]] = -f(coef)
+            L[m, mp[1] + 1] = f(coef)
+    return LoweredRows(L, sense, mappings, problem.type == "max")
+
+
+def row_counts(L, sense):
+    """(`=` rows, artificial rows, negated rows) per member of L (... x (m + 1) x (ncv + 1)) and sense (... x m): a
+    row is negated when its right-hand side is < 0.0 (:243-252; not -0.0, not NaN), and artificial when it is
+    `=` or, after the flip, `>=`."""
+    flip = L[..., :-1, -1] < 0.0
+    op = np.where(sense == 2, 2, np.where(flip, 1 - sense, sense))
+    return (sense == 2).sum(axis=-1), (op != 0).sum(axis=-1), flip.sum(axis=-1)
+
+
+def group_lowered_rows(problems):
+    """The grouping of mi355x_solve_problems(from_rows=True), host only: (host, groups).  host {k: why the member
+    goes through the default route} -- host_reason's words, "basis" for a single-phase member the default
+    route solves alone as well (a negated row leaves -0.0 in the other rows' slack columns: not the unit basis
+    its batches start from, simplex._unit_basis), "alone" for a member alone in its group; groups {(m, ncv, `=`
+    rows, artificial rows, is_max): [(k, LoweredRows)]}, each of two or more members."""
+    host, groups = {}, {}
+    for k, p in enumerate(problems):
+        low = lower_problem_rows(p)
+        if low is None:
+            host[k] = host_reason(p)
+            continue
+        m, ncv = low.L.shape[0] - 1, low.L.shape[1] - 1
+        n_eq, n_art, n_flip = (int(x) for x in row_counts(low.L, low.sense))
+        if n_art == 0 and n_flip > 0 and m > 1:
+            host[k] = "basis"
+            continue
+        groups.setdefault((m, ncv, n_eq, n_art, low.is_max), []).append((k, low))
+    for key in [key for key, members in groups.items() if len(members) == 1]:
+        host[groups.pop(key)[0][0]] = "alone"
+    return host, groups
+
+
+def _batch_in_chunks(mb, is_max, rows, cols, fp_tolerance, max_pivots):
+    """The glue's `multibatch-solve-in-chunks` (as in mi355x_solve_problems): bounded calls until no member is
+    left at MI_MAX_PIVOTS (or max_pivots are used up); -> (statuses, pivots per member)."""
+    from .simplex import chunk_pivots
+    chunk, done = chunk_pivots(rows, cols), 0
+    total = np.zeros(mb.n_lps, dtype=np.int64)
+    while True:
+        cap = min(chunk, max_pivots - done) if max_pivots > 0 else chunk
+        st, npv = mb.solve(is_max=is_max, fp_tolerance=fp_tolerance, max_pivots=cap)
+        total += npv
+        done += cap
+        if (max_pivots > 0 and done >= max_pivots) or not (st == capi.MI_MAX_PIVOTS).any():
+            return st, total
+
+
+def solve_batches(main, art, is_max, fp_tolerance=1024, max_pivots=0):
+    """A created group in bounded calls, exactly as mi355x_solve_problems solves its host-built groups: single
+    phase (art None), or phase 1 on the artificial batch, the per-member step between the phases
+    (mi355x_multibatch_two_phase_handover) and phase 2 on the main batch; max_pivots caps every phase.
+    -> (status per member, pivots per member: n, or n x 2 for a two-phase group)."""
+    if art is None:
+        return _batch_in_chunks(main, is_max, main.rows, main.cols, fp_tolerance, max_pivots)
+    st1, np1 = _batch_in_chunks(art, False, art.rows, art.cols, fp_tolerance, max_pivots)
+    between, nd = art.two_phase_handover(main, fp_tolerance=fp_tolerance, phase1_status=st1)
+    st2, np2 = _batch_in_chunks(main, is_max, art.rows, art.cols, fp_tolerance, max_pivots)
+    return np.where(between == capi.MI_OK, st2, between).astype(np.int32), np.stack([np1 + nd, np2], axis=1)
+
+
+def solve_group(problems, lowered, fp_tolerance=1024, device=0, devices=1, max_pivots=0):
+    """One group of group_lowered_rows: per member the solved (main) Tableau the default route returns -- matrix,
+    basis, n_pivots, var_mapping -- or the exception of its outcome."""
+    from .conditions import SolverError
+    from .simplex import Tableau, _raise_for
+    main, art = MultiDeviceBatch.from_lps(np.stack([l.L for l in lowered]), np.stack([l.sense for l in lowered]),
+                                          n_devices=devices)
+    st, npv = solve_batches(main, art, lowered[0].is_max, fp_tolerance, max_pivots)
+    out = []
+    for q, (p, low) in enumerate(zip(problems, lowered)):
+        try:
+            _raise_for(int(st[q]))
+        except SolverError as e:
+            out.append(e)
+            continue
+        G, gb = main.download(q)
+        t = Tableau(p, p, G, gb, main.cols - 1, main.rows - 1, low.mapping, fp_tolerance, device)
+        t.n_pivots = (int(npv[q, 0]), int(npv[q, 1])) if art is not None else int(npv[q])
+        out.append(t)
+    return out
+
+
+def solve_problems_from_rows(problems, host_route, fp_tolerance=1024, device=0, devices=1, max_pivots=0):
+    """mi355x_solve_problems(from_rows=True) less its last step: the list of results (a solved Tableau or the
+    member's exception).  host_route(problem) -> that member's result by the default route; it gets the members
+    group_lowered_rows names, one by one."""
+    results = [None] * len(problems)
+    host, groups = group_lowered_rows(problems)
+    for members in groups.values():
+        ks = [k for k, _ in members]
+        for k, r in zip(ks, solve_group([problems[k] for k in ks], [l for _, l in members], fp_tolerance, device,
+                                        devices, max_pivots)):
+            results[k] = r
+    for k in sorted(host):
+        results[k] = host_route(problems[k])
+    return results
+
+
+# ------------------------------------------------------------------ the array front end
+def solve_lps(lps, sense, is_max=True, fp_tolerance=1024, devices=1, max_pivots=0):
+    """One group given as arrays -- lps n x (m + 1) x (ncv + 1) float64 in column space (per member m rows of ncv
+    coefficients and the right-hand side, then the objective row as build-tableau stores it: -c for max / min
+    c . x over x >= 0, the constant last), sense n x m (0 `<=`, 1 `>=`, 2 `=`), every member with the same numbers
+    of `=` and of artificial rows: mi355x_multibatch_create_lps, the bounded solve calls of solve_batches and ONE
+    read-back.  No Python runs per entry and no matrix comes back.  -> (statuses n, pivots n or n x 2 for a
+    two-phase group, last rows n x cols, last columns n x rows, bases n x m): the objective value of member q is
+    last_rows[q, -1], the value of column j last_cols[q, i] where bases[q, i] == j (0 otherwise), its reduced
+    cost last_rows[q, j].  A member that did not end MI_OPTIMAL has no meaningful values."""
+    main, art = MultiDeviceBatch.from_lps(lps, sense, n_devices=devices)
+    st, npv = solve_batches(main, art, is_max, fp_tolerance, max_pivots)
+    last_rows, last_cols, bases = main.readback()
+    return st, npv, last_rows, last_cols, bases

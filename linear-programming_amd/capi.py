@@ -137,6 +137,10 @@ SIGNATURES = {
     "mi355x_multibatch_two_phase_handover": (_int, [_p, _p, _dbl, _p, _p, _p]),
     "mi355x_multibatch_cancel": (_int, [_p]),
     "mi355x_multibatch_destroy": (None, [_p]),
+    "mi355x_batch_create_lps": (_int, [_pp, _pp, _i64, _i64, _i64, _p, _p, _int]),
+    "mi355x_multibatch_create_lps": (_int, [_pp, _pp, _i64, _i64, _i64, _p, _p, _int, _p]),
+    "mi355x_batch_readback": (_int, [_p, _p, _p, _p]),
+    "mi355x_multibatch_readback": (_int, [_p, _p, _p, _p]),
     "mi355x_shard_set_compact": (_int, [_p, _i64, _p]),
     "mi355x_shard_columns": (_int, [_p, _p]),
     "mi355x_shard_price": (_int, [_p, _int, _i64, _p]),
@@ -196,6 +200,8 @@ _EXTRA = {
     "mi355x_tab_timing_read_kind": (_int, [_p, _int, _p, _p, _p]),
     "mi355x_debug_rhs": (_int, [_p, _p, _i64, _int]),
     "mi355x_debug_last_wait": (_int, [_p]),
+    "mi355x_batch_debug_stored": (_int, [_p, _i64, _p, _p]),
+    "mi355x_batch_lps_timing": (_int, [_int, _p, _p]),
     "mi355x_debug_repeat_sweep": (_int, [_p, _int, _p]),
     "mi355x_tune_variant_count": (_int, []),
     "mi355x_tune_variant_name": (ctypes.c_char_p, [_int]),

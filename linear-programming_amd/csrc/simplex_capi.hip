@@ -199,6 +199,7 @@ struct mi355x_multibatch {
 #include "capi_exact_batch.inc"  // mi355x_xbatch_*: batches of exact LPs, one workgroup per member
 #include "capi_exact_bb.inc"   // mi355x_xbb_base_*, mi355x_xbatch_create_nodes / _readback: exact branch-and-bound
 #include "capi_exact_lps.inc"  // mi355x_xbatch_create_lps: exact batches built from problem rows on the device
+#include "capi_batch_lps.inc"  // mi355x_*batch_create_lps, mi355x_*batch_readback: f64 batches built from problem rows on the device
 #include "capi_shard.inc"      // mi355x_shard_*
 #include "capi_colpart.inc"    // mi355x_colpart_*, mi355x_rccl_unique_id
 #include "capi_tune.inc"       // mi355x_tune_*, mi355x_debug_*

@@ -453,6 +453,17 @@ struct XbLpsView {
 // basis and D; status kXOverflow for a tableau that does not fit the view's width
 void launch_xb_assemble_lps(const XbView &mt, const XbView &at, const XbLpsView &sp, int64_t q0, int64_t count, hipStream_t s);
 size_t xb_assemble_lps_lds(int64_t m);                                      // its dynamic LDS in bytes
+// Double-precision batches built from problem rows (kernels_batch_lps.inc, capi_batch_lps.inc): the members of a
+// group in column space, member q's (m + 1) x (ncv + 1) doubles at q * (m + 1) * (ncv + 1).
+struct BatchLpsView {
+    const double  *L;                 // rows 0 .. m-1: ncv coefficients and the right-hand side; row m: the objective row
+    const int32_t *sense;             // (member, row) at member * m + row: 0 `<=`, 1 `>=`, 2 `=`
+    int64_t        m, ncv, n_slack, n_art;   // n_slack rows are not `=`; n_art rows end up `>=` or `=` (every member)
+};
+// every member of mt (and of at, a view whose M is NULL is left out): tableau and basis; scratch: 3 * m int32 per member
+void launch_batch_lps_assemble(const TabView &mt, const TabView &at, const BatchLpsView &sp, int32_t *scratch, hipStream_t s);
+// per member of a dense batch: last row (cols), last column (rows), basis (rows - 1), each plane member-major (device pointers)
+void launch_batch_readback(const TabView &t, double *last_rows, double *last_cols, int64_t *bases, hipStream_t s);
 #ifdef MI355X_TEST_HOOKS
 // test build: one arithmetic primitive of kernels_exact.inc applied element-wise (k_x_arith_probe; the
 // opcodes and the limb layout are mi355x_test_xarith's, include/mi355x_simplex_tune.h).  Device pointers.

@@ -74,6 +74,7 @@
 //     kernels_exact_batch.inc     batches of exact LPs, one workgroup per LP (k_xb_solve, k_xb_between)
 //     kernels_exact_bb.inc        exact branch-and-bound: integer node tableaux, light read-back (k_xbb_*)
 //     kernels_exact_lps.inc       exact batches built from problem rows on the device (k_xb_assemble_lps)
+//     kernels_batch_lps.inc       double-precision batches built from problem rows (k_blp_*), k_batch_readback
 //     kernels_launch.inc          host-side launchers, tuning state
 #include "simplex_kernels.h"
 #include <type_traits>
@@ -96,6 +97,7 @@ namespace mi355x {
 #include "kernels_exact_batch.inc"
 #include "kernels_exact_bb.inc"
 #include "kernels_exact_lps.inc"
+#include "kernels_batch_lps.inc"
 #include "kernels_launch.inc"
 
 }  // namespace mi355x

@@ -707,7 +707,8 @@ simplex_solver = mi355x_simplex_solver
 
 
 def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_pivots=0, errorp=True, native=False,
-                          exact=False, exact_bits=0, exact_max_bits=128, pivot_rule="dantzig", device_build=False):
+                          exact=False, exact_bits=0, exact_max_bits=128, pivot_rule="dantzig", device_build=False,
+                          from_rows=False):
     """The glue's `mi355x-solve-problems`: a LIST of problems -> the list of their solved tableaus,
     what [solve_problem(p) for p in problems] returns, with the independent LPs side by side on the
     GPU(s).  Single-phase problems are grouped by tableau shape and sense; a group of two or more
@@ -733,6 +734,14 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
     device_build=True (opt-in, with exact=True only -- an argument error otherwise): the exact members' tableaux are
     built on the device from their rows (exact_lps.py: mi355x_xbatch_create_lps) instead of on the host; the
     results are the same, member for member.
+    from_rows=True (opt-in, double precision only -- with exact=True an argument error that points to device_build,
+    as is native="many", which builds its members in the library): the members are only lowered to their rows
+    (batch_lps.py: lower_problem_rows) and the groups' tableaux are built on the device
+    (mi355x_multibatch_create_lps) instead of on the host and uploaded; groups are formed by (constraints,
+    structural columns, `=` rows, artificial rows, sense) and solved in the same bounded chunks, and every member
+    comes back as the Tableau the default route returns.  Integer problems, problems without constraints, members
+    alone in their group and single-phase members the default route solves alone go through the default route
+    one by one.
     pivot_rule: as for mi355x_simplex_solver, for every batch and every member solved alone; an unknown name
     and a rule other than "dantzig" with exact=False are argument errors, and a member with a float declines
     such a rule (its condition takes its slot when errorp is False)."""
@@ -742,6 +751,11 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
                          % (pivot_rule,))
     if device_build and not exact:
         raise ValueError("device_build=True needs exact=True: it builds the tableaux of the exact batches")
+    if from_rows and exact:
+        raise ValueError("from_rows=True builds the double-precision batches; with exact=True it is device_build=True "
+                         "that builds the tableaux on the device")
+    if from_rows and native == "many":
+        raise ValueError("from_rows=True does not go with native=\"many\": that route builds its members in the library")
     if exact:
         from .exact import solve_problems_exact
         kw = {"device_build": True} if device_build else {}               # (the default: the call as it was)
@@ -754,6 +768,19 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
         # back as NativeSolution objects (the glue's :native :many)
         from .native import solve_many
         results = solve_many(problems, fp_tolerance=fp_tolerance, devices=devices, max_pivots=max_pivots)
+        if errorp:
+            for r in results:
+                if isinstance(r, Exception):
+                    raise r
+        return results
+    if from_rows:
+        from .batch_lps import solve_problems_from_rows
+
+        def host_route(p):
+            return mi355x_solve_problems([p], fp_tolerance=fp_tolerance, device=device, devices=devices,
+                                         max_pivots=max_pivots, errorp=False, native=native)[0]
+        results = solve_problems_from_rows(problems, host_route, fp_tolerance=fp_tolerance, device=device,
+                                           devices=devices, max_pivots=max_pivots)
         if errorp:
             for r in results:
                 if isinstance(r, Exception):
