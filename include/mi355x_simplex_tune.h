@@ -185,6 +185,11 @@ int         mi355x_debug_last_wait(double *out2);            /* host microsecond
  * rows x ld doubles; *ld (may be NULL) = the leading dimension; out NULL: only *ld.  What a create entry left
  * in the columns [cols, ld) (mi355x_batch_create_lps writes them itself). */
 int         mi355x_batch_debug_stored(mi355x_batch *b, int64_t lp_index, double *out, int64_t *ld);
+/* Which driver mi355x_batch_solve ran on this batch so far, launches by class (the batch counterpart of
+ * mi355x_tab_path_counts): out4[0] resident launches (k_resident, every LP on chip), [1] blocks of the split
+ * form (a k_batch_block look-ahead per LP + ONE sweep over all LPs), [2] one-workgroup-per-LP launches
+ * (k_batch_block, or k_batch_solve without blocking), [3] lockstep (select, update) launch pairs. */
+int         mi355x_batch_path_counts(const mi355x_batch *b, int64_t *out4);
 /* measurement aid: enable != 0 brackets the assembly kernels (k_blp_rows, k_blp_assemble, k_blp_art_objective) of
  * every sub-batch mi355x_*batch_create_lps builds from now on with HIP events; every call returns the device
  * milliseconds and the sub-batches counted since the previous call (either may be NULL) and starts over. */

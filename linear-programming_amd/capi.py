@@ -201,6 +201,7 @@ _EXTRA = {
     "mi355x_debug_rhs": (_int, [_p, _p, _i64, _int]),
     "mi355x_debug_last_wait": (_int, [_p]),
     "mi355x_batch_debug_stored": (_int, [_p, _i64, _p, _p]),
+    "mi355x_batch_path_counts": (_int, [_p, _p]),
     "mi355x_batch_lps_timing": (_int, [_int, _p, _p]),
     "mi355x_debug_repeat_sweep": (_int, [_p, _int, _p]),
     "mi355x_tune_variant_count": (_int, []),

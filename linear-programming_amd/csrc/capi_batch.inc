@@ -121,8 +121,10 @@ int mi355x_batch_solve(mi355x_batch *b, int is_max, double f, int64_t max_pivots
         bool split_ok = true;
         int64_t blocks = 2;
         for (;;) {
-            for (int64_t i = 0; i < blocks && split_ok; ++i)
+            for (int64_t i = 0; i < blocks && split_ok; ++i) {
                 split_ok = launch_batch_block_split(t->c, is_max, f, t->stream);
+                if (split_ok) t->batch_counts[0]++;
+            }
             if (!split_ok) break;
             HIP_TRY(hipGetLastError());
             { const int rc_ = read_ctls(t, n); if (rc_ != MI_OK) return rc_; }
@@ -154,7 +156,7 @@ int mi355x_batch_solve(mi355x_batch *b, int is_max, double f, int64_t max_pivots
     }
     const bool want_persistent = t->tn.batch_mode != 1;
     bool persistent = want_persistent && launch_batch_solve(cur(t), is_max, f, t->stream);
-    if (persistent) t->n_part = 0;
+    if (persistent) { t->n_part = 0; t->batch_counts[1]++; }
     if (!persistent) enqueue_select(t, is_max, f);
     int64_t chunk = 16;
     for (;;) {
@@ -175,6 +177,7 @@ int mi355x_batch_solve(mi355x_batch *b, int is_max, double f, int64_t max_pivots
                 return batch_report(t, status, n_pivots, MI_CANCELLED);
             }
             if (!launch_batch_solve(cur(t), is_max, f, t->stream)) return fail(MI_HIP_ERROR, "batch relaunch failed");
+            t->batch_counts[1]++;
             continue;
         }
         for (int64_t i = 0; i < chunk; ++i) {
@@ -182,6 +185,7 @@ int mi355x_batch_solve(mi355x_batch *b, int is_max, double f, int64_t max_pivots
             if (rc != MI_OK) return rc;
             enqueue_select(t, is_max, f);
         }
+        t->batch_counts[2] += chunk;
         HIP_TRY(hipGetLastError());
         { const int rc_ = read_ctls(t, n); if (rc_ != MI_OK) return rc_; }
         bool running = false, need_dense = false;

@@ -102,6 +102,16 @@ int         mi355x_tab_path_counts(const mi355x_tab *t, int64_t *out8)
     for (int i = 0; i < 8; ++i) out8[i] = t->path_counts[i];
     return MI_OK;
 }
+// which driver mi355x_batch_solve ran on this batch so far: [0] resident launches, [1] blocks of the split
+// form (k_batch_block look-ahead per LP + one k_sweep over all LPs), [2] one-workgroup-per-LP launches
+// (k_batch_block / k_batch_solve), [3] lockstep (select, update) launch pairs
+int         mi355x_batch_path_counts(const mi355x_batch *b, int64_t *out4)
+{
+    if (!b || !b->t || !out4) return MI_BAD_ARG;
+    out4[0] = b->t->path_counts[kPathResident];
+    for (int i = 0; i < 3; ++i) out4[1 + i] = b->t->batch_counts[i];
+    return MI_OK;
+}
 #ifdef MI355X_TEST_HOOKS
 // one arithmetic primitive of the exact kernels (kernels_exact.inc) over n operand tuples, one launch
 // (limbs per element: 4 for mi355x_test_xarith, 8 for mi355x_test_xarith8)

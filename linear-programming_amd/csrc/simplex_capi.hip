@@ -158,6 +158,9 @@ struct mi355x_tab {
     int64_t     la_rearm_in = 0;          // two-launch blocks left before the next try
     // which implementation the dispatcher actually enqueued, per launch class (mi355x_tab_path_counts)
     int64_t     path_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // the same for the drivers of mi355x_batch_solve (mi355x_batch_path_counts): [0] blocks of the split form
+    // (look-ahead per LP + one sweep over all LPs), [1] one-workgroup-per-LP launches, [2] lockstep launch pairs
+    int64_t     batch_counts[3] = {0, 0, 0};
     bool        primed = false;           // every (look-ahead, sweep) form this handle's requests can pick was launched once (prime_block_kernels)
     int         n_timed = 0;
     std::vector<hipEvent_t> ev0, ev1;     // around the update / sweep launches
