@@ -222,6 +222,8 @@ struct CpShard {
 struct mi355x_colpart {
     int     world = 1;                       // shards in total
     bool    rccl = false, multi_process = false, compact = false;
+    bool    unit_dense = false;              // dense shards that cp_make_dense filled from compact ones and no pivot
+                                             // of the solve loop has touched since: basic columns = unit vectors, +-0 elsewhere
     int64_t rows = 0, var_count = 0;
     int     block = kMaxBlock, j = 0;        // pivots per sweep, steps of the current block enqueued
     int     is_max = 1;
@@ -754,6 +756,7 @@ void cp_abort(mi355x_colpart *p)
 int cp_run(mi355x_colpart *p, double f, int64_t n)
 {
     if (p->dead) return fail(MI_RCCL_ERROR, "this handle's communicators were aborted after an earlier failure");
+    p->unit_dense = false;                                   // (a pivot on an inf / NaN column writes NaNs into basic columns)
     if (p->exchange == 2 && !p->p2p_connected)
         return fail(MI_BAD_ARG, "exchange mode 2: the ranks' buffers are not connected yet (mi355x_colpart_p2p_connect)");
     if (n <= 0) return MI_OK;
@@ -1239,7 +1242,7 @@ int mi355x_colpart_sync(mi355x_colpart *p, int64_t *n_pivots)
 }
 
 }  // extern "C"
-namespace { int cp_make_dense(mi355x_colpart *art); }
+namespace { int cp_make_dense(mi355x_colpart *art, bool unit_columns_stay); }
 extern "C" {
 
 int mi355x_colpart_solve(mi355x_colpart *p, int is_max, double f, int64_t max_pivots, int64_t *n_pivots)
@@ -1268,7 +1271,7 @@ int mi355x_colpart_solve(mi355x_colpart *p, int is_max, double f, int64_t max_pi
             // redone there (round 6; until then the handle stopped with MI_NONFINITE and the host fell back to
             // one device).  What dense shards still cannot follow -- a NaN quotient in the ratio test, whose
             // outcome depends on the reference's scan order -- ends as MI_NONFINITE as before.
-            if ((rc = cp_make_dense(p)) != MI_OK) return rc;
+            if ((rc = cp_make_dense(p, /*unit_columns_stay=*/false)) != MI_OK) return rc;   // (the redone pivot writes NaNs into them)
             for (CpShard &s : p->sh) {
                 HIP_TRY(hipSetDevice(s.device));
                 launch_ctl_resume(s.t->v, s.t->stream, MI_NONFINITE);
@@ -1381,8 +1384,9 @@ namespace {
 // REDUCED BY THE STEPS BEFORE IT.  o[k] = objective entry of basis[k]; B[i][k] = entry of row i in column
 // basis[k] (B == nullptr: the basic columns are exact unit columns, B is the identity with +0 elsewhere).  One
 // workgroup, a barrier per step -- m steps of m / 1024 operations per thread; only what CAN make a later scale
-// differ from the original coefficient goes through here (an inf / NaN scale times a zero), the objective row
-// itself is then re-eliminated column-parallel with these scales (k_handover_objective_columns / k_shard_handover).
+// differ from the original coefficient goes through here (an entry of B above the diagonal in a row whose scale is
+// not zero; an inf / NaN scale times a zero), the objective row itself is then re-eliminated column-parallel with
+// these scales (k_handover_objective_columns).
 __global__ __launch_bounds__(1024) void k_handover_scales_seq(const double *B, int64_t m, double *o, double *scales)
 {
     for (int64_t i = 0; i < m; ++i) {
@@ -1399,19 +1403,16 @@ __global__ __launch_bounds__(1024) void k_handover_scales_seq(const double *B, i
     }
 }
 
-// the scales of the hand-over's re-elimination, as the sequential loop reads them: original objective
-// coefficients unless one of them is not finite (host-side shortcut: then every product scale * (+-0) is a zero
-// and no later scale can change), else through k_handover_scales_seq on `device`
+// the scales of the hand-over's re-elimination, as the sequential loop reads them: through k_handover_scales_seq on
+// `device` with the basic block B_host (m x m, row-major).  B_host == nullptr is the caller's word that the basic
+// columns are unit vectors with +-0 elsewhere AND every coefficient is finite: then every product scale * (+-0) is a
+// zero, no later scale can change, and the scales are the original objective coefficients (host-side shortcut).
 int cp_handover_scales(int device, hipStream_t st, int64_t m, const int64_t *basis, const double *main_obj,
                        const double *B_host, std::vector<double> &scales)
 {
     scales.resize((size_t)std::max<int64_t>(m, 1));
-    bool finite = true;
-    for (int64_t i = 0; i < m; ++i) {
-        scales[(size_t)i] = main_obj[basis[i]];
-        finite = finite && std::fabs(scales[(size_t)i]) <= 1.7976931348623157e308;
-    }
-    if (finite || m < 1) return MI_OK;
+    for (int64_t i = 0; i < m; ++i) scales[(size_t)i] = main_obj[basis[i]];
+    if (!B_host || m < 1) return MI_OK;
     HIP_TRY(hipSetDevice(device));
     double *d_o = nullptr, *d_s = nullptr, *d_B = nullptr;
     hipError_t e = hipMalloc((void **)&d_o, m * sizeof(double));
@@ -1513,7 +1514,7 @@ void cp_take_over(mi355x_colpart *p, mi355x_colpart *q)
 // The artificial tableau on DENSE shards (every logical column distributed, basic ones included) in place of its
 // compact shards: what a -0.0 in a basic column, or a NaN in the objective row of one, needs in order to exist.
 // The tableau goes through the host once (data movement only: the assembly mi355x_colpart_download does anyway).
-int cp_make_dense(mi355x_colpart *art)
+int cp_make_dense(mi355x_colpart *art, bool unit_columns_stay)
 {
     const int64_t rows = art->rows, cols = art->var_count + 1, m = rows - 1;
     std::vector<double> hm((size_t)rows * cols);
@@ -1550,6 +1551,7 @@ int cp_make_dense(mi355x_colpart *art)
     for (size_t i = 0; i < art->sh.size(); ++i) { ad->sh[i].comm = art->sh[i].comm; art->sh[i].comm = nullptr; }
     cp_take_over(art, ad);
     cp_free(ad);                                              // (now holds the compact shards)
+    art->unit_dense = unit_columns_stay;
     return MI_OK;
 }
 
@@ -1570,16 +1572,20 @@ int cp_dense_handover(mi355x_colpart *art, int64_t main_cols, const double *main
         hm[(size_t)(r * main_cols + num_vars)] = ha[(size_t)(r * acols + art->var_count)];
     }
     std::copy(main_obj, main_obj + main_cols, hm.begin() + m * main_cols);
-    // the basic block (row i, column basis[k]) for the scales -- only looked at if a scale is not finite
+    // The basic block (row i, column basis[k]) for the scales.  A tableau that was dense when the handle was created
+    // may hold anything there: an entry above the diagonal changes a later scale (:447), so the sequential loop runs
+    // on B.  Only shards that cp_make_dense filled from compact ones (unit columns, +-0 elsewhere: drive-out pivots
+    // keep that) may take the original coefficients -- and only while all of them are finite.
     std::vector<double> B, scales;
     bool finite = true;
     for (int64_t i = 0; i < m; ++i) finite = finite && std::fabs(main_obj[basis[(size_t)i]]) <= 1.7976931348623157e308;
-    if (!finite) {
+    const bool shortcut = art->unit_dense && finite;
+    if (!shortcut) {
         B.resize((size_t)m * m);
         for (int64_t i = 0; i < m; ++i)
             for (int64_t k = 0; k < m; ++k) B[(size_t)(i * m + k)] = hm[(size_t)(i * main_cols + basis[(size_t)k])];
     }
-    rc = cp_handover_scales(art->sh[0].device, art->sh[0].t->stream, m, basis.data(), main_obj, finite ? nullptr : B.data(), scales);
+    rc = cp_handover_scales(art->sh[0].device, art->sh[0].t->stream, m, basis.data(), main_obj, shortcut ? nullptr : B.data(), scales);
     if (rc != MI_OK) return rc;
     std::vector<int> devs;
     for (CpShard &s : art->sh) devs.push_back(s.device);
@@ -1628,6 +1634,11 @@ int mi355x_colpart_solve_two_phase(mi355x_colpart *art, int64_t main_cols, const
     std::vector<double> last_col((size_t)rows);
     rc = mi355x_colpart_download(art, nullptr, basis.data(), nullptr, last_col.data());
     if (rc != MI_OK) return rc;
+    // (a caller's basis may hold anything; from here on main_obj, the rows and is_basic are indexed with it)
+    for (int64_t i = 0; i < m; ++i)
+        if (basis[(size_t)i] < 0 || basis[(size_t)i] >= num_art_vars)
+            return fail(MI_BAD_ARG, "basis entry %lld of row %lld is outside [0, %lld)", (long long)basis[(size_t)i],
+                        (long long)i, (long long)num_art_vars);
     // (fp= 0 objective factor)                                                    simplex.lisp:405-407
     const double diff = 0.0 - last_col[(size_t)m];
     if (!((diff < 0.0 ? -diff : diff) <= f * kClEpsilon)) return MI_INFEASIBLE;
@@ -1646,7 +1657,7 @@ int mi355x_colpart_solve_two_phase(mi355x_colpart *art, int64_t main_cols, const
             const int st = cp_status(art, &np);
             if (st != MI_RUNNING) return st < 0 ? st : (st == MI_NONFINITE ? MI_NONFINITE : fail(MI_HIP_ERROR, "drive-out pivot failed (status %d)", st));
         }
-        if ((rc = cp_make_dense(art)) != MI_OK) return rc;
+        if ((rc = cp_make_dense(art, /*unit_columns_stay=*/true)) != MI_OK) return rc;
         reset_done = false;                                   // (the dense shards' first pivot sets them running)
         rc = cp_drive_out(art, num_vars, basis, stopped, &n1, &reset_done, &stopped);
         if (rc != MI_OK) return rc;
@@ -1663,9 +1674,11 @@ int mi355x_colpart_solve_two_phase(mi355x_colpart *art, int64_t main_cols, const
     // sign is skipped by the (/= 0 scale) test); an inf / NaN coefficient on a basic column turns the objective
     // entries of the OTHER basic columns into NaNs (inf * 0), which only a tableau that stores its basic
     // columns can hold: dense shards again (round 6), with the scales from the sequential loop on the basic block.
+    // That argument needs unit basic columns: a tableau that was dense at creation always takes the sequential loop
+    // (cp_dense_handover).
     bool finite = true;
     for (int64_t i = 0; i < m; ++i) finite = finite && std::fabs(main_obj[basis[(size_t)i]]) <= 1.7976931348623157e308;
-    if (!finite && art->compact && (rc = cp_make_dense(art)) != MI_OK) return rc;
+    if (!finite && art->compact && (rc = cp_make_dense(art, /*unit_columns_stay=*/true)) != MI_OK) return rc;
     mi355x_colpart *mp = nullptr;
     if (!art->compact) {
         rc = cp_dense_handover(art, main_cols, main_obj, basis, &mp);

@@ -1,0 +1,258 @@
+"""The two-phase hand-over (src/simplex.lisp:437-451) on bases that are NOT unit columns, through every form the
+library has of it: the sequential kernel of the single-device path (fresh handles, handles that have solved,
+whole solves, both hand-over modes), the per-member choice of the batches, and the column partition's dense
+shards.  Inputs and expectations come from tests/handover_cases.py (checked on the oracle alone by
+tests/test_handover_cases_host.py: on every case a hand-over that took the original objective coefficients as
+scales would give other bits).  Everything is compared bit for bit -- matrices as int64 views, with any NaN equal
+to any NaN only in the two cases that hold an infinite coefficient -- together with basis, status and pivot counts.
+Needs a real MI355X: `pytest -m gpu`."""
+import ctypes
+import importlib
+
+import numpy as np
+import pytest
+
+import oracle
+from tests import handover_cases as hc
+from tests.helpers import lp_amd, random_mixed_problem
+
+pytestmark = pytest.mark.gpu
+lp = lp_amd()
+
+SMALL = [n for n in hc.DIRECT if hc.SHAPE[n][0] * hc.SHAPE[n][1] <= 130 * 1100 and hc.SHAPE[n][1] <= 1100]
+REAL_PHASE2 = [n for n in hc.DIRECT if hc.SHAPE[n][0] <= 40 and hc.SHAPE[n][1] <= 70
+               and not n.endswith("-unbounded") and "unit" not in hc.CASES[n].ingredients
+               and hc.handed_over(hc.CASES[n])[1] is not None and "d" not in hc.CASES[n].ingredients]
+NONFINITE = [n for n in hc.DIRECT if "d" in hc.CASES[n].ingredients]
+ENDS_BEFORE = [n for n in hc.DIRECT if hc.handed_over(hc.CASES[n])[1] is None]
+
+
+def _eq(case, got, want):
+    if "d" in case.ingredients:
+        return hc.same_bits(got, want)
+    got = np.ascontiguousarray(got)
+    return got.shape == want.shape and np.array_equal(got.view(np.int64), want.view(np.int64))
+
+
+def _tabs(case):
+    m, nv, nav = case.art.shape[0] - 1, case.main.shape[1] - 1, case.art.shape[1] - 1
+    art = lp.Tableau(None, lp.Problem(type="min"), case.art, case.art_basis, nav, m, {}, hc.F)
+    main = lp.Tableau(None, lp.Problem(type="max"), case.main, case.main_basis, nv, m, {}, hc.F)
+    return [art, main]
+
+
+def _is_compact(t):
+    c, cols, ld = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    lp.capi.check(lp.capi.lib().mi355x_tab_layout(t._h, ctypes.byref(c), ctypes.byref(cols), ctypes.byref(ld)), "layout")
+    return bool(c.value)
+
+
+# =========================================================================== single device, the hand-over alone
+def _handover_alone(case, solve_first):
+    L = lp.capi.lib()
+    art, main = _tabs(case)
+    p, M = hc.handed_over(case)
+    n = ctypes.c_int64(-1)
+    if solve_first:                                          # phase 1 as its own call: the compaction attempt fails
+        rc = L.mi355x_tab_solve(art._h, 0, hc.F, 0, ctypes.byref(n))
+        assert (rc, n.value) == (oracle.OPTIMAL, p.n_phase1 - len(p.driveout_elements))
+        assert _is_compact(art) == ("unit" in case.ingredients)
+    rc = L.mi355x_two_phase_handover(art._h, main._h, hc.F, ctypes.byref(n))
+    art._touch()
+    main._touch()
+    assert (rc, n.value) == (p.status, len(p.driveout_elements))
+    assert _eq(case, art.matrix, p.art) and np.array_equal(art.basis_columns, p.art_basis)
+    if M is None:                                            # INFEASIBLE / ART_STUCK: the main tableau is as it was
+        assert _eq(case, main.matrix, case.main) and np.array_equal(main.basis_columns, case.main_basis)
+    else:
+        assert _eq(case, main.matrix, M) and np.array_equal(main.basis_columns, p.art_basis)
+
+
+@pytest.mark.parametrize("name", hc.DIRECT)
+def test_handover_alone_on_a_fresh_handle(name):
+    """mi355x_two_phase_handover on handles that were only uploaded, against the replay: every shape (one wave,
+    two waves of columns, 1024 and 1025 columns in the sequential loop, two and 17 trips of it, the column
+    grid-stride of the copy, 1030 rows) and every ingredient."""
+    _handover_alone(hc.CASES[name], solve_first=False)
+
+
+@pytest.mark.parametrize("name", hc.DIRECT + hc.LIVED_NAMES)
+def test_handover_alone_after_a_solve_of_the_artificial_tableau(name):
+    """The same after mi355x_tab_solve on the artificial tableau (what the chunked glue does): the basic columns
+    are no unit vectors, the compact representation is refused, mi355x_tab_layout says dense, and the hand-over
+    takes the sequential form.  On the lived cases that solve really pivots."""
+    _handover_alone(hc.CASES[name], solve_first=True)
+
+
+# =========================================================================== single device, the whole solve
+def _status_of(call):
+    try:
+        call()
+        return oracle.OPTIMAL
+    except lp.UnboundedProblemError:
+        return oracle.UNBOUNDED
+    except lp.InfeasibleProblemError:
+        return oracle.INFEASIBLE
+    except lp.SolverError as e:
+        assert "cannot be replaced" in str(e), e
+        return oracle.ART_STUCK
+
+
+def _check_whole_solve(case, tabs, want):
+    art, main = tabs
+    assert _eq(case, art.matrix, want.art) and np.array_equal(art.basis_columns, want.art_basis)
+    assert _eq(case, main.matrix, want.main) and np.array_equal(main.basis_columns, want.main_basis)
+
+
+@pytest.mark.parametrize("chunked", [False, True], ids=["one-call", "chunked"])
+@pytest.mark.parametrize("handover", [0, 1], ids=["mode-0", "mode-1"])
+@pytest.mark.parametrize("name", SMALL + hc.LIVED_NAMES)
+def test_whole_solve_bitwise_vs_oracle(name, handover, chunked):
+    """n_solve_tableau([art, main]) -- mi355x_solve_two_phase, or the chunked glue around
+    mi355x_two_phase_handover -- against orc_solve_two_phase.  Both hand-over modes: on a basis that is not a
+    set of unit columns both must take the sequential form, and agree."""
+    case = hc.CASES[name]
+    want = hc.expected(case)
+    tabs = _tabs(case)
+    L = lp.capi.lib()
+    L.mi355x_tune_set_handover_mode(handover)
+    try:
+        st = _status_of(lambda: lp.n_solve_tableau(tabs, chunked=chunked))
+    finally:
+        L.mi355x_tune_set_handover_mode(0)
+    assert st == want.status and tabs[1].n_pivots == want.npv
+    _check_whole_solve(case, tabs, want)
+
+
+@pytest.mark.parametrize("shape,seed", [((6, 3, 2, 1), 1), ((30, 10, 8, 4), 2), ((12, 4, 4, 4), 6)])
+def test_a_caller_pivot_before_the_solve(shape, seed):
+    """The flag's other edge: build-tableau's pair (unit basic columns), ONE mi355x_tab_pivot on the artificial
+    tableau before mi355x_solve_two_phase -- a caller-chosen pivot withdraws what the handle knew about its basic
+    columns, on data that are still consistent.  Against an oracle that made the same pivot."""
+    tabs = lp.build_tableau(random_mixed_problem(lp, *shape, seed))
+    art, main = tabs
+    A, ab = art.matrix.copy(), art.basis_columns.copy()
+    M, mb = main.matrix.copy(), main.basis_columns.copy()
+    ec = oracle.price(A, is_max=False)
+    cr = oracle.ratio(A, ec)
+    assert ec >= 0 and cr >= 0
+    oracle.pivot(A, ab, ec, cr)
+    st, npv = oracle.solve_two_phase(A, ab, M, mb, main_is_max=True, factor=main.fp_tolerance_factor)
+    lp.n_pivot_row(art, ec, cr)
+    got = _status_of(lambda: lp.n_solve_tableau(tabs))
+    assert got == st and main.n_pivots == (int(npv[0]), int(npv[1]))
+    assert np.array_equal(art.matrix.view(np.int64), A.view(np.int64)) and np.array_equal(art.basis_columns, ab)
+    if st in (oracle.OPTIMAL, oracle.UNBOUNDED):
+        assert np.array_equal(main.matrix.view(np.int64), M.view(np.int64)) and np.array_equal(main.basis_columns, mb)
+
+
+# =========================================================================== batches
+@pytest.fixture(params=[0, 3, 2, 1], ids=["default", "lookahead-per-LP+sweep-over-all-LPs", "one-workgroup-per-LP",
+                                           "lockstep-launch-pairs"])
+def batch_mode(request):
+    L = lp.capi.lib()
+    L.mi355x_tune_set_batch_mode(request.param)
+    yield request.param
+    L.mi355x_tune_set_batch_mode(0)
+
+
+def _batches(names):
+    cases = [hc.CASES[n] for n in names]
+    assert sum("unit" in c.ingredients for c in cases) == 1
+    art = lp.MultiDeviceBatch.from_arrays(np.stack([c.art for c in cases]), np.stack([c.art_basis for c in cases]), 1)
+    main = lp.MultiDeviceBatch.from_arrays(np.stack([c.main for c in cases]), np.stack([c.main_basis for c in cases]), 1)
+    return cases, art, main
+
+
+@pytest.mark.parametrize("shape", list(hc.BATCHES))
+def test_batch_handover_alone(batch_mode, shape):
+    """mi355x_multibatch_two_phase_handover on fresh batches against the replay, member by member: one member
+    with unit basic columns among members without, one with drive-out pivots, one ART_STUCK, one infeasible by
+    one ulp (5 x 9); two waves of columns (40 x 70)."""
+    cases, art, main = _batches(hc.BATCHES[shape])
+    st, nd = art.two_phase_handover(main, hc.F)
+    for k, case in enumerate(cases):
+        p, M = hc.handed_over(case)
+        assert (int(st[k]), int(nd[k])) == (p.status, len(p.driveout_elements)), case.name
+        A, ab = art.download(k)
+        assert _eq(case, A, p.art) and np.array_equal(ab, p.art_basis), case.name
+        if M is not None:
+            G, gb = main.download(k)
+            assert _eq(case, G, M) and np.array_equal(gb, p.art_basis), case.name
+
+
+@pytest.mark.parametrize("shape", list(hc.BATCHES))
+def test_batch_solve_two_phase(batch_mode, shape):
+    """mi355x_multibatch_solve_two_phase against orc_solve_two_phase run on every member alone."""
+    cases, art, main = _batches(hc.BATCHES[shape])
+    st, npv = art.solve_two_phase(main, True, hc.F)
+    for k, case in enumerate(cases):
+        want = hc.expected(case)
+        assert (int(st[k]), (int(npv[k, 0]), int(npv[k, 1]))) == (want.status, want.npv), case.name
+        A, ab = art.download(k)
+        assert _eq(case, A, want.art) and np.array_equal(ab, want.art_basis), case.name
+        if hc.handed_over(case)[1] is not None:
+            G, gb = main.download(k)
+            assert _eq(case, G, want.main) and np.array_equal(gb, want.main_basis), case.name
+
+
+# =========================================================================== column partition
+def _colpart(case, shards):
+    """mi355x_colpart_create on the artificial tableau (dense shards: its basic columns are no unit vectors) +
+    mi355x_colpart_solve_two_phase with the main objective row, against orc_solve_two_phase."""
+    cp = importlib.import_module("linear-programming_amd.colpart")
+    want = hc.expected(case)
+    tab = cp.NativeColumnPartition.from_arrays(case.art.copy(), case.art_basis.copy(), shards)
+    try:
+        assert not tab.is_compact()
+        rc, npv, mt = tab.solve_two_phase(case.main[-1].copy(), True, hc.F)
+        A, ab, _, _ = tab.download()
+        G = gb = None
+        if mt is not None:
+            G, gb, last_row, last_col = mt.download()
+            mt.close()
+    finally:
+        tab.close()
+    assert (rc, npv) == (want.status, want.npv)
+    assert _eq(case, A, want.art) and np.array_equal(ab, want.art_basis)
+    if hc.handed_over(case)[1] is None:
+        assert G is None
+    else:
+        assert _eq(case, G, want.main) and np.array_equal(gb, want.main_basis)
+        assert _eq(case, last_row, want.main[-1]) and _eq(case, last_col, np.ascontiguousarray(want.main[:, -1]))
+
+
+@pytest.mark.parametrize("shards", [1, 2, 3, 8])
+@pytest.mark.parametrize("name", [n for n in hc.UNBOUNDED_AT_ONCE if hc.SHAPE[n][0] < 1000])
+def test_colpart_handover_unbounded_at_once(name, shards):
+    """Phase 2 ends UNBOUNDED after 0 pivots: the main tableau read back is the dense-shard hand-over's output."""
+    _colpart(hc.CASES[name], shards)
+
+
+@pytest.mark.parametrize("shards", [1, 3])
+def test_colpart_handover_1030_rows(shards):
+    """More rows than k_handover_scales_seq has threads."""
+    _colpart(hc.CASES["1030x1100-unbounded"], shards)
+
+
+@pytest.mark.parametrize("shards", [1, 2, 3, 8])
+@pytest.mark.parametrize("name", REAL_PHASE2 + hc.LIVED_NAMES)
+def test_colpart_two_phase_bitwise_vs_oracle(name, shards):
+    """The hand-over followed by its real phase 2 (direct cases up to 40 x 70, drive-out pivots on a positive and
+    on a negative element included) and the lived cases, whose phase 1 pivots on dense shards."""
+    _colpart(hc.CASES[name], shards)
+
+
+@pytest.mark.parametrize("shards", [1, 2, 3, 8])
+@pytest.mark.parametrize("name", NONFINITE)
+def test_colpart_nonfinite_coefficient_on_a_non_identity_basic_block(name, shards):
+    """(d): NaN scales out of k_handover_scales_seq with real off-diagonal content in B."""
+    _colpart(hc.CASES[name], shards)
+
+
+@pytest.mark.parametrize("shards", [1, 2, 3, 8])
+@pytest.mark.parametrize("name", ENDS_BEFORE)
+def test_colpart_stuck_artificial_and_feasibility_boundary(name, shards):
+    """(f): a drive-out row whose only non-zero main entries sit in BASIC columns is MI_ART_STUCK on dense shards
+    (which store the basic columns and must skip them); one ulp beyond f * eps is MI_INFEASIBLE."""
+    _colpart(hc.CASES[name], shards)
