@@ -787,6 +787,51 @@ int  mi355x_colpart_trace(mi355x_colpart *p, int64_t *entering_cols, int64_t *pi
                           int64_t cap, int64_t *n);
 void mi355x_colpart_destroy(mi355x_colpart *p);
 
+/* ---- single-float tableaux (opt-in): the reference's single-float path ----------------------
+ * Common Lisp reads 0.5 as a SINGLE-FLOAT, and the reference then solves in single-float arithmetic with
+ * single-float thresholds (src/utils.lisp:84-124: fp<, fp>, fp= dispatch on float-contagion).  A mi355x_stab is
+ * one tableau of IEEE binary32 entries in HBM and these entries are that path: every product is rounded, then
+ * the difference is rounded (no FMA), division is true division, no double-precision intermediate anywhere;
+ * thresholds are computed in float from fp_factor f (rounded to float first): pricing v < 0 - (f/8) eps_s,
+ * ratio eligibility 0 + (f/2) eps_s < a, phase-1 feasibility |0 - obj| <= f eps_s, with
+ * eps_s = single-float-epsilon = 2^-24 (1 + 2^-23).  Tie and NaN rules are those of mi355x_tab_*: the lowest
+ * index of the strict extremum; a NaN key is no candidate except in column 0; a NaN quotient wins only as the
+ * first eligible row.  Statuses, argument validation and MI_NO_DEVICE as for mi355x_tab_*.
+ * A handle takes one of two forms when it is created (mi355x_stab_info): 2 = the whole solve loop in one
+ * workgroup with the tableau in LDS (tableaux whose stored bytes plus scratch fit the budget), 1 = a select and
+ * an update launch per pivot (any size).  Results never depend on the form. */
+typedef struct mi355x_stab mi355x_stab;     /* one single-float tableau resident in HBM */
+/* single-float-epsilon (src/utils.lisp:91), the float's value exactly, as a double */
+double mi355x_epsilon_single(void);
+/* Upload a build-tableau result (src/simplex.lisp:142-328) coerced to single-float: rows x cols, tightly packed. */
+int  mi355x_stab_create(mi355x_stab **out, int64_t rows, int64_t cols, const float *matrix_rowmajor,
+                        const int64_t *basis, int device);
+/* find-entering-column (src/simplex.lisp:362-379): *col = column or -1 */
+int  mi355x_stab_price(mi355x_stab *h, int is_max, double fp_factor, int64_t *col);
+/* find-pivoting-row (src/simplex.lisp:382-389): *row = row or -1 */
+int  mi355x_stab_ratio(mi355x_stab *h, int64_t entering_col, double fp_factor, int64_t *row);
+/* n-pivot-row (src/simplex.lisp:337-359) */
+int  mi355x_stab_pivot(mi355x_stab *h, int64_t entering_col, int64_t changing_row);
+/* n-solve-tableau, single tableau (src/simplex.lisp:453-461).  max_pivots > 0 caps the pivots of this call
+ * exactly (MI_MAX_PIVOTS); a solve continued call by call makes the pivots of one long call. */
+int  mi355x_stab_solve(mi355x_stab *h, int is_max, double fp_factor, int64_t max_pivots, int64_t *n_pivots);
+/* n-solve-tableau, two-phase branch (src/simplex.lisp:402-452): phase 1 on `art` (a min problem), (fp= 0
+ * objective) with eps_s, the exact /= 0 tests and the drive-out pivots, the copy, the sequential objective-row
+ * elimination in float, phase 2 on `main_tab`.  max_pivots > 0 caps the pivots of this call, both phases and the
+ * drive-outs together; a call that ends with MI_MAX_PIVOTS is continued by the next call on the same pair.
+ * pivots_out[0] = phase 1 + drive-outs, pivots_out[1] = phase 2, of this call. */
+int  mi355x_stab_solve_two_phase(mi355x_stab *art, mi355x_stab *main_tab, int main_is_max, double fp_factor,
+                                 int64_t max_pivots, int64_t *pivots_out);
+/* tableau-matrix / basis-columns and what the read-back needs (src/simplex.lisp:74-120); any pointer may be NULL */
+int  mi355x_stab_download(mi355x_stab *h, float *matrix, int64_t *basis, float *last_row, float *last_col);
+/* (entering column, row) of the pivots made since the upload; *n = their number (the buffers hold the first cap) */
+int  mi355x_stab_trace(mi355x_stab *h, int64_t *entering_cols, int64_t *rows, int64_t cap, int64_t *n);
+/* shape, leading dimension in floats, the form taken (1 pair, 2 LDS), the LDS budget in bytes; any pointer may be NULL */
+int  mi355x_stab_info(const mi355x_stab *h, int64_t *rows, int64_t *cols, int64_t *ld, int *form,
+                      int64_t *lds_budget_bytes);
+/* frees the handle (NULL: no-op); replaces the garbage collector's part in the reference */
+void mi355x_stab_destroy(mi355x_stab *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,14 @@ int         mi355x_bb_debug_assemble(const mi355x_problem *p, int64_t n_nodes, i
                                      double *art_out, int64_t *art_basis);
 
 /* ---- fault injection: TEST BUILD ONLY ---------------------------------------------------- */
+/* single-float tableaux (mi355x_stab_*): the form handles created from now on take -- 0 auto (LDS when the stored
+ * bytes plus scratch fit the budget), 1 always the select / update pair, 2 LDS (still only where it fits) */
+int         mi355x_tune_set_single_form(int form);
+/* measurement: k_s_update launched `reps` times on one prepared pivot, between two events: *avg_ms per launch,
+ * *bytes read + written per launch (rows x ld floats each way); the tableau is not preserved */
+int         mi355x_stab_debug_update_time(mi355x_stab *h, int64_t entering_col, int64_t changing_row, int reps,
+                                          double *avg_ms, int64_t *bytes);
+
 /* Compiled in with -DMI355X_TEST_HOOKS (libmi355x_simplex_test.so, built next to the product
  * library by linear-programming_amd/build.py and loaded by the tests that need it); the product
  * library neither exports these nor contains the code paths behind them. */

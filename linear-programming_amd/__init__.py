@@ -13,11 +13,12 @@ GPU, and fails loudly otherwise.
 (The directory name contains a hyphen; import it with
 ``importlib.import_module("linear-programming_amd")``.)
 """
-from . import batch, batch_lps, capi, exact, exact_bb, exact_lps, native, simplex, solver, synth       # noqa: F401
+from . import batch, batch_lps, capi, exact, exact_bb, exact_lps, native, simplex, single, solver, synth       # noqa: F401
 from .native import NativeProblem, NativeSolution               # noqa: F401
 from .batch import TableauBatch, MultiDeviceBatch               # noqa: F401
 from .batch_lps import lower_problem_rows, group_lowered_rows, solve_lps    # noqa: F401
 from .exact import ExactTableau                                  # noqa: F401
+from .single import SingleTableau, build_tableau_single, solve_single    # noqa: F401
 from .conditions import (SolverError, UnboundedProblemError, InfeasibleProblemError,   # noqa: F401
                          UnsupportedConstraintError, ParsingError)
 from .problem import Problem                                    # noqa: F401

@@ -163,6 +163,17 @@ SIGNATURES = {
     "mi355x_colpart_download": (_int, [_p, _p, _p, _p, _p]),
     "mi355x_colpart_trace": (_int, [_p, _p, _p, _i64, _p]),
     "mi355x_colpart_destroy": (None, [_p]),
+    "mi355x_epsilon_single": (_dbl, []),
+    "mi355x_stab_create": (_int, [_pp, _i64, _i64, _p, _p, _int]),
+    "mi355x_stab_price": (_int, [_p, _int, _dbl, _p]),
+    "mi355x_stab_ratio": (_int, [_p, _i64, _dbl, _p]),
+    "mi355x_stab_pivot": (_int, [_p, _i64, _i64]),
+    "mi355x_stab_solve": (_int, [_p, _int, _dbl, _i64, _p]),
+    "mi355x_stab_solve_two_phase": (_int, [_p, _p, _int, _dbl, _i64, _p]),
+    "mi355x_stab_download": (_int, [_p, _p, _p, _p, _p]),
+    "mi355x_stab_trace": (_int, [_p, _p, _p, _i64, _p]),
+    "mi355x_stab_info": (_int, [_p, _p, _p, _p, _p, _p]),
+    "mi355x_stab_destroy": (None, [_p]),
 }
 # tuning / measurement / test hooks: include/mi355x_simplex_tune.h (not the drop-in boundary)
 _EXTRA = {
@@ -217,6 +228,8 @@ _EXTRA = {
     "mi355x_tune_set_lookahead_mode": (_int, [_int]),
     "mi355x_tune_set_batch_block": (_int, [_int]),
     "mi355x_tune_set_sweep_shape": (_int, [_int, _int]),
+    "mi355x_tune_set_single_form": (_int, [_int]),
+    "mi355x_stab_debug_update_time": (_int, [_p, _i64, _i64, _int, _p, _p]),
     "mi355x_bb_debug_assemble": (_int, [_p, _i64, _i64, _p, _p, _p, _int, _p, _p, _p, _p, _p, _p, _p]),
 }
 

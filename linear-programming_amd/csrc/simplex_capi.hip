@@ -205,4 +205,5 @@ struct mi355x_multibatch {
 #include "capi_batch_lps.inc"  // mi355x_*batch_create_lps, mi355x_*batch_readback: f64 batches built from problem rows on the device
 #include "capi_shard.inc"      // mi355x_shard_*
 #include "capi_colpart.inc"    // mi355x_colpart_*, mi355x_rccl_unique_id
+#include "capi_single.inc"     // mi355x_stab_*: single-float tableaux (the reference's single-float path)
 #include "capi_tune.inc"       // mi355x_tune_*, mi355x_debug_*

@@ -478,6 +478,40 @@ enum XProbe8Op { kXProbe8Mul256 = 0, kXProbe8Add512, kXProbe8Sub512, kXProbe8Neg
 void launch_x_arith_probe8(int op, int64_t n, const int64_t *a, const int64_t *b, int64_t *out, int32_t *rc, hipStream_t s);
 #endif
 
+// Single-float tableaux (kernels_single.inc, capi_single.inc): the reference's single-float path in IEEE binary32.
+// Common Lisp SINGLE-FLOAT-EPSILON = 2^-24 (1 + 2^-23)  (src/utils.lisp:84-124)
+constexpr float kClEpsilonSingle = 0x1.000002p-24f;
+// One tableau of floats in HBM.  Row-major, leading dimension ld a multiple of 32 floats (128-byte row starts);
+// columns [cols, ld) are padding (zero in the pivot row).  The control block is the double path's Ctl.
+struct SView {
+    float   *M;
+    int64_t  ld, rows, cols;
+    int64_t *basis;       // rows-1 entries
+    float   *col;         // snapshot of the entering column before the pivot, rows entries
+    float   *prow;        // normalised pivot row, ld entries (padding zero)
+    Ctl     *ctl;
+    int64_t *trace_ec, *trace_cr;
+    int64_t  trace_cap;
+};
+struct SingleThresholds { float price, ratio, feasible; };    // (f/8) eps, 0 + (f/2) eps, f eps: float arithmetic
+SingleThresholds single_thresholds(double fp_factor);
+struct SingleUpdateShape { int strips, strip_quads, tr, row_chunks; };
+SingleUpdateShape single_update_shape(const SView &t);
+// the LDS-resident solve: the ONE budget (dynamic LDS bytes: stored tableau + pivot row + column snapshot; the
+// reductions' scratch is static and comes on top, inside the CU's 160 KiB), and the pivots one launch may make
+constexpr size_t kSingleLdsBudget = 156 * 1024;
+constexpr int    kSingleLaunchCap = 4096;
+size_t single_lds_bytes(const SView &t);
+bool   single_lds_available(const SView &t);   // fits the budget AND the kernel's dynamic-LDS attribute could be raised
+void launch_s_ctl_reset(const SView &t, int64_t max_pivots, int reset_trace, hipStream_t s);
+void launch_s_select(const SView &t, int is_max, double fp_factor, hipStream_t s);
+void launch_s_update(const SView &t, hipStream_t s);
+void launch_s_price_only(const SView &t, int is_max, double fp_factor, hipStream_t s);
+void launch_s_ratio_only(const SView &t, int64_t ec, double fp_factor, hipStream_t s);
+void launch_s_prepare_pivot(const SView &t, int64_t ec, int64_t cr, hipStream_t s);
+void launch_s_solve(const SView &t, int is_max, double fp_factor, int cap, hipStream_t s);
+void launch_s_handover_copy(const SView &art, const SView &mt, hipStream_t s);
+
 int         update_variant_count();
 const char *update_variant_name(int v);
 void        set_update_variant(int v);      // tuning hook (bench / microbench only)

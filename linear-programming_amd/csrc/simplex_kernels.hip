@@ -76,6 +76,7 @@
 //     kernels_exact_lps.inc       exact batches built from problem rows on the device (k_xb_assemble_lps)
 //     kernels_batch_lps.inc       double-precision batches built from problem rows (k_blp_*), k_batch_readback
 //     kernels_launch.inc          host-side launchers, tuning state
+//     kernels_single.inc          single-float tableaux: one copy of the selection code, k_s_select / k_s_update, k_s_solve (LDS)
 #include "simplex_kernels.h"
 #include <type_traits>
 
@@ -99,5 +100,6 @@ namespace mi355x {
 #include "kernels_exact_lps.inc"
 #include "kernels_batch_lps.inc"
 #include "kernels_launch.inc"
+#include "kernels_single.inc"
 
 }  // namespace mi355x

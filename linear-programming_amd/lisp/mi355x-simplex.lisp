@@ -218,6 +218,17 @@
   (sense :pointer) (bound :pointer) (min-bits :int))
 (cffi:defcfun ("mi355x_xbatch_readback" %xbatch-readback) :int
   (batch :pointer) (values-lo-hi :pointer) (basis :pointer) (status :pointer))
+;; single-float tableaux (include/mi355x_simplex.h, mi355x_stab_*): the reference's single-float path
+(cffi:defcfun ("mi355x_stab_create" %stab-create) :int
+  (out :pointer) (rows :int64) (cols :int64) (matrix :pointer) (basis :pointer) (device :int))
+(cffi:defcfun ("mi355x_stab_solve" %stab-solve) :int
+  (tab :pointer) (is-max :int) (fp-factor :double) (max-pivots :int64) (n-pivots :pointer))
+(cffi:defcfun ("mi355x_stab_solve_two_phase" %stab-solve-two-phase) :int
+  (art :pointer) (main :pointer) (main-is-max :int) (fp-factor :double) (max-pivots :int64)
+  (pivots-out :pointer))
+(cffi:defcfun ("mi355x_stab_download" %stab-download) :int
+  (tab :pointer) (matrix :pointer) (basis :pointer) (last-row :pointer) (last-col :pointer))
+(cffi:defcfun ("mi355x_stab_destroy" %stab-destroy) :void (tab :pointer))
 
 (define-condition mi355x-error (solver-error)
   ((code :initarg :code :reader mi355x-error-code)
@@ -522,6 +533,125 @@ Leaves the total in N-PIVOTS[0] and returns the last status."
                   (and (plusp max-pivots) (>= total max-pivots)))
           (setf (cffi:mem-aref n-pivots :int64 0) total)
           (return status))))))
+
+;;; ------------------------------------------------------------------ single-float solves
+;;; :precision :single.  The Lisp reader makes 0.5 a SINGLE-FLOAT, and the reference then solves in
+;;; single-float arithmetic with single-float thresholds (src/utils.lisp:84-124).  The reference's own
+;;; build-tableau produces the tableau; every entry must be a single-float or an integer of at most 2^24
+;;; in magnitude (anything else -- a double-float, a ratio, a larger integer -- is declined, never rounded
+;;; silently); the entries cross the boundary as single-floats, the library solves in IEEE binary32
+;;; (include/mi355x_simplex.h, mi355x_stab_*) in bounded chunks, and the solved single-floats are written
+;;; back into the same `tableau`, which the reference's own methods then serve (src/solver.lisp:61-80).
+(defun single-entry-p (x)
+  (or (typep x 'single-float) (and (integerp x) (<= (abs x) 16777216))))
+
+(defun single-tableau->vectors (tableau)
+  "tableau->vectors in single-float; an entry that is neither a single-float nor an integer a
+single-float holds exactly is declined: unsupported-constraint-error (single ENTRY)."
+  (let* ((matrix (tableau-matrix tableau))
+         (rows (array-dimension matrix 0))
+         (cols (array-dimension matrix 1))
+         (flat (make-array (* rows cols) :element-type 'single-float))
+         (basis-src (tableau-basis-columns tableau))
+         (basis (make-array (max 1 (length basis-src)) :element-type '(signed-byte 64)
+                                                       :initial-element 0)))
+    (dotimes (r rows)
+      (dotimes (c cols)
+        (let ((x (aref matrix r c)))
+          (unless (single-entry-p x)
+            (error 'unsupported-constraint-error :constraint (list 'single x)
+                                                 :solver-name "mi355x-simplex"))
+          (setf (aref flat (+ (* r cols) c)) (coerce x 'single-float)))))
+    (dotimes (i (length basis-src))
+      (setf (aref basis i) (aref basis-src i)))
+    (values flat basis rows cols)))
+
+(defun upload-single-tableau (tableau device)
+  "Returns (values handle flat basis): a mi355x_stab handle plus the host staging vectors."
+  (multiple-value-bind (flat basis rows cols) (single-tableau->vectors tableau)
+    (cffi:with-foreign-object (out :pointer)
+      (cffi:with-pointer-to-vector-data (pm flat)
+        (cffi:with-pointer-to-vector-data (pb basis)
+          (check (with-foreign-fp-mode
+                   (%stab-create out rows cols pm pb device)))))
+      (values (cffi:mem-ref out :pointer) flat basis))))
+
+(defun download-single-tableau (handle tableau flat basis)
+  "Every entry of the solved tableau, as single-floats, into the tableau's own arrays."
+  (cffi:with-pointer-to-vector-data (pm flat)
+    (cffi:with-pointer-to-vector-data (pb basis)
+      (check (%stab-download handle pm pb (cffi:null-pointer) (cffi:null-pointer)))))
+  (vectors->tableau tableau flat basis))
+
+(defun single-solve-two-phase-in-chunks (art-handle main-handle rows cols main-is-max factor max-pivots
+                                         n-pivots)
+  "mi355x_stab_solve_two_phase is resumable: CHUNK pivots per call (both phases and the drive-out
+pivots together) until the status is something else than MI_MAX_PIVOTS or MAX-PIVOTS (0 = no cap) are
+used up.  Returns the last status."
+  (let ((chunk (chunk-pivots rows cols))
+        (total 0))
+    (loop
+      (let* ((cap (if (plusp max-pivots) (min chunk (- max-pivots total)) chunk))
+             (status (check (with-foreign-fp-mode
+                              (%stab-solve-two-phase art-handle main-handle main-is-max factor cap
+                                                     n-pivots)))))
+        (incf total (+ (cffi:mem-aref n-pivots :int64 0) (cffi:mem-aref n-pivots :int64 1)))
+        (when (or (/= status +mi-max-pivots+)
+                  (and (plusp max-pivots) (>= total max-pivots)))
+          (return status))))))
+
+(defun check-precision (precision exact branch-and-bound devices native full-tableau pivot-rule)
+  "The argument errors of :PRECISION: an unknown value, and :SINGLE together with a keyword that asks for
+another path."
+  (unless (member precision '(:double :single))
+    (error "MI355X-SIMPLEX-SOLVER: :precision must be :double or :single, not ~S" precision))
+  (when (eq precision :single)
+    (let ((clash (cond (exact :exact)
+                       (branch-and-bound :branch-and-bound)
+                       ((> (device-count-of devices) 1) :devices)
+                       ((eq native t) :native)
+                       (full-tableau :full-tableau)
+                       ((not (eq pivot-rule :dantzig)) :pivot-rule))))
+      (when clash
+        (error "MI355X-SIMPLEX-SOLVER: :precision :single does not go with ~S" clash)))))
+
+(defun solve-in-single-precision (problem fp-tolerance device max-pivots)
+  "The :precision :single route of mi355x-simplex-solver: returns the solved `tableau`, every entry a
+single-float."
+  (when (problem-integer-vars problem)
+    (error 'unsupported-constraint-error
+           :constraint (cons 'integer (problem-integer-vars problem))
+           :solver-name "mi355x-simplex"))
+  (let ((tableaus (build-tableau problem problem :fp-tolerance-factor fp-tolerance))
+        (factor (coerce fp-tolerance 'double-float)))
+    (cffi:with-foreign-object (n-pivots :int64 2)
+      (if (listp tableaus)
+          (destructuring-bind (art-tab main-tab) tableaus
+            (multiple-value-bind (art-handle art-flat art-basis) (upload-single-tableau art-tab device)
+              (declare (ignorable art-flat art-basis))
+              (unwind-protect
+                   (multiple-value-bind (main-handle main-flat main-basis)
+                       (upload-single-tableau main-tab device)
+                     (unwind-protect
+                          (let ((status (single-solve-two-phase-in-chunks
+                                         art-handle main-handle
+                                         (array-dimension (tableau-matrix art-tab) 0)
+                                         (array-dimension (tableau-matrix art-tab) 1)
+                                         (max-problem-p main-tab) factor max-pivots n-pivots)))
+                            (signal-outcome status)
+                            (download-single-tableau main-handle main-tab main-flat main-basis))
+                       (%stab-destroy main-handle)))
+                (%stab-destroy art-handle))))
+          (multiple-value-bind (handle flat basis) (upload-single-tableau tableaus device)
+            (unwind-protect
+                 (let ((status (solve-in-chunks
+                                (lambda (cap) (%stab-solve handle (max-problem-p tableaus) factor cap
+                                                           n-pivots))
+                                (1+ (tableau-constraint-count tableaus))
+                                (1+ (tableau-var-count tableaus)) max-pivots n-pivots)))
+                   (signal-outcome status)
+                   (download-single-tableau handle tableaus flat basis))
+              (%stab-destroy handle)))))))
 
 ;;; ------------------------------------------------------------------ exact rational solves
 ;;; :exact t.  The reference's build-tableau already yields the rational matrix; its numerators and
@@ -1359,7 +1489,7 @@ phases together.  Returns the final status."
                               &key (fp-tolerance 1024) (device 0) (devices 1) (max-pivots 0)
                                 full-tableau (native :auto) branch-and-bound (bb-width 1)
                                 (int-tolerance 0) (max-nodes 0) exact (exact-max-bits 128)
-                                (pivot-rule :dantzig)
+                                (pivot-rule :dantzig) (precision :double)
                               &allow-other-keys)
   "Solver interface function for the MI355X backend (the value of
 linear-programming:*solver*, src/solver.lisp:39-49).  Takes a problem and backend keyword
@@ -1399,9 +1529,21 @@ on rationals a cycle never ends.  :bland takes the lowest eligible column and, a
 ratio, the one whose basis column is lowest; :dantzig-bland does so only after a degenerate pivot and until
 the next one that is not.  Both end on every input; they reach the exact branch-and-bound's root and node
 batches too.  An unknown rule, and a rule other than :dantzig without :exact T, are errors; with :exact T on a
-problem that holds a float such a rule is declined: unsupported-constraint-error (exact pivot-rule RULE)."
+problem that holds a float such a rule is declined: unsupported-constraint-error (exact pivot-rule RULE).
+:precision :single (opt-in; :double, the default, is everything above, unchanged) is the reference's
+single-float path: what the reader makes of 0.5 is a SINGLE-FLOAT, and the reference then solves in single-float
+arithmetic with single-float-epsilon thresholds (src/utils.lisp:84-124).  The reference's build-tableau builds
+the tableau, whose entries must all be single-floats or integers of at most 2^24 in magnitude -- anything else is
+declined, never rounded: unsupported-constraint-error (single ENTRY) --, the library solves it in IEEE binary32,
+and the solved `tableau` comes back with every entry a single-float.  Together with :exact, :branch-and-bound,
+more than one of :devices, :native T, :full-tableau or a :pivot-rule other than :dantzig it is an error, as is
+an unknown value."
   (declare (ignore args))
   (check-pivot-rule pivot-rule exact)
+  (check-precision precision exact branch-and-bound devices native full-tableau pivot-rule)
+  (when (eq precision :single)
+    (return-from mi355x-simplex-solver
+      (solve-in-single-precision problem fp-tolerance device max-pivots)))
   (when (and (plusp (pivot-rule-code pivot-rule)) (not (rational-numbers-p problem)))
     (exact-declined (list 'pivot-rule pivot-rule)))
   (unless (member exact-max-bits '(128 256))

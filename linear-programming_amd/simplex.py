@@ -153,6 +153,9 @@ def _value(tableau, x):
 
 def tableau_objective_value(tableau):
     """tableau-objective-value (src/simplex.lisp:74-78)."""
+    if getattr(tableau, "single", False):
+        from . import single
+        return single.tableau_objective_value(tableau)
     return _value(tableau, tableau._readback()[0][tableau.var_count])
 
 
@@ -164,6 +167,9 @@ def _basic_value(tableau, col):
 
 def tableau_variable(tableau, var):
     """tableau-variable (src/simplex.lisp:81-107)."""
+    if getattr(tableau, "single", False):
+        from . import single
+        return single.tableau_variable(tableau, var)
     if var == tableau.instance_problem.objective_var:
         return tableau_objective_value(tableau)
     mapping = tableau.var_mapping.get(var)
@@ -179,6 +185,9 @@ def tableau_variable(tableau, var):
 
 def tableau_reduced_cost(tableau, var):
     """tableau-reduced-cost (src/simplex.lisp:111-120)."""
+    if getattr(tableau, "single", False):
+        from . import single
+        return single.tableau_reduced_cost(tableau, var)
     mapping = tableau.var_mapping.get(var)
     if mapping is None:
         raise KeyError("%s is not a variable in the tableau" % (var,))
@@ -616,7 +625,7 @@ def _native_numbers(problem):
 def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_pivots=0,
                           full_tableau=False, native="auto", chunk=None, branch_and_bound=False,
                           bb_width=1, int_tolerance=0, max_nodes=0, exact=False, exact_bits=0, exact_max_bits=128,
-                          pivot_rule="dantzig", **_ignored):
+                          pivot_rule="dantzig", precision="double", **_ignored):
     """What the Lisp glue installs as `*solver*` (src/solver.lisp:39-56): takes a problem and
     backend keyword arguments, returns a solution object answering the four solution-*
     generics -- on the NATIVE route (default whenever the problem's numbers are floats / integers
@@ -654,7 +663,27 @@ def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_p
     Both end on every input.  It reaches the exact branch-and-bound's root and node batches as well.  An
     unknown name and a rule other than "dantzig" without exact=True are argument errors (in floating point
     neither rule is a theorem); with exact=True on a problem that holds a float -- which would take the double
-    path -- such a rule is declined: unsupported-constraint-error ("exact", "pivot-rule", name)."""
+    path -- such a rule is declined: unsupported-constraint-error ("exact", "pivot-rule", name).
+    precision="single" (opt-in; default "double": everything above, unchanged): the reference's single-float path
+    (single.py) -- build-tableau with Lisp's contagion, IEEE binary32 arithmetic and single-float-epsilon thresholds
+    on the GPU, the solved SingleTableau returned, its read-back in np.float32.  Every number of the problem must
+    be an integer with |x| <= 2**24 or a float whose value a binary32 holds exactly; anything else is declined:
+    unsupported-constraint-error ("single", number).  Together with exact, branch_and_bound, devices > 1,
+    native=True, full_tableau or a pivot_rule other than "dantzig" it is an argument error that names the pair; so
+    is an unknown precision."""
+    if precision not in ("double", "single"):
+        raise ValueError("precision=%r: \"double\" (default) or \"single\"" % (precision,))
+    if precision == "single":
+        for name, clash in (("exact", bool(exact)), ("branch_and_bound", bool(branch_and_bound)),
+                            ("devices", devices > 1), ("native", native is True), ("full_tableau", bool(full_tableau)),
+                            ("pivot_rule", pivot_rule != "dantzig")):
+            if clash:
+                raise ValueError("precision=\"single\" does not go with %s=%r: the single-float path is one tableau "
+                                 "on one device under the reference's rule"
+                                 % (name, {"exact": exact, "branch_and_bound": branch_and_bound, "devices": devices,
+                                           "native": native, "full_tableau": full_tableau, "pivot_rule": pivot_rule}[name]))
+        from .single import solve_single
+        return solve_single(problem, fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots, chunk=chunk)
     from .exact import pivot_rule_code
     if pivot_rule_code(pivot_rule) != 0 and not exact:
         raise ValueError("pivot_rule=%r needs exact=True: the double-precision paths keep the reference's rule"
