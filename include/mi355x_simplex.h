@@ -67,6 +67,8 @@ extern "C" {
 /* batches of exact tableaux (mi355x_xbatch_*, below) */
 #define MI355X_XBATCH_WORKGROUP 256    /* threads of the workgroup that owns a member */
 #define MI355X_XBATCH_TRACE_CAP 1024   /* pivots a member's trace buffers hold (mi355x_xbatch_trace) */
+/* batches of single-float tableaux (mi355x_sbatch_*, below) */
+#define MI355X_SBATCH_TRACE_CAP 1024   /* pivots a member's trace buffers hold (mi355x_sbatch_trace) */
 
 typedef struct mi355x_tab   mi355x_tab;     /* one tableau resident in HBM              */
 typedef struct mi355x_batch mi355x_batch;   /* a batch of same-shape tableaux in HBM    */
@@ -831,6 +833,44 @@ int  mi355x_stab_info(const mi355x_stab *h, int64_t *rows, int64_t *cols, int64_
                       int64_t *lds_budget_bytes);
 /* frees the handle (NULL: no-op); replaces the garbage collector's part in the reference */
 void mi355x_stab_destroy(mi355x_stab *h);
+
+/* ---- batches of single-float LPs (opt-in): one workgroup per member, the tableau in LDS ------
+ * n_lps single-float tableaux of ONE shape.  One workgroup owns one member for its whole solve, with the member's
+ * tableau, pivot row and column snapshot in LDS; both phases and everything between them run on the device.  The
+ * contract is member by member: what a member ends with -- status, pivot counts, trace, basis and every tableau
+ * entry, bit for bit (any NaN equal to any NaN) -- is what mi355x_stab_solve / mi355x_stab_solve_two_phase gives
+ * that member alone under the same sequence of calls; one member's outcome never changes another's.
+ * Per-member statuses: MI_OPTIMAL, MI_UNBOUNDED, MI_INFEASIBLE, MI_MAX_PIVOTS, MI_ART_NONZERO, MI_ART_STUCK, and
+ * MI_RUNNING for a member a cancel left unfinished.  The calls return MI_OK, MI_CANCELLED or an error.
+ * max_pivots (0: none) caps each member's pivots of THIS call; a further call carries every unfinished member on
+ * from where it stopped (calls in chunks make the pivots of one long call) and does not touch a finished one. */
+typedef struct mi355x_sbatch mi355x_sbatch;    /* (MI355X_SBATCH_TRACE_CAP, above: the pivots a member's trace holds) */
+/* matrices: the members back to back, each as for mi355x_stab_create (rows x cols, tightly packed); basis: rows - 1
+ * entries per member.  MI_UNSUPPORTED: the shape does not fit the LDS budget (its members go through mi355x_stab_*). */
+int  mi355x_sbatch_create(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, const float *matrices,
+                          const int64_t *basis, int device);
+/* n-solve-tableau (single phase) on every member; status[i], n_pivots[i] (pivots of this call) per member, either
+ * may be NULL. */
+int  mi355x_sbatch_solve(mi355x_sbatch *b, int is_max, double fp_factor, int64_t max_pivots, int32_t *status,
+                         int64_t *n_pivots);
+/* n-solve-tableau's two-phase branch per member: caps, drive-out counting and n_pivots (2 per member: phase 1 +
+ * drive-outs, phase 2, of this call) follow mi355x_stab_solve_two_phase. */
+int  mi355x_sbatch_solve_two_phase(mi355x_sbatch *art, mi355x_sbatch *main_b, int main_is_max, double fp_factor,
+                                   int64_t max_pivots, int32_t *status, int64_t *n_pivots);
+/* member lp_index as mi355x_stab_download gives it; any pointer may be NULL */
+int  mi355x_sbatch_download(mi355x_sbatch *b, int64_t lp_index, float *matrix, int64_t *basis, float *last_row,
+                            float *last_col);
+/* member lp_index's pivots since the batch was created: *n their number, the first min(*n, cap, TRACE_CAP) copied */
+int  mi355x_sbatch_trace(mi355x_sbatch *b, int64_t lp_index, int64_t *entering_cols, int64_t *rows, int64_t cap,
+                         int64_t *n);
+/* workgroup_threads: 256 or 1024, chosen from the shape at create; members_per_cu: workgroups of that size and LDS
+ * footprint the runtime reports resident per compute unit.  Any pointer may be NULL. */
+int  mi355x_sbatch_info(const mi355x_sbatch *b, int64_t *n_lps, int64_t *rows, int64_t *cols, int64_t *ld,
+                        int *workgroup_threads, int64_t *lds_bytes_per_member, int *members_per_cu);
+/* Any thread: the solve running on the batch -- or the next one -- stops between two rounds of launches with
+ * MI_CANCELLED; the members hold whole pivots only and the next call carries them on. */
+int  mi355x_sbatch_cancel(mi355x_sbatch *b);
+void mi355x_sbatch_destroy(mi355x_sbatch *b);
 
 #ifdef __cplusplus
 }

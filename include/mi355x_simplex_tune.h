@@ -215,6 +215,11 @@ int         mi355x_tune_set_single_form(int form);
  * *bytes read + written per launch (rows x ld floats each way); the tableau is not preserved */
 int         mi355x_stab_debug_update_time(mi355x_stab *h, int64_t entering_col, int64_t changing_row, int reps,
                                           double *avg_ms, int64_t *bytes);
+/* batches of single-float LPs (mi355x_sbatch_*), both snapshotted per handle at create: the workgroup a batch
+ * takes -- 0 auto (the shape's rule), 256 or 1024 -- and the pivots per member one launch may make -- 0 the
+ * default (4096), else a count */
+int         mi355x_tune_set_sbatch_threads(int threads);
+int         mi355x_tune_set_sbatch_launch_cap(int cap);
 
 /* Compiled in with -DMI355X_TEST_HOOKS (libmi355x_simplex_test.so, built next to the product
  * library by linear-programming_amd/build.py and loaded by the tests that need it); the product

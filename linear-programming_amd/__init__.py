@@ -18,7 +18,7 @@ from .native import NativeProblem, NativeSolution               # noqa: F401
 from .batch import TableauBatch, MultiDeviceBatch               # noqa: F401
 from .batch_lps import lower_problem_rows, group_lowered_rows, solve_lps    # noqa: F401
 from .exact import ExactTableau                                  # noqa: F401
-from .single import SingleTableau, build_tableau_single, solve_single    # noqa: F401
+from .single import SingleBatch, SingleTableau, build_tableau_single, solve_single    # noqa: F401
 from .conditions import (SolverError, UnboundedProblemError, InfeasibleProblemError,   # noqa: F401
                          UnsupportedConstraintError, ParsingError)
 from .problem import Problem                                    # noqa: F401

@@ -18,6 +18,7 @@ MI_BB_INFEASIBLE, MI_BB_PRUNED, MI_BB_BRANCHED, MI_BB_INCUMBENT, MI_BB_NOT_BETTE
 MI_BAD_ARG, MI_HIP_ERROR, MI_RCCL_ERROR, MI_NO_DEVICE, MI_NO_MEMORY, MI_UNSUPPORTED = -1, -2, -3, -4, -5, -6
 MI_EXACT_OVERFLOW, MI_EXACT_INEXACT = -7, -8
 XBATCH_WORKGROUP, XBATCH_TRACE_CAP = 256, 1024    # MI355X_XBATCH_WORKGROUP, MI355X_XBATCH_TRACE_CAP
+SBATCH_TRACE_CAP = 1024                           # MI355X_SBATCH_TRACE_CAP
 MI_RULE_DANTZIG, MI_RULE_BLAND, MI_RULE_DANTZIG_BLAND = 0, 1, 2    # mi355x_xtab_set_pivot_rule / mi355x_xbatch_set_pivot_rule
 
 _i64, _dbl, _p, _int = ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_int
@@ -174,6 +175,14 @@ SIGNATURES = {
     "mi355x_stab_trace": (_int, [_p, _p, _p, _i64, _p]),
     "mi355x_stab_info": (_int, [_p, _p, _p, _p, _p, _p]),
     "mi355x_stab_destroy": (None, [_p]),
+    "mi355x_sbatch_create": (_int, [_pp, _i64, _i64, _i64, _p, _p, _int]),
+    "mi355x_sbatch_solve": (_int, [_p, _int, _dbl, _i64, _p, _p]),
+    "mi355x_sbatch_solve_two_phase": (_int, [_p, _p, _int, _dbl, _i64, _p, _p]),
+    "mi355x_sbatch_download": (_int, [_p, _i64, _p, _p, _p, _p]),
+    "mi355x_sbatch_trace": (_int, [_p, _i64, _p, _p, _i64, _p]),
+    "mi355x_sbatch_info": (_int, [_p, _p, _p, _p, _p, _p, _p, _p]),
+    "mi355x_sbatch_cancel": (_int, [_p]),
+    "mi355x_sbatch_destroy": (None, [_p]),
 }
 # tuning / measurement / test hooks: include/mi355x_simplex_tune.h (not the drop-in boundary)
 _EXTRA = {
@@ -230,6 +239,8 @@ _EXTRA = {
     "mi355x_tune_set_sweep_shape": (_int, [_int, _int]),
     "mi355x_tune_set_single_form": (_int, [_int]),
     "mi355x_stab_debug_update_time": (_int, [_p, _i64, _i64, _int, _p, _p]),
+    "mi355x_tune_set_sbatch_threads": (_int, [_int]),
+    "mi355x_tune_set_sbatch_launch_cap": (_int, [_int]),
     "mi355x_bb_debug_assemble": (_int, [_p, _i64, _i64, _p, _p, _p, _int, _p, _p, _p, _p, _p, _p, _p]),
 }
 

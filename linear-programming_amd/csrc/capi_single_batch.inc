@@ -1,0 +1,291 @@
+// capi_single_batch.inc -- mi355x_sbatch_*: n_lps SINGLE-FLOAT tableaux of one shape behind a handle, one workgroup
+// per member for its whole solve (kernels_single_batch.inc).  The contract is member by member: what a member ends with
+// -- status, pivot counts, trace, basis, every tableau entry -- is what mi355x_stab_solve / _solve_two_phase gives that
+// member alone under the same sequence of calls.  No double touches a tableau entry.
+// Part of simplex_capi.hip (ONE translation unit: included there, in this order).
+
+namespace {
+int g_sbatch_threads = 0;                 // tuning / test hook: 0 auto (sbatch_threads_for), 256 or 1024
+int g_sbatch_launch_cap = 0;              // tuning / test hook: 0 = kSingleLaunchCap, else pivots per member and launch
+}  // namespace
+
+struct mi355x_sbatch {
+    int         device = 0;
+    SbView      v{};
+    hipStream_t stream = nullptr;
+    int         threads = 0;              // snapshot of the rule (or the hook) at create
+    int         launch_cap = kSingleLaunchCap;
+    int         members_per_cu = 0;       // hipOccupancyMaxActiveBlocksPerMultiprocessor of k_sb_solve<threads> at this shape
+    int32_t    *d_phase = nullptr;        // artificial batch of a two-phase pair: per member (state, status between the phases)
+    std::vector<Ctl>     h;               // the control blocks as the last read-back left them
+    std::vector<int32_t> h_phase;
+    std::atomic<int> cancel{0};
+};
+
+namespace {
+
+void free_sbatch(mi355x_sbatch *b)
+{
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    (void)hipFree(b->v.M);
+    (void)hipFree(b->v.basis);
+    (void)hipFree(b->v.ctl);
+    (void)hipFree(b->v.trace_ec);
+    (void)hipFree(b->v.trace_cr);
+    (void)hipFree(b->d_phase);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    delete b;
+}
+
+int sb_read(mi355x_sbatch *b, hipStream_t s, bool with_phase)
+{
+    HIP_TRY(hipMemcpyAsync(b->h.data(), b->v.ctl, b->h.size() * sizeof(Ctl), hipMemcpyDeviceToHost, s));
+    if (with_phase)
+        HIP_TRY(hipMemcpyAsync(b->h_phase.data(), b->d_phase, b->h_phase.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MI_OK;
+}
+
+inline bool sb_carried_on(int32_t st) { return st == kRunning || st == MI_MAX_PIVOTS; }
+
+}  // namespace
+
+extern "C" {
+
+int mi355x_sbatch_create(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, const float *matrices,
+                         const int64_t *basis, int device)
+{
+    if (!out) return fail(MI_BAD_ARG, "out is NULL");
+    *out = nullptr;
+    if (!matrices) return fail(MI_BAD_ARG, "matrices is NULL");
+    if (n_lps < 1 || n_lps > (1LL << 30)) return fail(MI_BAD_ARG, "n_lps=%lld must be in [1, 2^30]", (long long)n_lps);
+    if (rows < 1 || cols < 1) return fail(MI_BAD_ARG, "rows=%lld cols=%lld must be >= 1", (long long)rows, (long long)cols);
+    if (rows > 65535LL * 16) return fail(MI_BAD_ARG, "rows=%lld exceeds the supported 1048560", (long long)rows);
+    if (cols > (1LL << 30)) return fail(MI_BAD_ARG, "cols=%lld exceeds the supported 2^30", (long long)cols);
+    if (rows > 1 && !basis) return fail(MI_BAD_ARG, "basis is NULL");
+    const int ndev = device_count_checked();
+    if (ndev <= 0) return fail(MI_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(MI_BAD_ARG, "device %d out of range [0,%d)", device, ndev);
+    HIP_TRY(hipSetDevice(device));
+    mi355x_sbatch *b = new (std::nothrow) mi355x_sbatch;
+    if (!b) return fail(MI_NO_MEMORY, "host allocation failed");
+    b->device = device;
+    SbView &v = b->v;
+    v.n_lps = n_lps;
+    v.rows = rows;
+    v.cols = cols;
+    v.ld = (cols + kSingleLdAlign - 1) / kSingleLdAlign * kSingleLdAlign;
+    v.stride = rows * v.ld;
+    v.trace_cap = MI355X_SBATCH_TRACE_CAP;
+    b->threads = g_sbatch_threads ? g_sbatch_threads : sbatch_threads_for(rows, cols);
+    b->launch_cap = g_sbatch_launch_cap ? g_sbatch_launch_cap : kSingleLaunchCap;
+    // the shapes the LDS form does not hold (or may not have) are declined: their members go one by one
+    if (!sbatch_available(v, b->threads, &b->members_per_cu) || b->members_per_cu < 1) {
+        delete b;
+        return fail(MI_UNSUPPORTED, "a %lldx%lld single-float member does not fit the LDS budget of %lld bytes",
+                    (long long)rows, (long long)cols, (long long)kSingleLdsBudget);
+    }
+    const int64_t nb = std::max<int64_t>(rows - 1, 1);
+    try {
+        b->h.resize((size_t)n_lps);
+        b->h_phase.assign((size_t)(2 * n_lps), 0);
+    } catch (const std::bad_alloc &) {
+        delete b;
+        return fail(MI_NO_MEMORY, "host allocation failed");
+    }
+    const size_t mbytes = (size_t)n_lps * (size_t)v.stride * sizeof(float);
+    hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc((void **)&v.M, mbytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&v.basis, (size_t)(n_lps * nb) * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.ctl, (size_t)n_lps * sizeof(Ctl));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.trace_ec, (size_t)(n_lps * v.trace_cap) * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.trace_cr, (size_t)(n_lps * v.trace_cap) * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_phase, (size_t)(2 * n_lps) * sizeof(int32_t));
+    if (e == hipSuccess && v.ld != v.cols) e = hipMemsetAsync(v.M, 0, mbytes, b->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_phase, 0, (size_t)(2 * n_lps) * sizeof(int32_t), b->stream);
+    if (e == hipSuccess)
+        e = hipMemcpy2DAsync(v.M, v.ld * sizeof(float), matrices, cols * sizeof(float), cols * sizeof(float),
+                             (size_t)(n_lps * rows), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess && rows > 1)
+        e = hipMemcpyAsync(v.basis, basis, (size_t)(n_lps * (rows - 1)) * sizeof(int64_t), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess) {
+        launch_sb_ctl_reset(v, b->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(b->h.data(), v.ctl, (size_t)n_lps * sizeof(Ctl), hipMemcpyDeviceToHost, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        free_sbatch(b);
+        return fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "single-float batch upload failed: %s", hipGetErrorString(e));
+    }
+    *out = b;
+    return MI_OK;
+}
+
+void mi355x_sbatch_destroy(mi355x_sbatch *b) { free_sbatch(b); }
+
+int mi355x_sbatch_info(const mi355x_sbatch *b, int64_t *n_lps, int64_t *rows, int64_t *cols, int64_t *ld,
+                       int *workgroup_threads, int64_t *lds_bytes_per_member, int *members_per_cu)
+{
+    if (!b) return fail(MI_BAD_ARG, "handle is NULL");
+    if (n_lps) *n_lps = b->v.n_lps;
+    if (rows) *rows = b->v.rows;
+    if (cols) *cols = b->v.cols;
+    if (ld) *ld = b->v.ld;
+    if (workgroup_threads) *workgroup_threads = b->threads;
+    if (lds_bytes_per_member) *lds_bytes_per_member = (int64_t)sbatch_lds_bytes(b->v);
+    if (members_per_cu) *members_per_cu = b->members_per_cu;
+    return MI_OK;
+}
+
+// n-solve-tableau, single tableau (src/simplex.lisp:453-461), on every member the call carries on: bounded launches,
+// one read-back of the control blocks per round, the cancel flag looked at between rounds.
+int mi355x_sbatch_solve(mi355x_sbatch *b, int is_max, double f, int64_t max_pivots, int32_t *status, int64_t *n_pivots)
+{
+    if (!b) return fail(MI_BAD_ARG, "handle is NULL");
+    if (max_pivots < 0) return fail(MI_BAD_ARG, "max_pivots < 0");
+    HIP_TRY(hipSetDevice(b->device));
+    const int64_t n = b->v.n_lps;
+    std::vector<char> live((size_t)n);
+    for (int64_t q = 0; q < n; ++q) live[q] = sb_carried_on(b->h[q].status);
+    launch_sb_begin(b->v, max_pivots, nullptr, 0, b->stream);
+    bool cancelled = false;
+    for (;;) {
+        launch_sb_solve(b->v, b->threads, is_max, f, b->launch_cap, nullptr, b->stream);
+        HIP_TRY(hipGetLastError());
+        const int rc = sb_read(b, b->stream, false);
+        if (rc != MI_OK) return rc;
+        bool running = false;
+        for (int64_t q = 0; q < n && !running; ++q) running = b->h[q].status == kRunning;
+        // (a cancel that arrives while the last round finishes goes with the call: it never reaches the next one)
+        const int c = b->cancel.exchange(0, std::memory_order_acq_rel);
+        if (!running) break;
+        if (c) { cancelled = true; break; }                                  // (whole pivots only)
+    }
+    for (int64_t q = 0; q < n; ++q) {
+        if (status) status[q] = b->h[q].status;
+        if (n_pivots) n_pivots[q] = live[q] ? b->h[q].n_pivots : 0;
+    }
+    return cancelled ? MI_CANCELLED : MI_OK;
+}
+
+// n-solve-tableau's two-phase branch (src/simplex.lisp:402-452) per member, resumable as mi355x_stab_solve_two_phase
+// is: max_pivots caps a member's pivots of THIS call, both phases and the drive-outs together.  A round is phase 1 on
+// the artificial batch, the step between the phases for the members whose phase 1 just ended, phase 2 on the main batch.
+int mi355x_sbatch_solve_two_phase(mi355x_sbatch *art, mi355x_sbatch *mt, int main_is_max, double f, int64_t max_pivots,
+                                  int32_t *status, int64_t *n_pivots)
+{
+    if (!art || !mt) return fail(MI_BAD_ARG, "NULL handle");
+    if (art == mt) return fail(MI_BAD_ARG, "artificial and main batch are the same handle");
+    if (max_pivots < 0) return fail(MI_BAD_ARG, "max_pivots < 0");
+    if (art->v.n_lps != mt->v.n_lps || art->v.rows != mt->v.rows || art->v.cols < mt->v.cols || art->device != mt->device)
+        return fail(MI_BAD_ARG, "artificial and main batch do not match");
+    HIP_TRY(hipSetDevice(art->device));
+    const int64_t n = art->v.n_lps;
+    hipStream_t s = art->stream;
+    HIP_TRY(hipStreamSynchronize(mt->stream));
+    std::vector<char> live_a((size_t)n), live_m((size_t)n);
+    for (int64_t q = 0; q < n; ++q) {
+        const int32_t ph = art->h_phase[2 * q];
+        live_a[q] = ph == 0 && (sb_carried_on(art->h[q].status) || art->h[q].status == MI_OPTIMAL);
+        live_m[q] = ph == 1 && sb_carried_on(mt->h[q].status);
+    }
+    launch_sb_begin(art->v, max_pivots, art->d_phase, 0, s);
+    launch_sb_begin(mt->v, max_pivots, art->d_phase, 1, s);
+    bool cancelled = false, phase1 = false;
+    for (int64_t q = 0; q < n && !phase1; ++q) phase1 = live_a[q];
+    for (;;) {
+        if (phase1) {
+            launch_sb_solve(art->v, art->threads, /*is_max=*/0, f, art->launch_cap, nullptr, s);     // simplex.lisp:403
+            launch_sb_between(art->v, mt->v, art->threads, art->d_phase, f, max_pivots, s);
+        }
+        launch_sb_solve(mt->v, mt->threads, main_is_max, f, mt->launch_cap, art->d_phase, s);       // simplex.lisp:452
+        HIP_TRY(hipGetLastError());
+        int rc = sb_read(art, s, true);
+        if (rc == MI_OK) rc = sb_read(mt, s, false);
+        if (rc != MI_OK) return rc;
+        bool running = false;
+        phase1 = false;
+        for (int64_t q = 0; q < n; ++q) {
+            const int32_t ph = art->h_phase[2 * q];
+            if (ph == 0 && art->h[q].status == kRunning) phase1 = running = true;
+            else if (ph == 1 && mt->h[q].status == kRunning) running = true;
+        }
+        int c = art->cancel.exchange(0, std::memory_order_acq_rel);         // (as in mi355x_sbatch_solve)
+        c |= mt->cancel.exchange(0, std::memory_order_acq_rel);
+        if (!running) break;
+        if (c) { cancelled = true; break; }                                  // (whole pivots only)
+    }
+    for (int64_t q = 0; q < n; ++q) {
+        const int32_t ph = art->h_phase[2 * q];
+        if (status) status[q] = ph == 2 ? art->h_phase[2 * q + 1] : ph == 1 ? mt->h[q].status : art->h[q].status;
+        if (n_pivots) {
+            n_pivots[2 * q] = live_a[q] ? art->h[q].n_pivots : 0;
+            n_pivots[2 * q + 1] = ph == 1 && (live_a[q] || live_m[q]) ? mt->h[q].n_pivots : 0;
+        }
+    }
+    return cancelled ? MI_CANCELLED : MI_OK;
+}
+
+int mi355x_sbatch_download(mi355x_sbatch *b, int64_t q, float *hm, int64_t *hb, float *last_row, float *last_col)
+{
+    if (!b) return fail(MI_BAD_ARG, "handle is NULL");
+    if (q < 0 || q >= b->v.n_lps) return fail(MI_BAD_ARG, "lp_index %lld out of range [0,%lld)", (long long)q, (long long)b->v.n_lps);
+    HIP_TRY(hipSetDevice(b->device));
+    const SbView &v = b->v;
+    const float *M = v.M + q * v.stride;
+    if (hm)
+        HIP_TRY(hipMemcpy2DAsync(hm, v.cols * sizeof(float), M, v.ld * sizeof(float), v.cols * sizeof(float), v.rows,
+                                 hipMemcpyDeviceToHost, b->stream));
+    if (hb && v.rows > 1)
+        HIP_TRY(hipMemcpyAsync(hb, v.basis + q * (v.rows - 1), (v.rows - 1) * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+    if (last_row)
+        HIP_TRY(hipMemcpyAsync(last_row, M + (v.rows - 1) * v.ld, v.cols * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    if (last_col)
+        HIP_TRY(hipMemcpy2DAsync(last_col, sizeof(float), M + (v.cols - 1), v.ld * sizeof(float), sizeof(float), v.rows,
+                                 hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return MI_OK;
+}
+
+int mi355x_sbatch_trace(mi355x_sbatch *b, int64_t q, int64_t *ecs, int64_t *crs, int64_t cap, int64_t *n)
+{
+    if (!b) return fail(MI_BAD_ARG, "handle is NULL");
+    if (q < 0 || q >= b->v.n_lps) return fail(MI_BAD_ARG, "lp_index %lld out of range [0,%lld)", (long long)q, (long long)b->v.n_lps);
+    HIP_TRY(hipSetDevice(b->device));
+    Ctl c{};
+    HIP_TRY(hipMemcpyAsync(&c, b->v.ctl + q, sizeof(Ctl), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (n) *n = c.trace_n;
+    const int64_t k = std::min<int64_t>(std::min<int64_t>(c.trace_n, cap), b->v.trace_cap);
+    if (k > 0 && ecs) HIP_TRY(hipMemcpyAsync(ecs, b->v.trace_ec + q * b->v.trace_cap, k * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+    if (k > 0 && crs) HIP_TRY(hipMemcpyAsync(crs, b->v.trace_cr + q * b->v.trace_cap, k * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+    if (k > 0 && (ecs || crs)) HIP_TRY(hipStreamSynchronize(b->stream));
+    return MI_OK;
+}
+
+int mi355x_sbatch_cancel(mi355x_sbatch *b)
+{
+    if (!b) return fail(MI_BAD_ARG, "handle is NULL");
+    b->cancel.store(1, std::memory_order_release);
+    return MI_OK;
+}
+
+int mi355x_tune_set_sbatch_threads(int threads)
+{
+    if (threads != 0 && threads != 256 && threads != 1024) return fail(MI_BAD_ARG, "threads must be 0 (auto), 256 or 1024");
+    g_sbatch_threads = threads;
+    return MI_OK;
+}
+
+int mi355x_tune_set_sbatch_launch_cap(int cap)
+{
+    if (cap < 0) return fail(MI_BAD_ARG, "cap must be 0 (the default) or a count of pivots");
+    g_sbatch_launch_cap = cap;
+    return MI_OK;
+}
+
+}  // extern "C"

@@ -9,7 +9,8 @@
 // branches -- and two solve forms that are loops around it:
 //     k_s_select + k_s_update   any size: the tableau in HBM, two launches per pivot
 //     k_s_solve                 small tableaux: tableau, column snapshot and pivot row in LDS, the whole
-//                               n-solve-tableau loop in one launch of one 1024-thread workgroup
+//                               n-solve-tableau loop in one launch of one 1024-thread workgroup (s_solve_in_lds,
+//                               the loop that k_sb_solve of kernels_single_batch.inc runs once per member)
 // The functions take plain pointers: called on HBM rows by the pair, on LDS rows by k_s_solve.
 
 // ------------------------------------------------------------------ candidates and reductions
@@ -316,11 +317,12 @@ __global__ __launch_bounds__(BLOCK) void k_s_update(SView t, const int tr, const
 }
 
 // ------------------------------------------------------------------ the LDS-resident solve
-// One 1024-thread workgroup runs n-solve-tableau (src/simplex.lisp:453-461) on a tableau it holds in LDS: rows x
+// One workgroup of THREADS threads runs n-solve-tableau (src/simplex.lisp:453-461) on a tableau it holds in LDS: rows x
 // ldl floats (ldl = cols rounded up to a quad), then the pivot row (ldl), then the column snapshot (rows rounded up
 // to a quad).  At most `cap` pivots per launch; max_pivots is honoured exactly (k_s_select's order of tests).
 // On exit the tableau goes back to HBM, so a solve continued call by call makes the pivots of one long call.
-__global__ __launch_bounds__(kSelThreads) void k_s_solve(SView t, float sgn, float price_tol, float ratio_thr, int cap)
+template <int THREADS>
+__device__ __forceinline__ void s_solve_in_lds(const SView &t, float sgn, float price_tol, float ratio_thr, int cap)
 {
     extern __shared__ __attribute__((aligned(16))) float s_lds[];
     __shared__ SScratch sc;
@@ -336,11 +338,11 @@ __global__ __launch_bounds__(kSelThreads) void k_s_solve(SView t, float sgn, flo
     vec4f *L4 = reinterpret_cast<vec4f *>(L);
     vec4f *G4 = reinterpret_cast<vec4f *>(t.M);
     const int nq = rows * ldlq;                               // quads of the LDS tableau
-    // thread's walk over the quads: (row, quad of the row) advances by kSelThreads quads per step
-    const int step_r = kSelThreads / ldlq, step_q = kSelThreads % ldlq;
+    // thread's walk over the quads: (row, quad of the row) advances by THREADS quads per step
+    const int step_r = THREADS / ldlq, step_q = THREADS % ldlq;
     {
         int r = (int)threadIdx.x / ldlq, qd = (int)threadIdx.x % ldlq;
-        for (int idx = threadIdx.x; idx < nq; idx += kSelThreads) {
+        for (int idx = threadIdx.x; idx < nq; idx += THREADS) {
             L4[idx] = G4[(int64_t)r * ldq + qd];
             r += step_r; qd += step_q;
             if (qd >= ldlq) { qd -= ldlq; ++r; }
@@ -350,19 +352,19 @@ __global__ __launch_bounds__(kSelThreads) void k_s_solve(SView t, float sgn, flo
     int32_t status = kRunning;
     int64_t n = c0.n_pivots, trace_n = c0.trace_n, last_ec = c0.ec, last_cr = c0.cr;
     for (int k = 0; ; ++k) {
-        const SCand e = s_block_price<kSelThreads>(L + (size_t)(rows - 1) * ldl, vc, sgn, &sc);
+        const SCand e = s_block_price<THREADS>(L + (size_t)(rows - 1) * ldl, vc, sgn, &sc);
         if (s_price_says_optimal(e, price_tol)) { status = 0; break; }                 // MI_OPTIMAL
         if (c0.max_pivots > 0 && n >= c0.max_pivots) { status = 3; break; }            // MI_MAX_PIVOTS
         if (k >= cap) break;                                   // the launch's bound: still running
-        const SCand q = s_block_gather_ratio<kSelThreads>(L, ldl, rows, vc, e.i, col, ratio_thr, &sc);
+        const SCand q = s_block_gather_ratio<THREADS>(L, ldl, rows, vc, e.i, col, ratio_thr, &sc);
         if (q.i < 0) { status = 1; break; }                    // MI_UNBOUNDED
         const int cr = q.i;
-        s_block_scale_row<kSelThreads>(L + (size_t)cr * ldl, prow, ldlq, cols, __uint_as_float(q.s));
+        s_block_scale_row<THREADS>(L + (size_t)cr * ldl, prow, ldlq, cols, __uint_as_float(q.s));
         __syncthreads();
         {
             const vec4f *P4 = reinterpret_cast<const vec4f *>(prow);
             int r = (int)threadIdx.x / ldlq, qd = (int)threadIdx.x % ldlq;
-            for (int idx = threadIdx.x; idx < nq; idx += kSelThreads) {
+            for (int idx = threadIdx.x; idx < nq; idx += THREADS) {
                 const vec4f p = P4[qd], v = L4[idx];
                 const float s = col[r];
                 const float m0 = s * p.x, m1 = s * p.y, m2 = s * p.z, m3 = s * p.w;     // rounded products
@@ -387,7 +389,7 @@ __global__ __launch_bounds__(kSelThreads) void k_s_solve(SView t, float sgn, flo
     __syncthreads();
     {
         int r = (int)threadIdx.x / ldlq, qd = (int)threadIdx.x % ldlq;
-        for (int idx = threadIdx.x; idx < nq; idx += kSelThreads) {
+        for (int idx = threadIdx.x; idx < nq; idx += THREADS) {
             G4[(int64_t)r * ldq + qd] = L4[idx];
             r += step_r; qd += step_q;
             if (qd >= ldlq) { qd -= ldlq; ++r; }
@@ -396,6 +398,11 @@ __global__ __launch_bounds__(kSelThreads) void k_s_solve(SView t, float sgn, flo
     if (threadIdx.x == 0) {
         ctl->status = status; ctl->n_pivots = n; ctl->trace_n = trace_n; ctl->ec = last_ec; ctl->cr = last_cr;
     }
+}
+// one tableau behind a handle: one 1024-thread workgroup (the batch form is k_sb_solve, kernels_single_batch.inc)
+__global__ __launch_bounds__(kSelThreads) void k_s_solve(SView t, float sgn, float price_tol, float ratio_thr, int cap)
+{
+    s_solve_in_lds<kSelThreads>(t, sgn, price_tol, ratio_thr, cap);
 }
 
 // ------------------------------------------------------------------ two-phase hand-over, the copy

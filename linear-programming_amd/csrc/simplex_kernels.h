@@ -512,6 +512,31 @@ void launch_s_prepare_pivot(const SView &t, int64_t ec, int64_t cr, hipStream_t 
 void launch_s_solve(const SView &t, int is_max, double fp_factor, int cap, hipStream_t s);
 void launch_s_handover_copy(const SView &art, const SView &mt, hipStream_t s);
 
+// Batches of single-float tableaux of one shape (kernels_single_batch.inc, capi_single_batch.inc): one workgroup owns
+// one member for its whole solve (s_solve_in_lds, the loop of k_s_solve).  Member q: tableau at M + q * stride (stride
+// = rows * ld floats, a multiple of 32), basis at basis + q * max(rows - 1, 1), control block ctl + q, trace at
+// trace_ec / trace_cr + q * trace_cap.
+struct SbView {
+    float   *M;
+    int64_t  stride, ld, rows, cols, n_lps;
+    int64_t *basis;
+    Ctl     *ctl;
+    int64_t *trace_ec, *trace_cr;
+    int64_t  trace_cap;
+};
+// stored quads (rows x ceil(cols / 4)) up to which a member takes 256 threads.  Measured (profiles/sbatch_rate.txt, part 2):
+// at 1024 members 256 threads beat 1024 at every shape the LDS budget holds, 3.7 x at 425 quads, 1.15 x at 9700 -- no
+// crossover inside the budget, so the threshold is the budget itself and 1024 threads are the tuning hook's.
+constexpr int64_t kSbatchQuads1024 = (int64_t)(kSingleLdsBudget / 16);
+int    sbatch_threads_for(int64_t rows, int64_t cols);
+size_t sbatch_lds_bytes(const SbView &b);
+bool   sbatch_available(const SbView &b, int threads, int *members_per_cu);   // fits the budget AND the attributes could be raised
+void launch_sb_ctl_reset(const SbView &b, hipStream_t s);                  // every member: kRunning, no pivots, an empty trace
+void launch_sb_begin(const SbView &b, int64_t max_pivots, const int32_t *phase, int want_phase, hipStream_t s);
+void launch_sb_solve(const SbView &b, int threads, int is_max, double fp_factor, int cap, const int32_t *gate, hipStream_t s);
+void launch_sb_between(const SbView &art, const SbView &main_b, int threads, int32_t *phase, double fp_factor,
+                       int64_t max_pivots, hipStream_t s);
+
 int         update_variant_count();
 const char *update_variant_name(int v);
 void        set_update_variant(int v);      // tuning hook (bench / microbench only)

@@ -77,6 +77,7 @@
 //     kernels_batch_lps.inc       double-precision batches built from problem rows (k_blp_*), k_batch_readback
 //     kernels_launch.inc          host-side launchers, tuning state
 //     kernels_single.inc          single-float tableaux: one copy of the selection code, k_s_select / k_s_update, k_s_solve (LDS)
+//     kernels_single_batch.inc    batches of single-float tableaux: k_sb_solve (one workgroup per member, LDS), k_sb_between
 #include "simplex_kernels.h"
 #include <type_traits>
 
@@ -101,5 +102,6 @@ namespace mi355x {
 #include "kernels_batch_lps.inc"
 #include "kernels_launch.inc"
 #include "kernels_single.inc"
+#include "kernels_single_batch.inc"
 
 }  // namespace mi355x

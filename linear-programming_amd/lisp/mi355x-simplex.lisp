@@ -229,6 +229,20 @@
 (cffi:defcfun ("mi355x_stab_download" %stab-download) :int
   (tab :pointer) (matrix :pointer) (basis :pointer) (last-row :pointer) (last-col :pointer))
 (cffi:defcfun ("mi355x_stab_destroy" %stab-destroy) :void (tab :pointer))
+;; batches of single-float LPs (mi355x_sbatch_*): one workgroup per member, the member's tableau in LDS
+(cffi:defcfun ("mi355x_sbatch_create" %sbatch-create) :int
+  (out :pointer) (n-lps :int64) (rows :int64) (cols :int64) (matrices :pointer) (basis :pointer)
+  (device :int))
+(cffi:defcfun ("mi355x_sbatch_solve" %sbatch-solve) :int
+  (batch :pointer) (is-max :int) (fp-factor :double) (max-pivots :int64) (status :pointer)
+  (n-pivots :pointer))
+(cffi:defcfun ("mi355x_sbatch_solve_two_phase" %sbatch-solve-two-phase) :int
+  (art :pointer) (main :pointer) (main-is-max :int) (fp-factor :double) (max-pivots :int64)
+  (status :pointer) (n-pivots :pointer))
+(cffi:defcfun ("mi355x_sbatch_download" %sbatch-download) :int
+  (batch :pointer) (lp-index :int64) (matrix :pointer) (basis :pointer) (last-row :pointer)
+  (last-col :pointer))
+(cffi:defcfun ("mi355x_sbatch_destroy" %sbatch-destroy) :void (batch :pointer))
 
 (define-condition mi355x-error (solver-error)
   ((code :initarg :code :reader mi355x-error-code)
@@ -652,6 +666,186 @@ single-float."
                    (signal-outcome status)
                    (download-single-tableau handle tableaus flat basis))
               (%stab-destroy handle)))))))
+
+;;; Lists of problems under :precision :single (mi355x-solve-problems): the members of one shape and sense
+;;; side by side as ONE batch of single-float tableaux (mi355x_sbatch_*: one workgroup per member for its
+;;; whole solve, both phases and everything between them on the device), member by member what
+;;; solve-in-single-precision gives the member alone.  A member is a list (tableau flat basis): the
+;;; reference's build-tableau result and its single-float staging vectors.
+(defun single-member (tableau)
+  "(tableau flat basis); declines as single-tableau->vectors does."
+  (multiple-value-bind (flat basis) (single-tableau->vectors tableau)
+    (list tableau flat basis)))
+
+(defun sbatch-create (members device)
+  "MEMBERS of ONE shape, back to back behind one mi355x_sbatch handle.  Returns the handle, or NIL when the
+library declines the shape (MI_UNSUPPORTED: a member does not fit the LDS budget)."
+  (let* ((n (length members))
+         (matrix (tableau-matrix (first (first members))))
+         (rows (array-dimension matrix 0))
+         (cols (array-dimension matrix 1))
+         (m (1- rows))
+         (flat (make-array (* n rows cols) :element-type 'single-float))
+         (bases (make-array (max 1 (* n m)) :element-type '(signed-byte 64) :initial-element 0)))
+    (loop for (nil member-flat member-basis) in members for k from 0
+          do (dotimes (i (* rows cols))
+               (setf (aref flat (+ (* k rows cols) i)) (aref member-flat i)))
+             (dotimes (i m)
+               (setf (aref bases (+ (* k m) i)) (aref member-basis i))))
+    (cffi:with-foreign-object (out :pointer)
+      (let ((code (cffi:with-pointer-to-vector-data (pm flat)
+                    (cffi:with-pointer-to-vector-data (pb bases)
+                      (with-foreign-fp-mode
+                        (%sbatch-create out n rows cols pm pb device))))))
+        (if (= code +mi-unsupported+)
+            nil
+            (progn (check code) (cffi:mem-ref out :pointer)))))))
+
+(defun sbatch-solve-in-chunks (solve-fn rows cols max-pivots n status)
+  "Calls (funcall SOLVE-FN cap) -- one bounded foreign call on a batch, CAP pivots per member -- until no
+member is left at MI_MAX_PIVOTS or MAX-PIVOTS (0 = no cap) are used up: a further call carries every
+unfinished member on and does not touch a finished one.  STATUS (int32 x N) holds the members' statuses."
+  (let ((chunk (chunk-pivots rows cols))
+        (done 0))
+    (loop
+      (let ((cap (if (plusp max-pivots) (min chunk (- max-pivots done)) chunk)))
+        (check (with-foreign-fp-mode (funcall solve-fn cap)))
+        (incf done cap)
+        (when (or (and (plusp max-pivots) (>= done max-pivots))
+                  (loop for k below n
+                        never (= (cffi:mem-aref status :int32 k) +mi-max-pivots+)))
+          (return done))))))
+
+(defun sbatch-read-back (handle k member)
+  "Member K of a batch: every solved single-float into the member's own tableau."
+  (destructuring-bind (tableau flat basis) member
+    (cffi:with-pointer-to-vector-data (pm flat)
+      (cffi:with-pointer-to-vector-data (pb basis)
+        (check (%sbatch-download handle k pm pb (cffi:null-pointer) (cffi:null-pointer)))))
+    (vectors->tableau tableau flat basis)))
+
+(defun solve-single-batch (members device factor max-pivots)
+  "MEMBERS: single-phase members of ONE shape and ONE sense.  Returns a list parallel to MEMBERS -- the
+solved tableau, or a condition object -- or :DECLINED when the library declines the shape."
+  (let ((handle (sbatch-create members device)))
+    (if (null handle)
+        :declined
+        (unwind-protect
+             (let* ((n (length members))
+                    (tableau (first (first members)))
+                    (matrix (tableau-matrix tableau)))
+               (cffi:with-foreign-objects ((status :int32 n) (pivots :int64 n))
+                 (sbatch-solve-in-chunks
+                  (lambda (cap) (%sbatch-solve handle (max-problem-p tableau) factor cap status pivots))
+                  (array-dimension matrix 0) (array-dimension matrix 1) max-pivots n status)
+                 (loop for member in members for k from 0
+                       collect (or (outcome-condition (cffi:mem-aref status :int32 k))
+                                   (sbatch-read-back handle k member)))))
+          (%sbatch-destroy handle)))))
+
+(defun solve-single-two-phase-batch (pairs device factor max-pivots)
+  "PAIRS: lists (art-member main-member) of ONE shape each and one sense.  One pair of batches, both phases
+and the step between them per member on the device (mi355x_sbatch_solve_two_phase in bounded calls;
+MAX-PIVOTS caps both phases and the drive-outs together, as for a member alone).  Returns a list parallel
+to PAIRS, or :DECLINED."
+  (let ((art-handle (sbatch-create (mapcar #'first pairs) device))
+        (main-handle nil))
+    (if (null art-handle)
+        :declined
+        (unwind-protect
+             (progn
+               (setf main-handle (sbatch-create (mapcar #'second pairs) device))
+               (if (null main-handle)
+                   :declined
+                   (let* ((n (length pairs))
+                          (main-tableau (first (second (first pairs))))
+                          (art-matrix (tableau-matrix (first (first (first pairs))))))
+                     (cffi:with-foreign-objects ((status :int32 n) (pivots :int64 (* 2 n)))
+                       (sbatch-solve-in-chunks
+                        (lambda (cap) (%sbatch-solve-two-phase art-handle main-handle
+                                                               (max-problem-p main-tableau) factor cap
+                                                               status pivots))
+                        (array-dimension art-matrix 0) (array-dimension art-matrix 1) max-pivots n status)
+                       (loop for (nil main-member) in pairs for k from 0
+                             collect (or (outcome-condition (cffi:mem-aref status :int32 k))
+                                         (sbatch-read-back main-handle k main-member)))))))
+          (when main-handle (%sbatch-destroy main-handle))
+          (%sbatch-destroy art-handle)))))
+
+(defun check-list-precision (precision exact native devices pivot-rule)
+  "The argument errors of mi355x-solve-problems' :PRECISION: an unknown value, and :SINGLE together with a
+keyword that asks for another path (the single-float batch is one device and the reference's rule)."
+  (unless (member precision '(:double :single))
+    (error "MI355X-SOLVE-PROBLEMS: :precision must be :double or :single, not ~S" precision))
+  (when (eq precision :single)
+    (let ((clash (cond (exact :exact)
+                       ((eq native :many) :native)
+                       ((> (device-count-of devices) 1) :devices)
+                       ((not (eq pivot-rule :dantzig)) :pivot-rule))))
+      (when clash
+        (error "MI355X-SOLVE-PROBLEMS: :precision :single does not go with ~S" clash)))))
+
+(defun solve-problems-in-single-precision (problems fp-tolerance device max-pivots)
+  "The :precision :single route of mi355x-solve-problems: the reference's build-tableau and the
+single-entry-p check per member (a declined member's condition takes its place), single-phase members
+grouped by (rows cols sense), two-phase members by (rows art-cols main-cols sense), a group of two or more
+as one batch; members alone in their group, shapes the batch declines and integer problems go through
+(mi355x-simplex-solver p :precision :single) one by one.  Returns the list of results."
+  (let* ((n (length problems))
+         (results (make-array n :initial-element nil))
+         (groups (make-hash-table :test #'equal))
+         (groups2 (make-hash-table :test #'equal))
+         (factor (coerce fp-tolerance 'double-float)))
+    (flet ((solve-alone (k)
+             (setf (aref results k)
+                   (handler-case (mi355x-simplex-solver (nth k problems) :fp-tolerance fp-tolerance
+                                                                         :device device
+                                                                         :max-pivots max-pivots
+                                                                         :precision :single)
+                     (error (c) c)))))
+      (loop for problem in problems for k from 0
+            do (if (problem-integer-vars problem)
+                   (solve-alone k)                     ; -> unsupported-constraint-error
+                   (let ((built (handler-case
+                                    (let ((tableaus (build-tableau problem problem
+                                                                   :fp-tolerance-factor fp-tolerance)))
+                                      (if (listp tableaus)
+                                          (mapcar #'single-member tableaus)
+                                          (single-member tableaus)))
+                                  (error (c) c))))
+                     (cond
+                       ((typep built 'condition) (setf (aref results k) built))
+                       ((listp (first built))          ; two-phase: (art-member main-member)
+                        (let ((art (tableau-matrix (first (first built))))
+                              (main (tableau-matrix (first (second built)))))
+                          (push (cons k built)
+                                (gethash (list (array-dimension art 0) (array-dimension art 1)
+                                               (array-dimension main 1)
+                                               (max-problem-p (first (second built))))
+                                         groups2))))
+                       (t
+                        (let ((matrix (tableau-matrix (first built))))
+                          (push (cons k built)
+                                (gethash (list (array-dimension matrix 0) (array-dimension matrix 1)
+                                               (max-problem-p (first built)))
+                                         groups))))))))
+      (flet ((solve-groups (table solve-fn)
+               (maphash
+                (lambda (shape members)
+                  (declare (ignore shape))
+                  (setf members (reverse members))
+                  (let ((outcomes (if (rest members)
+                                      (funcall solve-fn (mapcar #'cdr members) device factor max-pivots)
+                                      :declined)))
+                    (if (eq outcomes :declined)
+                        (loop for (k . nil) in members do (solve-alone k))
+                        (loop for (k . nil) in members
+                              for outcome in outcomes
+                              do (setf (aref results k) outcome)))))
+                table)))
+        (solve-groups groups #'solve-single-batch)
+        (solve-groups groups2 #'solve-single-two-phase-batch)))
+    (coerce results 'list)))
 
 ;;; ------------------------------------------------------------------ exact rational solves
 ;;; :exact t.  The reference's build-tableau already yields the rational matrix; its numerators and
@@ -1786,7 +1980,7 @@ solution (unbounded-problem-error ...)."
 (defun mi355x-solve-problems (problems &rest args
                               &key (fp-tolerance 1024) (device 0) (devices 1) (max-pivots 0)
                                 full-tableau (errorp t) native exact (exact-max-bits 128)
-                                (pivot-rule :dantzig)
+                                (pivot-rule :dantzig) (precision :double)
                               &allow-other-keys)
   "Solves a LIST of problems and returns the list of their solved tableaus, in order -- what
   (mapcar #'solve-problem problems) returns, with the independent LPs running side by side on
@@ -1827,8 +2021,27 @@ the GPU(s) instead of one after the other.
     tolerance factor, src/simplex.lisp:506-511), :DEVICE (the GPU of members solved alone), :DEVICES
     (a count or a list of device ids: the sub-batches' GPUs), :MAX-PIVOTS (a cap per member; 0 = none,
     as the reference), :FULL-TABLEAU (every entry of every solved tableau written back).
+  * :PRECISION :SINGLE (opt-in; :DOUBLE, the default, is everything above, unchanged): every member takes the
+    reference's single-float path, what (mi355x-simplex-solver p :precision :single) returns for it -- the
+    reference's build-tableau, every entry a single-float or an integer of at most 2^24 in magnitude (a member
+    with anything else is declined, its unsupported-constraint-error (single ENTRY) takes its place),
+    single-float arithmetic and single-float-epsilon thresholds.  Single-phase members are grouped by shape
+    and sense, two-phase members by the shapes of their two tableaux (no unit-basis restriction), and a
+    group of two or more is ONE batch of single-float tableaux (mi355x_sbatch_*: one workgroup per member with
+    the member's tableau in LDS, both phases and everything between them on the device, in bounded foreign
+    calls); the solved single-floats are written back into each member's `tableau`.  Members alone in their
+    group, shapes beyond the batch's LDS budget and integer problems go one by one.  Together with :EXACT,
+    :NATIVE :MANY, more than one of :DEVICES or a :PIVOT-RULE other than :DANTZIG it is an error that names
+    the keyword; so is an unknown precision.
 Every returned solution object's results are bit-identical to the single-problem path's."
   (declare (ignore args))
+  (check-list-precision precision exact native devices pivot-rule)
+  (when (eq precision :single)
+    (let ((results (solve-problems-in-single-precision problems fp-tolerance device max-pivots)))
+      (when errorp
+        (let ((failed (find-if (lambda (r) (typep r 'condition)) results)))
+          (when failed (error failed))))
+      (return-from mi355x-solve-problems results)))
   (check-pivot-rule pivot-rule exact)
   (when (and (eq native :many) (not full-tableau) problems)
     ;; the whole list behind ONE job of the library: no build-tableau, no boxed matrices; the members

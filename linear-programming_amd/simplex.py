@@ -737,7 +737,7 @@ simplex_solver = mi355x_simplex_solver
 
 def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_pivots=0, errorp=True, native=False,
                           exact=False, exact_bits=0, exact_max_bits=128, pivot_rule="dantzig", device_build=False,
-                          from_rows=False):
+                          from_rows=False, precision="double"):
     """The glue's `mi355x-solve-problems`: a LIST of problems -> the list of their solved tableaus,
     what [solve_problem(p) for p in problems] returns, with the independent LPs side by side on the
     GPU(s).  Single-phase problems are grouped by tableau shape and sense; a group of two or more
@@ -773,7 +773,31 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
     one by one.
     pivot_rule: as for mi355x_simplex_solver, for every batch and every member solved alone; an unknown name
     and a rule other than "dantzig" with exact=False are argument errors, and a member with a float declines
-    such a rule (its condition takes its slot when errorp is False)."""
+    such a rule (its condition takes its slot when errorp is False).
+    precision="single" (opt-in; default "double": everything above, unchanged): every member takes the reference's
+    single-float path (single.py), what [mi355x_simplex_solver(p, precision="single") for p in problems] returns,
+    the solved SingleTableaus with their read-back in np.float32.  Single-phase members are grouped by (shape,
+    sense), two-phase members by (artificial shape, main shape, sense) -- no unit-basis restriction -- and a group
+    of two or more is ONE batch of single-float tableaux (mi355x_sbatch_create / _solve or _solve_two_phase in
+    bounded chunks, one workgroup per member with the member's tableau in LDS).  Members alone in their group,
+    shapes beyond the batch's LDS budget and integer problems go one by one; a member with a number no binary32
+    holds is declined: unsupported-constraint-error ("single", number) in its slot.  Together with exact,
+    native="many", from_rows, device_build, devices > 1 or a pivot_rule other than "dantzig" it is an argument
+    error that names the pair; so is an unknown precision."""
+    if precision not in ("double", "single"):
+        raise ValueError("precision=%r: \"double\" (default) or \"single\"" % (precision,))
+    if precision == "single":
+        given = {"exact": exact, "native": native, "from_rows": from_rows, "device_build": device_build,
+                 "devices": devices, "pivot_rule": pivot_rule}
+        for name, clash in (("exact", bool(exact)), ("native", native == "many"), ("from_rows", bool(from_rows)),
+                            ("device_build", bool(device_build)), ("devices", devices > 1),
+                            ("pivot_rule", pivot_rule != "dantzig")):
+            if clash:
+                raise ValueError("precision=\"single\" does not go with %s=%r: the single-float batch is one device "
+                                 "under the reference's rule" % (name, given[name]))
+        from .single import solve_problems_single
+        return solve_problems_single(problems, fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots,
+                                     errorp=errorp)
     from .exact import pivot_rule_code
     if pivot_rule_code(pivot_rule) != 0 and not exact:
         raise ValueError("pivot_rule=%r needs exact=True: the double-precision paths keep the reference's rule"

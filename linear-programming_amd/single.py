@@ -455,3 +455,219 @@ def solve_single(problem, fp_tolerance=1024, device=0, max_pivots=0, chunk=None)
         raise UnsupportedConstraintError(("integer",) + tuple(problem.integer_vars), "mi355x-simplex")
     tabs = build_tableau_single(problem, fp_tolerance_factor=fp_tolerance, device=device)
     return n_solve_tableau(tabs, max_pivots=max_pivots, chunk=chunk)
+
+
+# ------------------------------------------------------------------ batches: one workgroup per LP
+class SingleBatch:
+    """n single-float tableaux of one shape behind a mi355x_sbatch: one workgroup owns one member for its whole
+    solve, the member's tableau in LDS.  Member by member the result is what the member's own SingleTableau gives
+    under the same sequence of calls."""
+
+    def __init__(self, handle, n_lps, rows, cols):
+        self._handle, self.n_lps, self.rows, self.cols = handle, int(n_lps), int(rows), int(cols)
+
+    @classmethod
+    def from_arrays(cls, matrices, basis, device=0):
+        """matrices[n, rows, cols] float32, basis[n, rows - 1].  A shape the batch declines (beyond the LDS
+        budget) raises capi.Mi355xError with code MI_UNSUPPORTED."""
+        M = np.asarray(matrices)
+        if M.dtype != np.float32:
+            raise TypeError("a SingleBatch takes float32 matrices, not %s" % (M.dtype,))
+        if M.ndim != 3:
+            raise ValueError("matrices must be [n, rows, cols], not %r" % (M.shape,))
+        M = np.ascontiguousarray(M)
+        n, rows, cols = M.shape
+        b = np.ascontiguousarray(basis, dtype=np.int64)
+        if b.shape != (n, rows - 1):
+            raise ValueError("basis shape %r does not match [n, rows - 1] = %r" % (b.shape, (n, rows - 1)))
+        h = ctypes.c_void_p()
+        capi.check(capi.lib().mi355x_sbatch_create(ctypes.byref(h), n, rows, cols, _ptr(M), _ptr(b) if b.size else None,
+                                                   int(device)), "mi355x_sbatch_create")
+        return cls(h, n, rows, cols)
+
+    def solve(self, is_max, fp_tolerance=1024, max_pivots=0):
+        """-> (status[n] int32, n_pivots[n] int64) of this call; self.last_return is what the call itself returned
+        (MI_OK, or MI_CANCELLED after cancel(): the unfinished members are MI_RUNNING and the next call carries them on)."""
+        st, npv = np.empty(self.n_lps, dtype=np.int32), np.empty(self.n_lps, dtype=np.int64)
+        rc = capi.check(capi.lib().mi355x_sbatch_solve(self._handle, int(is_max), float(fp_tolerance), int(max_pivots),
+                                                       _ptr(st), _ptr(npv)), "mi355x_sbatch_solve")
+        self.last_return = rc
+        return st, npv
+
+    def solve_two_phase(self, main, main_is_max, fp_tolerance=1024, max_pivots=0):
+        """self: the batch of artificial tableaux.  -> (status[n], n_pivots[n, 2]: phase 1 + drive-outs, phase 2)."""
+        st, npv = np.empty(self.n_lps, dtype=np.int32), np.empty((self.n_lps, 2), dtype=np.int64)
+        rc = capi.check(capi.lib().mi355x_sbatch_solve_two_phase(self._handle, main._handle, int(main_is_max),
+                                                                 float(fp_tolerance), int(max_pivots), _ptr(st), _ptr(npv)),
+                        "mi355x_sbatch_solve_two_phase")
+        self.last_return = rc
+        return st, npv
+
+    def download(self, q):
+        """Member q: (matrix float32 [rows, cols], basis int64 [rows - 1])."""
+        M, b = np.empty((self.rows, self.cols), dtype=np.float32), np.empty(self.rows - 1, dtype=np.int64)
+        capi.check(capi.lib().mi355x_sbatch_download(self._handle, int(q), _ptr(M), _ptr(b) if b.size else None, None, None),
+                   "mi355x_sbatch_download")
+        return M, b
+
+    def trace(self, q):
+        """(entering column, row) of member q's pivots since the batch was created."""
+        n = ctypes.c_int64(0)
+        capi.check(capi.lib().mi355x_sbatch_trace(self._handle, int(q), None, None, 0, ctypes.byref(n)), "mi355x_sbatch_trace")
+        k = min(n.value, capi.SBATCH_TRACE_CAP)
+        ec, cr = np.empty(max(k, 1), dtype=np.int64), np.empty(max(k, 1), dtype=np.int64)
+        capi.check(capi.lib().mi355x_sbatch_trace(self._handle, int(q), _ptr(ec), _ptr(cr), k, ctypes.byref(n)),
+                   "mi355x_sbatch_trace")
+        return np.stack([ec[:k], cr[:k]], axis=1)
+
+    def info(self):
+        """mi355x_sbatch_info: {"n_lps", "rows", "cols", "ld", "workgroup_threads", "lds_bytes_per_member",
+        "members_per_cu"}."""
+        n, r, c, ld, lds = (ctypes.c_int64() for _ in range(5))
+        thr, per_cu = ctypes.c_int(), ctypes.c_int()
+        capi.check(capi.lib().mi355x_sbatch_info(self._handle, ctypes.byref(n), ctypes.byref(r), ctypes.byref(c),
+                                                 ctypes.byref(ld), ctypes.byref(thr), ctypes.byref(lds),
+                                                 ctypes.byref(per_cu)), "mi355x_sbatch_info")
+        return {"n_lps": n.value, "rows": r.value, "cols": c.value, "ld": ld.value, "workgroup_threads": thr.value,
+                "lds_bytes_per_member": lds.value, "members_per_cu": per_cu.value}
+
+    def cancel(self):
+        """mi355x_sbatch_cancel: the running call, or the next one, stops between two rounds with MI_CANCELLED."""
+        capi.check(capi.lib().mi355x_sbatch_cancel(self._handle), "mi355x_sbatch_cancel")
+
+    def close(self):
+        h, self._handle = self._handle, None
+        if h:
+            capi.lib().mi355x_sbatch_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def set_batch_threads(threads):
+    """mi355x_tune_set_sbatch_threads (tests and measurement): 0 auto, 256 or 1024 for batches created from now on."""
+    capi.check(capi.lib().mi355x_tune_set_sbatch_threads(int(threads)), "mi355x_tune_set_sbatch_threads")
+
+
+def set_batch_launch_cap(cap):
+    """mi355x_tune_set_sbatch_launch_cap (tests): pivots per member and launch, 0 the default."""
+    capi.check(capi.lib().mi355x_tune_set_sbatch_launch_cap(int(cap)), "mi355x_tune_set_sbatch_launch_cap")
+
+
+def group_single_problems(problems, fp_tolerance=1024, device=0):
+    """Host only: check_single_problem + build_tableau_single per member.
+    -> (slots, groups, groups2): slots[k] is None, "alone" (an integer problem: solve_single declines it in its own
+    words) or the condition that building member k raised; groups maps (shape, is_max) to [(k, tableau)] of the
+    single-phase members, groups2 maps (art shape, main shape, is_max) to [(k, art, main)] of the two-phase ones.
+    There is no unit-basis restriction: the path has no compact form."""
+    from .conditions import SolverError
+    slots, groups, groups2 = [None] * len(problems), {}, {}
+    for k, p in enumerate(problems):
+        if p.integer_vars:
+            slots[k] = "alone"
+            continue
+        try:
+            check_single_problem(p)
+            tabs = build_tableau_single(p, fp_tolerance_factor=fp_tolerance, device=device)
+        except SolverError as e:
+            slots[k] = e
+            continue
+        if isinstance(tabs, list):
+            art, main = tabs
+            groups2.setdefault((art.matrix.shape, main.matrix.shape, main.is_max), []).append((k, art, main))
+        else:
+            groups.setdefault((tabs.matrix.shape, tabs.is_max), []).append((k, tabs))
+    return slots, groups, groups2
+
+
+def _batch_in_chunks(call, n, rows, cols, max_pivots, chunk=None):
+    """Bounded foreign calls on a batch until no member is left at MI_MAX_PIVOTS or max_pivots (0: none) are used
+    up: call(cap) -> (status[n], pivots[n, ...] of that call); -> (status, pivots summed)."""
+    from .simplex import chunk_pivots
+    chunk, done, total = chunk or chunk_pivots(rows, cols), 0, None
+    while True:
+        cap = min(chunk, max_pivots - done) if max_pivots > 0 else chunk
+        st, npv = call(cap)
+        total = npv.copy() if total is None else total + npv
+        done += cap
+        if (max_pivots > 0 and done >= max_pivots) or not (st == capi.MI_MAX_PIVOTS).any():
+            return st, total
+
+
+def solve_problems_single(problems, fp_tolerance=1024, device=0, max_pivots=0, errorp=True, chunk=None):
+    """mi355x_solve_problems(..., precision="single"): what [solve_single(p) for p in problems] returns, the groups
+    of two or more as ONE SingleBatch (or a pair of them) in bounded chunks.  Members alone in their group, shapes
+    the batch declines and integer problems go through solve_single one by one."""
+    from .conditions import SolverError
+    from .simplex import _raise_for
+    results = [None] * len(problems)
+    slots, groups, groups2 = group_single_problems(problems, fp_tolerance, device)
+
+    def alone(k):
+        try:
+            results[k] = solve_single(problems[k], fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots,
+                                      chunk=chunk)
+        except SolverError as e:
+            results[k] = e
+
+    def make(mats, bases):
+        try:
+            return SingleBatch.from_arrays(np.stack(mats), np.stack(bases), device=device)
+        except capi.Mi355xError as e:
+            if e.code != capi.MI_UNSUPPORTED:
+                raise
+            return None                                       # (beyond the LDS budget: one by one)
+
+    def adopt(t, sb, q, st, npv):
+        try:
+            _raise_for(int(st))
+        except SolverError as e:
+            return e
+        t._matrix, t._basis = sb.download(q)
+        t._stale, t._handle = False, None                     # (never uploaded: no handle left behind)
+        t.n_pivots = npv
+        return t
+
+    for k, s in enumerate(slots):
+        if s == "alone":
+            alone(k)
+        elif s is not None:
+            results[k] = s
+    for (shape, is_max), members in groups.items():
+        sb = make([t.matrix for _, t in members], [t.basis_columns for _, t in members]) if len(members) > 1 else None
+        if sb is None:
+            for k, _ in members:
+                alone(k)
+            continue
+        try:
+            st, npv = _batch_in_chunks(lambda cap: sb.solve(is_max, fp_tolerance, cap), len(members), shape[0], shape[1],
+                                       max_pivots, chunk)
+            for q, (k, t) in enumerate(members):
+                results[k] = adopt(t, sb, q, st[q], int(npv[q]))
+        finally:
+            sb.close()
+    for (ashape, mshape, is_max), members in groups2.items():
+        ab = make([a.matrix for _, a, _ in members], [a.basis_columns for _, a, _ in members]) if len(members) > 1 else None
+        mb = make([t.matrix for _, _, t in members], [t.basis_columns for _, _, t in members]) if ab is not None else None
+        if mb is None:
+            if ab is not None:
+                ab.close()
+            for k, _, _ in members:
+                alone(k)
+            continue
+        try:
+            st, npv = _batch_in_chunks(lambda cap: ab.solve_two_phase(mb, is_max, fp_tolerance, cap), len(members),
+                                       ashape[0], ashape[1], max_pivots, chunk)
+            for q, (k, _, t) in enumerate(members):
+                results[k] = adopt(t, mb, q, st[q], (int(npv[q, 0]), int(npv[q, 1])))
+        finally:
+            ab.close()
+            mb.close()
+    if errorp:
+        for r in results:
+            if isinstance(r, Exception):
+                raise r
+    return results
