@@ -7,10 +7,7 @@ import ctypes
 import numpy as np
 
 from . import capi
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+from .capi import _ptr
 
 
 def _lps_arrays(lps, sense):

@@ -3,9 +3,9 @@ array front end ``solve_lps``).
 
 The default list route builds every member's tableau on the host -- build_tableau, a dense [A | I | b] matrix
 per member and its artificial twin for a two-phase member -- stacks them and uploads them all.  Here a problem
-is only *lowered*: the steps of build-tableau that need the problem's names (src/simplex.lisp:189-241, :270-283:
-var-mappings, bound rows, offsets, the objective row's signs) leave one row of doubles per constraint, in column
-space, and everything after that -- the flip of a negative right-hand side, slack and artificial columns, both
+is only *lowered*: the first stage of build-tableau, the one that needs the problem's names (lowering.lower,
+the very function build_tableau starts with: src/simplex.lisp:189-241, :270-283), leaves one row of doubles per
+constraint, in column space, and everything after that -- the flip of a negative right-hand side, slack and artificial columns, both
 bases, the artificial objective row (:243-328) -- is k_blp_rows / k_blp_assemble / k_blp_art_objective on the
 device (mi355x_multibatch_create_lps, csrc/kernels_batch_lps.inc).  What a batch starts from is what
 build_tableau produces, bit for bit, so are the pivot sequences and every result.  The exact batches have the
@@ -17,6 +17,7 @@ import numpy as np
 
 from . import capi
 from .batch import MultiDeviceBatch
+from .lowering import DOUBLE, lower
 
 SENSES = {"<=": 0, ">=": 1, "=": 2}
 
@@ -35,67 +36,16 @@ def host_reason(problem):
 
 
 def lower_problem_rows(problem):
-    """build_tableau's steps :189-241 and :270-283 without a dense tableau: (L, sense, mapping, is_max) with L a
-    float64 array (m + 1) x (ncv + 1) -- per constraint the structural coefficients and the right-hand side less
-    the offsets, then the objective row with its signs applied and its constant -- sense an int32 array (0 `<=`,
-    1 `>=`, 2 `=`), mapping build_tableau's var_mapping.  The statements are build_tableau's, in its order:
-    float() of every number, a coefficient assigned (a later term of the same variable replaces an earlier one),
-    the right-hand side float(rhs) less float(coef) * offset per term, the constant plus the same products.  None
-    for what stays on the default route (host_reason)."""
+    """lowering.lower in doubles, the first stage of build_tableau: (L, sense, mapping, is_max) with L a float64
+    array (m + 1) x (ncv + 1) -- per constraint the structural coefficients and the right-hand side less the
+    offsets, then the objective row with its signs applied and its constant -- sense an int32 array (0 `<=`,
+    1 `>=`, 2 `=`), mapping build_tableau's var_mapping.  None for what stays on the default route
+    (host_reason)."""
     if host_reason(problem) is not None:
         return None
-    f = float
-    constraints = [(op, list(expr), rhs) for op, expr, rhs in problem.constraints]
-    bounds = dict(problem.var_bounds)
-    mappings, column = {}, 0
-    for var in problem.vars:                                              # :189-212
-        if var not in bounds:
-            mappings[var] = ("positive", column, 0.0)
-        else:
-            lb, ub = bounds[var]
-            if lb is not None and ub is not None:
-                if 0 <= ub:
-                    constraints.insert(0, ("<=", [(var, 1)], ub))
-                else:
-                    constraints.insert(0, (">=", [(var, 1)], -ub))
-                mappings[var] = ("positive", column, f(lb))
-            elif lb is not None:
-                mappings[var] = ("positive", column, f(lb))
-            elif ub is not None:
-                mappings[var] = ("negative", column, f(ub))
-            else:
-                mappings[var] = ("signed", column)
-                column += 1
-        column += 1
-    ncv, m = column, len(constraints)
-    L = np.zeros((m + 1, ncv + 1))
-    sense = np.empty(m, dtype=np.int32)
-    for row, (op, expr, rhs) in enumerate(constraints):                   # :223-241
-        sense[row] = SENSES[op]
-        L[row, ncv] = f(rhs)
-        for var, coef in expr:
-            mp = mappings[var]
-            if mp[0] == "positive":
-                L[row, mp[1]] = f(coef)
-                L[row, ncv] -= f(coef) * mp[2]
-            elif mp[0] == "negative":
-                L[row, mp[1]] = -f(coef)
-                L[row, ncv] -= f(coef) * mp[2]
-            else:
-                L[row, mp[1]] = f(coef)
-                L[row, mp[1] + 1] = -f(coef)
-    for var, coef in problem.objective_func:                              # :270-283
-        mp = mappings[var]
-        if mp[0] == "positive":
-            L[m, mp[1]] = -f(coef)
-            L[m, ncv] += f(coef) * mp[2]
-        elif mp[0] == "negative":
-            L[m, mp[1]] = f(coef)
-            L[m, ncv] += f(coef) * mp[2]
-        else:
-            L[m, mp[1]] = -f(coef)
-            L[m, mp[1] + 1] = f(coef)
-    return LoweredRows(L, sense, mappings, problem.type == "max")
+    L, _, constraints, mapping = lower(problem, DOUBLE)
+    sense = np.array([SENSES[op] for op, _, _ in constraints], dtype=np.int32)
+    return LoweredRows(L, sense, mapping, problem.type == "max")
 
 
 def row_counts(L, sense):

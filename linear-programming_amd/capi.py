@@ -343,5 +343,10 @@ def check(code, where):
     return code
 
 
+def _ptr(a):
+    """A numpy array (or None) as the void pointer an entry takes."""
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
 def device_count():
     return int(lib().mi355x_device_count())

@@ -26,13 +26,12 @@ from fractions import Fraction
 import numpy as np
 
 from . import capi
+from .capi import _ptr
 from .conditions import UnsupportedConstraintError
+from .lowering import EXACT
+from .simplex import TableauStruct
 
 _I64_MAX = (1 << 63) - 1
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 def _declined(what):
@@ -89,21 +88,17 @@ def _num_den(matrix):
     return num, den
 
 
-class ExactTableau:
+class ExactTableau(TableauStruct):
     """The `tableau` struct (src/simplex.lisp:48-58) with rational entries, behind an exact device
     handle.  `.matrix` is an object array of Fractions (downloaded T / D), `.basis_columns` an int64
     array; `pivot_trace()` and `bits` as for Tableau."""
     exact = True
+    ns, _entry = EXACT, "xtab"
     pivot_rule = "dantzig"                 # set_pivot_rule; the handle gets it when it is made
 
     def __init__(self, problem, instance_problem, matrix, basis_columns, var_count, constraint_count,
                  var_mapping, device=0, min_bits=0, max_bits=128, pivot_rule="dantzig"):
-        self.problem = problem
-        self.instance_problem = instance_problem
-        self.var_count = int(var_count)
-        self.constraint_count = int(constraint_count)
-        self.var_mapping = var_mapping
-        self.device = device
+        self._struct(problem, instance_problem, var_count, constraint_count, var_mapping, device)
         self.min_bits = int(min_bits)
         self.max_bits = int(max_bits)            # the widest width its solves may escalate to: 128 or 256
         _check_widths(self.min_bits, self.max_bits)
@@ -145,9 +140,6 @@ class ExactTableau:
             capi.check(capi.lib().mi355x_xtab_set_pivot_rule(self._handle, code), "mi355x_xtab_set_pivot_rule")
         self.pivot_rule = name
 
-    def _touch(self):
-        self._stale = True
-
     def raw(self):
         """(T as Python ints, D, basis) as the device holds them."""
         R, C = self._matrix.shape
@@ -180,26 +172,6 @@ class ExactTableau:
             self._matrix, self._basis, self._stale = M, b, False
 
     @property
-    def matrix(self):
-        """tableau-matrix: Fractions."""
-        self._refresh()
-        return self._matrix
-
-    @property
-    def basis_columns(self):
-        """tableau-basis-columns."""
-        self._refresh()
-        return self._basis
-
-    def _readback(self):
-        M = self.matrix
-        return M[-1], M[:, -1], self.basis_columns
-
-    @property
-    def is_max(self):
-        return self.instance_problem.type == "max"
-
-    @property
     def bits(self):
         """The width the device uses for this tableau: 64, 128 or 256."""
         b = ctypes.c_int(0)
@@ -224,15 +196,6 @@ class ExactTableau:
             check(capi.lib().mi355x_xtab_trace(self._h, _ptr(ec), _ptr(cr), cap, ctypes.byref(n)), "mi355x_xtab_trace")
         k = min(n.value, cap)
         return np.stack([ec[:k], cr[:k]], axis=1)
-
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        self._handle = None
-        if h:
-            try:
-                capi.lib().mi355x_xtab_destroy(h)
-            except Exception:
-                pass
 
 
 def cancel_solve(tableau):

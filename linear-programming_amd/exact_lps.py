@@ -3,9 +3,9 @@ and the array front end ``solve_lps_exact``).
 
 The default exact route builds every member's tableau on the host -- build_tableau(exact=True), one Fraction
 per entry -- and uploads it, with its artificial twin for a two-phase member.  Here a problem is only
-*lowered*: the steps of build-tableau that need the problem's names (src/simplex.lisp:189-241, :270-283:
-var-mappings, bound rows, offsets, the objective row's signs) leave one row of numerators and denominators per
-constraint, in column space, and everything after that -- the flip of a negative right-hand side, slack and
+*lowered*: the first stage of build-tableau, the one that needs the problem's names (lowering.lower, the very
+function build_tableau(exact=True) starts with: src/simplex.lisp:189-241, :270-283), leaves one row of
+numerators and denominators per constraint, in column space, and everything after that -- the flip of a negative right-hand side, slack and
 artificial columns, the artificial objective row, the integer scale (:243-328 and x_start_state) -- is
 k_xb_assemble_lps on the device (mi355x_xbatch_create_lps, csrc/kernels_exact_lps.inc).  The members a batch
 solves are the ones the default route solves, entry for entry, so are the pivot sequences and every result.
@@ -23,6 +23,7 @@ from . import capi
 from .conditions import UnsupportedConstraintError
 from .exact import (ExactTableau, XBatch, _I64_MAX, _check_widths, _declined, _member_error, _ptr, batch_in_chunks,
                     pivot_rule_code, rational_problem)
+from .lowering import EXACT, lower
 from .problem import Problem
 
 SENSES = {"<=": 0, ">=": 1, "=": 2}
@@ -43,74 +44,26 @@ def host_reason(problem):
     return None
 
 
-def _put(num, den, row, col, x):
-    n, d = x.numerator, x.denominator
-    if abs(n) > _I64_MAX or d > _I64_MAX:
+def _check64(x):
+    if abs(x.numerator) > _I64_MAX or x.denominator > _I64_MAX:
         raise _declined(("coefficient", str(x)))
-    num[row][col], den[row][col] = n, d
 
 
 def lower_problem(problem):
-    """build-tableau's steps :189-241 and :270-283 without a dense object matrix: (num, den, sense, mapping,
-    is_max) with num / den int64 arrays (m + 1) x (ncv + 1) -- per constraint the structural coefficients and
-    the right-hand side less the offsets, then the objective row with its signs applied and its constant --
-    sense an int32 array (0 `<=`, 1 `>=`, 2 `=`), mapping build_tableau's var_mapping.  Numerators and
-    denominators are copied; Fraction arithmetic happens only where an offset meets a coefficient.  Raises the
-    ("exact", "coefficient", ...) decline for a value beyond 64 bits; None for what stays on the host route
-    (host_reason)."""
+    """lowering.lower in Fractions as what crosses the boundary: (num, den, sense, mapping, is_max) with num /
+    den int64 arrays (m + 1) x (ncv + 1) -- per constraint the structural coefficients and the right-hand side
+    less the offsets, then the objective row with its signs applied and its constant -- sense an int32 array
+    (0 `<=`, 1 `>=`, 2 `=`), mapping build_tableau's var_mapping.  Raises the ("exact", "coefficient", ...)
+    decline for a value beyond 64 bits as it is stored (also one that a later term of the same variable
+    replaces); None for what stays on the host route (host_reason)."""
     if host_reason(problem) is not None:
         return None
-    constraints = [(op, expr, rhs) for op, expr, rhs in problem.constraints]
-    bounds = dict(problem.var_bounds)
-    zero = Fraction(0)
-    mappings, column = {}, 0
-    for var in problem.vars:                                              # :189-212
-        if var not in bounds:
-            mappings[var] = ("positive", column, zero)
-        else:
-            lb, ub = bounds[var]
-            if lb is not None and ub is not None:
-                if 0 <= ub:
-                    constraints.insert(0, ("<=", [(var, 1)], ub))
-                else:
-                    constraints.insert(0, (">=", [(var, 1)], -ub))
-                mappings[var] = ("positive", column, Fraction(lb))
-            elif lb is not None:
-                mappings[var] = ("positive", column, Fraction(lb))
-            elif ub is not None:
-                mappings[var] = ("negative", column, Fraction(ub))
-            else:
-                mappings[var] = ("signed", column)
-                column += 1
-        column += 1
-    ncv, m = column, len(constraints)
-    num = [[0] * (ncv + 1) for _ in range(m + 1)]
-    den = [[1] * (ncv + 1) for _ in range(m + 1)]
-    sense = np.empty(m, dtype=np.int32)
-    for row, (op, expr, rhs) in enumerate(constraints):                   # :223-241
-        sense[row] = SENSES[op]
-        for var, coef in expr:
-            mp = mappings[var]
-            if mp[0] == "signed":
-                _put(num, den, row, mp[1], coef)
-                _put(num, den, row, mp[1] + 1, -coef)
-                continue
-            _put(num, den, row, mp[1], coef if mp[0] == "positive" else -coef)
-            if mp[2]:
-                rhs = rhs - coef * mp[2]
-        _put(num, den, row, ncv, rhs)
-    const = 0
-    for var, coef in problem.objective_func:                              # :270-283
-        mp = mappings[var]
-        if mp[0] == "signed":
-            _put(num, den, m, mp[1], -coef)
-            _put(num, den, m, mp[1] + 1, coef)
-            continue
-        _put(num, den, m, mp[1], -coef if mp[0] == "positive" else coef)
-        if mp[2]:
-            const = const + coef * mp[2]
-    _put(num, den, m, ncv, const)
-    return Lowered(np.array(num, dtype=np.int64), np.array(den, dtype=np.int64), sense, mappings, problem.type == "max")
+    L, _, constraints, mapping = lower(problem, EXACT, stored=_check64)
+    flat = L.ravel().tolist()                                             # (every stored value has been checked)
+    num = np.array([x.numerator for x in flat], dtype=np.int64).reshape(L.shape)
+    den = np.array([x.denominator for x in flat], dtype=np.int64).reshape(L.shape)
+    sense = np.array([SENSES[op] for op, _, _ in constraints], dtype=np.int32)
+    return Lowered(num, den, sense, EXACT.mapping(mapping), problem.type == "max")
 
 
 def row_counts(num, sense):

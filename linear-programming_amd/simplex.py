@@ -12,52 +12,96 @@ The tableau lives in HBM behind ``Tableau._h``; ``Tableau.matrix`` / ``basis_col
 host copies refreshed lazily after every device-side mutation.
 """
 import ctypes
-from fractions import Fraction
 
 import numpy as np
 
 from . import capi
-from .conditions import (InfeasibleProblemError, ParsingError, SolverError,
-                         UnboundedProblemError, UnsupportedConstraintError)
+from .capi import _ptr
+from .conditions import InfeasibleProblemError, SolverError, UnboundedProblemError, UnsupportedConstraintError
+from .lowering import DOUBLE, EXACT, build
 from .problem import Problem
 
-_i64p = ctypes.POINTER(ctypes.c_int64)
 
+class TableauStruct:
+    """What Tableau, SingleTableau and ExactTableau share: the fields of the `tableau` struct
+    (src/simplex.lisp:48-58: problem, instance-problem, matrix, basis-columns, var-count,
+    constraint-count, var-mapping), host copies of matrix and basis that the class's _refresh brings
+    up to date after a device-side mutation (_touch), and the release of the handle.  A class names
+    its number system (lowering.py) and the prefix of its C entries: mi355x_<_entry>_*."""
+    exact = False
+    ns = _entry = None
+    _handle = _light = None
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-
-
-class Tableau:
-    """The `tableau` struct (src/simplex.lisp:48-58): problem, instance-problem, matrix,
-    basis-columns, var-count, constraint-count, var-mapping, fp-tolerance-factor."""
-    exact = False                       # (exact.ExactTableau: the same read-back in Fractions)
-
-    def __init__(self, problem, instance_problem, matrix, basis_columns, var_count,
-                 constraint_count, var_mapping, fp_tolerance_factor=1024, device=0, _handle=None):
+    def _struct(self, problem, instance_problem, var_count, constraint_count, var_mapping, device,
+                matrix=None, basis_columns=None):
+        """The fields; matrix (contiguous, of the class's type) and basis_columns: the host copies a tableau
+        starts from (the upload happens at the first device operation)."""
         self.problem = problem
         self.instance_problem = instance_problem
         self.var_count = int(var_count)
         self.constraint_count = int(constraint_count)
         self.var_mapping = var_mapping
-        self.fp_tolerance_factor = fp_tolerance_factor
         self.device = device
-        self._matrix = None
-        self._basis = None
+        if matrix is None:
+            return
+        basis = np.ascontiguousarray(basis_columns, dtype=np.int64)
+        if matrix.shape != (self.constraint_count + 1, self.var_count + 1):
+            raise ValueError("matrix shape %r does not match counts" % (matrix.shape,))
+        if basis.shape != (self.constraint_count,):
+            raise ValueError("basis length %r does not match constraint count" % (basis.shape,))
+        self._matrix, self._basis, self._stale = matrix.copy(), basis.copy(), False
+
+    def _entry_point(self, name):
+        return getattr(capi.lib(), "mi355x_%s_%s" % (self._entry, name))
+
+    def _touch(self):
         self._stale = True
         self._light = None
+
+    def _readback(self):
+        """(objective row, RHS column, basis) -- all the read-back functions need (src/simplex.lisp:74-120)."""
+        M = self.matrix
+        return M[-1], M[:, -1], self.basis_columns
+
+    @property
+    def matrix(self):
+        """tableau-matrix (host copy of the device-resident matrix)."""
+        self._refresh()
+        return self._matrix
+
+    @property
+    def basis_columns(self):
+        """tableau-basis-columns."""
+        self._refresh()
+        return self._basis
+
+    @property
+    def is_max(self):
+        return self.instance_problem.type == "max"
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
         self._handle = None
+        if h:
+            try:
+                self._entry_point("destroy")(h)
+            except Exception:
+                pass
+
+
+class Tableau(TableauStruct):
+    """The `tableau` struct in double-float, with fp-tolerance-factor, behind a mi355x_tab."""
+    ns, _entry = DOUBLE, "tab"
+
+    def __init__(self, problem, instance_problem, matrix, basis_columns, var_count,
+                 constraint_count, var_mapping, fp_tolerance_factor=1024, device=0, _handle=None):
+        self.fp_tolerance_factor = fp_tolerance_factor
         if _handle is not None:
-            self._handle = _handle
+            self._struct(problem, instance_problem, var_count, constraint_count, var_mapping, device)
+            self._handle, self._matrix, self._basis, self._stale = _handle, None, None, True
         else:
-            matrix = np.ascontiguousarray(matrix, dtype=np.float64)
-            basis = np.ascontiguousarray(basis_columns, dtype=np.int64)
-            if matrix.shape != (self.constraint_count + 1, self.var_count + 1):
-                raise ValueError("matrix shape %r does not match counts" % (matrix.shape,))
-            if basis.shape != (self.constraint_count,):
-                raise ValueError("basis length %r does not match constraint count" % (basis.shape,))
-            # host arrays only; the upload happens at the first device operation
-            self._matrix, self._basis, self._stale = matrix.copy(), basis.copy(), False
+            self._struct(problem, instance_problem, var_count, constraint_count, var_mapping, device,
+                         np.ascontiguousarray(matrix, dtype=np.float64), basis_columns)
 
     # -- device <-> host
     @property
@@ -80,17 +124,12 @@ class Tableau:
                                                       None, None), "mi355x_tab_download")
             self._matrix, self._basis, self._stale = M, b, False
 
-    def _touch(self):
-        self._stale = True
-        self._light = None
-
     def _readback(self):
-        """(objective row, RHS column, basis) -- all the read-back functions need
-        (src/simplex.lisp:74-120).  Served from the host copy when it is current, otherwise
-        fetched alone (mi355x_tab_download without the matrix), never the whole tableau."""
+        """Served from the host copy when it is current, otherwise fetched alone
+        (mi355x_tab_download without the matrix), never the whole tableau."""
         if not self._stale:
             return self._matrix[-1], self._matrix[:, -1], self._basis
-        if getattr(self, "_light", None) is None:
+        if self._light is None:
             R, C = self.constraint_count + 1, self.var_count + 1
             row, col = np.empty(C), np.empty(R)
             b = np.empty(max(R - 1, 0), dtype=np.int64)
@@ -98,22 +137,6 @@ class Tableau:
                                                       _ptr(row), _ptr(col)), "mi355x_tab_download")
             self._light = (row, col, b)
         return self._light
-
-    @property
-    def matrix(self):
-        """tableau-matrix (host copy of the HBM-resident matrix)."""
-        self._refresh()
-        return self._matrix
-
-    @property
-    def basis_columns(self):
-        """tableau-basis-columns."""
-        self._refresh()
-        return self._basis
-
-    @property
-    def is_max(self):
-        return self.instance_problem.type == "max"
 
     def pivot_trace(self, cap=1 << 20):
         """(entering column, row) of every pivot made on this tableau since it was uploaded."""
@@ -124,15 +147,6 @@ class Tableau:
                    "mi355x_tab_trace")
         k = min(n.value, cap)
         return np.stack([ec[:k], cr[:k]], axis=1)
-
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        self._handle = None
-        if h:
-            try:
-                capi.lib().mi355x_tab_destroy(h)
-            except Exception:
-                pass
 
 
 def copy_tableau(tableau):
@@ -146,30 +160,22 @@ def copy_tableau(tableau):
 
 
 # ------------------------------------------------------------------ read-back (host, O(n))
-def _value(tableau, x):
-    """An entry as the read-back returns it: a double, or the exact Fraction of an ExactTableau."""
-    return Fraction(x) if tableau.exact else float(x)
-
-
+# One copy for the three tableau classes: entries come back as the tableau's number system returns them
+# (ns.value: float, Fraction, np.float32) and a mapping's offset is added as ns.offset of it (single-float: in
+# float32).
 def tableau_objective_value(tableau):
     """tableau-objective-value (src/simplex.lisp:74-78)."""
-    if getattr(tableau, "single", False):
-        from . import single
-        return single.tableau_objective_value(tableau)
-    return _value(tableau, tableau._readback()[0][tableau.var_count])
+    return tableau.ns.value(tableau._readback()[0][tableau.var_count])
 
 
 def _basic_value(tableau, col):
     _, rhs, basis = tableau._readback()
     pos = np.nonzero(basis == col)[0]                       # `position`: first match
-    return _value(tableau, rhs[pos[0]] if pos.size else 0)
+    return tableau.ns.value(rhs[pos[0]] if pos.size else 0)
 
 
 def tableau_variable(tableau, var):
-    """tableau-variable (src/simplex.lisp:81-107)."""
-    if getattr(tableau, "single", False):
-        from . import single
-        return single.tableau_variable(tableau, var)
+    """tableau-variable (src/simplex.lisp:81-107), the bound's offset included."""
     if var == tableau.instance_problem.objective_var:
         return tableau_objective_value(tableau)
     mapping = tableau.var_mapping.get(var)
@@ -177,23 +183,20 @@ def tableau_variable(tableau, var):
         raise KeyError("%s is not a variable in the tableau" % (var,))
     kind = mapping[0]
     if kind == "positive":
-        return mapping[2] + _basic_value(tableau, mapping[1])
+        return tableau.ns.offset(mapping[2]) + _basic_value(tableau, mapping[1])
     if kind == "negative":
-        return mapping[2] + (-_basic_value(tableau, mapping[1]))
+        return tableau.ns.offset(mapping[2]) + (-_basic_value(tableau, mapping[1]))
     return _basic_value(tableau, mapping[1]) - _basic_value(tableau, mapping[1] + 1)
 
 
 def tableau_reduced_cost(tableau, var):
     """tableau-reduced-cost (src/simplex.lisp:111-120)."""
-    if getattr(tableau, "single", False):
-        from . import single
-        return single.tableau_reduced_cost(tableau, var)
     mapping = tableau.var_mapping.get(var)
     if mapping is None:
         raise KeyError("%s is not a variable in the tableau" % (var,))
     if mapping[0] != "positive":
         raise ValueError("%s has no lower bound" % (var,))
-    return _value(tableau, tableau._readback()[0][mapping[1]])
+    return tableau.ns.value(tableau._readback()[0][mapping[1]])
 
 
 def with_tableau_variables(var_list, tableau):
@@ -211,7 +214,7 @@ def with_tableau_variables(var_list, tableau):
 def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, device=0, exact=False, min_bits=0,
                   general=False, max_bits=128):
     """build-tableau (src/simplex.lisp:142-328) in double-float: returns a Tableau, or
-    [art_tableau, main_tableau] when the trivial basis is infeasible.
+    [art_tableau, main_tableau] when the trivial basis is infeasible.  The steps are lowering.py's.
 
     This is the producer of what crosses the boundary; in the Lisp deployment the reference's
     own build-tableau does this job and the glue converts the result to double-float.
@@ -225,166 +228,40 @@ def build_tableau(problem, instance_problem=None, fp_tolerance_factor=1024, devi
     if instance_problem is None:
         instance_problem = problem
     if exact:
-        from fractions import Fraction
-        f, zero, one = Fraction, Fraction(0), Fraction(1)
+        from .exact import ExactTableau
 
-        def zeros(shape):
-            return np.full(shape, Fraction(0), dtype=object)
+        def make(inst, M, basis, mapping):
+            return ExactTableau(problem, inst, M, basis, M.shape[1] - 1, M.shape[0] - 1, mapping, device, min_bits,
+                                max_bits)
     else:
-        f, zero, one, zeros = float, 0.0, 1.0, np.zeros
-    constraints = [(op, list(expr), rhs) for op, expr, rhs in instance_problem.constraints]
-    pvars = list(problem.vars)
-    n = len(pvars)
-    bounds = dict(problem.var_bounds)
-    mappings = {}
-
-    def mk(matrix, basis, var_count, ccount, inst):
-        if exact:
-            from .exact import ExactTableau
-            return ExactTableau(problem, inst, matrix, basis, var_count, ccount, mappings, device, min_bits, max_bits)
-        return Tableau(problem, inst, matrix, basis, var_count, ccount, mappings,
-                       fp_tolerance_factor, device)
-
-    if not constraints and not general:                                  # :153-186
-        M = zeros((n + 1, n + 1))
-        basis = np.arange(n, dtype=np.int64)
-        objd = dict(problem.objective_func)
-        is_max = problem.type == "max"
-        objective_value = zero
-        for i, var in enumerate(pvars):
-            coef = objd[var]
-            lb, ub = bounds.get(var, (None, None))
-            M[i, i] = one
-            if (0 <= coef) == is_max:
-                if ub is None:
-                    raise UnboundedProblemError()
-                mappings[var] = ("positive", i, f(ub))
-                objective_value = objective_value + f(coef) * f(ub)
-            else:
-                if lb is None:
-                    raise UnboundedProblemError()
-                mappings[var] = ("positive", i, f(lb))
-                objective_value = objective_value + f(coef) * f(lb)
-        M[n, n] = objective_value
-        return mk(M, basis, n, n, problem)
-
-    ncv = n                                                              # :189-212
-    column = 0
-    for var in pvars:
-        if var not in bounds:
-            mappings[var] = ("positive", column, zero)
-        else:
-            lb, ub = bounds[var]
-            if lb is not None and ub is not None:
-                if 0 <= ub:
-                    constraints.insert(0, ("<=", [(var, 1)], ub))
-                else:
-                    constraints.insert(0, (">=", [(var, 1)], -ub))
-                mappings[var] = ("positive", column, f(lb))
-            elif lb is not None:
-                mappings[var] = ("positive", column, f(lb))
-            elif ub is not None:
-                mappings[var] = ("negative", column, f(ub))
-            else:
-                mappings[var] = ("signed", column)
-                column += 1
-                ncv += 1
-        column += 1
-
-    m = len(constraints)                                                 # :214-221
-    num_slack = sum(1 for c in constraints if c[0] != "=")
-    num_cols = ncv + num_slack + 1
-    M = zeros((m + 1, num_cols))
-    basis = np.zeros(m, dtype=np.int64)
-    art_rows = []
-    col_offset = 0
-    for row, (op, expr, rhs) in enumerate(constraints):                  # :223-268
-        M[row, num_cols - 1] = f(rhs)
-        for var, coef in expr:
-            mp = mappings[var]
-            if mp[0] == "positive":
-                M[row, mp[1]] = f(coef)
-                M[row, num_cols - 1] -= f(coef) * mp[2]
-            elif mp[0] == "negative":
-                M[row, mp[1]] = -f(coef)
-                M[row, num_cols - 1] -= f(coef) * mp[2]
-            else:
-                M[row, mp[1]] = f(coef)
-                M[row, mp[1] + 1] = -f(coef)
-        if M[row, num_cols - 1] < 0:                                     # :243-252
-            M[row, :] = -M[row, :]
-            op = {"<=": ">=", ">=": "<=", "=": "="}.get(op, op)
-        if op == "<=":                                                   # :254-265
-            M[row, ncv + col_offset] = one
-            basis[row] = ncv + col_offset
-            col_offset += 1
-        elif op == ">=":
-            art_rows.insert(0, row)
-            M[row, ncv + col_offset] = -one
-            basis[row] = num_cols
-            col_offset += 1
-        elif op == "=":
-            art_rows.insert(0, row)
-            basis[row] = num_cols
-        else:
-            raise ParsingError("%r is not a valid constraint equation" % ((op, expr, rhs),))
-    for var, coef in problem.objective_func:                             # :270-283
-        mp = mappings[var]
-        if mp[0] == "positive":
-            M[m, mp[1]] = -f(coef)
-            M[m, num_cols - 1] += f(coef) * mp[2]
-        elif mp[0] == "negative":
-            M[m, mp[1]] = f(coef)
-            M[m, num_cols - 1] += f(coef) * mp[2]
-        else:
-            M[m, mp[1]] = -f(coef)
-            M[m, mp[1] + 1] = f(coef)
-    main = mk(M, basis, num_cols - 1, m, instance_problem)
-    if not art_rows or general:
-        return main
-    num_art = len(art_rows)                                              # :292-325
-    nac = num_cols + num_art
-    A = zeros((m + 1, nac))
-    abasis = basis.copy()
-    for i, row in enumerate(art_rows):
-        abasis[row] = num_cols - 1 + i
-        A[row, num_cols - 1 + i] = one
-    A[:m, :num_cols - 1] = M[:m, :num_cols - 1]
-    A[:m, nac - 1] = M[:m, num_cols - 1]
-    for c in list(range(num_cols - 1)) + [nac - 1]:
-        s = zero
-        for r in range(m):                                               # same summation order
-            if r in art_rows:
-                s = s + A[r, c]
-        A[m, c] = s
-    art_problem = Problem(type="min", vars=list(problem.vars))           # artificial problem
-    art = mk(A, abasis, num_cols - 1 + num_art, m, art_problem)
-    return [art, main]
+        def make(inst, M, basis, mapping):
+            return Tableau(problem, inst, M, basis, M.shape[1] - 1, M.shape[0] - 1, mapping,
+                           fp_tolerance_factor, device)
+    return build(problem, instance_problem, EXACT if exact else DOUBLE, make, general)
 
 
 # ------------------------------------------------------------------ the hot path (device)
+# (a Tableau or a SingleTableau: the same three entries behind the class's prefix)
 def find_entering_column(tableau):
     """find-entering-column (src/simplex.lisp:362-379): column index or None."""
     col = ctypes.c_int64(-1)
-    capi.check(capi.lib().mi355x_tab_price(tableau._h, int(tableau.is_max),
-                                           float(tableau.fp_tolerance_factor), ctypes.byref(col)),
-               "mi355x_tab_price")
+    capi.check(tableau._entry_point("price")(tableau._h, int(tableau.is_max), float(tableau.fp_tolerance_factor),
+                                             ctypes.byref(col)), "mi355x_%s_price" % tableau._entry)
     return None if col.value < 0 else int(col.value)
 
 
 def find_pivoting_row(tableau, entering_col):
     """find-pivoting-row (src/simplex.lisp:382-389): row index or None."""
     row = ctypes.c_int64(-1)
-    capi.check(capi.lib().mi355x_tab_ratio(tableau._h, int(entering_col),
-                                           float(tableau.fp_tolerance_factor), ctypes.byref(row)),
-               "mi355x_tab_ratio")
+    capi.check(tableau._entry_point("ratio")(tableau._h, int(entering_col), float(tableau.fp_tolerance_factor),
+                                             ctypes.byref(row)), "mi355x_%s_ratio" % tableau._entry)
     return None if row.value < 0 else int(row.value)
 
 
 def n_pivot_row(tableau, entering_col, changing_row):
     """n-pivot-row (src/simplex.lisp:337-359): destructively applies a single pivot."""
-    capi.check(capi.lib().mi355x_tab_pivot(tableau._h, int(entering_col), int(changing_row)),
-               "mi355x_tab_pivot")
+    capi.check(tableau._entry_point("pivot")(tableau._h, int(entering_col), int(changing_row)),
+               "mi355x_%s_pivot" % tableau._entry)
     tableau._touch()
     return tableau
 

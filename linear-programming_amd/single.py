@@ -3,9 +3,10 @@ single-float-epsilon) over the mi355x_stab_* entries of the C ABI.
 
 Common Lisp reads ``0.5`` as a single-float, and the reference then solves in single-float arithmetic
 with single-float thresholds.  ``solve_single`` / ``mi355x_simplex_solver(problem, precision="single")``
-is that path: build-tableau with Lisp's contagion (integers stay exact Python ints among themselves, an
-int becomes float32 when it meets a float, every float operation is an explicit ``np.float32``
-operation), the solve in IEEE binary32 on the GPU (kernels_single.inc), the read-back in float32.
+is that path: build-tableau -- lowering.py's, the one copy every precision runs -- on a number system with
+Lisp's contagion (SINGLE: integers stay exact Python ints among themselves, an int becomes float32 when it
+meets a float, every float operation is an explicit ``np.float32`` operation), the solve in IEEE binary32
+on the GPU (kernels_single.inc), the read-back (simplex.tableau_variable and the others) in float32.
 
 Which problems qualify: every number is an integer with |x| <= 2**24 or a float whose value a binary32
 holds exactly (``np.float32``, or a Python float with ``float(np.float32(x)) == x``).  Anything else -- a
@@ -21,8 +22,11 @@ import ctypes
 import numpy as np
 
 from . import capi
-from .conditions import ParsingError, UnboundedProblemError, UnsupportedConstraintError
-from .problem import Problem
+from .capi import _ptr
+from .conditions import UnsupportedConstraintError
+from .lowering import NumberSystem, build
+from .simplex import (TableauStruct, find_entering_column, find_pivoting_row, n_pivot_row,      # noqa: F401
+                      tableau_objective_value, tableau_reduced_cost, tableau_variable)
 
 #: SBCL's single-float-epsilon = 2^-24 (1 + 2^-23)
 EPSILON_SINGLE = np.float32(2.0 ** -24 * (1 + 2.0 ** -23))
@@ -35,10 +39,6 @@ def thresholds(factor=1024):
     return (np.float32(np.float32(f / np.float32(8)) * EPSILON_SINGLE),
             np.float32(np.float32(0) + np.float32(np.float32(f / np.float32(2)) * EPSILON_SINGLE)),
             np.float32(f * EPSILON_SINGLE))
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
 
 
 # ------------------------------------------------------------------ which numbers qualify
@@ -74,64 +74,68 @@ def check_single_problem(problem):
 
 
 # ------------------------------------------------------------------ Lisp's contagion on (int | float32)
-def _n(x):
-    """A qualifying number as Lisp holds it: an exact int, or a single-float."""
-    return int(x) if isinstance(x, (int, np.integer)) else np.float32(x)
+class _Lisp:
+    """A qualifying number as Lisp holds it while build-tableau computes: v is an exact int or a single-float.
+    The operators are Lisp's contagion: two ints stay an exact int, anything else is a float32 operation."""
+    __slots__ = ("v",)
+
+    def __init__(self, v):
+        self.v = v
+
+    def __add__(self, other):
+        a, b = self.v, other.v
+        return _Lisp(a + b if type(a) is int and type(b) is int else np.float32(a) + np.float32(b))
+
+    def __sub__(self, other):
+        a, b = self.v, other.v
+        return _Lisp(a - b if type(a) is int and type(b) is int else np.float32(a) - np.float32(b))
+
+    def __mul__(self, other):
+        a, b = self.v, other.v
+        return _Lisp(a * b if type(a) is int and type(b) is int else np.float32(a) * np.float32(b))
+
+    def __neg__(self):
+        return _Lisp(-self.v)
+
+    def __lt__(self, number):
+        return self.v < number
 
 
-def _is_int(x):
-    return isinstance(x, int)
-
-
-def _mul(a, b):
-    return a * b if _is_int(a) and _is_int(b) else np.float32(np.float32(a) * np.float32(b))
-
-
-def _add(a, b):
-    return a + b if _is_int(a) and _is_int(b) else np.float32(np.float32(a) + np.float32(b))
-
-
-def _sub(a, b):
-    return a - b if _is_int(a) and _is_int(b) else np.float32(np.float32(a) - np.float32(b))
-
-
-def _neg(a):
-    return -a if _is_int(a) else np.float32(-np.float32(a))
+def _read(x):
+    return _Lisp(int(x) if isinstance(x, (int, np.integer)) else np.float32(x))
 
 
 def _to_f32(M):
-    out = np.empty(M.shape, dtype=np.float32)
-    for idx, x in np.ndenumerate(M):
-        out[idx] = np.float32(x)
-    return out
+    """A finished matrix, coerced to float32 entry by entry."""
+    return np.array([np.float32(x.v) for x in M.flat], dtype=np.float32).reshape(M.shape)
+
+
+def _zeros(shape):
+    M = np.empty(shape, dtype=object)
+    M.fill(SINGLE.zero)
+    return M
+
+
+#: the number system of the single-float build (lowering.py) and read-back: no _Lisp leaves the build -- matrices
+#: go out as float32 arrays, a mapping's offsets as the int or np.float32 they hold
+SINGLE = NumberSystem(_read, _zeros, value=np.float32, offset=np.float32, matrix=_to_f32,
+                      mapping=lambda d: {var: mp[:2] + tuple(x.v for x in mp[2:]) for var, mp in d.items()})
 
 
 # ------------------------------------------------------------------ the tableau
-class SingleTableau:
-    """The `tableau` struct (src/simplex.lisp:48-58) with a single-float matrix, behind a mi355x_stab."""
-    exact = False
-    single = True
+class SingleTableau(TableauStruct):
+    """The `tableau` struct (src/simplex.lisp:48-58) with a single-float matrix, behind a mi355x_stab; its
+    read-back (simplex.tableau_variable and the others) is in np.float32."""
+    ns, _entry = SINGLE, "stab"
 
     def __init__(self, problem, instance_problem, matrix, basis_columns, var_count, constraint_count,
                  var_mapping, fp_tolerance_factor=1024, device=0):
-        self.problem = problem
-        self.instance_problem = instance_problem
-        self.var_count = int(var_count)
-        self.constraint_count = int(constraint_count)
-        self.var_mapping = var_mapping
-        self.fp_tolerance_factor = fp_tolerance_factor
-        self.device = device
         matrix = np.asarray(matrix)
         if matrix.dtype != np.float32:
             raise TypeError("a SingleTableau takes a float32 matrix, not %s" % (matrix.dtype,))
-        matrix = np.ascontiguousarray(matrix)
-        basis = np.ascontiguousarray(basis_columns, dtype=np.int64)
-        if matrix.shape != (self.constraint_count + 1, self.var_count + 1):
-            raise ValueError("matrix shape %r does not match counts" % (matrix.shape,))
-        if basis.shape != (self.constraint_count,):
-            raise ValueError("basis length %r does not match constraint count" % (basis.shape,))
-        self._matrix, self._basis, self._stale = matrix.copy(), basis.copy(), False
-        self._handle = None
+        self._struct(problem, instance_problem, var_count, constraint_count, var_mapping, device,
+                     np.ascontiguousarray(matrix), basis_columns)
+        self.fp_tolerance_factor = fp_tolerance_factor
         self.n_pivots = 0
 
     @property
@@ -153,24 +157,6 @@ class SingleTableau:
                        "mi355x_stab_download")
             self._matrix, self._basis, self._stale = M, b, False
 
-    def _touch(self):
-        self._stale = True
-
-    @property
-    def matrix(self):
-        """tableau-matrix (host copy, float32)."""
-        self._refresh()
-        return self._matrix
-
-    @property
-    def basis_columns(self):
-        self._refresh()
-        return self._basis
-
-    @property
-    def is_max(self):
-        return self.instance_problem.type == "max"
-
     def info(self):
         """mi355x_stab_info: {"rows", "cols", "ld", "form" (1 pair, 2 LDS), "lds_budget"}."""
         r, c, ld, budget = (ctypes.c_int64() for _ in range(4))
@@ -188,215 +174,24 @@ class SingleTableau:
         capi.check(capi.lib().mi355x_stab_trace(self._h, _ptr(ec), _ptr(cr), k, ctypes.byref(n)), "mi355x_stab_trace")
         return np.stack([ec[:k], cr[:k]], axis=1)
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        self._handle = None
-        if h:
-            try:
-                capi.lib().mi355x_stab_destroy(h)
-            except Exception:
-                pass
-
 
 def set_form(form):
     """mi355x_tune_set_single_form (tests and measurement): the form handles created from now on take."""
     capi.check(capi.lib().mi355x_tune_set_single_form(int(form)), "mi355x_tune_set_single_form")
 
 
-# ------------------------------------------------------------------ read-back (host, O(n), float32)
-def tableau_objective_value(tableau):
-    """tableau-objective-value (src/simplex.lisp:74-78)."""
-    return np.float32(tableau.matrix[tableau.constraint_count, tableau.var_count])
-
-
-def _basic_value(tableau, col):
-    pos = np.nonzero(tableau.basis_columns == col)[0]        # `position`: first match
-    return np.float32(tableau.matrix[pos[0], tableau.var_count]) if pos.size else np.float32(0)
-
-
-def tableau_variable(tableau, var):
-    """tableau-variable (src/simplex.lisp:81-107) in float32, the lower-bound offset included."""
-    if var == tableau.instance_problem.objective_var:
-        return tableau_objective_value(tableau)
-    mapping = tableau.var_mapping.get(var)
-    if mapping is None:
-        raise KeyError("%s is not a variable in the tableau" % (var,))
-    if mapping[0] == "positive":
-        return np.float32(np.float32(mapping[2]) + _basic_value(tableau, mapping[1]))
-    if mapping[0] == "negative":
-        return np.float32(np.float32(mapping[2]) + np.float32(-_basic_value(tableau, mapping[1])))
-    return np.float32(_basic_value(tableau, mapping[1]) - _basic_value(tableau, mapping[1] + 1))
-
-
-def tableau_reduced_cost(tableau, var):
-    """tableau-reduced-cost (src/simplex.lisp:111-120)."""
-    mapping = tableau.var_mapping.get(var)
-    if mapping is None:
-        raise KeyError("%s is not a variable in the tableau" % (var,))
-    if mapping[0] != "positive":
-        raise ValueError("%s has no lower bound" % (var,))
-    return np.float32(tableau.matrix[tableau.constraint_count, mapping[1]])
-
-
 # ------------------------------------------------------------------ build-tableau (host)
 def build_tableau_single(problem, fp_tolerance_factor=1024, device=0):
     """build-tableau (src/simplex.lisp:142-328) on single-float input: a SingleTableau, or [art, main] when
-    the trivial basis is infeasible.  Numbers are combined the way Lisp's contagion does (module docstring);
-    the finished matrices are coerced to float32 entry by entry."""
+    the trivial basis is infeasible.  The steps are lowering.py's, the ones every precision takes, with the
+    numbers combined the way Lisp's contagion does (SINGLE; module docstring); the finished matrices are
+    coerced to float32 entry by entry."""
     check_single_problem(problem)
-    constraints = [(op, list(expr), rhs) for op, expr, rhs in problem.constraints]
-    pvars = list(problem.vars)
-    n = len(pvars)
-    bounds = dict(problem.var_bounds)
-    mappings = {}
 
-    def zeros(shape):
-        M = np.empty(shape, dtype=object)
-        M.fill(0)
-        return M
-
-    def mk(M, basis, var_count, ccount, inst):
-        return SingleTableau(problem, inst, _to_f32(M), basis, var_count, ccount, mappings, fp_tolerance_factor, device)
-
-    if not constraints:                                                  # :153-186
-        M = zeros((n + 1, n + 1))
-        basis = np.arange(n, dtype=np.int64)
-        objd = dict(problem.objective_func)
-        is_max = problem.type == "max"
-        objective_value = 0
-        for i, var in enumerate(pvars):
-            coef = _n(objd[var])
-            lb, ub = bounds.get(var, (None, None))
-            M[i, i] = 1
-            bound = ub if (0 <= coef) == is_max else lb
-            if bound is None:
-                raise UnboundedProblemError()
-            mappings[var] = ("positive", i, _n(bound))
-            objective_value = _add(objective_value, _mul(coef, _n(bound)))
-        M[n, n] = objective_value
-        return mk(M, basis, n, n, problem)
-
-    ncv = n                                                              # :189-212
-    column = 0
-    for var in pvars:
-        if var not in bounds:
-            mappings[var] = ("positive", column, 0)
-        else:
-            lb, ub = bounds[var]
-            if lb is not None and ub is not None:
-                if 0 <= ub:
-                    constraints.insert(0, ("<=", [(var, 1)], ub))
-                else:
-                    constraints.insert(0, (">=", [(var, 1)], _neg(_n(ub))))
-                mappings[var] = ("positive", column, _n(lb))
-            elif lb is not None:
-                mappings[var] = ("positive", column, _n(lb))
-            elif ub is not None:
-                mappings[var] = ("negative", column, _n(ub))
-            else:
-                mappings[var] = ("signed", column)
-                column += 1
-                ncv += 1
-        column += 1
-
-    m = len(constraints)                                                 # :214-221
-    num_slack = sum(1 for c in constraints if c[0] != "=")
-    num_cols = ncv + num_slack + 1
-    M = zeros((m + 1, num_cols))
-    basis = np.zeros(m, dtype=np.int64)
-    art_rows = []
-    col_offset = 0
-    last = num_cols - 1
-    for row, (op, expr, rhs) in enumerate(constraints):                  # :223-268
-        M[row, last] = _n(rhs)
-        for var, coef in expr:
-            mp, coef = mappings[var], _n(coef)
-            if mp[0] == "positive":
-                M[row, mp[1]] = coef
-                M[row, last] = _sub(M[row, last], _mul(coef, mp[2]))     # :235
-            elif mp[0] == "negative":
-                M[row, mp[1]] = _neg(coef)
-                M[row, last] = _sub(M[row, last], _mul(coef, mp[2]))     # :238
-            else:
-                M[row, mp[1]] = coef
-                M[row, mp[1] + 1] = _neg(coef)
-        if M[row, last] < 0:                                             # :243-252
-            for c in range(num_cols):
-                M[row, c] = _neg(M[row, c])
-            op = {"<=": ">=", ">=": "<=", "=": "="}.get(op, op)
-        if op == "<=":                                                   # :254-265
-            M[row, ncv + col_offset] = 1
-            basis[row] = ncv + col_offset
-            col_offset += 1
-        elif op == ">=":
-            art_rows.insert(0, row)
-            M[row, ncv + col_offset] = -1
-            basis[row] = num_cols
-            col_offset += 1
-        elif op == "=":
-            art_rows.insert(0, row)
-            basis[row] = num_cols
-        else:
-            raise ParsingError("%r is not a valid constraint equation" % ((op, expr, rhs),))
-    for var, coef in problem.objective_func:                             # :270-283
-        mp, coef = mappings[var], _n(coef)
-        if mp[0] == "positive":
-            M[m, mp[1]] = _neg(coef)
-            M[m, last] = _add(M[m, last], _mul(coef, mp[2]))
-        elif mp[0] == "negative":
-            M[m, mp[1]] = coef
-            M[m, last] = _add(M[m, last], _mul(coef, mp[2]))
-        else:
-            M[m, mp[1]] = _neg(coef)
-            M[m, mp[1] + 1] = coef
-    main = mk(M, basis, num_cols - 1, m, problem)
-    if not art_rows:
-        return main
-    num_art = len(art_rows)                                              # :292-325
-    nac = num_cols + num_art
-    A = zeros((m + 1, nac))
-    abasis = basis.copy()
-    for i, row in enumerate(art_rows):
-        abasis[row] = num_cols - 1 + i
-        A[row, num_cols - 1 + i] = 1
-    for c in range(num_cols - 1):
-        for r in range(m):
-            A[r, c] = M[r, c]
-    for r in range(m):
-        A[r, nac - 1] = M[r, last]
-    for c in list(range(num_cols - 1)) + [nac - 1]:
-        s = 0
-        for r in range(m):                                               # same summation order
-            if r in art_rows:
-                s = _add(s, A[r, c])
-        A[m, c] = s
-    art_problem = Problem(type="min", vars=list(problem.vars))           # artificial problem
-    art = mk(A, abasis, num_cols - 1 + num_art, m, art_problem)
-    return [art, main]
-
-
-# ------------------------------------------------------------------ the hot path (device)
-def find_entering_column(tableau):
-    """find-entering-column (src/simplex.lisp:362-379): column index or None."""
-    col = ctypes.c_int64(-1)
-    capi.check(capi.lib().mi355x_stab_price(tableau._h, int(tableau.is_max), float(tableau.fp_tolerance_factor),
-                                            ctypes.byref(col)), "mi355x_stab_price")
-    return None if col.value < 0 else int(col.value)
-
-
-def find_pivoting_row(tableau, entering_col):
-    """find-pivoting-row (src/simplex.lisp:382-389): row index or None."""
-    row = ctypes.c_int64(-1)
-    capi.check(capi.lib().mi355x_stab_ratio(tableau._h, int(entering_col), float(tableau.fp_tolerance_factor),
-                                            ctypes.byref(row)), "mi355x_stab_ratio")
-    return None if row.value < 0 else int(row.value)
-
-
-def n_pivot_row(tableau, entering_col, changing_row):
-    """n-pivot-row (src/simplex.lisp:337-359): destructively applies a single pivot."""
-    capi.check(capi.lib().mi355x_stab_pivot(tableau._h, int(entering_col), int(changing_row)), "mi355x_stab_pivot")
-    tableau._touch()
-    return tableau
+    def make(inst, M, basis, mapping):
+        return SingleTableau(problem, inst, M, basis, M.shape[1] - 1, M.shape[0] - 1, mapping, fp_tolerance_factor,
+                             device)
+    return build(problem, problem, SINGLE, make)
 
 
 def solve_status(tableau, max_pivots=0, chunk=None):
