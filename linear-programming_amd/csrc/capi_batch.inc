@@ -244,19 +244,9 @@ int mi355x_batch_download(mi355x_batch *b, int64_t k, double *hm, int64_t *hb, d
     if (rc != MI_OK) return rc;
     rc = ensure_dense(t);
     if (rc != MI_OK) return rc;
-    const double *M = v.M + k * v.rows * v.ld;
-    if (hm)
-        HIP_TRY(hipMemcpy2DAsync(hm, v.cols * sizeof(double), M, v.ld * sizeof(double),
-                                 v.cols * sizeof(double), v.rows, hipMemcpyDeviceToHost, t->stream));
-    if (hb && v.rows > 1)
-        HIP_TRY(hipMemcpyAsync(hb, v.basis + k * std::max<int64_t>(v.rows - 1, 1),
-                               (v.rows - 1) * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
-    if (last_row)
-        HIP_TRY(hipMemcpyAsync(last_row, M + (v.rows - 1) * v.ld, v.cols * sizeof(double),
-                               hipMemcpyDeviceToHost, t->stream));
-    if (last_col)
-        HIP_TRY(hipMemcpy2DAsync(last_col, sizeof(double), M + (v.cols - 1), v.ld * sizeof(double),
-                                 sizeof(double), v.rows, hipMemcpyDeviceToHost, t->stream));
+    rc = download_parts(v.M + k * v.rows * v.ld, v.ld, v.rows, v.cols, v.basis + k * std::max<int64_t>(v.rows - 1, 1),
+                        t->stream, hm, hb, last_row, last_col);
+    if (rc != MI_OK) return rc;
     HIP_TRY(wait_stream(t->stream));
     return MI_OK;
 }
@@ -463,12 +453,11 @@ void mi355x_multibatch_destroy(mi355x_multibatch *mb) { mb_free(mb); }
 // ---- n-solve-tableau, two-phase branch (src/simplex.lisp:402-452), for a batch -------------------
 // Member k of `art` is the artificial tableau of the problem whose main tableau is member k of
 // `main_mb` (build-tableau's two results, :326-328): phase 1 = the batch loop on `art` (min
-// problems); per member the feasibility test (fp= 0 objective) :405-407 and the hand-over :437-451
-// (mi355x_solve_two_phase's kernels on that member's slices of the two batches); phase 2 = the batch
-// loop on `main_mb`.  A member whose degenerate artificials would have to be driven out of the basis
-// first (:419-434 -- row fetches and single pivots, per member) is DECLINED: status MI_UNSUPPORTED,
-// the caller runs that problem through mi355x_solve_two_phase (its tableaux in the caller's memory
-// are untouched; what the batches hold of it is to be ignored).
+// problems); per member the feasibility test (fp= 0 objective) :405-407, the drive-out pivots of
+// degenerate artificials still basic (:419-434 -- row fetches and single pivots on that member's
+// slice of the batch) and the hand-over :437-451 (mi355x_solve_two_phase's kernels on that member's
+// slices of the two batches); phase 2 = the batch loop on `main_mb`.  A member that ends between the
+// phases (MI_INFEASIBLE, MI_ART_NONZERO, MI_ART_STUCK) keeps that status; the others are not held up.
 static TabView mb_member_view(const TabView &v, int64_t k)
 {
     TabView s = v;
@@ -503,7 +492,7 @@ int mi355x_multibatch_two_phase_handover(mi355x_multibatch *art, mi355x_multibat
     int rc = mb_two_phase_check(art, main_mb);
     if (rc != MI_OK) return rc;
     const int64_t rows = art->rows, m = rows - 1, num_vars = main_mb->cols - 1, num_art_vars = art->cols - 1;
-    std::vector<double> obj, row;
+    std::vector<double> obj;
     std::vector<int64_t> basis;
     for (size_t d = 0; d < art->sub.size(); ++d) {
         mi355x_tab *at = art->sub[d]->t, *mt = main_mb->sub[d]->t;
@@ -525,30 +514,22 @@ int mi355x_multibatch_two_phase_handover(mi355x_multibatch *art, mi355x_multibat
             bool drove_out = false;
             if (n_driveout) n_driveout[k] = 0;
             if (out == MI_OPTIMAL) {
-                const double diff = 0.0 - obj[(size_t)q];                                        // (fp= 0 objective factor) :405-407
-                if (!((diff < 0.0 ? -diff : diff) <= f * kClEpsilon)) out = MI_INFEASIBLE;
+                if (!tp_feasible(obj[(size_t)q], f * kClEpsilon)) out = MI_INFEASIBLE;            // (fp= 0 objective factor) :405-407
             }
             if (out == MI_OPTIMAL) {
                 // degenerate artificials still basic: pivot them out                             :419-434
-                int64_t *bq = basis.data() + q * m;
                 const TabView av = mb_member_view(at->v, q);
-                for (int64_t i = 0; i < m && out == MI_OPTIMAL; ++i) {
-                    if (bq[i] < num_vars) continue;
-                    row.resize((size_t)at->v.cols);
-                    HIP_TRY(hipMemcpyAsync(row.data(), av.M + i * av.ld, av.cols * sizeof(double), hipMemcpyDeviceToHost, at->stream));
-                    HIP_TRY(hipStreamSynchronize(at->stream));
-                    if (row[(size_t)num_art_vars] != 0.0) { out = MI_ART_NONZERO; break; }
-                    int64_t new_col = -1;
-                    for (int64_t j = 0; j < num_vars; ++j)
-                        if (row[(size_t)j] != 0.0 && std::find(bq, bq + m, j) == bq + m) { new_col = j; break; }
-                    if (new_col < 0) { out = MI_ART_STUCK; break; }
-                    launch_prepare_pivot(av, new_col, i, at->stream);                            // = mi355x_tab_pivot on the member
-                    launch_update(av, 1.0, 0, at->stream);
-                    HIP_TRY(hipGetLastError());
-                    bq[i] = new_col;
-                    drove_out = true;
-                    if (n_driveout) n_driveout[k]++;
-                }
+                out = tp_drive_out<double>(
+                    m, num_vars, num_art_vars, basis.data() + q * m, [](double x) { return x == 0.0; },
+                    [&](int64_t i, std::vector<double> &row) { return fetch_row(av.M + i * av.ld, av.cols, at->stream, row); },
+                    [&](int64_t col, int64_t i) {
+                        launch_prepare_pivot(av, col, i, at->stream);                            // = mi355x_tab_pivot on the member
+                        launch_update(av, 1.0, 0, at->stream);
+                        HIP_TRY(hipGetLastError());
+                        return (int)MI_OK;
+                    },
+                    [&] { drove_out = true; if (n_driveout) n_driveout[k]++; });
+                if (out < 0) return out;                                                         // (an error, not the member's outcome)
             }
             if (out == MI_OPTIMAL) {
                 status[k] = MI_OK;

@@ -295,18 +295,6 @@ template <class V> int x_download_limbs(mi355x_xtab *t, int limbs, int64_t *num_
     return MI_OK;
 }
 
-// the first min(total, cap, trace_cap) pivots of a trace (total: how many there were)
-int x_download_trace(const int64_t *trace_ec, const int64_t *trace_cr, int64_t total, int64_t trace_cap, hipStream_t s,
-                     int64_t *ecs, int64_t *crs, int64_t cap, int64_t *n)
-{
-    if (n) *n = total;
-    const int64_t k = std::min<int64_t>(std::min<int64_t>(total, cap), trace_cap);
-    if (k > 0 && ecs) HIP_TRY(hipMemcpyAsync(ecs, trace_ec, k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    if (k > 0 && crs) HIP_TRY(hipMemcpyAsync(crs, trace_cr, k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return MI_OK;
-}
-
 // between the phases (src/simplex.lisp:405-451): MI_OK (main ready for phase 2), MI_INFEASIBLE,
 // MI_ART_NONZERO, MI_ART_STUCK, kXOverflow, kXInexact, or an error
 template <class V> int x_handover_v(mi355x_xtab *a, mi355x_xtab *mt)
@@ -318,23 +306,17 @@ template <class V> int x_handover_v(mi355x_xtab *a, mi355x_xtab *mt)
     if (!x_zero(row[0])) return MI_INFEASIBLE;
     std::vector<int64_t> basis((size_t)m);
     if (m > 0) HIP_TRY(hipMemcpy(basis.data(), a->v.basis, m * sizeof(int64_t), hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < m; ++i) {
-        if (basis[i] < nv) continue;
-        rc = x_download_values(a->v.T, a->bits, a->stream, i * C, C, row);
-        if (rc != MI_OK) return rc;
-        if (!x_zero(row[nav])) return MI_ART_NONZERO;
-        int64_t j = 0;
-        for (; j < nv; ++j)
-            if (!x_zero(row[j]) && std::find(basis.begin(), basis.end(), j) == basis.end()) break;
-        if (j == nv) return MI_ART_STUCK;
-        launch_x_force(a->v, j, i, a->stream);
-        launch_x_update(a->v, a->stream);
-        rc = x_read_ctl(a);
-        if (rc != MI_OK) return rc;
-        if (a->h.err) return a->h.err;
-        basis[i] = j;
-        a->tp_driveouts += 1;
-    }
+    rc = tp_drive_out<V>(
+        m, nv, nav, basis.data(), [](const V &x) { return x_zero(x); },
+        [&](int64_t i, std::vector<V> &r) { return x_download_values(a->v.T, a->bits, a->stream, i * C, C, r); },
+        [&](int64_t col, int64_t i) {
+            launch_x_force(a->v, col, i, a->stream);
+            launch_x_update(a->v, a->stream);
+            const int rc2 = x_read_ctl(a);
+            return rc2 != MI_OK ? rc2 : (int)a->h.err;
+        },
+        [&] { a->tp_driveouts += 1; });
+    if (rc != MI_OK) return rc;
     // multipliers of the re-elimination: L_c (LCM of the original objective row's denominators),
     // w_i = L_c * c[b_i], cl_j = L_c * c_j
     const int64_t Cm = mt->cols;
@@ -585,7 +567,7 @@ int mi355x_xtab_trace(mi355x_xtab *t, int64_t *ecs, int64_t *crs, int64_t cap, i
     if (!t) return fail(MI_BAD_ARG, "handle is NULL");
     int rc = use_device_id(t->device);
     if (rc != MI_OK) return rc;
-    return x_download_trace(t->v.trace_ec, t->v.trace_cr, t->h.trace_n, kXTraceCap, t->stream, ecs, crs, cap, n);
+    return download_trace(t->v.trace_ec, t->v.trace_cr, t->h.trace_n, kXTraceCap, t->stream, ecs, crs, cap, n);
 }
 
 int mi355x_xtab_bits(const mi355x_xtab *t, int *bits)

@@ -1,7 +1,7 @@
 // capi_exact_batch.inc -- mi355x_xbatch_*: many exact rational LPs of one shape side by side, one
 // workgroup per member (kernels_exact_batch.inc).  Part of simplex_capi.hip (ONE translation unit:
 // included there after capi_exact.inc, whose host helpers -- x_start_state, x_start_ok,
-// x_objective_multipliers, x_put, x_download_lo_hi, x_download_trace, x_exact_status -- it shares).
+// x_objective_multipliers, x_put, x_download_lo_hi, x_exact_status -- it shares).
 //
 // A handle keeps the callers' rationals of every member on the host and up to two sub-batches on the
 // device, one per width.  Every member has a slot in each: it runs in the slot of its current width,
@@ -442,8 +442,8 @@ int mi355x_xbatch_trace(mi355x_xbatch *b, int64_t q, int64_t *ecs, int64_t *crs,
     int rc = use_device_id(b->device);
     if (rc != MI_OK) return rc;
     const XbWidth &w = b->w[xb_wi(b->width[q])];
-    return x_download_trace(w.v.trace_ec + q * kXbTraceCap, w.v.trace_cr + q * kXbTraceCap, w.h[q].trace_n, kXbTraceCap,
-                            b->stream, ecs, crs, cap, n);
+    return download_trace(w.v.trace_ec + q * kXbTraceCap, w.v.trace_cr + q * kXbTraceCap, w.h[q].trace_n, kXbTraceCap,
+                          b->stream, ecs, crs, cap, n);
 }
 
 int mi355x_xbatch_bits(const mi355x_xbatch *b, int64_t q, int *bits)

@@ -215,29 +215,17 @@ static int stab_handover(mi355x_stab *art, mi355x_stab *mt, double f, int64_t *n
     float art_obj = 0.0f;
     HIP_TRY(hipMemcpyAsync(&art_obj, a.M + m * a.ld + nav, sizeof(float), hipMemcpyDeviceToHost, art->stream));
     HIP_TRY(hipStreamSynchronize(art->stream));
-    const float diff = 0.0f - art_obj;
-    if (!((diff < 0.0f ? -diff : diff) <= single_thresholds(f).feasible)) return MI_INFEASIBLE;
+    if (!tp_feasible(art_obj, single_thresholds(f).feasible)) return MI_INFEASIBLE;
     std::vector<int64_t> basis((size_t)std::max<int64_t>(m, 1));
     if (m > 0) {
         HIP_TRY(hipMemcpyAsync(basis.data(), a.basis, m * sizeof(int64_t), hipMemcpyDeviceToHost, art->stream));
         HIP_TRY(hipStreamSynchronize(art->stream));
     }
-    std::vector<float> row;
-    for (int64_t i = 0; i < m; ++i) {
-        if (basis[i] < nv) continue;
-        row.resize((size_t)a.cols);
-        HIP_TRY(hipMemcpyAsync(row.data(), a.M + i * a.ld, a.cols * sizeof(float), hipMemcpyDeviceToHost, art->stream));
-        HIP_TRY(hipStreamSynchronize(art->stream));
-        if (row[nav] != 0.0f) return MI_ART_NONZERO;
-        int64_t new_col = -1;
-        for (int64_t j = 0; j < nv; ++j)
-            if (row[j] != 0.0f && std::find(basis.begin(), basis.begin() + m, j) == basis.begin() + m) { new_col = j; break; }
-        if (new_col < 0) return MI_ART_STUCK;
-        const int rc = stab_forced_pivot(art, new_col, i);
-        if (rc != MI_OK) return rc;
-        basis[i] = new_col;
-        ++*n_driveout;
-    }
+    const int rc = tp_drive_out<float>(
+        m, nv, nav, basis.data(), [](float x) { return x == 0.0f; },
+        [&](int64_t i, std::vector<float> &row) { return fetch_row(a.M + i * a.ld, a.cols, art->stream, row); },
+        [&](int64_t col, int64_t i) { return stab_forced_pivot(art, col, i); }, [&] { ++*n_driveout; });
+    if (rc != MI_OK) return rc;
     HIP_TRY(hipStreamSynchronize(mt->stream));
     launch_s_handover_copy(a, mv, art->stream);
     HIP_TRY(hipGetLastError());
@@ -300,16 +288,8 @@ int mi355x_stab_download(mi355x_stab *t, float *hm, int64_t *hb, float *last_row
     int rc = stab_use(t);
     if (rc != MI_OK) return rc;
     const SView &v = t->v;
-    if (hm)
-        HIP_TRY(hipMemcpy2DAsync(hm, v.cols * sizeof(float), v.M, v.ld * sizeof(float), v.cols * sizeof(float), v.rows,
-                                 hipMemcpyDeviceToHost, t->stream));
-    if (hb && v.rows > 1)
-        HIP_TRY(hipMemcpyAsync(hb, v.basis, (v.rows - 1) * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
-    if (last_row)
-        HIP_TRY(hipMemcpyAsync(last_row, v.M + (v.rows - 1) * v.ld, v.cols * sizeof(float), hipMemcpyDeviceToHost, t->stream));
-    if (last_col)
-        HIP_TRY(hipMemcpy2DAsync(last_col, sizeof(float), v.M + (v.cols - 1), v.ld * sizeof(float), sizeof(float), v.rows,
-                                 hipMemcpyDeviceToHost, t->stream));
+    rc = download_parts(v.M, v.ld, v.rows, v.cols, v.basis, t->stream, hm, hb, last_row, last_col);
+    if (rc != MI_OK) return rc;
     HIP_TRY(hipStreamSynchronize(t->stream));
     return MI_OK;
 }
@@ -321,13 +301,7 @@ int mi355x_stab_trace(mi355x_stab *t, int64_t *ecs, int64_t *crs, int64_t cap, i
     if (rc != MI_OK) return rc;
     rc = stab_read_ctl(t);
     if (rc != MI_OK) return rc;
-    const int64_t total = t->h_ctl.trace_n;
-    if (n) *n = total;
-    const int64_t k = std::min<int64_t>(std::min<int64_t>(total, cap), kTraceCap);
-    if (k > 0 && ecs) HIP_TRY(hipMemcpyAsync(ecs, t->v.trace_ec, k * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
-    if (k > 0 && crs) HIP_TRY(hipMemcpyAsync(crs, t->v.trace_cr, k * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
-    if (k > 0 && (ecs || crs)) HIP_TRY(hipStreamSynchronize(t->stream));
-    return MI_OK;
+    return download_trace(t->v.trace_ec, t->v.trace_cr, t->h_ctl.trace_n, kTraceCap, t->stream, ecs, crs, cap, n);
 }
 
 // measurement (tools/single_rate.py): the forced pivot (ec, cr) prepared once, then k_s_update launched `reps` times

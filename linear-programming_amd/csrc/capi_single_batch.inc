@@ -236,17 +236,9 @@ int mi355x_sbatch_download(mi355x_sbatch *b, int64_t q, float *hm, int64_t *hb, 
     if (q < 0 || q >= b->v.n_lps) return fail(MI_BAD_ARG, "lp_index %lld out of range [0,%lld)", (long long)q, (long long)b->v.n_lps);
     HIP_TRY(hipSetDevice(b->device));
     const SbView &v = b->v;
-    const float *M = v.M + q * v.stride;
-    if (hm)
-        HIP_TRY(hipMemcpy2DAsync(hm, v.cols * sizeof(float), M, v.ld * sizeof(float), v.cols * sizeof(float), v.rows,
-                                 hipMemcpyDeviceToHost, b->stream));
-    if (hb && v.rows > 1)
-        HIP_TRY(hipMemcpyAsync(hb, v.basis + q * (v.rows - 1), (v.rows - 1) * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-    if (last_row)
-        HIP_TRY(hipMemcpyAsync(last_row, M + (v.rows - 1) * v.ld, v.cols * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    if (last_col)
-        HIP_TRY(hipMemcpy2DAsync(last_col, sizeof(float), M + (v.cols - 1), v.ld * sizeof(float), sizeof(float), v.rows,
-                                 hipMemcpyDeviceToHost, b->stream));
+    const int rc = download_parts(v.M + q * v.stride, v.ld, v.rows, v.cols, v.basis + q * (v.rows - 1), b->stream, hm, hb,
+                                  last_row, last_col);
+    if (rc != MI_OK) return rc;
     HIP_TRY(hipStreamSynchronize(b->stream));
     return MI_OK;
 }
@@ -259,12 +251,8 @@ int mi355x_sbatch_trace(mi355x_sbatch *b, int64_t q, int64_t *ecs, int64_t *crs,
     Ctl c{};
     HIP_TRY(hipMemcpyAsync(&c, b->v.ctl + q, sizeof(Ctl), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    if (n) *n = c.trace_n;
-    const int64_t k = std::min<int64_t>(std::min<int64_t>(c.trace_n, cap), b->v.trace_cap);
-    if (k > 0 && ecs) HIP_TRY(hipMemcpyAsync(ecs, b->v.trace_ec + q * b->v.trace_cap, k * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-    if (k > 0 && crs) HIP_TRY(hipMemcpyAsync(crs, b->v.trace_cr + q * b->v.trace_cap, k * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-    if (k > 0 && (ecs || crs)) HIP_TRY(hipStreamSynchronize(b->stream));
-    return MI_OK;
+    return download_trace(b->v.trace_ec + q * b->v.trace_cap, b->v.trace_cr + q * b->v.trace_cap, c.trace_n, b->v.trace_cap,
+                          b->stream, ecs, crs, cap, n);
 }
 
 int mi355x_sbatch_cancel(mi355x_sbatch *b)

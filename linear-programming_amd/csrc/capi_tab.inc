@@ -607,8 +607,7 @@ static int two_phase_handover_impl(mi355x_tab *art, mi355x_tab *mt, double f, in
     HIP_TRY(hipMemcpyAsync(&art_obj, art->v.M + m * art->v.ld + num_art_vars, sizeof(double),
                            hipMemcpyDeviceToHost, art->stream));
     HIP_TRY(hipStreamSynchronize(art->stream));
-    const double diff = 0.0 - art_obj;
-    if (!((diff < 0.0 ? -diff : diff) <= f * kClEpsilon)) return MI_INFEASIBLE;
+    if (!tp_feasible(art_obj, f * kClEpsilon)) return MI_INFEASIBLE;
     // degenerate artificials still basic: pivot them out               simplex.lisp:419-434
     std::vector<int64_t> basis((size_t)std::max<int64_t>(m, 1));
     if (m > 0) {
@@ -616,27 +615,12 @@ static int two_phase_handover_impl(mi355x_tab *art, mi355x_tab *mt, double f, in
                                art->stream));
         HIP_TRY(hipStreamSynchronize(art->stream));
     }
-    std::vector<double> row;
-    for (int64_t i = 0; i < m; ++i) {
-        if (basis[i] < num_vars) continue;
-        row.resize((size_t)art->v.cols);
-        HIP_TRY(hipMemcpyAsync(row.data(), art->v.M + i * art->v.ld, art->v.cols * sizeof(double),
-                               hipMemcpyDeviceToHost, art->stream));
-        HIP_TRY(hipStreamSynchronize(art->stream));
-        if (row[num_art_vars] != 0.0) return MI_ART_NONZERO;
-        int64_t new_col = -1;
-        for (int64_t j = 0; j < num_vars; ++j) {
-            if (row[j] != 0.0 && std::find(basis.begin(), basis.begin() + m, j) == basis.begin() + m) {
-                new_col = j;
-                break;
-            }
-        }
-        if (new_col < 0) return MI_ART_STUCK;
-        rc = mi355x_tab_pivot(art, new_col, i);
-        if (rc != MI_OK) return rc;
-        basis[i] = new_col;
-        if (n_driveout) ++*n_driveout;
-    }
+    rc = tp_drive_out<double>(
+        m, num_vars, num_art_vars, basis.data(), [](double x) { return x == 0.0; },
+        [&](int64_t i, std::vector<double> &row) { return fetch_row(art->v.M + i * art->v.ld, art->v.cols, art->stream, row); },
+        [&](int64_t col, int64_t i) { return mi355x_tab_pivot(art, col, i); },
+        [&] { if (n_driveout) ++*n_driveout; });
+    if (rc != MI_OK) return rc;
     // copy rows + basis, re-eliminate the objective row                simplex.lisp:437-451
     HIP_TRY(hipStreamSynchronize(mt->stream));
     launch_handover(art->v, mt->v, art->unit_basis && art->tn.handover_mode != 1, art->stream);
@@ -709,18 +693,8 @@ int mi355x_tab_download(mi355x_tab *t, double *hm, int64_t *hb, double *last_row
     rc = ensure_dense(t);
     if (rc != MI_OK) return rc;
     const TabView &v = t->v;
-    if (hm)
-        HIP_TRY(hipMemcpy2DAsync(hm, v.cols * sizeof(double), v.M, v.ld * sizeof(double),
-                                 v.cols * sizeof(double), v.rows, hipMemcpyDeviceToHost, t->stream));
-    if (hb && v.rows > 1)
-        HIP_TRY(hipMemcpyAsync(hb, v.basis, (v.rows - 1) * sizeof(int64_t), hipMemcpyDeviceToHost,
-                               t->stream));
-    if (last_row)
-        HIP_TRY(hipMemcpyAsync(last_row, v.M + (v.rows - 1) * v.ld, v.cols * sizeof(double),
-                               hipMemcpyDeviceToHost, t->stream));
-    if (last_col)
-        HIP_TRY(hipMemcpy2DAsync(last_col, sizeof(double), v.M + (v.cols - 1), v.ld * sizeof(double),
-                                 sizeof(double), v.rows, hipMemcpyDeviceToHost, t->stream));
+    rc = download_parts(v.M, v.ld, v.rows, v.cols, v.basis, t->stream, hm, hb, last_row, last_col);
+    if (rc != MI_OK) return rc;
     HIP_TRY(hipStreamSynchronize(t->stream));
     return MI_OK;
 }
@@ -753,16 +727,7 @@ int mi355x_tab_trace(mi355x_tab *t, int64_t *ecs, int64_t *crs, int64_t cap, int
     if (rc != MI_OK) return rc;
     rc = read_ctl(t);
     if (rc != MI_OK) return rc;
-    const int64_t total = t->h_ctl->trace_n;
-    if (n) *n = total;
-    const int64_t k = std::min<int64_t>(std::min<int64_t>(total, cap), kTraceCap);
-    // (on the handle's stream: a synchronous hipMemcpy on the null stream out of these 8 MB buffers
-    // left 8 MB of device memory unaccounted for per handle once the handle was destroyed -- found by
-    // a 37 000-handle fuzz run that ended in hipErrorOutOfMemory)
-    if (k > 0 && ecs) HIP_TRY(hipMemcpyAsync(ecs, t->v.trace_ec, k * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
-    if (k > 0 && crs) HIP_TRY(hipMemcpyAsync(crs, t->v.trace_cr, k * sizeof(int64_t), hipMemcpyDeviceToHost, t->stream));
-    if (k > 0 && (ecs || crs)) HIP_TRY(hipStreamSynchronize(t->stream));
-    return MI_OK;
+    return download_trace(t->v.trace_ec, t->v.trace_cr, t->h_ctl->trace_n, kTraceCap, t->stream, ecs, crs, cap, n);
 }
 
 int mi355x_tab_set_stream(mi355x_tab *t, void *hip_stream, int use_own)

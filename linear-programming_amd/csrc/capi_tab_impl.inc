@@ -17,6 +17,46 @@ int use_device(const mi355x_tab *t)
     return MI_OK;
 }
 
+// `cols` entries from `src` on (one tableau row) into `row`, synchronised: what tp_drive_out fetches per drive-out
+template <class T> int fetch_row(const T *src, int64_t cols, hipStream_t s, std::vector<T> &row)
+{
+    row.resize((size_t)cols);
+    HIP_TRY(hipMemcpyAsync(row.data(), src, cols * sizeof(T), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return MI_OK;
+}
+
+// What every tableau download hands out, each part only where its pointer is not NULL: the matrix tightly packed,
+// the basis, the objective row, the RHS column.  M and basis are the tableau's own (a batch member's: already
+// offset), T its number type.  Only enqueues on `s`: the wait is the caller's.
+template <class T>
+int download_parts(const T *M, int64_t ld, int64_t rows, int64_t cols, const int64_t *basis, hipStream_t s, T *hm,
+                   int64_t *hb, T *last_row, T *last_col)
+{
+    if (hm)
+        HIP_TRY(hipMemcpy2DAsync(hm, cols * sizeof(T), M, ld * sizeof(T), cols * sizeof(T), rows, hipMemcpyDeviceToHost, s));
+    if (hb && rows > 1) HIP_TRY(hipMemcpyAsync(hb, basis, (rows - 1) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (last_row) HIP_TRY(hipMemcpyAsync(last_row, M + (rows - 1) * ld, cols * sizeof(T), hipMemcpyDeviceToHost, s));
+    if (last_col)
+        HIP_TRY(hipMemcpy2DAsync(last_col, sizeof(T), M + (cols - 1), ld * sizeof(T), sizeof(T), rows, hipMemcpyDeviceToHost, s));
+    return MI_OK;
+}
+
+// the first min(total, cap, trace_cap) pivots of a trace (total: how many there were); waits only for what it enqueued
+// (on the handle's stream: a synchronous hipMemcpy on the null stream out of these 8 MB buffers left 8 MB of device
+// memory unaccounted for per handle once the handle was destroyed -- found by a 37 000-handle fuzz run that ended in
+// hipErrorOutOfMemory)
+int download_trace(const int64_t *trace_ec, const int64_t *trace_cr, int64_t total, int64_t trace_cap, hipStream_t s,
+                   int64_t *ecs, int64_t *crs, int64_t cap, int64_t *n)
+{
+    if (n) *n = total;
+    const int64_t k = std::min<int64_t>(std::min<int64_t>(total, cap), trace_cap);
+    if (k > 0 && ecs) HIP_TRY(hipMemcpyAsync(ecs, trace_ec, k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (k > 0 && crs) HIP_TRY(hipMemcpyAsync(crs, trace_cr, k * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    if (k > 0 && (ecs || crs)) HIP_TRY(hipStreamSynchronize(s));
+    return MI_OK;
+}
+
 void free_tab(mi355x_tab *t)
 {
     if (!t) return;

@@ -8,6 +8,7 @@
 #include "../../include/mi355x_simplex.h"
 #include "../../include/mi355x_simplex_tune.h"
 #include "simplex_kernels.h"
+#include "two_phase_host.h"               // the rule of the step between the phases (host only)
 
 #include <rccl/rccl.h>                    // types and prototypes only: the library is bound at run time
 #include <dlfcn.h>

@@ -218,6 +218,7 @@ int orc_solve_two_phase(double *art, int64_t art_ld, int64_t rows, int64_t art_c
             if (new_col < 0) return ORC_ART_STUCK;
             orc_pivot(art, art_ld, rows, art_cols, art_basis, new_col, i);
             ++n1;
+            if (n_pivots_out) n_pivots_out[0] = n1; /* (counted at once: a later row may end the step) */
         }
     }
     /* copy coefficients and rhs                                    :437-441 */

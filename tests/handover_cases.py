@@ -200,13 +200,15 @@ def _small_inf(name, seed, sign):
     return case
 
 
-def _small_driveout(name, seed, stuck=False):
+def _small_driveout(name, seed, stuck=False, nonzero=False):
     """(e): rows 1 and 3 hold basic ARTIFICIAL columns at level 0; the only eligible main columns of row 1 are
     the last two non-basic ones (+1/2 in the first of them), and -- once that pivot is made -- the only one
     of row 3 is the last (-3/4).  Basic main columns with non-zero entries in these rows come before them
     and must be skipped.
-    (f) stuck=True: row 3 alone, and its only non-zero main entries sit in basic columns: ART_STUCK."""
-    case = _small(name, seed, ingredients=("f",) if stuck else ("e",))
+    (f) stuck=True: row 3 alone, and its only non-zero main entries sit in basic columns: ART_STUCK.
+    (g) nonzero=True: (e) with 2**-60 as the level of row 3's artificial -- tiny, and no exact zero (:423 tests
+    /= 0, not fp=): row 1 is driven out, then row 3 ends the step with ART_NONZERO."""
+    case = _small(name, seed, ingredients=("f",) if stuck else ("g",) if nonzero else ("e",))
     A, b = case.art, case.art_basis
     nv = case.main.shape[1] - 1
     for r, art_col in ((3, nv + 2),) if stuck else ((1, nv + 1), (3, nv + 2)):
@@ -223,6 +225,8 @@ def _small_driveout(name, seed, stuck=False):
         A[1, free], A[3, free] = 0.0, 0.0
         A[1, free[-2]], A[1, free[-1]] = 0.5, 0.25
         A[3, free[-1]] = -0.75                             # (a zero in free[-2]: the first pivot leaves row 3 as it is)
+    if nonzero:
+        A[3, -1] = 2.0 ** -60
     return case
 
 
@@ -278,6 +282,7 @@ def _build_cases():
         _small_inf("5x9-minus-inf", 12, -1.0),
         _small_driveout("5x9-driveout", 13),
         _small_driveout("5x9-stuck", 13, stuck=True),
+        _small_driveout("5x9-nonzero", 13, nonzero=True),
         _with_unit_basis("5x9-unit", 5, 9, 14, na=4),
         _boundary("5x9-beyond", 5, 9, 15, -1.0, True, na=4),
         direct("40x70", 40, 70, 21, 0.05),
@@ -310,4 +315,5 @@ BOUNDARY = [n for n in DIRECT if n.startswith("3x7-")]
 SHAPE = {n: (c.art.shape[0] - 1, c.main.shape[1] - 1) for n, c in CASES.items()}
 # Batches: members of one shape; exactly one of each has unit basic columns.
 BATCHES = {"5x9": ["5x9-unit", "5x9", "5x9-driveout", "5x9-stuck", "5x9-beyond"],
+           "5x9-nonzero": ["5x9-unit", "5x9-nonzero", "5x9-driveout"],      # ART_NONZERO between members that go on
            "40x70": ["40x70", "40x70-unit", "40x70-b"]}

@@ -15,6 +15,8 @@ is never replaced where it is the first candidate.
     variable / objective / reduced_cost    the read-back (:74-120) in float32
 and the shapes and special tableaux the tests share.  Nothing here touches the library.
 """
+import functools
+
 import numpy as np
 
 F32 = np.float32
@@ -322,6 +324,23 @@ DRIVEOUT_LP = dict(type="max", vars=["x", "y", "z"], objective_var="w", objectiv
                                         ("<=", [("x", 1), ("y", 2), ("z", F32(0.7))], F32(3.5))])
 INFEASIBLE_LP = dict(type="max", vars=["x", "y"], objective_var="z", objective=[("x", 1), ("y", 1)], bounds=[],
                   constraints=[("<=", [("x", 1), ("y", 1)], F32(1.5)), (">=", [("x", 1)], F32(2.5))])
+
+
+def hand_problem(constraints, objective):
+    return dict(type="max", vars=["x", "y"], objective_var="z", objective=objective, bounds=[], constraints=constraints)
+
+
+@functools.lru_cache(maxsize=None)
+def small_pairs():
+    """Five 2 x 2 two-phase pairs (art, art basis, main, main basis), one of every outcome: OPTIMAL after one drive-out,
+    INFEASIBLE, OPTIMAL, UNBOUNDED, and ART_NONZERO (1e-6 x >= 1e-5: phase 1 ends inside f eps with the artificial
+    still basic at a level that is no exact zero)."""
+    ds = [DRIVEOUT_LP, INFEASIBLE_LP,
+          hand_problem([("<=", [("x", 1), ("y", 1)], F32(3.5)), (">=", [("x", 1)], F32(0.5))], [("x", 1), ("y", F32(0.5))]),
+          hand_problem([("<=", [("x", 1), ("y", -1)], F32(1.5)), (">=", [("x", 1)], F32(0.5))], [("x", 1), ("y", 1)]),
+          hand_problem([("<=", [("x", 1), ("y", 1)], F32(1.5)), (">=", [("x", F32(1e-6))], F32(1e-5))], [("x", 1), ("y", 1)])]
+    built = [build(d) for d in ds]
+    return tuple((b["art"][0], b["art"][1], b["main"][0], b["main"][1]) for b in built)
 
 
 def tiny_coefficient_problem():

@@ -257,6 +257,26 @@ def test_two_phase_handover_bases_that_are_not_unit_columns(name, form):
     _check_two_phase(case.art.astype(F32), case.art_basis, case.main.astype(F32), case.main_basis, True, form, chunk=3)
 
 
+@pytest.mark.parametrize("form", [PAIR, LDS])
+def test_two_phase_ends_art_stuck(form):
+    """The host's step between the phases run to MI_ART_STUCK: the artificial of row 3 is basic at zero and the only
+    non-zero main entries of its row sit in basic columns."""
+    from tests import handover_cases as hc
+    case = hc.CASES["5x9-stuck"]
+    for a in (case.art, case.main):
+        assert np.array_equal(a.astype(F32).astype(np.float64), a)          # converts to float32 exactly
+    want = _check_two_phase(case.art.astype(F32), case.art_basis, case.main.astype(F32), case.main_basis, True, form)
+    assert want["status"] == sc.ART_STUCK and (want["n1"], want["n2"]) == (0, 0)
+
+
+@pytest.mark.parametrize("form", [PAIR, LDS])
+def test_two_phase_ends_art_nonzero(form):
+    """... and to MI_ART_NONZERO: 1e-6 x >= 1e-5 ends phase 1 inside f eps with the artificial still basic at a
+    level that is no exact zero."""
+    want = _check_two_phase(*sc.small_pairs()[4], True, form)
+    assert want["status"] == sc.ART_NONZERO and want["n2"] == 0
+
+
 # ---- through the public function
 def test_tiny_coefficient_through_the_public_function():
     """max 1e-6 x s.t. x <= 1: the single-float pricing threshold is 7.6e-6, so the path makes 0 pivots and returns

@@ -226,18 +226,7 @@ def test_overflow_member_beside_an_ordinary_one(threads):
 
 
 # ------------------------------------------------------------------ two-phase
-def _hand(constraints, objective):
-    return dict(type="max", vars=["x", "y"], objective_var="z", objective=objective, bounds=[], constraints=constraints)
-
-
-@functools.lru_cache(maxsize=None)
-def small_pairs():
-    ds = [sc.DRIVEOUT_LP, sc.INFEASIBLE_LP,
-          _hand([("<=", [("x", 1), ("y", 1)], F32(3.5)), (">=", [("x", 1)], F32(0.5))], [("x", 1), ("y", F32(0.5))]),
-          _hand([("<=", [("x", 1), ("y", -1)], F32(1.5)), (">=", [("x", 1)], F32(0.5))], [("x", 1), ("y", 1)]),
-          _hand([("<=", [("x", 1), ("y", 1)], F32(1.5)), (">=", [("x", F32(1e-6))], F32(1e-5))], [("x", 1), ("y", 1)])]
-    built = [sc.build(d) for d in ds]
-    return tuple((b["art"][0], b["art"][1], b["main"][0], b["main"][1]) for b in built)
+_hand, small_pairs = sc.hand_problem, sc.small_pairs
 
 
 @functools.lru_cache(maxsize=None)

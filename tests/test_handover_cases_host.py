@@ -119,6 +119,24 @@ def test_ingredients_e_and_f():
     assert not np.array_equal(stuck.art[:-1][:, stuck.art_basis], np.eye(5))
 
 
+def test_ingredient_g():
+    case, twin = hc.CASES["5x9-nonzero"], hc.CASES["5x9-driveout"]
+    nv = hc.SHAPE[case.name][1]
+    differs = np.argwhere(case.art != twin.art).tolist()
+    assert differs == [[3, case.art.shape[1] - 1]] and np.array_equal(case.art_basis, twin.art_basis)
+    value = case.art[3, -1]
+    assert 0.0 < value <= hc.F * oracle.EPSILON                              # an fp= test would let it pass: /= 0 does not
+    p, M = hc.handed_over(case)
+    assert M is None and p.status == oracle.ART_NONZERO
+    assert p.n_phase1 == 1 and len(p.driveout_elements) == 1                 # row 1 was driven out before row 3 stopped the step
+    assert p.art_basis[1] < nv <= p.art_basis[3] and p.art[3, -1] == value
+    want = hc.expected(case)
+    assert want.status == oracle.ART_NONZERO and want.npv == (1, 0)
+    # as a batch member it stands between members that go on
+    assert [hc.handed_over(hc.CASES[n])[0].status for n in hc.BATCHES["5x9-nonzero"]] == \
+        [oracle.OPTIMAL, oracle.ART_NONZERO, oracle.OPTIMAL]
+
+
 @pytest.mark.parametrize("name", hc.BOUNDARY + ["5x9-beyond"])
 def test_feasibility_boundary(name):
     case = hc.CASES[name]
