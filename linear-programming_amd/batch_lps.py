@@ -15,24 +15,17 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import capi
+from . import capi, lists
 from .batch import MultiDeviceBatch
+from .lists import SENSES                                     # noqa: F401
 from .lowering import DOUBLE, lower
-
-SENSES = {"<=": 0, ">=": 1, "=": 2}
 
 LoweredRows = namedtuple("LoweredRows", "L sense mapping is_max")
 
 
 def host_reason(problem):
     """Why a problem stays on the default route (None: lower_problem_rows takes it)."""
-    if problem.integer_vars:
-        return "integer variables"
-    if not problem.constraints:
-        return "no constraints"
-    if any(op not in SENSES for op, _, _ in problem.constraints):
-        return "constraint"
-    return None
+    return "integer variables" if problem.integer_vars else lists.rows_reason(problem)
 
 
 def lower_problem_rows(problem):
@@ -53,8 +46,7 @@ def row_counts(L, sense):
     row is negated when its right-hand side is < 0.0 (:243-252; not -0.0, not NaN), and artificial when it is
     `=` or, after the flip, `>=`."""
     flip = L[..., :-1, -1] < 0.0
-    op = np.where(sense == 2, 2, np.where(flip, 1 - sense, sense))
-    return (sense == 2).sum(axis=-1), (op != 0).sum(axis=-1), flip.sum(axis=-1)
+    return (*lists.row_counts(flip, sense), flip.sum(axis=-1))
 
 
 def group_lowered_rows(problems):
@@ -63,70 +55,55 @@ def group_lowered_rows(problems):
     route solves alone as well (a negated row leaves -0.0 in the other rows' slack columns: not the unit basis
     its batches start from, simplex._unit_basis), "alone" for a member alone in its group; groups {(m, ncv, `=`
     rows, artificial rows, is_max): [(k, LoweredRows)]}, each of two or more members."""
-    host, groups = {}, {}
+    host, lowered = {}, []
     for k, p in enumerate(problems):
         low = lower_problem_rows(p)
         if low is None:
             host[k] = host_reason(p)
             continue
-        m, ncv = low.L.shape[0] - 1, low.L.shape[1] - 1
         n_eq, n_art, n_flip = (int(x) for x in row_counts(low.L, low.sense))
-        if n_art == 0 and n_flip > 0 and m > 1:
+        if n_art == 0 and n_flip > 0 and len(low.sense) > 1:
             host[k] = "basis"
             continue
-        groups.setdefault((m, ncv, n_eq, n_art, low.is_max), []).append((k, low))
-    for key in [key for key, members in groups.items() if len(members) == 1]:
-        host[groups.pop(key)[0][0]] = "alone"
-    return host, groups
-
-
-def _batch_in_chunks(mb, is_max, rows, cols, fp_tolerance, max_pivots):
-    """The glue's `multibatch-solve-in-chunks` (as in mi355x_solve_problems): bounded calls until no member is
-    left at MI_MAX_PIVOTS (or max_pivots are used up); -> (statuses, pivots per member)."""
-    from .simplex import chunk_pivots
-    chunk, done = chunk_pivots(rows, cols), 0
-    total = np.zeros(mb.n_lps, dtype=np.int64)
-    while True:
-        cap = min(chunk, max_pivots - done) if max_pivots > 0 else chunk
-        st, npv = mb.solve(is_max=is_max, fp_tolerance=fp_tolerance, max_pivots=cap)
-        total += npv
-        done += cap
-        if (max_pivots > 0 and done >= max_pivots) or not (st == capi.MI_MAX_PIVOTS).any():
-            return st, total
+        lowered.append((k, low.L, n_eq, n_art, low))
+    return host, lists.group_by_rows(lowered, host)
 
 
 def solve_batches(main, art, is_max, fp_tolerance=1024, max_pivots=0):
-    """A created group in bounded calls, exactly as mi355x_solve_problems solves its host-built groups: single
-    phase (art None), or phase 1 on the artificial batch, the per-member step between the phases
-    (mi355x_multibatch_two_phase_handover) and phase 2 on the main batch; max_pivots caps every phase.
+    """A created group in bounded calls (the glue's `multibatch-solve-in-chunks`: lists.batch_in_chunks), what
+    mi355x_solve_problems does with its host-built groups as well: single phase (art None), or phase 1 on the
+    artificial batch, the per-member step between the phases (mi355x_multibatch_two_phase_handover) and phase 2 on
+    the main batch; max_pivots caps every phase.
     -> (status per member, pivots per member: n, or n x 2 for a two-phase group)."""
+    first = main if art is None else art
+
+    def phase(mb, is_max):
+        return lists.batch_in_chunks(
+            lambda cap: (False,) + mb.solve(is_max=is_max, fp_tolerance=fp_tolerance, max_pivots=cap),
+            first.rows, first.cols, max_pivots)
     if art is None:
-        return _batch_in_chunks(main, is_max, main.rows, main.cols, fp_tolerance, max_pivots)
-    st1, np1 = _batch_in_chunks(art, False, art.rows, art.cols, fp_tolerance, max_pivots)
+        return phase(main, is_max)
+    st1, np1 = phase(art, False)
     between, nd = art.two_phase_handover(main, fp_tolerance=fp_tolerance, phase1_status=st1)
-    st2, np2 = _batch_in_chunks(main, is_max, art.rows, art.cols, fp_tolerance, max_pivots)
+    st2, np2 = phase(main, is_max)
     return np.where(between == capi.MI_OK, st2, between).astype(np.int32), np.stack([np1 + nd, np2], axis=1)
 
 
 def solve_group(problems, lowered, fp_tolerance=1024, device=0, devices=1, max_pivots=0):
     """One group of group_lowered_rows: per member the solved (main) Tableau the default route returns -- matrix,
     basis, n_pivots, var_mapping -- or the exception of its outcome."""
-    from .conditions import SolverError
-    from .simplex import Tableau, _raise_for
+    from .simplex import Tableau, _error_for
     main, art = MultiDeviceBatch.from_lps(np.stack([l.L for l in lowered]), np.stack([l.sense for l in lowered]),
                                           n_devices=devices)
     st, npv = solve_batches(main, art, lowered[0].is_max, fp_tolerance, max_pivots)
     out = []
     for q, (p, low) in enumerate(zip(problems, lowered)):
-        try:
-            _raise_for(int(st[q]))
-        except SolverError as e:
-            out.append(e)
-            continue
-        G, gb = main.download(q)
-        t = Tableau(p, p, G, gb, main.cols - 1, main.rows - 1, low.mapping, fp_tolerance, device)
-        t.n_pivots = (int(npv[q, 0]), int(npv[q, 1])) if art is not None else int(npv[q])
-        out.append(t)
+        r = _error_for(int(st[q]))
+        if r is None:
+            G, gb = main.download(q)
+            r = Tableau(p, p, G, gb, main.cols - 1, main.rows - 1, low.mapping, fp_tolerance, device)
+            r.n_pivots = lists.member_pivots(npv, q)
+        out.append(r)
     return out
 
 
@@ -138,9 +115,8 @@ def solve_problems_from_rows(problems, host_route, fp_tolerance=1024, device=0, 
     host, groups = group_lowered_rows(problems)
     for members in groups.values():
         ks = [k for k, _ in members]
-        for k, r in zip(ks, solve_group([problems[k] for k in ks], [l for _, l in members], fp_tolerance, device,
-                                        devices, max_pivots)):
-            results[k] = r
+        lists.place(results, ks, solve_group([problems[k] for k in ks], [l for _, l in members], fp_tolerance, device,
+                                             devices, max_pivots))
     for k in sorted(host):
         results[k] = host_route(problems[k])
     return results

@@ -25,7 +25,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from . import capi
+from . import capi, lists
 from .capi import _ptr
 from .conditions import UnsupportedConstraintError
 from .lowering import EXACT
@@ -208,7 +208,7 @@ def n_solve_exact(tabs, max_pivots=0, chunk=None, pivot_rule=None):
     """n-solve-tableau (src/simplex.lisp:399-461) on an ExactTableau or a list [art, main], in bounded
     calls (the glue's solve-in-chunks).  Returns the solved (main) tableau; raises as n_solve_tableau.
     pivot_rule: set on the tableau (on both of a pair) first; None leaves them as they are."""
-    from .simplex import _raise_for, _solve_in_chunks
+    from .simplex import _raise_for
     if pivot_rule is not None:
         for t in (tabs if isinstance(tabs, (list, tuple)) else [tabs]):
             t.set_pivot_rule(pivot_rule)
@@ -226,7 +226,7 @@ def n_solve_exact(tabs, max_pivots=0, chunk=None, pivot_rule=None):
             done[1] += int(npv[1])
             return rc, int(npv[0]) + int(npv[1])
         try:
-            rc, _ = _solve_in_chunks(call, art.constraint_count + 1, art.var_count + 1, int(max_pivots), chunk=chunk)
+            rc, _ = lists.solve_in_chunks(call, art.constraint_count + 1, art.var_count + 1, int(max_pivots), chunk=chunk)
         finally:
             art._touch()
             main._touch()
@@ -240,7 +240,7 @@ def n_solve_exact(tabs, max_pivots=0, chunk=None, pivot_rule=None):
                    tabs.max_bits)
         return rc, int(n.value)
     try:
-        rc, total = _solve_in_chunks(call, tabs.constraint_count + 1, tabs.var_count + 1, int(max_pivots), chunk=chunk)
+        rc, total = lists.solve_in_chunks(call, tabs.constraint_count + 1, tabs.var_count + 1, int(max_pivots), chunk=chunk)
     finally:
         tabs._touch()
     tabs.n_pivots = total
@@ -384,14 +384,8 @@ def group_exact_problems(problems, device=0, min_bits=0):
         except SolverError as e:                       # e.g. the unbounded no-constraint special case
             failed[k] = e
             continue
-        if isinstance(tabs, list):                     # two-phase: (art main), src/simplex.lisp:326-328
-            art, main = tabs
-            groups2.setdefault((art._matrix.shape, main._matrix.shape, main.is_max), []).append((k, art, main))
-        else:
-            groups.setdefault((tabs._matrix.shape, tabs.is_max), []).append((k, tabs))
-    for g in (groups, groups2):
-        for key in [key for key, members in g.items() if len(members) == 1]:
-            alone.append(g.pop(key)[0][0])
+        lists.file_by_shape(groups, groups2, k, tabs)
+    alone += lists.pop_singletons(groups) + lists.pop_singletons(groups2)
     return sorted(alone), groups, groups2, failed
 
 
@@ -410,17 +404,10 @@ def _member_error(st):
 def batch_in_chunks(xa, xm, is_max, max_pivots=0, chunk=None):
     """A batch (xm None) or a two-phase pair of batches in bounded calls (the glue's solve-in-chunks):
     -> (final member statuses, pivots per member -- (n, 2) for a pair)."""
-    from .simplex import chunk_pivots
-    chunk = chunk or chunk_pivots(xa.rows, xa.cols)
-    total = np.zeros((xa.n_lps, 2) if xm else xa.n_lps, dtype=np.int64)
-    done = 0
-    while True:
-        cap = min(chunk, max_pivots - done) if max_pivots > 0 else chunk
+    def call(cap):
         rc, st, npv = xa.solve_two_phase(xm, is_max, cap) if xm else xa.solve(is_max, cap)
-        total += npv
-        done += cap
-        if rc == capi.MI_CANCELLED or (max_pivots > 0 and done >= max_pivots) or not (st == capi.MI_MAX_PIVOTS).any():
-            return st, total
+        return rc == capi.MI_CANCELLED, st, npv                # (a cancelled call ends the loop: cancel())
+    return lists.batch_in_chunks(call, xa.rows, xa.cols, max_pivots, chunk)
 
 
 def solve_exact_batch(members, is_max, device=0, max_pivots=0, min_bits=0, chunk=None, pivot_rule="dantzig"):
@@ -448,9 +435,7 @@ def solve_exact_batch(members, is_max, device=0, max_pivots=0, min_bits=0, chunk
         if two:
             m[0]._batch, m[0]._stale = (xa, q), True
             t.phase1 = m[0]
-            t.n_pivots = (int(total[q, 0]), int(total[q, 1]))
-        else:
-            t.n_pivots = int(total[q])
+        t.n_pivots = lists.member_pivots(total, q)
         out.append(t)
     return out
 
@@ -465,7 +450,6 @@ def solve_problems_exact(problems, fp_tolerance=1024, device=0, max_pivots=0, er
     built on the device (exact_lps.py); members alone in their group, members exact_lps.lower_problem does not
     take, groups the batch declines and members that end past 128 bits go through the route above, whose
     outcomes, exceptions and errorp these are."""
-    from .conditions import SolverError
     from .simplex import mi355x_simplex_solver
     _check_widths(min_bits, exact_max_bits)
     if device_build:
@@ -476,50 +460,32 @@ def solve_problems_exact(problems, fp_tolerance=1024, device=0, max_pivots=0, er
             return solve_problems_exact(ps, fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots, errorp=False,
                                         native=native, min_bits=min_bits, chunk=chunk, exact_max_bits=exact_max_bits,
                                         pivot_rule=pivot_rule)
-        results = solve_problems_device_built(problems, host_route, device=device, max_pivots=max_pivots,
-                                              min_bits=min(min_bits, 128), chunk=chunk, pivot_rule=pivot_rule)
-        if errorp:
-            for r in results:
-                if isinstance(r, Exception):
-                    raise r
-        return results
+        return lists.finish(solve_problems_device_built(problems, host_route, device=device, max_pivots=max_pivots,
+                                                        min_bits=min(min_bits, 128), chunk=chunk,
+                                                        pivot_rule=pivot_rule), errorp)
     rule_kw = {} if pivot_rule_code(pivot_rule) == capi.MI_RULE_DANTZIG else {"pivot_rule": pivot_rule}   # (the default: the calls as they were)
     results = [None] * len(problems)
     batch_bits = min(min_bits, 128)                    # (a batch member is at most 128 bits wide)
-    alone, groups, groups2, failed = group_exact_problems(problems, device=device, min_bits=batch_bits)
+    ones, groups, groups2, failed = group_exact_problems(problems, device=device, min_bits=batch_bits)
 
-    def results_of(ks, rs):
-        for k, r in zip(ks, rs):
-            results[k] = r
-
-    def one_by_one(ks):
-        for k in ks:
-            try:
-                results[k] = mi355x_simplex_solver(problems[k], fp_tolerance=fp_tolerance, device=device,
-                                                   max_pivots=max_pivots, native=native, exact=True,
-                                                   exact_bits=min_bits, exact_max_bits=exact_max_bits, chunk=chunk,
-                                                   **rule_kw)
-            except SolverError as e:
-                results[k] = e
+    def alone(k):
+        return mi355x_simplex_solver(problems[k], fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots,
+                                     native=native, exact=True, exact_bits=min_bits, exact_max_bits=exact_max_bits,
+                                     chunk=chunk, **rule_kw)
 
     def batch(ks, members, is_max):
         try:
-            results_of(ks, solve_exact_batch(members, is_max, device, max_pivots, batch_bits, chunk, **rule_kw))
+            lists.place(results, ks, solve_exact_batch(members, is_max, device, max_pivots, batch_bits, chunk, **rule_kw))
         except UnsupportedConstraintError:              # a shape the batch declines
-            one_by_one(ks)
+            lists.one_by_one(results, ks, alone)
             return
         if exact_max_bits > 128:
-            one_by_one([k for k in ks if overflowed_128(results[k])])
+            lists.one_by_one(results, [k for k in ks if overflowed_128(results[k])], alone)
 
-    for k, e in failed.items():
-        results[k] = e
-    one_by_one(alone)
+    lists.place(results, failed, failed.values())
+    lists.one_by_one(results, ones, alone)
     for (_, is_max), members in groups.items():
         batch([k for k, _ in members], [t for _, t in members], is_max)
     for (_, _, is_max), members in groups2.items():
         batch([k for k, _, _ in members], [(a, t) for _, a, t in members], is_max)
-    if errorp:
-        for r in results:
-            if isinstance(r, Exception):
-                raise r
-    return results
+    return lists.finish(results, errorp)

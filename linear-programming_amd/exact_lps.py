@@ -19,14 +19,13 @@ from fractions import Fraction
 
 import numpy as np
 
-from . import capi
+from . import capi, lists
 from .conditions import UnsupportedConstraintError
 from .exact import (ExactTableau, XBatch, _I64_MAX, _check_widths, _declined, _member_error, _ptr, batch_in_chunks,
                     pivot_rule_code, rational_problem)
+from .lists import SENSES                                     # noqa: F401
 from .lowering import EXACT, lower
 from .problem import Problem
-
-SENSES = {"<=": 0, ">=": 1, "=": 2}
 
 Lowered = namedtuple("Lowered", "num den sense mapping is_max")
 
@@ -37,11 +36,7 @@ def host_reason(problem):
         return "integer variables"
     if not rational_problem(problem):
         return "float"
-    if not problem.constraints:
-        return "no constraints"
-    if any(op not in SENSES for op, _, _ in problem.constraints):
-        return "constraint"
-    return None
+    return lists.rows_reason(problem)
 
 
 def _check64(x):
@@ -69,9 +64,7 @@ def lower_problem(problem):
 def row_counts(num, sense):
     """(`=` rows, artificial rows) per member of num (... x (m + 1) x (ncv + 1)) and sense (... x m): a row is
     artificial when it is `=` or, after the flip of a negative right-hand side (:243-252), `>=`."""
-    flip = num[..., :-1, -1] < 0
-    op = np.where(sense == 2, 2, np.where(flip, 1 - sense, sense))
-    return (sense == 2).sum(axis=-1), (op != 0).sum(axis=-1)
+    return lists.row_counts(num[..., :-1, -1] < 0, sense)
 
 
 def group_lowered(problems):
@@ -79,7 +72,7 @@ def group_lowered(problems):
     host {k: why the member goes through the host-built route} -- host_reason's words, "coefficient" for a value
     beyond 64 bits, "alone" for a member alone in its group; groups {(m, ncv, `=` rows, artificial rows, is_max):
     [(k, Lowered)]}, each of two or more members."""
-    host, groups = {}, {}
+    host, lowered = {}, []
     for k, p in enumerate(problems):
         why = host_reason(p)
         if why is None:
@@ -90,12 +83,8 @@ def group_lowered(problems):
         if why is not None:
             host[k] = why
             continue
-        n_eq, n_art = row_counts(low.num, low.sense)
-        key = (low.num.shape[0] - 1, low.num.shape[1] - 1, int(n_eq), int(n_art), low.is_max)
-        groups.setdefault(key, []).append((k, low))
-    for key in [key for key, members in groups.items() if len(members) == 1]:
-        host[groups.pop(key)[0][0]] = "alone"
-    return host, groups
+        lowered.append((k, low.num, *row_counts(low.num, low.sense), low))
+    return host, lists.group_by_rows(lowered, host)
 
 
 def create_lps(num, den, sense, device=0, min_bits=0, pivot_rule="dantzig"):
@@ -158,9 +147,7 @@ def solve_group(problems, lowered, device=0, max_pivots=0, min_bits=0, chunk=Non
         t = _member_tableau(p, p, low.mapping, main, q, device, min_bits)
         if art:
             t.phase1 = _member_tableau(p, Problem(type="min", vars=list(p.vars)), low.mapping, art, q, device, min_bits)
-            t.n_pivots = (int(total[q, 0]), int(total[q, 1]))
-        else:
-            t.n_pivots = int(total[q])
+        t.n_pivots = lists.member_pivots(total, q)
         out.append(t)
     return out
 
@@ -182,15 +169,11 @@ def solve_problems_device_built(problems, host_route, device=0, max_pivots=0, mi
         except UnsupportedConstraintError:              # a shape the batch declines
             back += ks
             continue
-        for k, r in zip(ks, rs):
-            if r is None:
-                back.append(k)
-            else:
-                results[k] = r
+        lists.place(results, ks, rs)
+        back += [k for k, r in zip(ks, rs) if r is None]
     back.sort()
     if back:
-        for k, r in zip(back, host_route([problems[k] for k in back])):
-            results[k] = r
+        lists.place(results, back, host_route([problems[k] for k in back]))
     return results
 
 

@@ -78,7 +78,8 @@ class NativeProblem:
         """The Lisp glue's `solve-natively`, call for call: mi355x_simplex_solver_begin, ..._step in
         bounded chunks (`solve-in-chunks`; the phases of a two-phase problem included), ..._finish;
         the job is abandoned on every other way out."""
-        from .simplex import _solve_in_chunks, _raise_for
+        from .lists import solve_in_chunks
+        from .simplex import _raise_for
         L = capi.lib()
         job, s, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64(0)
         rc = L.mi355x_simplex_solver_begin(self._h, float(fp_tolerance), device, ctypes.byref(job))
@@ -95,7 +96,7 @@ class NativeProblem:
                                 "mi355x_simplex_solver_step")
                 return rc, int(n.value)
             rows = len(self.problem.constraints) + 1
-            rc, _ = _solve_in_chunks(call, rows, rows + len(self.problem.vars), int(max_pivots), chunk=chunk)
+            rc, _ = solve_in_chunks(call, rows, rows + len(self.problem.vars), int(max_pivots), chunk=chunk)
             _raise_for(rc)
             consumed = True
             capi.check(L.mi355x_simplex_solver_finish(job, ctypes.byref(s)), "mi355x_simplex_solver_finish")
@@ -255,7 +256,8 @@ def solve_many(problems, fp_tolerance=1024, devices=1, device_ids=None, max_pivo
     members by tableau shape and sense into multi-device batches), ..._many_step in bounded chunks,
     ..._many_finish.  Returns a list parallel to `problems`: a NativeSolution or the exception the
     one-problem hook would raise for that member."""
-    from .simplex import _raise_for, chunk_pivots
+    from .lists import solve_in_chunks
+    from .simplex import _raise_for
     L = capi.lib()
     nps = [NativeProblem(p) for p in problems]
     n = len(nps)
@@ -269,14 +271,10 @@ def solve_many(problems, fp_tolerance=1024, devices=1, device_ids=None, max_pivo
     try:
         rows = max(len(p.constraints) for p in problems) + 1
         cols = rows + max(len(p.vars) for p in problems)
-        step = chunk or chunk_pivots(rows, cols)
-        done = 0
-        while True:
-            cap = min(step, max_pivots - done) if max_pivots > 0 else step
-            rc = capi.check(L.mi355x_simplex_solver_many_step(job, int(cap), status), "mi355x_simplex_solver_many_step")
-            done += cap
-            if rc != capi.MI_MAX_PIVOTS or (max_pivots > 0 and done >= max_pivots):
-                break
+
+        def call(cap):                                 # (the job reports no count: a call uses up the cap it was granted)
+            return capi.check(L.mi355x_simplex_solver_many_step(job, int(cap), status), "mi355x_simplex_solver_many_step"), cap
+        solve_in_chunks(call, rows, cols, max_pivots, chunk)
         out = (ctypes.c_void_p * n)()
         consumed = True
         capi.check(L.mi355x_simplex_solver_many_finish(job, status, out), "mi355x_simplex_solver_many_finish")

@@ -18,6 +18,8 @@ import numpy as np
 from . import capi
 from .capi import _ptr
 from .conditions import InfeasibleProblemError, SolverError, UnboundedProblemError, UnsupportedConstraintError
+from .lists import chunk_pivots                              # noqa: F401  (simplex.chunk_pivots: its name for tools)
+from .lists import file_by_shape, finish, member_pivots, one_by_one, place, solve_in_chunks
 from .lowering import DOUBLE, EXACT, build
 from .problem import Problem
 
@@ -286,6 +288,14 @@ def _raise_for(rc):
         raise SolveCancelled("solve cancelled (mi355x_tab_cancel)")
 
 
+def _error_for(rc):
+    """The exception of a member's final status (None: it has a solution)."""
+    try:
+        _raise_for(rc)
+    except SolverError as e:
+        return e
+
+
 class SolveCancelled(SolverError):
     """cancel_solve() was called from another thread: the solve stopped between two chunks of
     launches.  The tableau holds whole pivots only and can be solved further.  (In Lisp the same
@@ -298,26 +308,6 @@ def cancel_solve(tableau):
     (src/simplex.lisp:453-461); in Lisp a cycling LP is interruptible, a foreign call is not."""
     for t in (tableau if isinstance(tableau, (list, tuple)) else [tableau]):
         capi.check(capi.lib().mi355x_tab_cancel(t._h), "mi355x_tab_cancel")
-
-
-def chunk_pivots(rows, cols):
-    """The glue's `chunk-pivots`: pivots per foreign call, about a tenth to half a second of GPU
-    time at every size, so that a single-threaded host is back in its own code (where interrupts
-    are served) a few times per second."""
-    return max(1024, min(65536, (1 << 36) // max(1, rows * cols)))
-
-
-def _solve_in_chunks(call, rows, cols, max_pivots, chunk=None):
-    """The glue's `solve-in-chunks`: call(cap) -> (status, pivots of that call) until the status is
-    something else than MI_MAX_PIVOTS or max_pivots (0 = no cap) are used up.  A solve continued
-    call by call takes exactly the pivots of one long call.  (chunk: tests force a small one.)"""
-    chunk, total = chunk or chunk_pivots(rows, cols), 0
-    while True:
-        cap = min(chunk, max_pivots - total) if max_pivots > 0 else chunk
-        rc, k = call(cap)
-        total += k
-        if rc != capi.MI_MAX_PIVOTS or (max_pivots > 0 and total >= max_pivots):
-            return rc, total
 
 
 def _solve_two_phase_in_chunks(art, main, max_pivots=0, chunk=None):
@@ -335,7 +325,7 @@ def _solve_two_phase_in_chunks(art, main, max_pivots=0, chunk=None):
             return rc, int(n.value)
         return call
     try:
-        rc, n1 = _solve_in_chunks(phase(art, 0), rows, cols, int(max_pivots), chunk=chunk)
+        rc, n1 = solve_in_chunks(phase(art, 0), rows, cols, int(max_pivots), chunk=chunk)
         main.n_pivots = (n1, 0)
         if rc != capi.MI_OPTIMAL:
             return rc
@@ -346,7 +336,7 @@ def _solve_two_phase_in_chunks(art, main, max_pivots=0, chunk=None):
             return rc
         if max_pivots > 0 and n1 >= max_pivots:
             return capi.MI_MAX_PIVOTS
-        rc, n2 = _solve_in_chunks(phase(main, main.is_max), rows, cols, max_pivots - n1 if max_pivots > 0 else 0, chunk=chunk)
+        rc, n2 = solve_in_chunks(phase(main, main.is_max), rows, cols, max_pivots - n1 if max_pivots > 0 else 0, chunk=chunk)
         main.n_pivots = (n1, n2)
         return rc
     finally:
@@ -386,7 +376,7 @@ def n_solve_tableau(tableau, max_pivots=0, chunked=False, chunk=None):
                         "mi355x_tab_solve")
         return rc, int(n.value)
     if chunked:
-        rc, total = _solve_in_chunks(call, tableau.constraint_count + 1, tableau.var_count + 1, int(max_pivots), chunk=chunk)
+        rc, total = solve_in_chunks(call, tableau.constraint_count + 1, tableau.var_count + 1, int(max_pivots), chunk=chunk)
     else:
         rc, total = call(max_pivots)
     tableau._touch()
@@ -420,7 +410,7 @@ def _solve_column_partitioned(tableau, devices, max_pivots=0):
             rc = capi.check(L.mi355x_colpart_solve(h, int(tableau.is_max), float(tableau.fp_tolerance_factor),
                                                    int(cap), ctypes.byref(n)), "mi355x_colpart_solve")
             return rc, int(n.value)
-        rc, total = _solve_in_chunks(call, M.shape[0], M.shape[1], int(max_pivots))
+        rc, total = solve_in_chunks(call, M.shape[0], M.shape[1], int(max_pivots))
         if rc == capi.MI_NONFINITE:
             return False
         tableau.n_pivots = total
@@ -697,119 +687,67 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
         # the whole list behind ONE job of the library (mi355x_simplex_solver_many_*): members come
         # back as NativeSolution objects (the glue's :native :many)
         from .native import solve_many
-        results = solve_many(problems, fp_tolerance=fp_tolerance, devices=devices, max_pivots=max_pivots)
-        if errorp:
-            for r in results:
-                if isinstance(r, Exception):
-                    raise r
-        return results
+        return finish(solve_many(problems, fp_tolerance=fp_tolerance, devices=devices, max_pivots=max_pivots), errorp)
     if from_rows:
         from .batch_lps import solve_problems_from_rows
 
         def host_route(p):
             return mi355x_solve_problems([p], fp_tolerance=fp_tolerance, device=device, devices=devices,
                                          max_pivots=max_pivots, errorp=False, native=native)[0]
-        results = solve_problems_from_rows(problems, host_route, fp_tolerance=fp_tolerance, device=device,
-                                           devices=devices, max_pivots=max_pivots)
-        if errorp:
-            for r in results:
-                if isinstance(r, Exception):
-                    raise r
-        return results
+        return finish(solve_problems_from_rows(problems, host_route, fp_tolerance=fp_tolerance, device=device,
+                                               devices=devices, max_pivots=max_pivots), errorp)
+    from .batch_lps import solve_batches
     results = [None] * len(problems)
     groups, groups2 = {}, {}
 
     def alone(k):
-        try:
-            # (native: what the one-problem hook may return for a member solved alone -- False keeps the
-            # list homogeneous, every member a Tableau; "auto" lets lone members take the native route)
-            results[k] = mi355x_simplex_solver(problems[k], fp_tolerance=fp_tolerance, device=device,
-                                               max_pivots=max_pivots, native=native)
-        except SolverError as e:
-            results[k] = e
+        # (native: what the one-problem hook may return for a member solved alone -- False keeps the
+        # list homogeneous, every member a Tableau; "auto" lets lone members take the native route)
+        return mi355x_simplex_solver(problems[k], fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots,
+                                     native=native)
 
     for k, p in enumerate(problems):
         if p.integer_vars:
-            alone(k)
+            one_by_one(results, [k], alone)
             continue
         try:
             tabs = build_tableau(p, p, fp_tolerance_factor=fp_tolerance, device=device)
         except SolverError as e:                       # e.g. the unbounded no-constraint special case
             results[k] = e
             continue
-        if isinstance(tabs, list):                     # two-phase: (art main), src/simplex.lisp:326-328
-            art, main = tabs
-            groups2.setdefault((art.matrix.shape, main.matrix.shape, main.is_max), []).append((k, art, main))
-        elif not _unit_basis(tabs):
-            alone(k)
+        if isinstance(tabs, Tableau) and not _unit_basis(tabs):
+            one_by_one(results, [k], alone)
         else:
-            groups.setdefault((tabs.matrix.shape, tabs.is_max), []).append((k, tabs))
-    def batch_in_chunks(mb, is_max, rows, cols):
-        """The glue's `multibatch-solve-in-chunks`: bounded calls until no member is left at
-        MI_MAX_PIVOTS (or max_pivots are used up); -> (statuses, pivots per member)."""
-        chunk, done = chunk_pivots(rows, cols), 0
-        total = np.zeros(mb.n_lps, dtype=np.int64)
-        while True:
-            cap = min(chunk, max_pivots - done) if max_pivots > 0 else chunk
-            st, npv = mb.solve(is_max=is_max, fp_tolerance=fp_tolerance, max_pivots=cap)
-            total += npv
-            done += cap
-            if (max_pivots > 0 and done >= max_pivots) or not (st == capi.MI_MAX_PIVOTS).any():
-                return st, total
+            file_by_shape(groups, groups2, k, tabs)
 
-    def adopt(t, mb, q):
+    def batch(tabs):
+        return MultiDeviceBatch.from_arrays(np.stack([t.matrix for t in tabs]),
+                                            np.stack([t.basis_columns for t in tabs]), n_devices=devices)
+
+    def adopt(t, mb, q, st, npv):
+        e = _error_for(int(st[q]))
+        if e is not None:
+            return e
         G, gb = mb.download(q)
         old, t._handle = t._handle, None
         if old:
             capi.lib().mi355x_tab_destroy(old)
         t._matrix, t._basis, t._stale, t._light = G, gb, False, None
+        t.n_pivots = member_pivots(npv, q)
+        return t
 
-    for (shape, is_max), members in groups.items():
+    # a group of two or more is one batch, or for two-phase members a batch of artificial and a batch of main
+    # tableaux: phase 1, the per-member step between the phases and phase 2 in bounded calls (solve_batches)
+    for members in [*groups.values(), *groups2.values()]:
+        ks, mains = [m[0] for m in members], [m[-1] for m in members]
         if len(members) == 1:
-            alone(members[0][0])
+            one_by_one(results, ks, alone)
             continue
-        rows, cols = shape
-        mb = MultiDeviceBatch.from_arrays(np.stack([t.matrix for _, t in members]),
-                                          np.stack([t.basis_columns for _, t in members]), n_devices=devices)
-        st, npv = batch_in_chunks(mb, is_max, rows, cols)
-        for q, (k, t) in enumerate(members):
-            try:
-                _raise_for(int(st[q]))
-            except SolverError as e:
-                results[k] = e
-                continue
-            adopt(t, mb, q)
-            t.n_pivots = int(npv[q])
-            results[k] = t
-    # two-phase members of one shape: phase 1 in bounded calls on the batch of artificial tableaux, the
-    # per-member step between the phases (feasibility test, drive-out pivots, hand-over:
-    # mi355x_multibatch_two_phase_handover), phase 2 in bounded calls on the batch of main tableaux
-    for (ashape, mshape, is_max), members in groups2.items():
-        if len(members) == 1:
-            alone(members[0][0])
-            continue
-        amb = MultiDeviceBatch.from_arrays(np.stack([a.matrix for _, a, _ in members]),
-                                           np.stack([a.basis_columns for _, a, _ in members]), n_devices=devices)
-        mmb = MultiDeviceBatch.from_arrays(np.stack([t.matrix for _, _, t in members]),
-                                           np.stack([t.basis_columns for _, _, t in members]), n_devices=devices)
-        st1, np1 = batch_in_chunks(amb, False, ashape[0], ashape[1])
-        between, nd = amb.two_phase_handover(mmb, fp_tolerance=fp_tolerance, phase1_status=st1)
-        st2, np2 = batch_in_chunks(mmb, is_max, ashape[0], ashape[1])
-        for q, (k, a, t) in enumerate(members):
-            st = int(st2[q]) if int(between[q]) == capi.MI_OK else int(between[q])
-            try:
-                _raise_for(st)
-            except SolverError as e:
-                results[k] = e
-                continue
-            adopt(t, mmb, q)
-            t.n_pivots = (int(np1[q] + nd[q]), int(np2[q]))
-            results[k] = t
-    if errorp:
-        for r in results:
-            if isinstance(r, Exception):
-                raise r
-    return results
+        amb = batch([m[1] for m in members]) if len(members[0]) == 3 else None
+        mmb = batch(mains)
+        st, npv = solve_batches(mmb, amb, mains[0].is_max, fp_tolerance, max_pivots)
+        place(results, ks, [adopt(t, mmb, q, st, npv) for q, t in enumerate(mains)])
+    return finish(results, errorp)
 
 
 def _unit_basis(tableau):

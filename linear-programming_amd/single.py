@@ -21,7 +21,7 @@ import ctypes
 
 import numpy as np
 
-from . import capi
+from . import capi, lists
 from .capi import _ptr
 from .conditions import UnsupportedConstraintError
 from .lowering import NumberSystem, build
@@ -198,40 +198,38 @@ def solve_status(tableau, max_pivots=0, chunk=None):
     """n-solve-tableau (src/simplex.lisp:399-461) in bounded foreign calls, without raising: a SingleTableau or
     [art, main] -> (status, pivots); pivots is a number, or (phase 1 + drive-outs, phase 2) for a pair.
     max_pivots (0: none) caps the pivots, for a pair both phases together; chunk: pivots per foreign call."""
-    from .simplex import chunk_pivots
     L = capi.lib()
     if isinstance(tableau, (list, tuple)):
         art, main = tableau
-        chunk = chunk or chunk_pivots(art.constraint_count + 1, art.var_count + 1)
         npv = (ctypes.c_int64 * 2)()
-        n1 = n2 = 0
+        done = [0, 0]
+
+        def call(cap):
+            rc = capi.check(L.mi355x_stab_solve_two_phase(art._h, main._h, int(main.is_max),
+                                                          float(main.fp_tolerance_factor), int(cap), npv),
+                            "mi355x_stab_solve_two_phase")
+            done[0] += int(npv[0])
+            done[1] += int(npv[1])
+            return rc, int(npv[0]) + int(npv[1])
         try:
-            while True:
-                done = n1 + n2
-                cap = min(chunk, max_pivots - done) if max_pivots > 0 else chunk
-                rc = capi.check(L.mi355x_stab_solve_two_phase(art._h, main._h, int(main.is_max),
-                                                              float(main.fp_tolerance_factor), int(cap), npv),
-                                "mi355x_stab_solve_two_phase")
-                n1, n2 = n1 + int(npv[0]), n2 + int(npv[1])
-                if rc != capi.MI_MAX_PIVOTS or (max_pivots > 0 and n1 + n2 >= max_pivots):
-                    main.n_pivots = (n1, n2)
-                    return rc, (n1, n2)
+            rc, _ = lists.solve_in_chunks(call, art.constraint_count + 1, art.var_count + 1, max_pivots, chunk)
+            main.n_pivots = tuple(done)
+            return rc, main.n_pivots
         finally:
             art._touch()
             main._touch()
     if not isinstance(tableau, SingleTableau):                # (check-type tableau tableau) :454
         raise TypeError("%r is not a single-float tableau" % (tableau,))
-    chunk = chunk or chunk_pivots(tableau.constraint_count + 1, tableau.var_count + 1)
-    n, total = ctypes.c_int64(0), 0
+    n = ctypes.c_int64(0)
+
+    def call(cap):
+        rc = capi.check(L.mi355x_stab_solve(tableau._h, int(tableau.is_max), float(tableau.fp_tolerance_factor),
+                                            int(cap), ctypes.byref(n)), "mi355x_stab_solve")
+        return rc, int(n.value)
     try:
-        while True:
-            cap = min(chunk, max_pivots - total) if max_pivots > 0 else chunk
-            rc = capi.check(L.mi355x_stab_solve(tableau._h, int(tableau.is_max), float(tableau.fp_tolerance_factor),
-                                                int(cap), ctypes.byref(n)), "mi355x_stab_solve")
-            total += int(n.value)
-            if rc != capi.MI_MAX_PIVOTS or (max_pivots > 0 and total >= max_pivots):
-                tableau.n_pivots = total
-                return rc, total
+        rc, tableau.n_pivots = lists.solve_in_chunks(call, tableau.constraint_count + 1, tableau.var_count + 1,
+                                                     max_pivots, chunk)
+        return rc, tableau.n_pivots
     finally:
         tableau._touch()
 
@@ -370,99 +368,65 @@ def group_single_problems(problems, fp_tolerance=1024, device=0):
         except SolverError as e:
             slots[k] = e
             continue
-        if isinstance(tabs, list):
-            art, main = tabs
-            groups2.setdefault((art.matrix.shape, main.matrix.shape, main.is_max), []).append((k, art, main))
-        else:
-            groups.setdefault((tabs.matrix.shape, tabs.is_max), []).append((k, tabs))
+        lists.file_by_shape(groups, groups2, k, tabs)
     return slots, groups, groups2
-
-
-def _batch_in_chunks(call, n, rows, cols, max_pivots, chunk=None):
-    """Bounded foreign calls on a batch until no member is left at MI_MAX_PIVOTS or max_pivots (0: none) are used
-    up: call(cap) -> (status[n], pivots[n, ...] of that call); -> (status, pivots summed)."""
-    from .simplex import chunk_pivots
-    chunk, done, total = chunk or chunk_pivots(rows, cols), 0, None
-    while True:
-        cap = min(chunk, max_pivots - done) if max_pivots > 0 else chunk
-        st, npv = call(cap)
-        total = npv.copy() if total is None else total + npv
-        done += cap
-        if (max_pivots > 0 and done >= max_pivots) or not (st == capi.MI_MAX_PIVOTS).any():
-            return st, total
 
 
 def solve_problems_single(problems, fp_tolerance=1024, device=0, max_pivots=0, errorp=True, chunk=None):
     """mi355x_solve_problems(..., precision="single"): what [solve_single(p) for p in problems] returns, the groups
     of two or more as ONE SingleBatch (or a pair of them) in bounded chunks.  Members alone in their group, shapes
     the batch declines and integer problems go through solve_single one by one."""
-    from .conditions import SolverError
-    from .simplex import _raise_for
+    from .simplex import _error_for
     results = [None] * len(problems)
     slots, groups, groups2 = group_single_problems(problems, fp_tolerance, device)
 
     def alone(k):
-        try:
-            results[k] = solve_single(problems[k], fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots,
-                                      chunk=chunk)
-        except SolverError as e:
-            results[k] = e
+        return solve_single(problems[k], fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots, chunk=chunk)
 
-    def make(mats, bases):
+    def make(*members):
+        """One SingleBatch per list of tableaux, or None when the batch declines a shape (beyond the LDS budget)."""
+        made = []
         try:
-            return SingleBatch.from_arrays(np.stack(mats), np.stack(bases), device=device)
+            for tabs in members:
+                made.append(SingleBatch.from_arrays(np.stack([t.matrix for t in tabs]),
+                                                    np.stack([t.basis_columns for t in tabs]), device=device))
         except capi.Mi355xError as e:
+            for b in made:
+                b.close()
             if e.code != capi.MI_UNSUPPORTED:
                 raise
-            return None                                       # (beyond the LDS budget: one by one)
+            return None
+        return made
 
     def adopt(t, sb, q, st, npv):
-        try:
-            _raise_for(int(st))
-        except SolverError as e:
+        e = _error_for(int(st[q]))
+        if e is not None:
             return e
         t._matrix, t._basis = sb.download(q)
         t._stale, t._handle = False, None                     # (never uploaded: no handle left behind)
-        t.n_pivots = npv
+        t.n_pivots = lists.member_pivots(npv, q)
         return t
 
     for k, s in enumerate(slots):
         if s == "alone":
-            alone(k)
+            lists.one_by_one(results, [k], alone)
         elif s is not None:
             results[k] = s
-    for (shape, is_max), members in groups.items():
-        sb = make([t.matrix for _, t in members], [t.basis_columns for _, t in members]) if len(members) > 1 else None
-        if sb is None:
-            for k, _ in members:
-                alone(k)
+    # a group of two or more is one batch, or for two-phase members a batch of artificial and one of main tableaux
+    for members in [*groups.values(), *groups2.values()]:
+        ks, firsts, mains = [m[0] for m in members], [m[1] for m in members], [m[-1] for m in members]
+        two, is_max = len(members[0]) == 3, mains[0].is_max
+        made = (make(firsts, mains) if two else make(mains)) if len(members) > 1 else None
+        if made is None:
+            lists.one_by_one(results, ks, alone)
             continue
         try:
-            st, npv = _batch_in_chunks(lambda cap: sb.solve(is_max, fp_tolerance, cap), len(members), shape[0], shape[1],
-                                       max_pivots, chunk)
-            for q, (k, t) in enumerate(members):
-                results[k] = adopt(t, sb, q, st[q], int(npv[q]))
+            first, sb = made[0], made[-1]
+            st, npv = lists.batch_in_chunks(
+                lambda cap: (False,) + (first.solve_two_phase(sb, is_max, fp_tolerance, cap) if two else
+                                        sb.solve(is_max, fp_tolerance, cap)), first.rows, first.cols, max_pivots, chunk)
+            lists.place(results, ks, [adopt(t, sb, q, st, npv) for q, t in enumerate(mains)])
         finally:
-            sb.close()
-    for (ashape, mshape, is_max), members in groups2.items():
-        ab = make([a.matrix for _, a, _ in members], [a.basis_columns for _, a, _ in members]) if len(members) > 1 else None
-        mb = make([t.matrix for _, _, t in members], [t.basis_columns for _, _, t in members]) if ab is not None else None
-        if mb is None:
-            if ab is not None:
-                ab.close()
-            for k, _, _ in members:
-                alone(k)
-            continue
-        try:
-            st, npv = _batch_in_chunks(lambda cap: ab.solve_two_phase(mb, is_max, fp_tolerance, cap), len(members),
-                                       ashape[0], ashape[1], max_pivots, chunk)
-            for q, (k, _, t) in enumerate(members):
-                results[k] = adopt(t, mb, q, st[q], (int(npv[q, 0]), int(npv[q, 1])))
-        finally:
-            ab.close()
-            mb.close()
-    if errorp:
-        for r in results:
-            if isinstance(r, Exception):
-                raise r
-    return results
+            for b in made:
+                b.close()
+    return lists.finish(results, errorp)
