@@ -872,6 +872,43 @@ int  mi355x_sbatch_info(const mi355x_sbatch *b, int64_t *n_lps, int64_t *rows, i
 int  mi355x_sbatch_cancel(mi355x_sbatch *b);
 void mi355x_sbatch_destroy(mi355x_sbatch *b);
 
+/* ---- single-float branch-and-bound (opt-in): node LPs assembled on the device ------------------
+ * simplex-solver (src/simplex.lisp:462-542) on a problem whose numbers Lisp reads as integers and single-floats.
+ * The search, build-tableau of the base problem and the reading of a solution stay in the host language; the
+ * library builds the node tableaux -- what build-tableau (src/simplex.lisp:142-328) makes of `node rows ++ problem
+ * constraints` under Lisp's contagion, bit for bit -- as members of mi355x_sbatch handles, and gathers what
+ * tableau-objective-value and tableau-variable read (src/simplex.lisp:74-107).
+ * Base: the base problem's general-form main tableau in floats (rows x cols, tightly packed; a basis entry == cols
+ * marks a row that needs an artificial variable, :254-265), ncv structural columns, nb rows of doubly-bounded
+ * variables in front (:198-202), and per variable kind (0 positive, 1 negative, 2 signed), first column and offset
+ * (:189-212).  col_int_sum[c]: the sum of the absolute values of the entries of column c that are INTEGERS in Lisp
+ * (not floats with integer values), over the constraint rows -- the guard below rests on it.
+ * Node rows: (var, sense 0 `<=` / 1 `>=`, bound), depth rows per node, newest first; they go between the nb bound
+ * rows and the constraints (:214-221).  A row's right-hand side is float(bound) - offset (one rounding, the same
+ * value as Lisp's bound - 1 * offset, :230-237); a negative one negates the row and flips its sense (:243-252),
+ * leaving +0.0 in its other columns, as the d slack columns inserted into base rows hold +0.0.  Artificial columns
+ * are dealt in decreasing row order (:257, :261, :296-300); the artificial objective row is per column the float
+ * sum of the artificial rows in increasing row order from 0 (:302-316).
+ * The guard: Lisp keeps integers exact among themselves in that sum, so a group is taken only when for every
+ * column col_int_sum plus the node rows' own integer entries is at most 2^24 -- every integer partial sum is then
+ * exact in a float.  Otherwise MI_UNSUPPORTED: the caller builds those nodes on the host (mi355x_sbatch_create).
+ * MI_UNSUPPORTED as well for a shape beyond the batch's LDS budget (mi355x_sbatch_create's rule).
+ * create_nodes: n_nodes nodes of ONE depth and ONE number of artificial rows (MI_BAD_ARG otherwise).  *out_main:
+ * the main tableaux (rows + depth) x (cols + depth); *out_art: the artificial tableaux, (cols + depth + artificial
+ * rows) columns, or NULL without artificial rows.  Every member is MI_RUNNING with an empty trace; the pair goes to
+ * mi355x_sbatch_solve_two_phase, a main batch alone to mi355x_sbatch_solve.  The caller owns both handles. */
+typedef struct mi355x_sbb_base mi355x_sbb_base;
+int  mi355x_sbb_base_create(mi355x_sbb_base **out, int64_t rows, int64_t cols, const float *matrix, const int64_t *basis,
+                            int64_t ncv, int64_t nb, int64_t n_vars, const int32_t *kind, const int64_t *col,
+                            const float *offset, const double *col_int_sum, int device);
+void mi355x_sbb_base_destroy(mi355x_sbb_base *base);
+int  mi355x_sbatch_create_nodes(mi355x_sbatch **out_main, mi355x_sbatch **out_art, const mi355x_sbb_base *base,
+                                int64_t n_nodes, int64_t depth, const int64_t *var, const int32_t *sense,
+                                const int64_t *bound);
+/* Per member the last column (rhs: rows values), the last row (obj_row: cols values) and the basis (rows - 1
+ * entries), member-major: one gather kernel and one copy for the whole batch. */
+int  mi355x_sbatch_readback(mi355x_sbatch *b, float *rhs, float *obj_row, int64_t *basis);
+
 #ifdef __cplusplus
 }
 #endif

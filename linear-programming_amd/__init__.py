@@ -13,7 +13,7 @@ GPU, and fails loudly otherwise.
 (The directory name contains a hyphen; import it with
 ``importlib.import_module("linear-programming_amd")``.)
 """
-from . import batch, batch_lps, capi, exact, exact_bb, exact_lps, lists, lowering, native, simplex, single, solver, synth       # noqa: F401
+from . import batch, batch_lps, capi, exact, exact_bb, exact_lps, lists, lowering, native, simplex, single, single_bb, solver, synth       # noqa: F401
 from .native import NativeProblem, NativeSolution               # noqa: F401
 from .batch import TableauBatch, MultiDeviceBatch               # noqa: F401
 from .batch_lps import lower_problem_rows, group_lowered_rows, solve_lps    # noqa: F401

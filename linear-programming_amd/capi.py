@@ -183,6 +183,10 @@ SIGNATURES = {
     "mi355x_sbatch_info": (_int, [_p, _p, _p, _p, _p, _p, _p, _p]),
     "mi355x_sbatch_cancel": (_int, [_p]),
     "mi355x_sbatch_destroy": (None, [_p]),
+    "mi355x_sbb_base_create": (_int, [_pp, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _int]),
+    "mi355x_sbb_base_destroy": (None, [_p]),
+    "mi355x_sbatch_create_nodes": (_int, [_pp, _pp, _p, _i64, _i64, _p, _p, _p]),
+    "mi355x_sbatch_readback": (_int, [_p, _p, _p, _p]),
 }
 # tuning / measurement / test hooks: include/mi355x_simplex_tune.h (not the drop-in boundary)
 _EXTRA = {

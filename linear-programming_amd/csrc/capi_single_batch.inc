@@ -16,6 +16,7 @@ struct mi355x_sbatch {
     int         threads = 0;              // snapshot of the rule (or the hook) at create
     int         launch_cap = kSingleLaunchCap;
     int         members_per_cu = 0;       // hipOccupancyMaxActiveBlocksPerMultiprocessor of k_sb_solve<threads> at this shape
+    void       *rb = nullptr;         // mi355x_sbatch_readback's gather buffer (made at its first call)
     int32_t    *d_phase = nullptr;        // artificial batch of a two-phase pair: per member (state, status between the phases)
     std::vector<Ctl>     h;               // the control blocks as the last read-back left them
     std::vector<int32_t> h_phase;
@@ -35,6 +36,7 @@ void free_sbatch(mi355x_sbatch *b)
     (void)hipFree(b->v.trace_ec);
     (void)hipFree(b->v.trace_cr);
     (void)hipFree(b->d_phase);
+    (void)hipFree(b->rb);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -50,21 +52,15 @@ int sb_read(mi355x_sbatch *b, hipStream_t s, bool with_phase)
 
 inline bool sb_carried_on(int32_t st) { return st == kRunning || st == MI_MAX_PIVOTS; }
 
-}  // namespace
-
-extern "C" {
-
-int mi355x_sbatch_create(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, const float *matrices,
-                         const int64_t *basis, int device)
+// An empty batch of the shape: the checks of mi355x_sbatch_create, the handle, its stream and its device buffers
+// (zero_padding: the tableaux zeroed where a row has padding -- for members that are uploaded tight).
+// MI_UNSUPPORTED: the shape does not fit the LDS budget.
+int sb_new(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, int device, bool zero_padding)
 {
-    if (!out) return fail(MI_BAD_ARG, "out is NULL");
-    *out = nullptr;
-    if (!matrices) return fail(MI_BAD_ARG, "matrices is NULL");
     if (n_lps < 1 || n_lps > (1LL << 30)) return fail(MI_BAD_ARG, "n_lps=%lld must be in [1, 2^30]", (long long)n_lps);
     if (rows < 1 || cols < 1) return fail(MI_BAD_ARG, "rows=%lld cols=%lld must be >= 1", (long long)rows, (long long)cols);
     if (rows > 65535LL * 16) return fail(MI_BAD_ARG, "rows=%lld exceeds the supported 1048560", (long long)rows);
     if (cols > (1LL << 30)) return fail(MI_BAD_ARG, "cols=%lld exceeds the supported 2^30", (long long)cols);
-    if (rows > 1 && !basis) return fail(MI_BAD_ARG, "basis is NULL");
     const int ndev = device_count_checked();
     if (ndev <= 0) return fail(MI_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
     if (device < 0 || device >= ndev) return fail(MI_BAD_ARG, "device %d out of range [0,%d)", device, ndev);
@@ -103,19 +99,48 @@ int mi355x_sbatch_create(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64
     if (e == hipSuccess) e = hipMalloc((void **)&v.trace_ec, (size_t)(n_lps * v.trace_cap) * sizeof(int64_t));
     if (e == hipSuccess) e = hipMalloc((void **)&v.trace_cr, (size_t)(n_lps * v.trace_cap) * sizeof(int64_t));
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_phase, (size_t)(2 * n_lps) * sizeof(int32_t));
-    if (e == hipSuccess && v.ld != v.cols) e = hipMemsetAsync(v.M, 0, mbytes, b->stream);
+    if (e == hipSuccess && zero_padding && v.ld != v.cols) e = hipMemsetAsync(v.M, 0, mbytes, b->stream);
     if (e == hipSuccess) e = hipMemsetAsync(b->d_phase, 0, (size_t)(2 * n_lps) * sizeof(int32_t), b->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        free_sbatch(b);
+        return fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "single-float batch allocation failed: %s", hipGetErrorString(e));
+    }
+    *out = b;
+    return MI_OK;
+}
+
+// every member MI_RUNNING with no pivots and an empty trace, on the device and in b->h; waits for the batch's stream
+hipError_t sb_fresh_ctl(mi355x_sbatch *b)
+{
+    launch_sb_ctl_reset(b->v, b->stream);
+    hipError_t e = hipGetLastError();
     if (e == hipSuccess)
-        e = hipMemcpy2DAsync(v.M, v.ld * sizeof(float), matrices, cols * sizeof(float), cols * sizeof(float),
-                             (size_t)(n_lps * rows), hipMemcpyHostToDevice, b->stream);
+        e = hipMemcpyAsync(b->h.data(), b->v.ctl, (size_t)b->v.n_lps * sizeof(Ctl), hipMemcpyDeviceToHost, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    return e;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi355x_sbatch_create(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, const float *matrices,
+                         const int64_t *basis, int device)
+{
+    if (!out) return fail(MI_BAD_ARG, "out is NULL");
+    *out = nullptr;
+    if (!matrices) return fail(MI_BAD_ARG, "matrices is NULL");
+    if (rows > 1 && !basis) return fail(MI_BAD_ARG, "basis is NULL");
+    mi355x_sbatch *b = nullptr;
+    const int rc = sb_new(&b, n_lps, rows, cols, device, /*zero_padding=*/true);
+    if (rc != MI_OK) return rc;
+    SbView &v = b->v;
+    hipError_t e = hipMemcpy2DAsync(v.M, v.ld * sizeof(float), matrices, cols * sizeof(float), cols * sizeof(float),
+                                    (size_t)(n_lps * rows), hipMemcpyHostToDevice, b->stream);
     if (e == hipSuccess && rows > 1)
         e = hipMemcpyAsync(v.basis, basis, (size_t)(n_lps * (rows - 1)) * sizeof(int64_t), hipMemcpyHostToDevice, b->stream);
-    if (e == hipSuccess) {
-        launch_sb_ctl_reset(v, b->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(b->h.data(), v.ctl, (size_t)n_lps * sizeof(Ctl), hipMemcpyDeviceToHost, b->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e == hipSuccess) e = sb_fresh_ctl(b);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         free_sbatch(b);

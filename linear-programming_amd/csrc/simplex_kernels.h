@@ -536,6 +536,21 @@ void launch_sb_begin(const SbView &b, int64_t max_pivots, const int32_t *phase, 
 void launch_sb_solve(const SbView &b, int threads, int is_max, double fp_factor, int cap, const int32_t *gate, hipStream_t s);
 void launch_sb_between(const SbView &art, const SbView &main_b, int threads, int32_t *phase, double fp_factor,
                        int64_t max_pivots, hipStream_t s);
+// Single-float branch-and-bound (kernels_single_bb.inc, capi_single_bb.inc): the base problem's general-form
+// tableau in floats; the node rows of the members are an XbbNodeRows, as for the exact search.
+struct SbbBaseView {
+    const float   *B;                 // rows x cols floats, tight
+    const float   *voff;              // per variable: its offset (not read for a free variable)
+    int64_t        rows, cols, ncv, nb;
+    const int64_t *basis;             // rows - 1; an entry == cols: an artificial row
+    const int32_t *kind;              // per variable: 0 positive, 1 negative, 2 signed
+    const int64_t *vcol;
+};
+size_t sbb_assemble_lds(int64_t m, int64_t d);                              // its dynamic LDS in bytes (m constraint rows)
+// every member of mt and of at (at.M == nullptr: no artificial rows): tableau over the whole leading dimension, basis
+void launch_sbb_assemble(const SbView &mt, const SbView &at, const SbbBaseView &b, const XbbNodeRows &nr, hipStream_t s);
+// per member: last column (rows), last row (cols), basis (rows - 1), each plane member-major (device pointers)
+void launch_sb_readback(const SbView &b, float *rhs, float *obj, int64_t *basis, hipStream_t s);
 
 int         update_variant_count();
 const char *update_variant_name(int v);

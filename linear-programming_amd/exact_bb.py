@@ -53,10 +53,16 @@ class SearchResult:
         return {"processed": len(self.trace), "solved": self.n_solved, "max_depth": self.max_depth}
 
 
-def search(problem, solve_round, width=1, max_nodes=0):
+def _fractional(v):
+    return v.denominator != 1
+
+
+def search(problem, solve_round, width=1, max_nodes=0, fractional=_fractional, floor=math.floor, ceil=math.ceil):
     """simplex-solver (src/simplex.lisp:506-542).  solve_round(list of entries) -> per entry (status,
     objective, values): an entry is a tuple of rows (var, sense 0 `<=` / 1 `>=`, bound), newest first;
-    values[var] is the variable's Fraction.  Up to `width` node LPs per round."""
+    values[var] is the variable's Fraction.  Up to `width` node LPs per round.
+    fractional(v): the integrality test's negation (:474-479), floor / ceil: the branching bounds (:465-472) --
+    the defaults are the rational search's; single_bb.py passes the float32 readings."""
     is_max = problem.type == "max"
 
     def better(inc, v):                                               # the comparator, :515
@@ -71,7 +77,7 @@ def search(problem, solve_round, width=1, max_nodes=0):
         n = nodes[i]
         if n.child[which] is None:
             v = n.values[n.viol]
-            bound = math.floor(v) if which == 0 else math.ceil(v)
+            bound = floor(v) if which == 0 else ceil(v)
             nodes.append(_Node(i, (n.viol, which, bound), n.depth + 1))
             n.child[which] = len(nodes) - 1
         return n.child[which]
@@ -115,7 +121,7 @@ def search(problem, solve_round, width=1, max_nodes=0):
                 res.n_solved += 1
                 if status == capi.MI_OPTIMAL:
                     n.obj, n.values = obj, values
-                    n.viol = next((v for v in problem.integer_vars if values[v].denominator != 1), None)   # :474-479
+                    n.viol = next((v for v in problem.integer_vars if fractional(values[v])), None)   # :474-479
             continue
         stack.pop()
         n = nodes[i]

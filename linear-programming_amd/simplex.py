@@ -535,11 +535,24 @@ def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_p
     (single.py) -- build-tableau with Lisp's contagion, IEEE binary32 arithmetic and single-float-epsilon thresholds
     on the GPU, the solved SingleTableau returned, its read-back in np.float32.  Every number of the problem must
     be an integer with |x| <= 2**24 or a float whose value a binary32 holds exactly; anything else is declined:
-    unsupported-constraint-error ("single", number).  Together with exact, branch_and_bound, devices > 1,
-    native=True, full_tableau or a pivot_rule other than "dantzig" it is an argument error that names the pair; so
-    is an unknown precision."""
+    unsupported-constraint-error ("single", number).  Together with exact, devices > 1, native=True, full_tableau
+    or a pivot_rule other than "dantzig" it is an argument error that names the pair; so is an unknown precision.
+    precision="single" together with branch_and_bound=True, on a problem WITH integer variables (opt-in): the
+    reference's branch-and-bound in single-float arithmetic (single_bb.py) -- the search of the exact route with
+    the float32 reading of `integerp` (v == floor(v); int_tolerance > 0: within int_tolerance *
+    single-float-epsilon of an integer), floor / ceiling bounds as exact integers, up to bb_width node LPs side by
+    side as batches of single-float tableaux assembled on the device; max_nodes, max_pivots (per node LP, both
+    phases together) and chunk as on the exact search.  Returns the incumbent's solved SingleTableau.  On a problem
+    without integer variables the pair stays an argument error that names "single" and "branch_and_bound"; without
+    branch_and_bound an integer problem is declined: unsupported-constraint-error ("integer" ...)."""
     if precision not in ("double", "single"):
         raise ValueError("precision=%r: \"double\" (default) or \"single\"" % (precision,))
+    if precision == "single" and branch_and_bound and problem.integer_vars and not exact and devices <= 1 and \
+            native is not True and not full_tableau and pivot_rule == "dantzig":
+        from .single_bb import solve_branch_and_bound_single
+        return solve_branch_and_bound_single(problem, width=bb_width, fp_tolerance=fp_tolerance,
+                                             int_tolerance=int_tolerance, device=device, max_pivots=max_pivots,
+                                             max_nodes=max_nodes, chunk=chunk)
     if precision == "single":
         for name, clash in (("exact", bool(exact)), ("branch_and_bound", bool(branch_and_bound)),
                             ("devices", devices > 1), ("native", native is True), ("full_tableau", bool(full_tableau)),

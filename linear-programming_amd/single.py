@@ -13,6 +13,9 @@ holds exactly (``np.float32``, or a Python float with ``float(np.float32(x)) == 
 double that is not a float32 value, a Fraction, a larger integer -- is DECLINED, never rounded silently:
 ``UnsupportedConstraintError(("single", x), "mi355x-simplex")``.
 
+Integer problems are declined here (``solve_single``); ``precision="single", branch_and_bound=True`` solves them
+with the reference's branch-and-bound in single-float arithmetic (single_bb.py).
+
 Known departure (stated the way the double path states its own): integer-only sub-expressions that the
 reference would keep as exact ratios through a pivot are floats here from the start -- the tableau that
 crosses the boundary is all float32.
@@ -243,7 +246,8 @@ def n_solve_tableau(tableau, max_pivots=0, chunk=None):
 
 
 def solve_single(problem, fp_tolerance=1024, device=0, max_pivots=0, chunk=None):
-    """What mi355x_simplex_solver(problem, precision="single") returns: the solved SingleTableau."""
+    """What mi355x_simplex_solver(problem, precision="single") returns: the solved SingleTableau.  An integer
+    problem is declined here; single_bb.py solves it (precision="single", branch_and_bound=True)."""
     if problem.integer_vars:
         raise UnsupportedConstraintError(("integer",) + tuple(problem.integer_vars), "mi355x-simplex")
     tabs = build_tableau_single(problem, fp_tolerance_factor=fp_tolerance, device=device)
