@@ -909,6 +909,32 @@ int  mi355x_sbatch_create_nodes(mi355x_sbatch **out_main, mi355x_sbatch **out_ar
  * entries), member-major: one gather kernel and one copy for the whole batch. */
 int  mi355x_sbatch_readback(mi355x_sbatch *b, float *rhs, float *obj_row, int64_t *basis);
 
+/* ---- single-float batches from problem rows (opt-in): build-tableau on the device ---------------
+ * What mi355x_batch_create_lps is for doubles, in floats and under Lisp's int / single-float contagion: the members
+ * arrive in column space, and the device writes what build-tableau (src/simplex.lisp:243-328) makes of each, bit
+ * for bit, sign of zero included.  Member q: lps + q (m+1)(ncv+1) holds m rows of ncv coefficients and the
+ * right-hand side, offsets already subtracted (:189-241), then the objective row (:270-283, signs applied, constant
+ * last); sense is n_lps x m (0 `<=`, 1 `>=`, 2 `=`).
+ * A row with right-hand side < 0.0f (false for -0.0 and NaN) is negated and its sense flipped (:243-252).  Lisp's
+ * matrix starts as INTEGER zeros and (- 0) is 0: the slack columns of a negated row and its zero coefficients come
+ * out +0.0 (mi355x_batch_create_lps leaves -0.0 there).  A ZERO IN A NEGATED ROW IS READ AS LISP'S INTEGER ZERO: a
+ * single-float zero the user wrote there would be -0.0, and the caller keeps such members out.
+ * Artificial columns are dealt in decreasing row order (:257, :261, :296-300); the artificial objective row is per
+ * column the float sum of the artificial rows in increasing row order from 0 (:302-316).
+ * The guard: Lisp keeps integers exact among themselves in that sum.  col_int_sum is n_lps x (ncv + 1) (NULL: all
+ * zero): per member and column the sum of the absolute values of the entries Lisp holds as INTEGERS, over the
+ * constraint rows.  An entry beyond 2^24 answers MI_UNSUPPORTED (the message names the member) and nothing is
+ * allocated.  MI_UNSUPPORTED as well for a main or artificial shape beyond the batch's LDS budget
+ * (mi355x_sbatch_create's rule).  MI_BAD_ARG, before any device is looked for: NULL out / lps / sense, n_lps, m or
+ * ncv < 1, a sense outside 0..2, members that differ in their number of `=` rows or of artificial rows (the
+ * message names the member).
+ * *out_main: the main tableaux, (m + 1) x (ncv + slack columns + 1); *out_art: the artificial tableaux, with one
+ * more column per artificial row, or NULL when no row is artificial.  Both are ordinary mi355x_sbatch handles in
+ * the state mi355x_sbatch_create leaves: every member MI_RUNNING with an empty trace; the pair goes to
+ * mi355x_sbatch_solve_two_phase, a main batch alone to mi355x_sbatch_solve.  The caller owns both handles. */
+int  mi355x_sbatch_create_lps(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n_lps, int64_t m, int64_t ncv,
+                              const float *lps, const int32_t *sense, const double *col_int_sum, int device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -220,6 +220,10 @@ int         mi355x_stab_debug_update_time(mi355x_stab *h, int64_t entering_col, 
  * default (4096), else a count */
 int         mi355x_tune_set_sbatch_threads(int threads);
 int         mi355x_tune_set_sbatch_launch_cap(int cap);
+/* test aid: member lp_index of a single-float batch as it is STORED, padding columns included -- rows x ld floats;
+ * *ld (may be NULL) = the leading dimension; out NULL: only *ld.  What a create entry left in the columns
+ * [cols, ld) (mi355x_sbatch_create_lps writes them itself). */
+int         mi355x_sbatch_debug_stored(mi355x_sbatch *b, int64_t lp_index, float *out, int64_t *ld);
 
 /* Compiled in with -DMI355X_TEST_HOOKS (libmi355x_simplex_test.so, built next to the product
  * library by linear-programming_amd/build.py and loaded by the tests that need it); the product

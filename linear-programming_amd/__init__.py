@@ -13,12 +13,14 @@ GPU, and fails loudly otherwise.
 (The directory name contains a hyphen; import it with
 ``importlib.import_module("linear-programming_amd")``.)
 """
-from . import batch, batch_lps, capi, exact, exact_bb, exact_lps, lists, lowering, native, simplex, single, single_bb, solver, synth       # noqa: F401
+from . import batch, batch_lps, capi, exact, exact_bb, exact_lps, lists, lowering, native, simplex, single, single_bb, single_lps, solver, synth       # noqa: F401
 from .native import NativeProblem, NativeSolution               # noqa: F401
 from .batch import TableauBatch, MultiDeviceBatch               # noqa: F401
 from .batch_lps import lower_problem_rows, group_lowered_rows, solve_lps    # noqa: F401
 from .exact import ExactTableau                                  # noqa: F401
 from .single import SingleBatch, SingleTableau, build_tableau_single, solve_single    # noqa: F401
+from .single_lps import (lower_problem_rows_single, group_lowered_rows_single,      # noqa: F401
+                         solve_problems_single_from_rows, solve_lps_single)
 from .conditions import (SolverError, UnboundedProblemError, InfeasibleProblemError,   # noqa: F401
                          UnsupportedConstraintError, ParsingError)
 from .problem import Problem                                    # noqa: F401

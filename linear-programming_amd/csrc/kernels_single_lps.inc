@@ -1,0 +1,127 @@
+// kernels_single_lps.inc -- batches of single-float LPs assembled from the members' problem rows: build-tableau's
+// steps src/simplex.lisp:243-328 under Lisp's int / single-float contagion, written in float straight into the
+// padded members of two batches of single-float tableaux (capi_single_lps.inc drives it).
+// Part of simplex_kernels.hip (ONE translation unit: included there after kernels_single_bb.inc, inside namespace
+// mi355x).  No double appears in this file; it holds no product, and every sum is one rounded float addition
+// (-ffp-contract=off).
+//
+//   k_slp_assemble   one 256-thread workgroup per member, the form of k_sbb_assemble.  A member arrives in column
+//                    space as for kernels_batch_lps.inc, in floats: m rows of ncv structural coefficients and the
+//                    right-hand side (offsets already subtracted, :189-241), then the objective row (:270-283), one
+//                    sense per row.  What it writes is what build_tableau_single makes of the problem, bit for bit:
+//                      (a) a row whose right-hand side is < 0.0f (false for -0.0 and NaN) is negated and its sense
+//                          flipped (:243-252).  Lisp's matrix starts as INTEGER zeros and (- 0) is 0, so the slack
+//                          columns of a negated row and the coefficients the problem never mentions stay +0.0:
+//                          the kernel writes x == 0 ? +0.0f : -x and never computes -(0.0f).  (k_blp_assemble's
+//                          double rows carry -0.0 there.)  A zero of a negated row is therefore read as Lisp's
+//                          integer zero; a member with a single-float zero in such a row is not for this kernel.
+//                      (b) slack columns in row order for the rows that are not `=` (:254-265); main-basis entries
+//                          of artificial rows = the member's num-cols; artificial columns dealt in DECREASING row
+//                          order (push, :257, :261, :296-300); the artificial objective row per column the float sum
+//                          over the artificial rows in INCREASING row order from 0.0f (:302-316), recomputed from
+//                          the entries, never updated.
+//                      (c) Lisp keeps integers exact among themselves in that sum; the host lets a member in only
+//                          when every integer partial sum is exact in a float (capi_single_lps.inc: the guard).
+//                    Row pass: thread R owns constraint row R.  One trip of the workgroup covers every member a batch
+//                    can hold: a batch of m rows has a tableau (main, or artificial when there are artificial rows)
+//                    of m + 1 rows and at least m + 2 columns, and the LDS budget of the solve (kSingleLdsBudget,
+//                    single_lds_bytes) declines that from m = 197 on (198 x 199 floats stored as 198 x 200, plus the
+//                    pivot row and the column snapshot: 160 000 bytes > 159 744), so m <= 196 < 256; the launcher's
+//                    caller checks m <= kSlpMaxRows all the same.  Per row three LDS words: flip and sense after the
+//                    flip, slack column, artificial column; the slack columns and artificial ranks are a workgroup
+//                    prefix count (one ballot per wave, the four wave totals through LDS).
+//                    Write pass: both tableaux over their whole leading dimension (padding 0), consecutive threads
+//                    consecutive floats, then both bases and the artificial objective row.
+
+constexpr int kSlpThreads = 256;
+
+// entry (R, C) of the main tableau, C < cols: Lr the member's row R, word / scol row R's (objective row: 0 / -1)
+__device__ __forceinline__ float slp_main_elem(const float *Lr, int ncv, int word, int scol, int C, int cols)
+{
+    if (C < ncv || C == cols - 1) {
+        const float x = Lr[C < ncv ? C : ncv];
+        if (!(word & 1)) return x;
+        return x == 0.0f ? 0.0f : -x;                                       // (a): Lisp's (- 0) is 0
+    }
+    if (C == scol) return (word >> 1) == 0 ? 1.0f : -1.0f;
+    return 0.0f;
+}
+
+// Member blockIdx.x.  at.M == nullptr: the group has no artificial rows.  sp.m <= kSlpMaxRows.
+__global__ __launch_bounds__(kSlpThreads) void k_slp_assemble(SbView mt, SbView at, SlpView sp)
+{
+    // per row: word = flip | op << 1 (op after the flip: 0 `<=`, 1 `>=`, 2 `=`), slack column (-1: none),
+    // artificial column (-1: none)
+    __shared__ int32_t word[kSlpMaxRows], scol[kSlpMaxRows], acol[kSlpMaxRows];
+    __shared__ int32_t wave_slack[kSlpThreads / 64], wave_art[kSlpThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t q = blockIdx.x;
+    const int m = (int)sp.m, ncv = (int)sp.ncv, W = ncv + 1, cols = ncv + (int)sp.n_slack + 1;
+    const float *L = sp.L + q * (int64_t)(m + 1) * W;
+    // ---- the row pass
+    int w = 0;
+    bool slack = false, art = false;
+    if (tid < m) {
+        const bool flip = L[(int64_t)tid * W + ncv] < 0.0f;                 // :243
+        const int s = sp.sense[q * m + tid];
+        const int op = s == 2 ? 2 : (flip ? 1 - s : s);
+        w = (flip ? 1 : 0) | (op << 1);
+        slack = op != 2;
+        art = op != 0;
+    }
+    const unsigned long long bs = __ballot(slack), ba = __ballot(art), below = (1ull << lane) - 1ull;
+    if (lane == 0) {
+        wave_slack[wave] = __popcll(bs);
+        wave_art[wave] = __popcll(ba);
+    }
+    __syncthreads();
+    int slack_before = __popcll(bs & below), art_through = __popcll(ba & below) + (art ? 1 : 0), art_all = 0;
+    for (int k = 0; k < kSlpThreads / 64; ++k) {
+        if (k < wave) { slack_before += wave_slack[k]; art_through += wave_art[k]; }
+        art_all += wave_art[k];
+    }
+    if (tid < m) {
+        word[tid] = w;
+        scol[tid] = slack ? ncv + slack_before : -1;
+        acol[tid] = art ? cols - 1 + (art_all - art_through) : -1;          // rank: artificial rows with a greater index
+    }
+    __syncthreads();
+    // ---- the write pass
+    {
+        const int ld = (int)mt.ld;
+        float *M = mt.M + q * mt.stride;
+        for (int k = tid; k < (m + 1) * ld; k += kSlpThreads) {
+            const int R = k / ld, C = k - R * ld;
+            M[k] = C < cols ? slp_main_elem(L + (int64_t)R * W, ncv, R < m ? word[R] : 0, R < m ? scol[R] : -1, C, cols) : 0.0f;
+        }
+        if (tid < m) mt.basis[q * m + tid] = acol[tid] < 0 ? scol[tid] : cols;
+    }
+    if (at.M) {
+        const int nac = (int)at.cols, ld = (int)at.ld;
+        float *A = at.M + q * at.stride;
+        for (int k = tid; k < m * ld; k += kSlpThreads) {
+            const int R = k / ld, C = k - R * ld;
+            float x = 0.0f;
+            if (C < cols - 1) x = slp_main_elem(L + (int64_t)R * W, ncv, word[R], scol[R], C, cols);
+            else if (C == nac - 1) x = slp_main_elem(L + (int64_t)R * W, ncv, word[R], scol[R], cols - 1, cols);
+            else if (C == acol[R]) x = 1.0f;
+            A[k] = x;
+        }
+        if (tid < m) at.basis[q * m + tid] = acol[tid] < 0 ? scol[tid] : acol[tid];
+        // the artificial objective row (:302-316): per column the sum of the artificial rows, increasing rows, from 0
+        for (int C = tid; C < ld; C += kSlpThreads) {
+            float acc = 0.0f;
+            if (C < cols - 1 || C == nac - 1) {
+                const int src = C == nac - 1 ? cols - 1 : C;
+                for (int R = 0; R < m; ++R)
+                    if (acol[R] >= 0) acc = acc + slp_main_elem(L + (int64_t)R * W, ncv, word[R], scol[R], src, cols);
+            }
+            A[(int64_t)m * ld + C] = acc;
+        }
+    }
+}
+
+void launch_slp_assemble(const SbView &mt, const SbView &at, const SlpView &sp, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_slp_assemble, dim3((unsigned)mt.n_lps), dim3(kSlpThreads), 0, s, mt, at, sp);
+}

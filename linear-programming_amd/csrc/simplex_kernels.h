@@ -551,6 +551,16 @@ size_t sbb_assemble_lds(int64_t m, int64_t d);                              // i
 void launch_sbb_assemble(const SbView &mt, const SbView &at, const SbbBaseView &b, const XbbNodeRows &nr, hipStream_t s);
 // per member: last column (rows), last row (cols), basis (rows - 1), each plane member-major (device pointers)
 void launch_sb_readback(const SbView &b, float *rhs, float *obj, int64_t *basis, hipStream_t s);
+// Single-float batches from problem rows (kernels_single_lps.inc, capi_single_lps.inc): the members in column space,
+// in floats (device pointers) -- per member (m + 1) x (ncv + 1) rows, then m senses (0 `<=`, 1 `>=`, 2 `=`)
+struct SlpView {
+    const float   *L;
+    const int32_t *sense;
+    int64_t        m, ncv, n_slack, n_art;
+};
+constexpr int kSlpMaxRows = 256;                                            // k_slp_assemble: one row per thread, one trip
+// every member of mt and of at (at.M == nullptr: no artificial rows): tableau over the whole leading dimension, basis
+void launch_slp_assemble(const SbView &mt, const SbView &at, const SlpView &sp, hipStream_t s);
 
 int         update_variant_count();
 const char *update_variant_name(int v);

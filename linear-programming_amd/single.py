@@ -282,6 +282,37 @@ class SingleBatch:
                                                    int(device)), "mi355x_sbatch_create")
         return cls(h, n, rows, cols)
 
+    @classmethod
+    def from_lps(cls, lps, sense, col_int_sum=None, device=0):
+        """mi355x_sbatch_create_lps: the members' tableaux built on the device from their rows.  lps[n, m + 1,
+        ncv + 1] float32 in column space (per member m rows of coefficients and the right-hand side, then the
+        objective row), sense[n, m] (0 `<=`, 1 `>=`, 2 `=`), col_int_sum[n, ncv + 1] or None: per member and column
+        the sum of the absolute values of the entries Lisp holds as integers (the guard).  Every member has the same
+        numbers of `=` and of artificial rows.  -> (main, art or None).  A group the library declines (the guard,
+        the LDS budget) raises capi.Mi355xError with code MI_UNSUPPORTED."""
+        L = np.asarray(lps)
+        if L.dtype != np.float32:
+            raise TypeError("SingleBatch.from_lps takes float32 rows, not %s" % (L.dtype,))
+        if L.ndim != 3:
+            raise ValueError("lps must be [n, m + 1, ncv + 1], not %r" % (L.shape,))
+        L = np.ascontiguousarray(L)
+        n, m, ncv = L.shape[0], L.shape[1] - 1, L.shape[2] - 1
+        s = np.ascontiguousarray(sense, dtype=np.int32)
+        if s.shape != (n, m):
+            raise ValueError("sense shape %r does not match [n, m] = %r" % (s.shape, (n, m)))
+        sums = None
+        if col_int_sum is not None:
+            sums = np.ascontiguousarray(col_int_sum, dtype=np.float64)
+            if sums.shape != (n, ncv + 1):
+                raise ValueError("col_int_sum shape %r does not match [n, ncv + 1] = %r" % (sums.shape, (n, ncv + 1)))
+        hm, ha = ctypes.c_void_p(), ctypes.c_void_p()
+        capi.check(capi.lib().mi355x_sbatch_create_lps(ctypes.byref(hm), ctypes.byref(ha), n, m, ncv, _ptr(L), _ptr(s),
+                                                       _ptr(sums) if sums is not None else None, int(device)),
+                   "mi355x_sbatch_create_lps")
+        n_eq, n_art = (int(x[0]) for x in lists.row_counts(L[:1, :-1, -1] < 0, s[:1]))
+        cols = ncv + (m - n_eq) + 1
+        return cls(hm, n, m + 1, cols), (cls(ha, n, m + 1, cols + n_art) if ha else None)
+
     def solve(self, is_max, fp_tolerance=1024, max_pivots=0):
         """-> (status[n] int32, n_pivots[n] int64) of this call; self.last_return is what the call itself returned
         (MI_OK, or MI_CANCELLED after cancel(): the unfinished members are MI_RUNNING and the next call carries them on)."""
@@ -376,11 +407,29 @@ def group_single_problems(problems, fp_tolerance=1024, device=0):
     return slots, groups, groups2
 
 
+def solve_made_batches(made, is_max, take, fp_tolerance=1024, max_pivots=0, chunk=None):
+    """A created group -- [main], or [art, main] for two-phase members -- in bounded chunks (lists.batch_in_chunks):
+    per member take(main batch, q, n_pivots) for a solved one, or the exception of its outcome.  Closes the batches."""
+    from .simplex import _error_for
+    first, sb, two = made[0], made[-1], len(made) == 2
+    try:
+        st, npv = lists.batch_in_chunks(
+            lambda cap: (False,) + (first.solve_two_phase(sb, is_max, fp_tolerance, cap) if two else
+                                    sb.solve(is_max, fp_tolerance, cap)), first.rows, first.cols, max_pivots, chunk)
+        out = []
+        for q in range(sb.n_lps):
+            e = _error_for(int(st[q]))
+            out.append(take(sb, q, lists.member_pivots(npv, q)) if e is None else e)
+        return out
+    finally:
+        for b in made:
+            b.close()
+
+
 def solve_problems_single(problems, fp_tolerance=1024, device=0, max_pivots=0, errorp=True, chunk=None):
     """mi355x_solve_problems(..., precision="single"): what [solve_single(p) for p in problems] returns, the groups
     of two or more as ONE SingleBatch (or a pair of them) in bounded chunks.  Members alone in their group, shapes
     the batch declines and integer problems go through solve_single one by one."""
-    from .simplex import _error_for
     results = [None] * len(problems)
     slots, groups, groups2 = group_single_problems(problems, fp_tolerance, device)
 
@@ -402,13 +451,10 @@ def solve_problems_single(problems, fp_tolerance=1024, device=0, max_pivots=0, e
             return None
         return made
 
-    def adopt(t, sb, q, st, npv):
-        e = _error_for(int(st[q]))
-        if e is not None:
-            return e
+    def adopt(t, sb, q, n_pivots):
         t._matrix, t._basis = sb.download(q)
         t._stale, t._handle = False, None                     # (never uploaded: no handle left behind)
-        t.n_pivots = lists.member_pivots(npv, q)
+        t.n_pivots = n_pivots
         return t
 
     for k, s in enumerate(slots):
@@ -419,18 +465,11 @@ def solve_problems_single(problems, fp_tolerance=1024, device=0, max_pivots=0, e
     # a group of two or more is one batch, or for two-phase members a batch of artificial and one of main tableaux
     for members in [*groups.values(), *groups2.values()]:
         ks, firsts, mains = [m[0] for m in members], [m[1] for m in members], [m[-1] for m in members]
-        two, is_max = len(members[0]) == 3, mains[0].is_max
+        two = len(members[0]) == 3
         made = (make(firsts, mains) if two else make(mains)) if len(members) > 1 else None
         if made is None:
             lists.one_by_one(results, ks, alone)
             continue
-        try:
-            first, sb = made[0], made[-1]
-            st, npv = lists.batch_in_chunks(
-                lambda cap: (False,) + (first.solve_two_phase(sb, is_max, fp_tolerance, cap) if two else
-                                        sb.solve(is_max, fp_tolerance, cap)), first.rows, first.cols, max_pivots, chunk)
-            lists.place(results, ks, [adopt(t, sb, q, st, npv) for q, t in enumerate(mains)])
-        finally:
-            for b in made:
-                b.close()
+        lists.place(results, ks, solve_made_batches(made, mains[0].is_max, lambda sb, q, n: adopt(mains[q], sb, q, n),
+                                                    fp_tolerance, max_pivots, chunk))
     return lists.finish(results, errorp)
