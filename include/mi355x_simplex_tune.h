@@ -190,12 +190,12 @@ int         mi355x_batch_debug_stored(mi355x_batch *b, int64_t lp_index, double 
  * form (a k_batch_block look-ahead per LP + ONE sweep over all LPs), [2] one-workgroup-per-LP launches
  * (k_batch_block, or k_batch_solve without blocking), [3] lockstep (select, update) launch pairs. */
 int         mi355x_batch_path_counts(const mi355x_batch *b, int64_t *out4);
-/* measurement aid: enable != 0 brackets the assembly kernels (k_blp_rows, k_blp_assemble, k_blp_art_objective) of
+/* measurement aid: enable != 0 brackets the assembly kernels (k_blp_rows, k_assemble, k_art_objective) of
  * every sub-batch mi355x_*batch_create_lps builds from now on with HIP events; every call returns the device
  * milliseconds and the sub-batches counted since the previous call (either may be NULL) and starts over. */
 int         mi355x_batch_lps_timing(int enable, double *sum_ms, int64_t *n_sub_batches);
 
-/* ---- branch-and-bound: device assembly of node tableaux (k_bb_assemble) ------------------------ */
+/* ---- branch-and-bound: device assembly of node tableaux (k_bb_rows, k_assemble) ------------------------ */
 /* n_nodes nodes of one depth of problem p's search -- node q's rows (var, sense 0 `<=` / 1 `>=`, bound)
  * at [q * depth, (q + 1) * depth), newest first, as mi355x_simplex_solver_bb_trace reports them --
  * assembled on `device` and downloaded: per node the main tableau (rows x cols, tight), its basis

@@ -6,7 +6,7 @@ per member and its artificial twin for a two-phase member -- stacks them and upl
 is only *lowered*: the first stage of build-tableau, the one that needs the problem's names (lowering.lower,
 the very function build_tableau starts with: src/simplex.lisp:189-241, :270-283), leaves one row of doubles per
 constraint, in column space, and everything after that -- the flip of a negative right-hand side, slack and artificial columns, both
-bases, the artificial objective row (:243-328) -- is k_blp_rows / k_blp_assemble / k_blp_art_objective on the
+bases, the artificial objective row (:243-328) -- is k_blp_rows / k_assemble / k_art_objective on the
 device (mi355x_multibatch_create_lps, csrc/kernels_batch_lps.inc).  What a batch starts from is what
 build_tableau produces, bit for bit, so are the pivot sequences and every result.  The exact batches have the
 same entry in exact_lps.py.

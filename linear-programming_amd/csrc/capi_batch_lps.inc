@@ -2,40 +2,10 @@
 // tableaux the device builds from the members' problem rows (build-tableau, src/simplex.lisp:243-328, as
 // kernels_batch_lps.inc), and mi355x_batch_readback / mi355x_multibatch_readback: all the read-back functions
 // need of every member in one copy per sub-batch.
-// Part of simplex_capi.hip (ONE translation unit: included there after capi_exact_lps.inc; alloc_tab, free_tab,
-// ensure_dense are capi_tab_impl.inc's, mb_layout and mb_free capi_batch.inc's).
+// Part of simplex_capi.hip (ONE translation unit: included there after capi_exact_lps.inc; ensure_dense is
+// capi_tab_impl.inc's, lps_check, tab_pair_build and multibatch_pair_build capi_assemble.inc's).
 
 namespace {
-
-// the argument checks of both create entries (no device is looked for): the numbers of `=` rows and of artificial
-// rows every member has.  O(m) per member: only the signs of the right-hand sides are read.
-int blp_check(int64_t n_lps, int64_t m, int64_t ncv, const double *lps, const int32_t *sense, int64_t *n_eq_out,
-              int64_t *n_art_out)
-{
-    if (!lps) return fail(MI_BAD_ARG, "lps is NULL");
-    if (!sense) return fail(MI_BAD_ARG, "sense is NULL");
-    if (n_lps < 1) return fail(MI_BAD_ARG, "n_lps=%lld must be >= 1", (long long)n_lps);
-    if (m < 1 || ncv < 1) return fail(MI_BAD_ARG, "m=%lld ncv=%lld must be >= 1", (long long)m, (long long)ncv);
-    if (m > (1 << 24) || ncv > (1 << 24)) return fail(MI_BAD_ARG, "m=%lld ncv=%lld out of range", (long long)m, (long long)ncv);
-    const int64_t W = ncv + 1, per = (m + 1) * W;
-    int64_t n_eq = -1, n_art = -1;
-    for (int64_t q = 0; q < n_lps; ++q) {
-        int64_t e = 0, a = 0;
-        for (int64_t i = 0; i < m; ++i) {
-            const int32_t s = sense[q * m + i];
-            if (s < 0 || s > 2) return fail(MI_BAD_ARG, "member %lld: sense %d of row %lld", (long long)q, (int)s, (long long)i);
-            const bool flip = lps[q * per + i * W + ncv] < 0.0;              // :243-252
-            e += s == 2;
-            a += s == 2 || (flip ? 1 - s : s) == 1;
-        }
-        if (n_eq >= 0 && (e != n_eq || a != n_art))
-            return fail(MI_BAD_ARG, "member %lld has %lld `=` and %lld artificial rows, the members before it %lld and %lld",
-                        (long long)q, (long long)e, (long long)a, (long long)n_eq, (long long)n_art);
-        n_eq = e; n_art = a;
-    }
-    *n_eq_out = n_eq; *n_art_out = n_art;
-    return MI_OK;
-}
 
 // mi355x_batch_lps_timing (measurement aid): HIP events around the assembly kernels of every sub-batch built since
 std::atomic<int> g_blp_timing{0};
@@ -43,71 +13,35 @@ std::mutex       g_blp_mutex;
 double           g_blp_ms = 0.0;
 int64_t          g_blp_n = 0;
 
-// n members (checked) on one device: t[0] the main batch, t[1] the artificial one or NULL, both in the state
-// upload() leaves.  The rows, the senses and the kernels' scratch live on the device until the assembly is over.
+// n members (checked) on one device: t[0] the main batch, t[1] the artificial one or NULL (tab_pair_build).  The rows,
+// the senses and the kernels' scratch live on the device until the assembly is over.
 int blp_build(mi355x_tab *t[2], int64_t n, int64_t m, int64_t ncv, int64_t n_eq, int64_t n_art, const double *lps,
               const int32_t *sense, int device)
 {
-    t[0] = t[1] = nullptr;
-    const int64_t rows = m + 1, cols = ncv + (m - n_eq) + 1;
-    int rc = alloc_tab(&t[0], rows, cols, device, n);
-    if (rc == MI_OK && n_art) rc = alloc_tab(&t[1], rows, cols + n_art, device, n);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t bL = (size_t)n * (size_t)rows * (size_t)(ncv + 1) * sizeof(double), bS = (size_t)n * (size_t)m * sizeof(int32_t);
-    const size_t oS = al(bL), oX = al(oS + bS), total = al(oX + 3 * bS);
-    void *mem = nullptr;
-    hipError_t e = hipSuccess;
-    if (rc == MI_OK) e = hipMalloc(&mem, total);
     hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timed = rc == MI_OK && g_blp_timing.load(std::memory_order_relaxed) &&
+    const bool timed = g_blp_timing.load(std::memory_order_relaxed) && hipSetDevice(device) == hipSuccess &&
                        hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-    // alloc_tab left memsets of the artificial batch's basis and control blocks on ITS stream; the assembly below
-    // writes both from the main batch's stream, so those memsets have to be over first (capi_bb.inc)
-    if (rc == MI_OK && e == hipSuccess && t[1]) e = hipStreamSynchronize(t[1]->stream);
-    if (rc == MI_OK && e == hipSuccess) {
-        char *p = (char *)mem;
-        hipStream_t st = t[0]->stream;
-        e = hipMemcpyAsync(p, lps, bL, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(p + oS, sense, bS, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) {
-            TabView none{};
-            const BatchLpsView sp{(const double *)p, (const int32_t *)(p + oS), m, ncv, m - n_eq, n_art};
-            if (timed) (void)hipEventRecord(ev[0], st);
-            launch_batch_lps_assemble(t[0]->v, t[1] ? t[1]->v : none, sp, (int32_t *)(p + oX), st);
-            if (timed) (void)hipEventRecord(ev[1], st);
-            launch_ctl_reset(t[0]->v, 0, 1, st);
-            if (t[1]) launch_ctl_reset(t[1]->v, 0, 1, st);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(st);          // (the caller's arrays and `mem` may go)
-    }
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t bL = (size_t)n * (size_t)(m + 1) * (size_t)(ncv + 1) * sizeof(double), bS = (size_t)n * (size_t)m * sizeof(int32_t);
+    const size_t oS = al(bL), oX = al(oS + bS), total = al(oX + 3 * bS);
+    const int rc = tab_pair_build(t, n, m + 1, ncv + (m - n_eq) + 1, n_art, device, total,
+                                  [&](hipStream_t st, const TabView &mv, const TabView &av, char *p) {
+        HIP_TRY(hipMemcpyAsync(p, lps, bL, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(p + oS, sense, bS, hipMemcpyHostToDevice, st));
+        const BatchLpsView sp{(const double *)p, (const int32_t *)(p + oS), m, ncv, m - n_eq, n_art};
+        if (timed) (void)hipEventRecord(ev[0], st);
+        launch_batch_lps_assemble(mv, av, sp, (int32_t *)(p + oX), st);
+        if (timed) (void)hipEventRecord(ev[1], st);
+        return (int)MI_OK;
+    });
     float ms = 0.0f;
-    if (timed && rc == MI_OK && e == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) {
+    if (timed && rc == MI_OK && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) {
         std::lock_guard<std::mutex> lock(g_blp_mutex);
         g_blp_ms += ms;
         g_blp_n++;
     }
     for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
-    if (mem) (void)hipFree(mem);
-    if (rc == MI_OK && e != hipSuccess)
-        rc = fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "assembly from rows failed: %s", hipGetErrorString(e));
-    if (rc != MI_OK) {
-        free_tab(t[0]); free_tab(t[1]);
-        t[0] = t[1] = nullptr;
-        return rc;
-    }
-    for (int w = 0; w < 2 && t[w]; ++w) {
-        // what upload() leaves behind: the dense logical tableau, defined by the caller
-        t[w]->n_part = 0; t[w]->compact = false; t[w]->compact_failed = false; t[w]->unit_basis = false;
-    }
-    return MI_OK;
-}
-
-mi355x_batch *blp_wrap(mi355x_tab *t)
-{
-    mi355x_batch *b = new (std::nothrow) mi355x_batch;
-    if (b) b->t = t;
-    return b;
+    return rc;
 }
 
 // one sub-batch's planes to the host: last rows (n x cols), last columns (n x rows), bases (n x (rows - 1))
@@ -148,12 +82,12 @@ int mi355x_batch_create_lps(mi355x_batch **out_main, mi355x_batch **out_art, int
     if (!out_main || !out_art) return fail(MI_BAD_ARG, "out is NULL");
     *out_main = *out_art = nullptr;
     int64_t n_eq = 0, n_art = 0;
-    int rc = blp_check(n_lps, m, ncv, lps, sense, &n_eq, &n_art);
+    int rc = lps_check(n_lps, 0, m, ncv, lps, sense, &n_eq, &n_art);
     if (rc != MI_OK) return rc;
     mi355x_tab *t[2];
     rc = blp_build(t, n_lps, m, ncv, n_eq, n_art, lps, sense, device);
     if (rc != MI_OK) return rc;
-    mi355x_batch *b0 = blp_wrap(t[0]), *b1 = t[1] ? blp_wrap(t[1]) : nullptr;
+    mi355x_batch *b0 = batch_of(t[0]), *b1 = t[1] ? batch_of(t[1]) : nullptr;
     if (!b0 || (t[1] && !b1)) {
         free_tab(t[0]); free_tab(t[1]);
         delete b0; delete b1;
@@ -172,38 +106,13 @@ int mi355x_multibatch_create_lps(mi355x_multibatch **out_main, mi355x_multibatch
     if (!out_main || !out_art) return fail(MI_BAD_ARG, "out is NULL");
     *out_main = *out_art = nullptr;
     int64_t n_eq = 0, n_art = 0;
-    int rc = blp_check(n_lps, m, ncv, lps, sense, &n_eq, &n_art);
+    int rc = lps_check(n_lps, 0, m, ncv, lps, sense, &n_eq, &n_art);
     if (rc != MI_OK) return rc;
     const int64_t rows = m + 1, cols = ncv + (m - n_eq) + 1, per = rows * (ncv + 1);
-    mi355x_multibatch *mb[2] = {new (std::nothrow) mi355x_multibatch, n_art ? new (std::nothrow) mi355x_multibatch : nullptr};
-    auto cleanup = [&](int code) { mb_free(mb[0]); mb_free(mb[1]); return code; };
-    if (!mb[0] || (n_art && !mb[1])) return cleanup(fail(MI_NO_MEMORY, "host allocation failed"));
-    std::vector<int> devs;
-    int nd = n_devices;
-    rc = mb_layout(mb[0], n_lps, rows, cols, &nd, device_ids, devs);
-    if (rc == MI_OK && mb[1]) { int nd2 = n_devices; std::vector<int> dv2; rc = mb_layout(mb[1], n_lps, rows, cols + n_art, &nd2, device_ids, dv2); }
-    if (rc != MI_OK) return cleanup(rc);
-    std::vector<int64_t> f2;
-    for (int s = 0; s < nd; ++s) {
-        const int64_t k0 = mb[0]->first[(size_t)s], k1 = mb[0]->first[(size_t)s + 1];
-        if (k1 <= k0) continue;                                   // (an empty sub-batch: first[] keeps only the boundaries in use)
-        mi355x_tab *t[2];
-        rc = blp_build(t, k1 - k0, m, ncv, n_eq, n_art, lps + k0 * per, sense + k0 * m, devs[(size_t)s]);
-        if (rc != MI_OK) return cleanup(rc);
-        for (int w = 0; w < 2 && t[w]; ++w) {
-            mi355x_batch *bt = blp_wrap(t[w]);
-            if (!bt) { free_tab(t[w]); rc = fail(MI_NO_MEMORY, "host allocation failed"); continue; }
-            mb[w]->sub.push_back(bt);
-        }
-        if (rc != MI_OK) return cleanup(rc);
-        f2.push_back(k0);
-    }
-    f2.push_back(n_lps);
-    mb[0]->first = f2;
-    if (mb[1]) mb[1]->first = f2;
-    *out_main = mb[0];
-    *out_art = mb[1];
-    return MI_OK;
+    return multibatch_pair_build(out_main, out_art, n_lps, rows, cols, n_art, n_devices, device_ids,
+                                 [&](mi355x_tab *t[2], int64_t k0, int64_t count, int device) {
+        return blp_build(t, count, m, ncv, n_eq, n_art, lps + k0 * per, sense + k0 * m, device);
+    });
 }
 
 // tableau-objective-value / tableau-variable / tableau-reduced-cost (src/simplex.lisp:74-120) read the last row, the

@@ -58,7 +58,7 @@ static int bb_base_on(mi355x_bb_base *b, int device, hipStream_t s, BBBaseView *
 
 // n nodes of depth d >= 1 and n_art artificial rows each, node k's rows at var/sense/bound[k*d ..]:
 // their main tableaux (and, n_art > 0, artificial tableaux) as multibatches over n_devices devices,
-// written by k_bb_assemble.  Every node must have exactly n_art artificial rows (the caller groups).
+// written by launch_node_assemble.  Every node must have exactly n_art artificial rows (the caller groups).
 extern "C" __attribute__((visibility("hidden"))) int mi355x_bb_assemble_(mi355x_bb_base *b, int64_t n, int64_t d, const int64_t *var, const int32_t *sense,
                                    const double *bound, int64_t n_art, int n_devices, const int *device_ids,
                                    mi355x_multibatch **main_out, mi355x_multibatch **art_out)
@@ -67,68 +67,22 @@ extern "C" __attribute__((visibility("hidden"))) int mi355x_bb_assemble_(mi355x_
     if (!b || n < 1 || d < 1 || !var || !sense || !bound || n_art < 0) return fail(MI_BAD_ARG, "bad arguments");
     for (int64_t i = 0; i < n * d; ++i)
         if (var[i] < 0 || var[i] >= b->n_vars || sense[i] < 0 || sense[i] > 1) return fail(MI_BAD_ARG, "bad node row");
-    const int64_t rows = b->rows + d, cols = b->cols + d, acols = cols + n_art;
-    mi355x_multibatch *mb[2] = {new (std::nothrow) mi355x_multibatch, n_art ? new (std::nothrow) mi355x_multibatch : nullptr};
-    auto cleanup = [&](int rc) { mb_free(mb[0]); mb_free(mb[1]); return rc; };
-    if (!mb[0] || (n_art && !mb[1])) return cleanup(fail(MI_NO_MEMORY, "host allocation failed"));
-    std::vector<int> devs;
-    int nd = n_devices;
-    int rc = mb_layout(mb[0], n, rows, cols, &nd, device_ids, devs);
-    if (rc == MI_OK && mb[1]) { int nd2 = n_devices; std::vector<int> dv2; rc = mb_layout(mb[1], n, rows, acols, &nd2, device_ids, dv2); }
-    if (rc != MI_OK) return cleanup(rc);
-    std::vector<int64_t> f2;
-    for (int s = 0; s < nd; ++s) {
-        const int64_t k0 = mb[0]->first[(size_t)s], k1 = mb[0]->first[(size_t)s + 1];
-        if (k1 <= k0) continue;
-        mi355x_tab *t[2] = {nullptr, nullptr};
-        rc = alloc_tab(&t[0], rows, cols, devs[(size_t)s], k1 - k0);
-        if (rc == MI_OK && n_art) rc = alloc_tab(&t[1], rows, acols, devs[(size_t)s], k1 - k0);
-        BBBaseView bv{};
-        if (rc == MI_OK) rc = bb_base_on(b, devs[(size_t)s], t[0]->stream, &bv);
-        const size_t nrow = (size_t)(k1 - k0) * d;
-        void *mem = nullptr;
-        hipError_t e = hipSuccess;
-        if (rc == MI_OK) e = hipMalloc(&mem, nrow * (8 + 4 + 8) + (size_t)(k1 - k0) * 2 * (rows - 1) * 4 + 64);
-        // alloc_tab left memsets of the artificial batch's basis and control blocks on ITS stream; the assembly
-        // below writes both from the main batch's stream, so those memsets have to be over first
-        // (which stream the hardware serves first decided the outcome: no deterministic test can show it; the
-        // random searches of tests/test_gpu_branch_and_bound.py failed now and then without this wait)
-        if (rc == MI_OK && e == hipSuccess && t[1]) e = hipStreamSynchronize(t[1]->stream);
-        if (rc == MI_OK && e == hipSuccess) {
-            char *p = (char *)mem;
+    const int64_t rows = b->rows + d, cols = b->cols + d;
+    return multibatch_pair_build(main_out, art_out, n, rows, cols, n_art, n_devices, device_ids,
+                                 [&](mi355x_tab *t[2], int64_t k0, int64_t count, int device) {
+        const size_t nrow = (size_t)count * d;
+        return tab_pair_build(t, count, rows, cols, n_art, device, nrow * (8 + 4 + 8) + (size_t)count * (rows - 1) * 4 + 64,
+                              [&](hipStream_t st, const TabView &mv, const TabView &av, char *p) {
+            BBBaseView bv{};
+            const int rc = bb_base_on(b, device, st, &bv);
+            if (rc != MI_OK) return rc;
             int64_t *dv = (int64_t *)p; double *db = (double *)(p + nrow * 8); int32_t *ds = (int32_t *)(p + nrow * 16);
             int32_t *scratch = (int32_t *)(p + ((nrow * 20 + 63) & ~(size_t)63));
-            hipStream_t st = t[0]->stream;
-            e = hipMemcpyAsync(dv, var + k0 * d, nrow * 8, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(db, bound + k0 * d, nrow * 8, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(ds, sense + k0 * d, nrow * 4, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) {
-                TabView none{};
-                launch_bb_assemble(t[0]->v, t[1] ? t[1]->v : none, bv, BBNodeRows{dv, ds, db, d, 0}, scratch, st);
-                launch_ctl_reset(t[0]->v, 0, 1, st);
-                if (t[1]) launch_ctl_reset(t[1]->v, 0, 1, st);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-        }
-        if (mem) (void)hipFree(mem);
-        if (rc == MI_OK && e != hipSuccess) rc = fail(MI_HIP_ERROR, "node assembly failed: %s", hipGetErrorString(e));
-        for (int w = 0; w < 2 && t[w]; ++w) {
-            if (rc != MI_OK) { free_tab(t[w]); continue; }
-            // what upload() leaves behind: the dense logical tableau, defined by the caller
-            t[w]->n_part = 0; t[w]->compact = false; t[w]->compact_failed = false; t[w]->unit_basis = false;
-            mi355x_batch *bt = new (std::nothrow) mi355x_batch;
-            if (!bt) { free_tab(t[w]); rc = fail(MI_NO_MEMORY, "host allocation failed"); continue; }
-            bt->t = t[w];
-            mb[w]->sub.push_back(bt);
-        }
-        if (rc != MI_OK) return cleanup(rc);
-        f2.push_back(k0);
-    }
-    f2.push_back(n);
-    mb[0]->first = f2;
-    if (mb[1]) mb[1]->first = f2;
-    *main_out = mb[0];
-    if (art_out) *art_out = mb[1];
-    return MI_OK;
+            HIP_TRY(hipMemcpyAsync(dv, var + k0 * d, nrow * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(db, bound + k0 * d, nrow * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ds, sense + k0 * d, nrow * 4, hipMemcpyHostToDevice, st));
+            launch_node_assemble(mv, av, bv, BBNodeRows{dv, ds, db, d, 0}, scratch, st);
+            return (int)MI_OK;
+        });
+    });
 }

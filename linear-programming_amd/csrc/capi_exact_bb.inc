@@ -98,7 +98,7 @@ bool xbb_row_artificial(const XbbBase &b, int64_t var, int sense, int64_t bound)
 {
     bool neg = bound < 0;
     if (b.kind[var] != 2) neg = (i128_t)bound * b.off_den[var] < (i128_t)b.off_num[var];
-    return (neg ? 1 - sense : sense) == 1;
+    return row_word_artificial(row_word(neg, sense));
 }
 
 XbbNodeRows xbb_rows(const XbbNodes &nd) { return XbbNodeRows{nd.var, nd.sense, nd.bound, nd.d}; }

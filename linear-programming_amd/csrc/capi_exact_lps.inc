@@ -103,28 +103,16 @@ int mi355x_xbatch_create_lps(mi355x_xbatch **out_main, mi355x_xbatch **out_art, 
     if (min_bits != 0 && min_bits != 64 && min_bits != 128) return fail(MI_BAD_ARG, "min_bits must be 0, 64 or 128");
     if (m > (1 << 24) || ncv > (1 << 24) || n_lps > (1 << 24)) return fail(MI_BAD_ARG, "shape out of range");
     const int64_t W = ncv + 1, per = (m + 1) * W;
-    int64_t n_eq = -1, n_art = -1;
-    for (int64_t q = 0; q < n_lps; ++q) {
-        for (int64_t k = q * per; k < (q + 1) * per; ++k) {
-            const uint64_t a = num[k] < 0 ? 0 - (uint64_t)num[k] : (uint64_t)num[k];
-            if (den[k] <= 0 || xlp_gcd(a, (uint64_t)den[k]) != 1)
-                return fail(MI_BAD_ARG, "member %lld: entry %lld, %lld / %lld, is not a reduced fraction", (long long)q,
-                            (long long)(k - q * per), (long long)num[k], (long long)den[k]);
-        }
-        int64_t e = 0, a = 0;
-        for (int64_t i = 0; i < m; ++i) {
-            const int32_t s = sense[q * m + i];
-            if (s < 0 || s > 2) return fail(MI_BAD_ARG, "member %lld: sense %d of row %lld", (long long)q, (int)s, (long long)i);
-            const bool flip = num[q * per + i * W + ncv] < 0;               // :243-252
-            e += s == 2;
-            a += s == 2 || (flip ? 1 - s : s) == 1;
-        }
-        if (n_eq >= 0 && (e != n_eq || a != n_art))
-            return fail(MI_BAD_ARG, "member %lld has %lld `=` and %lld artificial rows, the members before it %lld and %lld",
-                        (long long)q, (long long)e, (long long)a, (long long)n_eq, (long long)n_art);
-        n_eq = e; n_art = a;
+    for (int64_t k = 0; k < n_lps * per; ++k) {
+        const uint64_t a = num[k] < 0 ? 0 - (uint64_t)num[k] : (uint64_t)num[k];
+        if (den[k] <= 0 || xlp_gcd(a, (uint64_t)den[k]) != 1)
+            return fail(MI_BAD_ARG, "member %lld: entry %lld, %lld / %lld, is not a reduced fraction", (long long)(k / per),
+                        (long long)(k % per), (long long)num[k], (long long)den[k]);
     }
-    int rc = x_check_device(device);
+    int64_t n_eq = 0, n_art = 0;
+    int rc = lps_check(n_lps, 24, m, ncv, num, sense, &n_eq, &n_art);
+    if (rc != MI_OK) return rc;
+    rc = x_check_device(device);
     if (rc != MI_OK) return rc;
     const int64_t rows = m + 1, cols = ncv + (m - n_eq) + 1, nac = cols + n_art;
     if ((size_t)(rows + (n_art ? nac : cols)) * 16 > kXbSnapshotLimit)

@@ -51,6 +51,33 @@ struct SbbNodeArrays {
     ~SbbNodeArrays() { (void)hipFree(var); (void)hipFree(bound); (void)hipFree(sense); }
 };
 
+// a (main, artificial) pair of n-member batches on `device` around an assembly (also capi_single_lps.inc's):
+// fill(stream, main view, artificial view) -> hipError_t allocates, uploads and launches; what it allocates has to
+// live until this function returns.  n_art == 0: no artificial batch.
+template <class Fill>
+int sb_pair_build(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n, int64_t rows, int64_t cols, int64_t n_art,
+                  int device, const char *what, Fill fill)
+{
+    mi355x_sbatch *mt = nullptr, *art = nullptr;
+    int rc = MI_OK;
+    // (the larger shape first: a pair the budget declines allocates nothing)
+    if (n_art) rc = sb_new(&art, n, rows, cols + n_art, device, /*zero_padding=*/false);
+    if (rc == MI_OK) rc = sb_new(&mt, n, rows, cols, device, /*zero_padding=*/false);
+    auto undo = [&](int code) { free_sbatch(mt); free_sbatch(art); return code; };
+    if (rc != MI_OK) return undo(rc);
+    hipError_t e = fill(mt->stream, mt->v, art ? art->v : SbView{});
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = sb_fresh_ctl(mt);                              // (waits for the assembly as well)
+    if (e == hipSuccess && art) e = sb_fresh_ctl(art);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return undo(fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "%s failed: %s", what, hipGetErrorString(e)));
+    }
+    *out_main = mt;
+    *out_art = art;
+    return MI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -132,7 +159,7 @@ int mi355x_sbatch_create_nodes(mi355x_sbatch **out_main, mi355x_sbatch **out_art
             if (var[k] < 0 || var[k] >= b.n_vars || sense[k] < 0 || sense[k] > 1 || bound[k] == INT64_MIN)
                 return fail(MI_BAD_ARG, "bad node row %lld", (long long)k);
             const float rhs = sbb_rhs(b, var[k], bound[k]);
-            a += (rhs < 0.0f ? 1 - sense[k] : sense[k]) == 1;
+            a += row_word_artificial(row_word(rhs < 0.0f, sense[k]));
             // the guard: this member's integer entries on top of the base's, column by column
             const int64_t c = b.vcol[var[k]];
             const double r = std::fabs((double)rhs);
@@ -158,37 +185,25 @@ int mi355x_sbatch_create_nodes(mi355x_sbatch **out_main, mi355x_sbatch **out_art
     if (!exact_sums)
         return fail(MI_UNSUPPORTED, "a column's integer entries sum beyond 2^24: the float sum of the artificial "
                                     "objective row would not be the reference's");
-    const int64_t rows = b.rows + depth, cols = b.cols + depth, nac = cols + n_art;
+    const int64_t rows = b.rows + depth, cols = b.cols + depth;
     if (sbb_assemble_lds(rows - 1, depth) > kSbbAssembleLdsLimit)
         return fail(MI_UNSUPPORTED, "%lld rows at depth %lld do not fit the assembly's LDS", (long long)rows, (long long)depth);
-    mi355x_sbatch *mt = nullptr, *art = nullptr;
-    int rc = sb_new(&mt, n_nodes, rows, cols, b.device, /*zero_padding=*/false);
-    if (rc == MI_OK && n_art) rc = sb_new(&art, n_nodes, rows, nac, b.device, /*zero_padding=*/false);
-    auto undo = [&](int code) { free_sbatch(mt); free_sbatch(art); return code; };
-    if (rc != MI_OK) return undo(rc);
     SbbNodeArrays nd;
-    const size_t nk = (size_t)(n_nodes * depth);
-    hipStream_t s = mt->stream;
-    hipError_t e = hipMalloc((void **)&nd.var, nk * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&nd.bound, nk * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&nd.sense, nk * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpyAsync(nd.var, var, nk * sizeof(int64_t), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(nd.bound, bound, nk * sizeof(int64_t), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(nd.sense, sense, nk * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        const SbbBaseView bv{b.d_B, b.d_off, b.rows, b.cols, b.ncv, b.nb, b.d_basis, b.d_kind, b.d_vcol};
-        launch_sbb_assemble(mt->v, art ? art->v : SbView{}, bv, XbbNodeRows{nd.var, nd.sense, nd.bound, depth}, s);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = sb_fresh_ctl(mt);                              // (waits for the assembly as well)
-    if (e == hipSuccess && art) e = sb_fresh_ctl(art);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return undo(fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "node assembly failed: %s", hipGetErrorString(e)));
-    }
-    *out_main = mt;
-    *out_art = art;
-    return MI_OK;
+    return sb_pair_build(out_main, out_art, n_nodes, rows, cols, n_art, b.device, "node assembly",
+                         [&](hipStream_t s, const SbView &mv, const SbView &av) {
+        const size_t nk = (size_t)(n_nodes * depth);
+        hipError_t e = hipMalloc((void **)&nd.var, nk * sizeof(int64_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&nd.bound, nk * sizeof(int64_t));
+        if (e == hipSuccess) e = hipMalloc((void **)&nd.sense, nk * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMemcpyAsync(nd.var, var, nk * sizeof(int64_t), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(nd.bound, bound, nk * sizeof(int64_t), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(nd.sense, sense, nk * sizeof(int32_t), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) {
+            const SbbBaseView bv{b.d_B, b.d_off, b.rows, b.cols, b.ncv, b.nb, b.d_basis, b.d_kind, b.d_vcol};
+            launch_sbb_assemble(mv, av, bv, XbbNodeRows{nd.var, nd.sense, nd.bound, depth}, s);
+        }
+        return e;
+    });
 }
 
 int mi355x_sbatch_readback(mi355x_sbatch *b, float *rhs, float *obj_row, int64_t *basis)

@@ -134,7 +134,7 @@ void bb_collect(mi355x_bb &j, int64_t id, std::vector<int64_t> &out)
     bb_collect(j, ge, out);
 }
 
-// the base problem's general form on the devices, once: what k_bb_assemble turns into node tableaux
+// the base problem's general form on the devices, once: what launch_node_assemble turns into node tableaux
 int bb_prepare_base(mi355x_bb &j)
 {
     if (j.dbase) return MI_OK;
@@ -153,19 +153,19 @@ int bb_prepare_base(mi355x_bb &j)
                                   kind.data(), col.data(), off.data());
 }
 
-// does node row (var, sense, bound) end up artificial?  (the sign test of k_bb_assemble, same arithmetic)
+// does node row (var, sense, bound) end up artificial?  (the sign test of k_bb_rows, same arithmetic)
 bool bb_row_artificial(const mi355x_bb &j, int64_t var, int sense, double bound)
 {
     const Mapping &mp = j.gmap[(size_t)var];
     double rhs = bound;
     if (mp.kind != kSigned) rhs = rhs - 1.0 * mp.offset;
-    return (rhs < 0.0 ? 1 - sense : sense) == 1;
+    return mi355x::row_word_artificial(mi355x::row_word(rhs < 0.0, sense));
 }
 
 // start a speculation round: the collected nodes' LPs as ONE mi355x_simplex_solver_many job whose
 // units are built here -- the root (depth 0: the problem itself, the no-constraint special case
 // included) as an ordinary solver job, every other node in a batch of its shape (depth, artificial
-// rows) assembled on the devices by k_bb_assemble
+// rows) assembled on the devices by launch_node_assemble
 int bb_round_begin(mi355x_bb &j)
 {
     std::vector<int64_t> ids;
@@ -412,7 +412,7 @@ int mi355x_simplex_solver_bb_trace(const mi355x_bb *job, int64_t *parent, int64_
     return MI_OK;
 }
 
-// test hook (mi355x_simplex_tune.h): n_nodes nodes of one depth assembled on `device` by k_bb_assemble and
+// test hook (mi355x_simplex_tune.h): n_nodes nodes of one depth assembled on `device` by launch_node_assemble and
 // downloaded (tight rows x cols / rows x art_cols per node, NULL arrays: the shapes only)
 int mi355x_bb_debug_assemble(const mi355x_problem *p, int64_t n_nodes, int64_t depth, const int64_t *var,
                              const int32_t *sense, const double *bound, int device, int64_t *rows, int64_t *cols,

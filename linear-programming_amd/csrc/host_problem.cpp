@@ -14,6 +14,7 @@
 // (MI_UNSUPPORTED -> unsupported-constraint-error) by every entry point but the opt-in
 // branch-and-bound job of host_bb.inc (mi355x_simplex_solver_bb_*).
 #include "../../include/mi355x_simplex.h"
+#include "simplex_kernels.h"             // row_word: build-tableau's rule for a row, shared with the kernels
 
 extern "C" void mi355x_set_last_error_(const char *msg);   // simplex_capi.hip (thread-local message)
 // simplex_capi.hip (same library, not exported): a compact handle whose stored rows are PRODUCED

@@ -4,7 +4,7 @@
 // arithmetic -- xmul, xsub, xsub_ovf, xfit -- is kernels_exact.inc's, nothing of it is repeated here).
 //
 //   k_xbb_assemble<T>  one workgroup per node of a group (same depth d, same number of artificial rows):
-//                      the exact counterpart of k_bb_rows + k_bb_assemble + k_bb_art_objective.  Rows,
+//                      the exact counterpart of k_bb_rows + k_assemble + k_art_objective.  Rows,
 //                      columns, bases and the order in which artificial columns are dealt are those of the
 //                      header of kernels_bb.inc (src/simplex.lisp:146, 198-202, 243-265, 292-325).  The base
 //                      problem's general-form tableau comes as integers B = Db * b with ONE denominator Db,
@@ -30,7 +30,7 @@ template <class T> __device__ __forceinline__ bool xbb_node_row(const XbbBaseVie
     rhs = 0;
     const bool fits = xfit(wide, &rhs);
     flip = rhs < 0;
-    op = flip ? 1 - nr.sense[i] : nr.sense[i];
+    op = row_word(flip, nr.sense[i]) >> 1;
     return fits;
 }
 
@@ -60,7 +60,7 @@ template <class T> __device__ __forceinline__ T xbb_main_elem(const XbbBaseView 
 }
 
 // Members q0 + blockIdx.x.  mt.T / at.T == nullptr: that tableau is not written.  Dynamic LDS: one int32 per
-// constraint row (its artificial-basis entry; an artificial row is one whose entry is >= num_cols - 1).
+// constraint row (its artificial-basis entry: deal_artificial_columns and ab_artificial of simplex_kernels.h).
 template <class T> __global__ __launch_bounds__(kXThreads) void k_xbb_assemble(XbView mt, XbView at, XbbBaseView b, XbbNodeRows nr, int64_t q0)
 {
     extern __shared__ __int128 xb_lds[];
@@ -85,16 +85,12 @@ template <class T> __global__ __launch_bounds__(kXThreads) void k_xbb_assemble(X
         ab[R] = (int32_t)bas;
     }
     __syncthreads();
-    if (tid == 0) {                                                         // push order, :257, :261, :296-300
-        int32_t n = 0;
-        for (int R = m - 1; R >= 0; --R)
-            if (ab[R] == num_cols) ab[R] = num_cols - 1 + n++;
-    }
+    if (tid == 0) deal_artificial_columns(ab, m, num_cols);
     __syncthreads();
     if (mt.T) {
         T *M = (T *)mt.T + q * (int64_t)(m + 1) * num_cols;
         int64_t *mb = mt.basis + q * m;
-        for (int R = tid; R < m; R += kXThreads) mb[R] = ab[R] >= num_cols - 1 ? num_cols : ab[R];
+        for (int R = tid; R < m; R += kXThreads) mb[R] = ab_main_basis(ab[R], num_cols);
         for (int k = tid; k < (m + 1) * num_cols; k += kXThreads) {
             const int R = k / num_cols;
             M[k] = xbb_main_elem<T>(b, nr, q, R, k - R * num_cols);
@@ -121,7 +117,7 @@ template <class T> __global__ __launch_bounds__(kXThreads) void k_xbb_assemble(X
             bool ok = true;
             if (C < num_cols - 1 || C == nac - 1)
                 for (int R = 0; R < m; ++R)
-                    if (ab[R] >= num_cols - 1) ok = xsub_ovf(acc, xmul(A[(int64_t)R * nac + C], (T)-1)) && ok;
+                    if (ab_artificial(ab[R], num_cols)) ok = xsub_ovf(acc, xmul(A[(int64_t)R * nac + C], (T)-1)) && ok;
             T s = 0;
             if (!ok || !xfit(acc, &s)) { err = kXOverflow; s = 0; }
             A[(int64_t)m * nac + C] = s;

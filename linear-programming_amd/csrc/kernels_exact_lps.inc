@@ -76,7 +76,7 @@ template <class T> __device__ __forceinline__ bool xl_entry(const XbLpsView &sp,
 
 // Members q0 + blockIdx.x.  mt.T / at.T == nullptr: that tableau is not written.  Dynamic LDS: three int32 per
 // constraint row -- fl (bit 0: the row is negated; bits 1-2: its sense after that), sc (its slack column, -1
-// for `=`) and ab (its artificial-basis entry; an artificial row is one whose entry is >= num_cols - 1).
+// for `=`) and ab (its artificial-basis entry: row_word, deal_artificial_columns and ab_artificial of simplex_kernels.h).
 template <class T> __global__ __launch_bounds__(kXThreads) void k_xb_assemble_lps(XbView mt, XbView at, XbLpsView sp, int64_t q0)
 {
     typedef typename XUnsigned<T>::type U;
@@ -106,22 +106,19 @@ template <class T> __global__ __launch_bounds__(kXThreads) void k_xb_assemble_lp
             continue;
         }
         ok_p = ok_p && ok && xfit(xmul(part, l), &part);
-        const int flip = sp.num[i0 + ncv] < 0 ? 1 : 0;
-        const int s = sp.sense[q * m + R];
-        fl[R] = flip | ((s == 2 ? 2 : (flip ? 1 - s : s)) << 1);
+        fl[R] = row_word(sp.num[i0 + ncv] < 0, sp.sense[q * m + R]);
     }
     red[tid] = ok_p ? part : (T)1;
     if (!ok_p) s_err_p = kXOverflow;
     __syncthreads();
     if (tid == 0) {
-        int32_t ns = 0, na = 0;
+        int32_t ns = 0;
         for (int R = 0; R < m; ++R) {                                        // slack columns in row order, :254-265
             const int op = fl[R] >> 1;
             sc[R] = op == 2 ? -1 : ncv + ns++;
             ab[R] = op == 0 ? sc[R] : num_cols;
         }
-        for (int R = m - 1; R >= 0; --R)                                     // push order, :257, :261, :296-300
-            if (ab[R] == num_cols) ab[R] = num_cols - 1 + na++;
+        deal_artificial_columns(ab, m, num_cols);
     }
     for (int s = kXThreads / 2; s > 0; s >>= 1) {                            // P = prod L_i
         if (tid < s && !xfit(xmul(red[tid], red[tid + s]), &red[tid])) { red[tid] = 1; s_err_p = kXOverflow; }
@@ -145,7 +142,7 @@ template <class T> __global__ __launch_bounds__(kXThreads) void k_xb_assemble_lp
         if (d_ok) {
             T *M = (T *)mt.T + q * (int64_t)(m + 1) * num_cols;
             int64_t *mb = mt.basis + q * m;
-            for (int R = tid; R < m; R += kXThreads) mb[R] = ab[R] >= num_cols - 1 ? num_cols : ab[R];
+            for (int R = tid; R < m; R += kXThreads) mb[R] = ab_main_basis(ab[R], num_cols);
             for (int k = tid; k < (m + 1) * num_cols; k += kXThreads) {
                 const int R = k / num_cols, C = k - R * num_cols;
                 const bool neg = R < m && (fl[R] & 1);
@@ -174,7 +171,7 @@ template <class T> __global__ __launch_bounds__(kXThreads) void k_xb_assemble_lp
             auto acc = xmul((T)0, (T)0);
             bool ok = true;
             for (int R = 0; R < m; ++R) {
-                if (ab[R] < num_cols - 1) continue;
+                if (!ab_artificial(ab[R], num_cols)) continue;
                 const int64_t i = in0 + (int64_t)R * W + c;
                 const int64_t n = sp.num[i];
                 if (n == 0) continue;

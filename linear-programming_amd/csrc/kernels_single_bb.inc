@@ -18,8 +18,7 @@
 //                    rows).  The artificial objective row (:302-316) is the column sum over the artificial rows
 //                    in increasing row order from 0.0f, recomputed from the entries; the host lets a group in only
 //                    when every integer partial sum of it is exact in a float (capi_single_bb.inc: the guard).
-//                    Every row is written over its whole leading dimension (padding 0), consecutive threads
-//                    consecutive floats.
+//                    The write pass is assemble_member_lds (kernels_assemble.inc).
 //   k_sb_readback    per member: the right-hand-side column, the objective row and the basis, gathered into
 //                    one buffer -- what tableau-objective-value and tableau-variable read (src/simplex.lisp:74-107).
 
@@ -71,7 +70,7 @@ __global__ __launch_bounds__(kSbbThreads) void k_sbb_assemble(SbView mt, SbView 
         float rhs = (float)nr.bound[i];                                     // (a floor or ceiling of a float: exact)
         if (kind != 2) rhs = rhs - b.voff[v];                               // coef 1, :230-237
         const bool flip = rhs < 0.0f;
-        const int op = flip ? 1 - nr.sense[i] : nr.sense[i];
+        const int op = row_word(flip, nr.sense[i]) >> 1;
         l.rhs[k] = flip ? -rhs : rhs;
         l.col[k] = (int32_t)b.vcol[v];
         l.flags[k] = kind | (flip ? 4 : 0) | (op ? 8 : 0);
@@ -88,46 +87,9 @@ __global__ __launch_bounds__(kSbbThreads) void k_sbb_assemble(SbView mt, SbView 
         l.ab[R] = (int32_t)bas;
     }
     __syncthreads();
-    if (tid == 0) {                                                         // push order, :257, :261, :296-300
-        int32_t n = 0;
-        for (int R = m - 1; R >= 0; --R)
-            if (l.ab[R] == num_cols) l.ab[R] = num_cols - 1 + n++;
-    }
+    if (tid == 0) deal_artificial_columns(l.ab, m, num_cols);
     __syncthreads();
-    {
-        const int ld = (int)mt.ld;
-        float *M = mt.M + q * mt.stride;
-        int64_t *mb = mt.basis + q * m;
-        for (int R = tid; R < m; R += kSbbThreads) mb[R] = l.ab[R] >= num_cols - 1 ? num_cols : l.ab[R];
-        for (int k = tid; k < (m + 1) * ld; k += kSbbThreads) {
-            const int R = k / ld, C = k - R * ld;
-            M[k] = C < num_cols ? sbb_main_elem(b, l, d, R, C) : 0.0f;
-        }
-    }
-    if (at.M) {
-        const int nac = (int)at.cols, ld = (int)at.ld;
-        float *A = at.M + q * at.stride;
-        int64_t *abasis = at.basis + q * m;
-        for (int R = tid; R < m; R += kSbbThreads) abasis[R] = l.ab[R];
-        for (int k = tid; k < m * ld; k += kSbbThreads) {
-            const int R = k / ld, C = k - R * ld;
-            float x = 0.0f;
-            if (C < num_cols - 1) x = sbb_main_elem(b, l, d, R, C);
-            else if (C == nac - 1) x = sbb_main_elem(b, l, d, R, num_cols - 1);
-            else if (C < nac && l.ab[R] == C) x = 1.0f;
-            A[k] = x;
-        }
-        // the artificial objective row (:302-316): per column the sum of the artificial rows, increasing rows, from 0
-        for (int C = tid; C < ld; C += kSbbThreads) {
-            float acc = 0.0f;
-            if (C < num_cols - 1 || C == nac - 1) {
-                const int src = C == nac - 1 ? num_cols - 1 : C;
-                for (int R = 0; R < m; ++R)
-                    if (l.ab[R] >= num_cols - 1) acc = acc + sbb_main_elem(b, l, d, R, src);
-            }
-            A[(int64_t)m * ld + C] = acc;
-        }
-    }
+    assemble_member_lds(mt, at, q, m, num_cols, l.ab, [&](int R, int C) { return sbb_main_elem(b, l, d, R, C); });
 }
 
 // Member blockIdx.x: rhs + q * rows its last column, obj + q * cols its last row, basis + q * (rows - 1) its basis.

@@ -12,14 +12,12 @@
 //                      (a) a row whose right-hand side is < 0.0f (false for -0.0 and NaN) is negated and its sense
 //                          flipped (:243-252).  Lisp's matrix starts as INTEGER zeros and (- 0) is 0, so the slack
 //                          columns of a negated row and the coefficients the problem never mentions stay +0.0:
-//                          the kernel writes x == 0 ? +0.0f : -x and never computes -(0.0f).  (k_blp_assemble's
-//                          double rows carry -0.0 there.)  A zero of a negated row is therefore read as Lisp's
+//                          the kernel writes x == 0 ? +0.0f : -x and never computes -(0.0f).  (The double rows of
+//                          kernels_batch_lps.inc carry -0.0 there.)  A zero of a negated row is therefore read as Lisp's
 //                          integer zero; a member with a single-float zero in such a row is not for this kernel.
-//                      (b) slack columns in row order for the rows that are not `=` (:254-265); main-basis entries
-//                          of artificial rows = the member's num-cols; artificial columns dealt in DECREASING row
-//                          order (push, :257, :261, :296-300); the artificial objective row per column the float sum
-//                          over the artificial rows in INCREASING row order from 0.0f (:302-316), recomputed from
-//                          the entries, never updated.
+//                      (b) slack columns in row order for the rows that are not `=` (:254-265); the bases, the
+//                          artificial columns and the artificial objective row (a float sum in increasing row
+//                          order, :302-316) as kernels_assemble.inc lays them out.
 //                      (c) Lisp keeps integers exact among themselves in that sum; the host lets a member in only
 //                          when every integer partial sum is exact in a float (capi_single_lps.inc: the guard).
 //                    Row pass: thread R owns constraint row R.  One trip of the workgroup covers every member a batch
@@ -28,10 +26,9 @@
 //                    single_lds_bytes) declines that from m = 197 on (198 x 199 floats stored as 198 x 200, plus the
 //                    pivot row and the column snapshot: 160 000 bytes > 159 744), so m <= 196 < 256; the launcher's
 //                    caller checks m <= kSlpMaxRows all the same.  Per row three LDS words: flip and sense after the
-//                    flip, slack column, artificial column; the slack columns and artificial ranks are a workgroup
+//                    flip, slack column, artificial-basis entry; the slack columns and artificial ranks are a workgroup
 //                    prefix count (one ballot per wave, the four wave totals through LDS).
-//                    Write pass: both tableaux over their whole leading dimension (padding 0), consecutive threads
-//                    consecutive floats, then both bases and the artificial objective row.
+//                    Write pass: assemble_member_lds (kernels_assemble.inc).
 
 constexpr int kSlpThreads = 256;
 
@@ -50,9 +47,8 @@ __device__ __forceinline__ float slp_main_elem(const float *Lr, int ncv, int wor
 // Member blockIdx.x.  at.M == nullptr: the group has no artificial rows.  sp.m <= kSlpMaxRows.
 __global__ __launch_bounds__(kSlpThreads) void k_slp_assemble(SbView mt, SbView at, SlpView sp)
 {
-    // per row: word = flip | op << 1 (op after the flip: 0 `<=`, 1 `>=`, 2 `=`), slack column (-1: none),
-    // artificial column (-1: none)
-    __shared__ int32_t word[kSlpMaxRows], scol[kSlpMaxRows], acol[kSlpMaxRows];
+    // per row: its word (row_word), slack column (-1: none), artificial-basis entry (simplex_kernels.h)
+    __shared__ int32_t word[kSlpMaxRows], scol[kSlpMaxRows], ab[kSlpMaxRows];
     __shared__ int32_t wave_slack[kSlpThreads / 64], wave_art[kSlpThreads / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t q = blockIdx.x;
@@ -62,12 +58,9 @@ __global__ __launch_bounds__(kSlpThreads) void k_slp_assemble(SbView mt, SbView 
     int w = 0;
     bool slack = false, art = false;
     if (tid < m) {
-        const bool flip = L[(int64_t)tid * W + ncv] < 0.0f;                 // :243
-        const int s = sp.sense[q * m + tid];
-        const int op = s == 2 ? 2 : (flip ? 1 - s : s);
-        w = (flip ? 1 : 0) | (op << 1);
-        slack = op != 2;
-        art = op != 0;
+        w = row_word(L[(int64_t)tid * W + ncv] < 0.0f, sp.sense[q * m + tid]);      // :243
+        slack = (w >> 1) != 2;
+        art = row_word_artificial(w);
     }
     const unsigned long long bs = __ballot(slack), ba = __ballot(art), below = (1ull << lane) - 1ull;
     if (lane == 0) {
@@ -83,42 +76,14 @@ __global__ __launch_bounds__(kSlpThreads) void k_slp_assemble(SbView mt, SbView 
     if (tid < m) {
         word[tid] = w;
         scol[tid] = slack ? ncv + slack_before : -1;
-        acol[tid] = art ? cols - 1 + (art_all - art_through) : -1;          // rank: artificial rows with a greater index
+        // what deal_artificial_columns leaves: cols - 1 + the artificial rows with a greater index
+        ab[tid] = art ? cols - 1 + (art_all - art_through) : ncv + slack_before;
     }
     __syncthreads();
     // ---- the write pass
-    {
-        const int ld = (int)mt.ld;
-        float *M = mt.M + q * mt.stride;
-        for (int k = tid; k < (m + 1) * ld; k += kSlpThreads) {
-            const int R = k / ld, C = k - R * ld;
-            M[k] = C < cols ? slp_main_elem(L + (int64_t)R * W, ncv, R < m ? word[R] : 0, R < m ? scol[R] : -1, C, cols) : 0.0f;
-        }
-        if (tid < m) mt.basis[q * m + tid] = acol[tid] < 0 ? scol[tid] : cols;
-    }
-    if (at.M) {
-        const int nac = (int)at.cols, ld = (int)at.ld;
-        float *A = at.M + q * at.stride;
-        for (int k = tid; k < m * ld; k += kSlpThreads) {
-            const int R = k / ld, C = k - R * ld;
-            float x = 0.0f;
-            if (C < cols - 1) x = slp_main_elem(L + (int64_t)R * W, ncv, word[R], scol[R], C, cols);
-            else if (C == nac - 1) x = slp_main_elem(L + (int64_t)R * W, ncv, word[R], scol[R], cols - 1, cols);
-            else if (C == acol[R]) x = 1.0f;
-            A[k] = x;
-        }
-        if (tid < m) at.basis[q * m + tid] = acol[tid] < 0 ? scol[tid] : acol[tid];
-        // the artificial objective row (:302-316): per column the sum of the artificial rows, increasing rows, from 0
-        for (int C = tid; C < ld; C += kSlpThreads) {
-            float acc = 0.0f;
-            if (C < cols - 1 || C == nac - 1) {
-                const int src = C == nac - 1 ? cols - 1 : C;
-                for (int R = 0; R < m; ++R)
-                    if (acol[R] >= 0) acc = acc + slp_main_elem(L + (int64_t)R * W, ncv, word[R], scol[R], src, cols);
-            }
-            A[(int64_t)m * ld + C] = acc;
-        }
-    }
+    assemble_member_lds(mt, at, q, m, cols, ab, [&](int R, int C) {
+        return slp_main_elem(L + (int64_t)R * W, ncv, R < m ? word[R] : 0, R < m ? scol[R] : -1, C, cols);
+    });
 }
 
 void launch_slp_assemble(const SbView &mt, const SbView &at, const SlpView &sp, hipStream_t s)

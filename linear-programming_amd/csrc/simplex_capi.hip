@@ -198,6 +198,7 @@ struct mi355x_multibatch {
 #include "capi_tab_impl.inc"   // one tableau behind a handle: internal helpers
 #include "capi_tab.inc"        // mi355x_tab_*, mi355x_solve_two_phase, mi355x_init
 #include "capi_batch.inc"      // mi355x_batch_*, mi355x_multibatch_*
+#include "capi_assemble.inc"  // lps_check, tab_pair_build, multibatch_pair_build: what the device-side build-tableau entries share
 #include "capi_bb.inc"         // branch-and-bound node batches assembled on the devices (internal)
 #include "capi_exact.inc"      // mi355x_xtab_*: exact rational solves on fraction-free integer tableaux
 #include "capi_exact_batch.inc"  // mi355x_xbatch_*: batches of exact LPs, one workgroup per member

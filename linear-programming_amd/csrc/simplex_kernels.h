@@ -285,6 +285,30 @@ void launch_ctl_publish(const TabView &t, int64_t n, void *host_dst, unsigned lo
 // `from` -> kRunning (kNeedDense: after the host has rebuilt the dense tableau; kSyncLost: after
 // it has switched the handle to the two-launch look-ahead)
 void launch_ctl_resume(const TabView &t, hipStream_t s, int32_t from);
+// build-tableau's rules for a constraint row (src/simplex.lisp:243-265, 296-300): the one copy every assembly
+// kernel (kernels_assemble.inc and the family files) and the host's checks use.
+// The row's word: bit 0 = its right-hand side is negative, so the row is negated whole and its sense flipped
+// (:243-252); bits 1-2 = its sense after that: 0 `<=` (slack +1, basic), 1 `>=` (slack -1, artificial), 2 `=`
+// (no slack, artificial).
+XW_HD inline int row_word(bool rhs_negative, int sense)
+{
+    const int op = sense == 2 ? 2 : (rhs_negative ? 1 - sense : sense);
+    return (rhs_negative ? 1 : 0) | (op << 1);
+}
+XW_HD inline bool row_word_artificial(int word) { return (word >> 1) != 0; }
+// ab[R], row R's artificial-basis entry: its slack column for a `<=` row; for an artificial row num_cols (the
+// main tableau's columns) until the artificial columns are dealt, in DECREASING row order (push, :257, :261,
+// :296-300), then that column, num_cols - 1 + rank.  One thread.
+XW_HD inline void deal_artificial_columns(int32_t *ab, int m, int32_t num_cols)
+{
+    int32_t n = 0;
+    for (int R = m - 1; R >= 0; --R)
+        if (ab[R] == num_cols) ab[R] = num_cols - 1 + n++;
+}
+// from a dealt ab[R]: is the row artificial, and its main-basis entry (num_cols for an artificial row); the
+// artificial basis is ab[R] itself
+XW_HD inline bool    ab_artificial(int32_t ab, int32_t num_cols) { return ab >= num_cols - 1; }
+XW_HD inline int32_t ab_main_basis(int32_t ab, int32_t num_cols) { return ab >= num_cols - 1 ? num_cols : ab; }
 // branch-and-bound node tableaux (kernels_bb.inc): the base problem's GENERAL-form main tableau
 // (tight rows x cols, last row = objective), per base row the build-tableau negation flag, its basis,
 // and the var-mapping; the node rows of LPs [first, first + n_lps) of the descriptor arrays
@@ -303,8 +327,9 @@ struct BBNodeRows {
     const double  *bound;
     int64_t        d, first;
 };
-void launch_bb_assemble(const TabView &mt, const TabView &at, const BBBaseView &b, const BBNodeRows &nr,
-                        int32_t *scratch, hipStream_t s);
+// every node of mt (and of at, a view whose M is NULL is left out): tableau and basis; scratch: m int32 per node
+void launch_node_assemble(const TabView &mt, const TabView &at, const BBBaseView &b, const BBNodeRows &nr,
+                          int32_t *scratch, hipStream_t s);
 // synthetic LP straight into HBM
 void launch_synth_fill(const TabView &t, int64_t n_vars, int64_t n_cons, uint64_t seed,
                        const uint64_t *dev_seeds, int64_t col_begin, int64_t col_end, hipStream_t s);

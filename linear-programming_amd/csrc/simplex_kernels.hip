@@ -69,7 +69,8 @@
 //     kernels_batch.inc           k_batch_solve, k_batch_block
 //     kernels_resident.inc        k_resident
 //     kernels_layout.inc          dense <-> compact, control block, two-phase hand-over, synthetic LPs
-//     kernels_bb.inc              branch-and-bound node tableaux assembled in HBM (k_bb_assemble)
+//     kernels_assemble.inc        build-tableau's layout, one copy: k_assemble<Src>, k_art_objective, assemble_member_lds
+//     kernels_bb.inc              branch-and-bound node tableaux assembled in HBM (k_bb_rows, BbSrc)
 //     kernels_exact.inc           exact rational solves on fraction-free integer tableaux (k_x_*)
 //     kernels_exact_batch.inc     batches of exact LPs, one workgroup per LP (k_xb_solve, k_xb_between)
 //     kernels_exact_bb.inc        exact branch-and-bound: integer node tableaux, light read-back (k_xbb_*)
@@ -96,6 +97,7 @@ namespace mi355x {
 #include "kernels_batch.inc"
 #include "kernels_resident.inc"
 #include "kernels_layout.inc"
+#include "kernels_assemble.inc"
 #include "kernels_bb.inc"
 #include "kernels_exact.inc"
 #include "kernels_exact_batch.inc"

@@ -211,7 +211,7 @@ def random_cases(count=40, max_nodes=80, first_seed=1000):
 
 
 # ---- base problems and node lists for the node-assembly tests (test_bb_host.py, test_gpu_bb_assembly.py) ----
-# Shapes at which k_bb_rows / k_bb_assemble / k_bb_art_objective (linear-programming_amd/csrc/kernels_bb.inc)
+# Shapes at which k_bb_rows / k_assemble / k_art_objective (linear-programming_amd/csrc/kernels_bb.inc, kernels_assemble.inc)
 # make more than one trip of their strided loops, and numbers whose sums and differences round.
 _KINDS = [("v1", (2.5, None)), ("v2", (-1.0, 3.25)), ("v3", (None, 4.5)), ("v4", (None, None)), ("v5", (1.0, 2.0))]
 _OFFSET = {"v0": 0.0, "v1": 2.5, "v2": -1.0, "v3": 4.5, "v4": 0.0, "v5": 1.0}      # what a row's rhs is shifted by

@@ -1,5 +1,5 @@
 """Shared by the tests of the device-built double-precision batches (mi355x_multibatch_create_lps): a seeded
-generator of small problems, the plain numpy statement of what k_blp_rows / k_blp_assemble / k_blp_art_objective
+generator of small problems, the plain numpy statement of what k_blp_rows / k_assemble / k_art_objective
 write (linear-programming_amd/csrc/kernels_batch_lps.inc) -- pinned to build_tableau by
 tests/test_batch_lps_host.py -- and members given as arrays that have a known outcome."""
 import random

@@ -141,7 +141,7 @@ def _artificial_rows(name):
 
 
 def test_assembly_cases_reach_the_shapes_they_are_made_for():
-    # tall: past one workgroup of k_bb_rows (256 rows) and past k_bb_assemble's row grid (1024), with
+    # tall: past one workgroup of k_bb_rows (256 rows) and past k_assemble's row grid (1024), with
     # artificial and negated rows in every range
     for name, edges in (("tall_300", (0, 256, 512)), ("tall_1030", (0, 256, 512, 1024, 2048))):
         p, nodes = B.assembly_case(name)
@@ -153,7 +153,7 @@ def test_assembly_cases_reach_the_shapes_they_are_made_for():
             # (artificial columns dealt in decreasing row order: the lowest artificial row holds the last one)
             assert hab[art[0]] == ha.shape[1] - 2 and hab[art[-1]] == hm.shape[1] - 1
     assert B.host_node_tableaux("tall_1030")[0][0].shape[0] - 1 > 1024
-    # wide: main past k_bb_assemble's column grid (16 * 256 entries of a padded row); main inside it and the
+    # wide: main past k_assemble's column grid (16 * 256 entries of a padded row); main inside it and the
     # artificial tableau past it, for any row padding up to 256 entries
     for hm, _, ha, _ in B.host_node_tableaux("wide_main"):
         assert hm.shape[1] > 4096 and ha.shape[1] > hm.shape[1]

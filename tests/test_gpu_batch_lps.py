@@ -1,5 +1,5 @@
 """Double-precision batches built on the device (mi355x_batch_create_lps / mi355x_multibatch_create_lps: k_blp_rows,
-k_blp_assemble, k_blp_art_objective) against the batches the host builds from build_tableau -- start states bit for
+k_assemble, k_art_objective) against the batches the host builds from build_tableau -- start states bit for
 bit, then statuses, pivot counts and final entries through the unchanged solve entries -- and against the numpy
 statement of the kernels (tests/lps_cases.assemble) at the shapes where their loops take more than one trip; the
 one-copy read-back (k_batch_readback); then the public functions on top: solve_problems(from_rows=True) and
@@ -108,6 +108,31 @@ def test_assembly_at_the_shapes_where_a_loop_takes_another_trip(n, m, ncv, patte
         assert _stored(main, 0).shape[1] == main.cols == 16
     if (m, ncv, pattern) == (3, 13, "mixed"):
         assert _stored(main, 0).shape[1] == main.cols == 16 and _stored(art, 0).shape[1] == 32
+
+
+def test_assembly_where_the_launcher_caps_its_grid():
+    """16390 members of 16 rows: one column block times 16 row blocks times the members is 262 240 workgroups, past
+    the launcher's 2^18, so it halves the row blocks to 8 and every workgroup's row loop takes two trips of stride
+    8.  Six distinct members of one group, tiled: the stored tableaux (padding included) of the first six, of six
+    around the middle and of the last six, and the read-back planes and bases of every member of both batches."""
+    n, m, ncv = 16390, 15, 2
+    L6, sense6 = lc.random_rows(6, m, ncv, 7 * m + ncv, PATTERNS["mixed"])
+    expected = [lc.assemble(L6[q], sense6[q]) for q in range(6)]
+    assert len({lc.bits(e[2]).tobytes() for e in expected}) == 6
+    reps = -(-n // 6)
+    main, art = lp.TableauBatch.from_lps(np.tile(L6, (reps, 1, 1))[:n], np.tile(sense6, (reps, 1))[:n])
+    assert main.n_lps == art.n_lps == n and (art.rows, art.cols) == expected[0][2].shape
+    assert min(main.rows, 1024) * n > 1 << 18 and -(-_stored(art, 0).shape[1] // 256) == 1
+    for batch, k in ((main, 0), (art, 2)):
+        for q in list(range(6)) + list(range(n // 2 - 3, n // 2 + 3)) + list(range(n - 6, n)):
+            S = _stored(batch, q)
+            assert _same_bits(S[:, :batch.cols], expected[q % 6][k]), q
+            assert not lc.bits(S[:, batch.cols:]).any(), q
+        tiled = lambda plane: np.tile(np.stack(plane), (reps,) + (1,) * plane[0].ndim)[:n]
+        rows, cols, bases = batch.readback()
+        assert _same_bits(rows, tiled([e[k][-1] for e in expected]))
+        assert _same_bits(cols, tiled([e[k][:, -1] for e in expected]))
+        assert np.array_equal(bases, tiled([e[k + 1] for e in expected]))
 
 
 # ------------------------------------------------------------------ solves through the existing entries

@@ -1,4 +1,4 @@
-"""k_bb_assemble: branch-and-bound node tableaux assembled on the device (mi355x_bb_debug_assemble) are
+"""k_assemble<BbSrc>: branch-and-bound node tableaux assembled on the device (mi355x_bb_debug_assemble) are
 bit-identical -- main tableau, artificial tableau and both bases, -0.0 included -- to the host
 build-tableau (mi355x_build_tableau) of the node problem."""
 import ctypes
@@ -127,14 +127,14 @@ def _check_case(name):
 
 @pytest.mark.parametrize("name,rows_over", [("tall_300", 256), ("tall_1030", 1024)])
 def test_tall_nodes_past_one_workgroup_and_past_the_row_grid(name, rows_over):
-    """k_bb_rows strides over more than 256 rows and its rank scan crosses the trips; k_bb_assemble's row
+    """k_bb_rows strides over more than 256 rows and its rank scan crosses the trips; k_assemble's row
     grid (1024 blocks) wraps.  Artificial and negated rows lie in every range (tests/test_bb_host.py)."""
     for (rows, cols), acols in _check_case(name):
         assert rows - 1 > rows_over and acols > cols
 
 
 def test_wide_nodes_past_the_column_grid():
-    """k_bb_assemble's column loop (16 blocks of 256 threads) makes a second trip: over the main tableau's
+    """k_assemble's column loop (16 blocks of 256 threads) makes a second trip: over the main tableau's
     row, and -- main inside one trip whatever the row padding up to 256 -- over the artificial tableau's."""
     for (rows, cols), acols in _check_case("wide_main"):
         assert cols > 4096 and acols > cols

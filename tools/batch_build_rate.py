@@ -15,7 +15,7 @@ solves read their status back, the read-backs wait for their copy):
             only, as many as hold --e2e-terms coefficients: the Problem objects cost Python per coefficient
             on both routes (tens of milliseconds per config-4 member), which is what this leg shows and why
             it can be bounded.
-  kernels   device time of k_blp_rows + k_blp_assemble + k_blp_art_objective by HIP events
+  kernels   device time of k_blp_rows + k_assemble + k_art_objective by HIP events
             (mi355x_batch_lps_timing), the bytes they write -- rows x ld of both tableaux and both bases, from the
             shapes -- and that rate as a share of the HBM peak (8 TB/s).
 

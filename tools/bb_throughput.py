@@ -9,11 +9,11 @@ ones included), the deepest node, and whether the trace equals the width-1 trace
 
 With exact integrality (the product default) the knapsack dives on values a few ulps off an integer,
 as the reference would; the node budget bounds the run.  A last line compares assembling
---assembly-nodes node tableaux of one depth on the device (k_bb_assemble, through the test hook
+--assembly-nodes node tableaux of one depth on the device (k_assemble, through the test hook
 mi355x_bb_debug_assemble, download included) with the host build-tableau of the same nodes, and gives
 the bytes per node the device assembly keeps off PCIe.
 
-Node tableaux of depth >= 1 are assembled on the device by k_bb_assemble; the per-kernel view comes
+Node tableaux of depth >= 1 are assembled on the device by k_assemble; the per-kernel view comes
 from running this under `rocprofv3 --kernel-trace --stats -- python ...`."""
 import argparse
 import json
@@ -76,7 +76,7 @@ def main():
 
 
 def assembly(p, n, seed):
-    """n nodes of depth 4 with no artificial rows: device assembly (k_bb_assemble + download) against
+    """n nodes of depth 4 with no artificial rows: device assembly (k_assemble + download) against
     the host build-tableau of the same node problems."""
     import ctypes
     rng = np.random.default_rng(seed)
