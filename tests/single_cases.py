@@ -142,7 +142,8 @@ def _op(fn, *xs):
     """One Lisp arithmetic operation: exact on ints, a single-float operation once a float takes part."""
     if all(isinstance(x, int) for x in xs):
         return fn(*xs)
-    return F32(fn(*[F32(x) for x in xs]))
+    with np.errstate(all="ignore"):                          # (an overflow is an infinity, as on the device)
+        return F32(fn(*[F32(x) for x in xs]))
 
 
 def build(problem):

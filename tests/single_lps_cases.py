@@ -60,8 +60,9 @@ def assemble_rows(L, sense, col_int_sum=None, guard=True):
     A = np.zeros((m + 1, cols + len(art_rows)), dtype=F32)
     A[:m, :cols - 1], A[:m, -1] = M[:m, :cols - 1], M[:m, -1]
     acc = np.zeros(A.shape[1], dtype=F32)
-    for r in art_rows:
-        acc = (acc + A[r]).astype(F32)
+    with np.errstate(all="ignore"):
+        for r in art_rows:
+            acc = (acc + A[r]).astype(F32)
     A[m] = acc
     abasis = basis.copy()
     for i, r in enumerate(reversed(art_rows)):
@@ -172,6 +173,32 @@ def zero_rhs_group():
                                             (">=", [("y", b), ("z", 0)], F32(-1.5)),     # negated out of `>=`
                                             ("=", [("x", 0), ("y", 1), ("z", 1)], -2)])
     return [one(2, F32(1.5)), one(F32(0.25), 3)]
+
+
+BIG, ULP_HALF, SUB = F32(3e38), F32(2.0 ** -24), F32(1e-40)     # near FLT_MAX, half an ulp of 1, a subnormal
+
+
+@functools.lru_cache(maxsize=None)
+def extreme_rows_group():
+    """m = 5, ncv = 4, float32 coefficients; rows 0 .. 2 are the artificial ones.  Per member the three artificial
+    rows hold 3e38, 3e38, -3e38 in column x and 1, 2**-24, 2**-24 in column y, each member in another order: the
+    artificial objective row is the float sum in increasing row order from +0.0 --
+        x   (3e38, 3e38, -3e38) -> inf     (3e38, -3e38, 3e38) -> 3e38      (-3e38, 3e38, 3e38) -> 3e38
+        y   (1, h, h) -> 1                 (h, 1, h) -> 1                   (h, h, 1) -> 1 + 2**-23
+    and any other order of the same rows gives another value.  Row 3 is a `>=` row with a subnormal negative
+    right-hand side and subnormal coefficients: negated exactly, its sense flipped into `<=`.  Row 4 has the
+    right-hand side -0.0: not flipped."""
+    def one(xs, ys, k):
+        return dict(type="max", vars=["x", "y", "z", "u"], objective_var="w",
+                    objective=[("x", 1), ("y", F32(0.5)), ("z", 2), ("u", 1)], bounds=[],
+                    constraints=[(">=", [("x", xs[0]), ("y", ys[0]), ("z", 1)], 1 + k),
+                                 ("=", [("x", xs[1]), ("y", ys[1]), ("u", F32(0.5))], F32(2.5)),
+                                 (">=", [("x", xs[2]), ("y", ys[2]), ("z", 2), ("u", 1)], 2),
+                                 (">=", [("z", -SUB), ("u", F32(-3e-39)), ("x", -1)], -SUB),
+                                 ("<=", [("x", 1), ("y", -1), ("z", F32(1.5))], F32(-0.0))])
+    return [one((BIG, BIG, -BIG), (F32(1), ULP_HALF, ULP_HALF), 0),
+            one((BIG, -BIG, BIG), (ULP_HALF, F32(1), ULP_HALF), 1),
+            one((-BIG, BIG, BIG), (ULP_HALF, ULP_HALF, F32(1)), 2)]
 
 
 @functools.lru_cache(maxsize=None)

@@ -121,6 +121,27 @@ def test_assembly_rows_that_move_zero_right_hand_sides_and_bounds(group):
         assert np.signbit(M[0, -1]) and M[0, -1] == 0        # -0.0 stays: the row is not negated
 
 
+def test_assembly_of_extreme_rows():
+    """k_slp_assemble / assemble_member_lds on coefficients near FLT_MAX and below FLT_MIN: the artificial objective
+    row is the float sum in INCREASING row order (3e38 + 3e38 - 3e38 = inf, any other order 3e38; 1 + 2**-24 + 2**-24
+    = 1, the other way round 1 + 2**-23), a row with a subnormal negative right-hand side is negated exactly (no
+    flush) and its sense flipped, a right-hand side -0.0 is not."""
+    ds = C.extreme_rows_group()
+    assert check_assembly(ds) == (9, 12)
+    main, art = create(ds)
+    try:
+        got = [(art.download(q)[0][-1, 0], art.download(q)[0][-1, 1]) for q in range(3)]
+        assert got == [(F32(np.inf), F32(1)), (C.BIG, F32(1)), (C.BIG, F32(1 + 2.0 ** -23))]
+        for q in range(3):
+            M = main.download(q)[0]
+            assert M[3, -1].view(np.uint32) == C.SUB.view(np.uint32)
+            assert M[3, 3].view(np.uint32) == F32(3e-39).view(np.uint32)
+            assert M[4, -1] == 0 and np.signbit(M[4, -1])
+    finally:
+        main.close()
+        art.close()
+
+
 @pytest.mark.parametrize("kw,cols", [(dict(main_cols=32), (32, None)), (dict(main_cols=33), (33, None)),
                                      (dict(art_cols=64), (54, 64)), (dict(art_cols=65), (55, 65))])
 def test_assembly_at_the_steps_of_the_leading_dimension(kw, cols):
@@ -177,7 +198,7 @@ def solve_group(ds, wants, threads, per_call=0):
 
 SOLVED = {"outcome": (C.outcome_group, ()), "driveout": (C.driveout_group, ()), "single_phase": (C.single_phase_group, ()),
           "medium_max": (C.medium_group, ("max",)), "medium_min": (C.medium_group, ("min",)),
-          "moving": (C.moving_group, ()), "zero_rhs": (C.zero_rhs_group, ())}
+          "moving": (C.moving_group, ()), "zero_rhs": (C.zero_rhs_group, ()), "extreme_rows": (C.extreme_rows_group, ())}
 
 
 @pytest.mark.parametrize("threads", THREADS)
@@ -192,6 +213,10 @@ def test_solves_from_device_built_members(name, threads):
         assert all(len(sc.solve(w["build"]["art"][0], w["build"]["art"][1], False)[1]) == 0 for w in wants)
     if name == "single_phase":
         assert [w["status"] for w in wants] == [sc.OPTIMAL, sc.OPTIMAL, sc.UNBOUNDED] and all(len(w["n"]) == 1 for w in wants)
+    if name == "extreme_rows":                               # phase 1 pivots with inf and NaN in its objective row
+        assert all(w["status"] == sc.INFEASIBLE and w["n"][0] >= 1 for w in wants)
+        assert not any(np.isfinite(w["A"][-1]).all() for w in wants)
+        assert np.isnan(wants[0]["A"][-1, -1])               # (fp= 0 NaN) in the step between the phases
     if name.startswith("medium"):
         assert all(w["status"] == sc.OPTIMAL and min(w["n"]) > 0 for w in wants)
     solve_group(fn(*args), wants, threads)

@@ -24,7 +24,7 @@ def _all_groups():
                ("main 32", C.ld_step_group(main_cols=32)), ("main 33", C.ld_step_group(main_cols=33)),
                ("art 64", C.ld_step_group(art_cols=64)), ("art 65", C.ld_step_group(art_cols=65)),
                ("outcomes", C.outcome_group()), ("driveout", C.driveout_group()), ("single phase", C.single_phase_group()),
-               ("medium", C.medium_group()), ("medium min", C.medium_group("min")),
+               ("medium", C.medium_group()), ("medium min", C.medium_group("min")), ("extreme rows", C.extreme_rows_group()),
                ("96x300", C.big_group(False)), ("%dx300" % C.BIG_TWO_PHASE_M, C.big_group(True))]
     return groups
 
@@ -105,6 +105,40 @@ def test_a_float_zero_in_a_negated_row_is_minus_zero_in_lisp():
     d2 = dict(d, constraints=[("<=", [("x", 1), ("y", F32(0.0)), ("z", 0)], 3)] + d["constraints"][1:])
     assert not lp.single_lps.lower_problem_rows_single(C.to_problem(lp, d2)).float_zero
     _check_lowering(d2)
+
+
+def test_extreme_rows_sums_depend_on_the_order_and_tiny_rows_are_negated_exactly():
+    """Conditions on C.extreme_rows_group() (the model alone): the artificial objective row's entries in columns x and
+    y are the increasing-row-order sums, every other order of the same three rows gives another float32, and the
+    negated row holds the exact negatives of its subnormals."""
+    import itertools
+    wanted = [(F32(np.inf), F32(1)), (C.BIG, F32(1)), (C.BIG, F32(1 + 2.0 ** -23))]
+    for d, (wx, wy) in zip(C.extreme_rows_group(), wanted):
+        b = sc.build(d)
+        A, M = b["art"][0], b["main"][0]
+        assert A.shape == (6, 12) and M.shape == (6, 9) and sorted(np.where(b["main"][1] == 9)[0]) == [0, 1, 2]
+        assert A[-1, 0] == wx and A[-1, 1] == wy
+        for col, want in ((0, wx), (1, wy)):
+            sums = set()
+            with np.errstate(all="ignore"):
+                for order in itertools.permutations(range(3)):
+                    s = F32(0)
+                    for r in order:
+                        s = F32(s + A[r, col])
+                    sums.add(float(s))
+            assert float(want) in sums and len(sums) > 1
+        assert A[:3, 0].tolist().count(C.BIG) == 2 and sorted(A[:3, 1].tolist()) == [2.0 ** -24, 2.0 ** -24, 1]
+        # row 3: `>=` with a subnormal negative right-hand side -> `<=`, every entry the exact negative
+        assert M[3, -1] == C.SUB and M[3, 2] == C.SUB and M[3, 3] == F32(3e-39) and M[3, 0] == 1
+        assert 0 < M[3, -1] < np.finfo(F32).tiny and 0 < M[3, 3] < np.finfo(F32).tiny
+        assert b["main"][1][3] < 8 and M[3, b["main"][1][3]] == 1               # a slack column: no artificial
+        # row 4: -0.0 is not < 0: not flipped
+        assert M[4, -1] == 0 and np.signbit(M[4, -1]) and M[4, :3].tolist() == [1, -1, 1.5]
+    host, groups = lp.group_lowered_rows_single([C.to_problem(lp, d) for d in C.extreme_rows_group()])
+    assert host == {} and len(groups) == 1                   # the guard accepts all three members
+    wants = C.model_solution(C.extreme_rows_group)
+    assert all(w["status"] == sc.INFEASIBLE and w["n"][0] >= 1 and not np.isfinite(w["A"][-1]).all() for w in wants)
+    assert np.isnan(wants[0]["A"][-1, -1]) and len({w["n"] for w in wants}) == 2
 
 
 def test_the_guard_integer_sums_beyond_2_to_24():
