@@ -201,10 +201,10 @@ def planted(case):
     return Planted(M, basis, R, X, Y, Rj, base_trace)
 
 
-def solve(M0, b0, kind, cap):
+def solve(M0, b0, kind, cap, factor=1024.0):
     M, b = M0.copy(), b0.copy()
     with np.errstate(all="ignore"):
-        st, npiv, trace = oracle.solve(M, b, is_max=(kind == "max"), max_pivots=cap, trace_cap=max(cap, 1),
+        st, npiv, trace = oracle.solve(M, b, is_max=(kind == "max"), factor=factor, max_pivots=cap, trace_cap=max(cap, 1),
                                        omp=M.size > 4_000_000)
     for a in (trace, M, b):
         a.setflags(write=False)

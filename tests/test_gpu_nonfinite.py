@@ -66,21 +66,22 @@ def _same(t, ref, what):
     _same_bits(t.matrix, ref.M, what)
 
 
-def _tableau(case):
-    p = nc.planted(case)
+def _tableau(case, cases=nc):
+    p = cases.planted(case)
     return lp.Tableau(None, lp.Problem(type=case.kind), p.M, p.basis, case.n + case.m, case.m, {})
 
 
-def _capped_run(L, case, prepare=False):
-    ref = nc.reference(case)
-    t = _tableau(case)
+def _capped_run(L, case, prepare=False, factor=1024.0, cases=nc):
+    """`cases`: the module that plants the case (planted, reference, cap_of); `factor`: the call's tolerance factor."""
+    ref = cases.reference(case)
+    t = _tableau(case, cases)
     k = ctypes.c_int64(0)
     is_max = int(case.kind == "max")
     if prepare:                                            # -> the compact representation, nothing solved
-        lp.capi.check(L.mi355x_tab_solve_async(t._h, is_max, 1024.0, 0, 1), "prepare")
+        lp.capi.check(L.mi355x_tab_solve_async(t._h, is_max, factor, 0, 1), "prepare")
         L.mi355x_tab_sync(t._h, ctypes.byref(k))
         assert L.mi355x_tab_resident(t._h) == 1
-    rc = L.mi355x_tab_solve(t._h, is_max, 1024.0, nc.cap_of(case), ctypes.byref(k))
+    rc = L.mi355x_tab_solve(t._h, is_max, factor, cases.cap_of(case), ctypes.byref(k))
     path = _path(L, t._h)
     t._touch()
     assert (rc, k.value) == (ref.status, ref.pivots), (rc, k.value, ref.status, ref.pivots, path.counts)
@@ -88,21 +89,21 @@ def _capped_run(L, case, prepare=False):
     return path, ref
 
 
-def _request_sequence(L, case, first_piece):
+def _request_sequence(L, case, first_piece, factor=1024.0, cases=nc):
     """The same solve as two requests, the first of `first_piece` pivots.  A request that meets the hand-over
     answers MI_RUNNING with exactly j pivots applied -- short of what was asked --, and the next request goes on
     from there; nothing else may cut a request short, and no solve is cut twice.  With the piece boundary before
     or behind step j some request crosses the event and MUST be cut; with the boundary AT step j the first
     request ends there on its cap and the second one may be cut before its first pivot.  -> what ran."""
-    ref, j, cap = nc.reference(case), case.j, nc.cap_of(case)
-    t = _tableau(case)
+    ref, j, cap = cases.reference(case), case.j, cases.cap_of(case)
+    t = _tableau(case, cases)
     is_max = int(case.kind == "max")
     k = ctypes.c_int64(0)
     done = short = calls = 0
     rc = lp.capi.MI_RUNNING
     for goal in (first_piece, cap):
         while rc == lp.capi.MI_RUNNING:
-            lp.capi.check(L.mi355x_tab_solve_async(t._h, is_max, 1024.0, goal - done, 1 if calls == 0 else 0), "solve_async")
+            lp.capi.check(L.mi355x_tab_solve_async(t._h, is_max, factor, goal - done, 1 if calls == 0 else 0), "solve_async")
             rc = L.mi355x_tab_sync(t._h, ctypes.byref(k))
             calls += 1
             done = k.value
@@ -111,7 +112,7 @@ def _request_sequence(L, case, first_piece):
             assert _hands_over(case) and (rc, done) == (lp.capi.MI_RUNNING, j) and short == 0, (rc, done, j, goal, short)
             short += 1
     if rc == lp.capi.MI_RUNNING and ref.status != oracle.MAX_PIVOTS:     # the LP's last pivot was a request's last: one more look
-        lp.capi.check(L.mi355x_tab_solve_async(t._h, is_max, 1024.0, 1, 0), "solve_async")
+        lp.capi.check(L.mi355x_tab_solve_async(t._h, is_max, factor, 1, 0), "solve_async")
         rc = L.mi355x_tab_sync(t._h, ctypes.byref(k))
     assert k.value == ref.pivots and rc == (lp.capi.MI_RUNNING if ref.status == oracle.MAX_PIVOTS else ref.status), (rc, k.value)
     if _hands_over(case):
@@ -238,14 +239,14 @@ def _check_batch(batch, st, npv, refs, what):
         _same_bits(G, ref.M, (what, k))
 
 
-def _batch_case(L, shape, kind, path):
-    Ms, Bs, _ = nc.batch(*shape, kind)
-    for cap in (nc.BATCH_CAP, 4):                          # to the members' ends; a cap between the members' events
+def _batch_case(L, shape, kind, path, factor=1024.0, cases=nc):
+    Ms, Bs, _ = cases.batch(*shape, kind)
+    for cap in (cases.BATCH_CAP, 4):                       # to the members' ends; a cap between the members' events
         batch = lp.TableauBatch.from_arrays(Ms, Bs)
-        st, npv = batch.solve(is_max=(kind == "max"), max_pivots=cap)
+        st, npv = batch.solve(is_max=(kind == "max"), fp_tolerance=factor, max_pivots=cap)
         c = _batch_counts(L, batch)
         assert c[path] > 0, (cap, c)
-        _check_batch(batch, st, npv, nc.batch_reference(*shape, kind, cap), "cap %d" % cap)
+        _check_batch(batch, st, npv, cases.batch_reference(*shape, kind, cap), "cap %d" % cap)
 
 
 @pytest.mark.parametrize("kind", ["max", "min"])
