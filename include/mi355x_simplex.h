@@ -871,6 +871,19 @@ int  mi355x_sbatch_info(const mi355x_sbatch *b, int64_t *n_lps, int64_t *rows, i
  * MI_CANCELLED; the members hold whole pivots only and the next call carries them on. */
 int  mi355x_sbatch_cancel(mi355x_sbatch *b);
 void mi355x_sbatch_destroy(mi355x_sbatch *b);
+/* The GLOBAL form (opt-in), for members beyond the LDS budget: one workgroup still owns one member for its whole
+ * solve, but the member's tableau stays in device memory; LDS holds the pivot row and the column snapshot only.
+ * Arguments, checks and their order are mi355x_sbatch_create's; the handle is an ordinary mi355x_sbatch, and
+ * _solve, _solve_two_phase (both handles of ONE form, else MI_BAD_ARG), _download, _trace, _readback, _info,
+ * _cancel and _destroy work on it under the same member-by-member contract.  Every shape the argument checks accept
+ * is taken, small ones included; MI_UNSUPPORTED only where pivot row + column snapshot exceed the LDS budget (rows +
+ * cols beyond about 39 000), and from _solve_two_phase where the step between the phases (two rows + a column of the
+ * artificial shape) does.  Large members in small numbers are faster one by one through mi355x_stab_*: DESIGN 4.6k. */
+int  mi355x_sbatch_create_global(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, const float *matrices,
+                                 const int64_t *basis, int device);
+/* *form: 2 the members' tableaux in LDS, 3 the global form (continuing mi355x_stab_info: 1 pair, 2 LDS).  For form 3
+ * mi355x_sbatch_info reports that form's workgroup, its dynamic LDS per member and its kernel's occupancy. */
+int  mi355x_sbatch_form(const mi355x_sbatch *b, int *form);
 
 /* ---- single-float branch-and-bound (opt-in): node LPs assembled on the device ------------------
  * simplex-solver (src/simplex.lisp:462-542) on a problem whose numbers Lisp reads as integers and single-floats.

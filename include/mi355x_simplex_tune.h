@@ -217,9 +217,11 @@ int         mi355x_stab_debug_update_time(mi355x_stab *h, int64_t entering_col, 
                                           double *avg_ms, int64_t *bytes);
 /* batches of single-float LPs (mi355x_sbatch_*), both snapshotted per handle at create: the workgroup a batch
  * takes -- 0 auto (the shape's rule), 256 or 1024 -- and the pivots per member one launch may make -- 0 the
- * default (4096), else a count */
+ * default (4096; global form: 4096 scaled down by stored bytes over the LDS budget, at least 1), else a count.
+ * _global_threads: the workgroup of batches made by mi355x_sbatch_create_global -- 0 auto, 256 or 1024 */
 int         mi355x_tune_set_sbatch_threads(int threads);
 int         mi355x_tune_set_sbatch_launch_cap(int cap);
+int         mi355x_tune_set_sbatch_global_threads(int threads);
 /* test aid: member lp_index of a single-float batch as it is STORED, padding columns included -- rows x ld floats;
  * *ld (may be NULL) = the leading dimension; out NULL: only *ld.  What a create entry left in the columns
  * [cols, ld) (mi355x_sbatch_create_lps writes them itself). */

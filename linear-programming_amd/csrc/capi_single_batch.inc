@@ -1,21 +1,26 @@
 // capi_single_batch.inc -- mi355x_sbatch_*: n_lps SINGLE-FLOAT tableaux of one shape behind a handle, one workgroup
-// per member for its whole solve (kernels_single_batch.inc).  The contract is member by member: what a member ends with
+// per member for its whole solve, the member's tableau in LDS (form 2, kernels_single_batch.inc) or left in HBM (form
+// 3, the opt-in global form for members beyond the LDS budget: kernels_single_global.inc).  The contract is member by
+// member: what a member ends with
 // -- status, pivot counts, trace, basis, every tableau entry -- is what mi355x_stab_solve / _solve_two_phase gives that
 // member alone under the same sequence of calls.  No double touches a tableau entry.
 // Part of simplex_capi.hip (ONE translation unit: included there, in this order).
 
 namespace {
 int g_sbatch_threads = 0;                 // tuning / test hook: 0 auto (sbatch_threads_for), 256 or 1024
-int g_sbatch_launch_cap = 0;              // tuning / test hook: 0 = kSingleLaunchCap, else pivots per member and launch
+int g_sbatch_launch_cap = 0;              // tuning / test hook: 0 = the form's default, else pivots per member and launch
+int g_sbatch_global_threads = 0;          // tuning / test hook, global form: 0 auto (sgbatch_threads_for), 256 or 1024
+constexpr int kSbFormLds = 2, kSbFormGlobal = 3;     // (continuing mi355x_stab_info's numbering: 1 pair, 2 LDS)
 }  // namespace
 
 struct mi355x_sbatch {
     int         device = 0;
     SbView      v{};
     hipStream_t stream = nullptr;
-    int         threads = 0;              // snapshot of the rule (or the hook) at create
+    int         form = 2;                 // 2: the member's tableau in LDS (k_sb_solve), 3: in HBM (k_sg_solve)
+    int         threads = 0;              // snapshot of the form's rule (or its hook) at create
     int         launch_cap = kSingleLaunchCap;
-    int         members_per_cu = 0;       // hipOccupancyMaxActiveBlocksPerMultiprocessor of k_sb_solve<threads> at this shape
+    int         members_per_cu = 0;       // hipOccupancyMaxActiveBlocksPerMultiprocessor of the form's solve kernel at this shape
     void       *rb = nullptr;         // mi355x_sbatch_readback's gather buffer (made at its first call)
     int32_t    *d_phase = nullptr;        // artificial batch of a two-phase pair: per member (state, status between the phases)
     std::vector<Ctl>     h;               // the control blocks as the last read-back left them
@@ -54,8 +59,9 @@ inline bool sb_carried_on(int32_t st) { return st == kRunning || st == MI_MAX_PI
 
 // An empty batch of the shape: the checks of mi355x_sbatch_create, the handle, its stream and its device buffers
 // (zero_padding: the tableaux zeroed where a row has padding -- for members that are uploaded tight).
-// MI_UNSUPPORTED: the shape does not fit the LDS budget.
-int sb_new(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, int device, bool zero_padding)
+// MI_UNSUPPORTED: the shape does not fit the LDS budget (form 3: its pivot row and column snapshot do not).
+int sb_new(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, int device, bool zero_padding,
+           int form = kSbFormLds)
 {
     if (n_lps < 1 || n_lps > (1LL << 30)) return fail(MI_BAD_ARG, "n_lps=%lld must be in [1, 2^30]", (long long)n_lps);
     if (rows < 1 || cols < 1) return fail(MI_BAD_ARG, "rows=%lld cols=%lld must be >= 1", (long long)rows, (long long)cols);
@@ -75,12 +81,22 @@ int sb_new(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, int d
     v.ld = (cols + kSingleLdAlign - 1) / kSingleLdAlign * kSingleLdAlign;
     v.stride = rows * v.ld;
     v.trace_cap = MI355X_SBATCH_TRACE_CAP;
-    b->threads = g_sbatch_threads ? g_sbatch_threads : sbatch_threads_for(rows, cols);
-    b->launch_cap = g_sbatch_launch_cap ? g_sbatch_launch_cap : kSingleLaunchCap;
-    // the shapes the LDS form does not hold (or may not have) are declined: their members go one by one
-    if (!sbatch_available(v, b->threads, &b->members_per_cu) || b->members_per_cu < 1) {
+    b->form = form;
+    bool fits;
+    if (form == kSbFormGlobal) {
+        b->threads = g_sbatch_global_threads ? g_sbatch_global_threads : sgbatch_threads_for(rows, v.ld);
+        b->launch_cap = g_sbatch_launch_cap ? g_sbatch_launch_cap : sgbatch_launch_cap_for(rows, v.ld);
+        fits = sgbatch_available(v, b->threads, &b->members_per_cu);
+    } else {
+        b->threads = g_sbatch_threads ? g_sbatch_threads : sbatch_threads_for(rows, cols);
+        b->launch_cap = g_sbatch_launch_cap ? g_sbatch_launch_cap : kSingleLaunchCap;
+        fits = sbatch_available(v, b->threads, &b->members_per_cu);
+    }
+    // the shapes the form does not hold (or may not have) are declined: the LDS form's members go one by one
+    if (!fits || b->members_per_cu < 1) {
         delete b;
-        return fail(MI_UNSUPPORTED, "a %lldx%lld single-float member does not fit the LDS budget of %lld bytes",
+        return fail(MI_UNSUPPORTED, "%s %lldx%lld single-float member does not fit the LDS budget of %lld bytes",
+                    form == kSbFormGlobal ? "the pivot row and column snapshot of a" : "a",
                     (long long)rows, (long long)cols, (long long)kSingleLdsBudget);
     }
     const int64_t nb = std::max<int64_t>(rows - 1, 1);
@@ -121,19 +137,23 @@ hipError_t sb_fresh_ctl(mi355x_sbatch *b)
     return e;
 }
 
-}  // namespace
+// the form's solve kernel on every member the gate lets run
+void sb_launch_solve(const mi355x_sbatch *b, int is_max, double f, const int32_t *gate, hipStream_t s)
+{
+    if (b->form == kSbFormGlobal) launch_sg_solve(b->v, b->threads, is_max, f, b->launch_cap, gate, s);
+    else launch_sb_solve(b->v, b->threads, is_max, f, b->launch_cap, gate, s);
+}
 
-extern "C" {
-
-int mi355x_sbatch_create(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, const float *matrices,
-                         const int64_t *basis, int device)
+// mi355x_sbatch_create / _create_global: the checks, the handle of the form, the upload
+int sb_create(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, const float *matrices, const int64_t *basis,
+              int device, int form)
 {
     if (!out) return fail(MI_BAD_ARG, "out is NULL");
     *out = nullptr;
     if (!matrices) return fail(MI_BAD_ARG, "matrices is NULL");
     if (rows > 1 && !basis) return fail(MI_BAD_ARG, "basis is NULL");
     mi355x_sbatch *b = nullptr;
-    const int rc = sb_new(&b, n_lps, rows, cols, device, /*zero_padding=*/true);
+    const int rc = sb_new(&b, n_lps, rows, cols, device, /*zero_padding=*/true, form);
     if (rc != MI_OK) return rc;
     SbView &v = b->v;
     hipError_t e = hipMemcpy2DAsync(v.M, v.ld * sizeof(float), matrices, cols * sizeof(float), cols * sizeof(float),
@@ -150,6 +170,22 @@ int mi355x_sbatch_create(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64
     return MI_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int mi355x_sbatch_create(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, const float *matrices,
+                         const int64_t *basis, int device)
+{
+    return sb_create(out, n_lps, rows, cols, matrices, basis, device, kSbFormLds);
+}
+
+int mi355x_sbatch_create_global(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, const float *matrices,
+                                const int64_t *basis, int device)
+{
+    return sb_create(out, n_lps, rows, cols, matrices, basis, device, kSbFormGlobal);
+}
+
 void mi355x_sbatch_destroy(mi355x_sbatch *b) { free_sbatch(b); }
 
 int mi355x_sbatch_info(const mi355x_sbatch *b, int64_t *n_lps, int64_t *rows, int64_t *cols, int64_t *ld,
@@ -161,8 +197,16 @@ int mi355x_sbatch_info(const mi355x_sbatch *b, int64_t *n_lps, int64_t *rows, in
     if (cols) *cols = b->v.cols;
     if (ld) *ld = b->v.ld;
     if (workgroup_threads) *workgroup_threads = b->threads;
-    if (lds_bytes_per_member) *lds_bytes_per_member = (int64_t)sbatch_lds_bytes(b->v);
+    if (lds_bytes_per_member)
+        *lds_bytes_per_member = (int64_t)(b->form == kSbFormGlobal ? sgbatch_lds_bytes(b->v) : sbatch_lds_bytes(b->v));
     if (members_per_cu) *members_per_cu = b->members_per_cu;
+    return MI_OK;
+}
+
+int mi355x_sbatch_form(const mi355x_sbatch *b, int *form)
+{
+    if (!b) return fail(MI_BAD_ARG, "handle is NULL");
+    if (form) *form = b->form;
     return MI_OK;
 }
 
@@ -179,7 +223,7 @@ int mi355x_sbatch_solve(mi355x_sbatch *b, int is_max, double f, int64_t max_pivo
     launch_sb_begin(b->v, max_pivots, nullptr, 0, b->stream);
     bool cancelled = false;
     for (;;) {
-        launch_sb_solve(b->v, b->threads, is_max, f, b->launch_cap, nullptr, b->stream);
+        sb_launch_solve(b, is_max, f, nullptr, b->stream);
         HIP_TRY(hipGetLastError());
         const int rc = sb_read(b, b->stream, false);
         if (rc != MI_OK) return rc;
@@ -208,6 +252,10 @@ int mi355x_sbatch_solve_two_phase(mi355x_sbatch *art, mi355x_sbatch *mt, int mai
     if (max_pivots < 0) return fail(MI_BAD_ARG, "max_pivots < 0");
     if (art->v.n_lps != mt->v.n_lps || art->v.rows != mt->v.rows || art->v.cols < mt->v.cols || art->device != mt->device)
         return fail(MI_BAD_ARG, "artificial and main batch do not match");
+    if (art->form != mt->form) return fail(MI_BAD_ARG, "artificial and main batch are of different forms");
+    if (art->form == kSbFormGlobal && sgbatch_between_lds_bytes(art->v) > kSingleLdsBudget)
+        return fail(MI_UNSUPPORTED, "the step between the phases of a %lldx%lld artificial member does not fit the LDS "
+                    "budget of %lld bytes", (long long)art->v.rows, (long long)art->v.cols, (long long)kSingleLdsBudget);
     HIP_TRY(hipSetDevice(art->device));
     const int64_t n = art->v.n_lps;
     hipStream_t s = art->stream;
@@ -224,10 +272,11 @@ int mi355x_sbatch_solve_two_phase(mi355x_sbatch *art, mi355x_sbatch *mt, int mai
     for (int64_t q = 0; q < n && !phase1; ++q) phase1 = live_a[q];
     for (;;) {
         if (phase1) {
-            launch_sb_solve(art->v, art->threads, /*is_max=*/0, f, art->launch_cap, nullptr, s);     // simplex.lisp:403
-            launch_sb_between(art->v, mt->v, art->threads, art->d_phase, f, max_pivots, s);
+            sb_launch_solve(art, /*is_max=*/0, f, nullptr, s);                                       // simplex.lisp:403
+            if (art->form == kSbFormGlobal) launch_sg_between(art->v, mt->v, art->threads, art->d_phase, f, max_pivots, s);
+            else launch_sb_between(art->v, mt->v, art->threads, art->d_phase, f, max_pivots, s);
         }
-        launch_sb_solve(mt->v, mt->threads, main_is_max, f, mt->launch_cap, art->d_phase, s);       // simplex.lisp:452
+        sb_launch_solve(mt, main_is_max, f, art->d_phase, s);                                        // simplex.lisp:452
         HIP_TRY(hipGetLastError());
         int rc = sb_read(art, s, true);
         if (rc == MI_OK) rc = sb_read(mt, s, false);
@@ -291,6 +340,13 @@ int mi355x_tune_set_sbatch_threads(int threads)
 {
     if (threads != 0 && threads != 256 && threads != 1024) return fail(MI_BAD_ARG, "threads must be 0 (auto), 256 or 1024");
     g_sbatch_threads = threads;
+    return MI_OK;
+}
+
+int mi355x_tune_set_sbatch_global_threads(int threads)
+{
+    if (threads != 0 && threads != 256 && threads != 1024) return fail(MI_BAD_ARG, "threads must be 0 (auto), 256 or 1024");
+    g_sbatch_global_threads = threads;
     return MI_OK;
 }
 

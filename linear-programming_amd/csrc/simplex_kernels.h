@@ -561,6 +561,17 @@ void launch_sb_begin(const SbView &b, int64_t max_pivots, const int32_t *phase, 
 void launch_sb_solve(const SbView &b, int threads, int is_max, double fp_factor, int cap, const int32_t *gate, hipStream_t s);
 void launch_sb_between(const SbView &art, const SbView &main_b, int threads, int32_t *phase, double fp_factor,
                        int64_t max_pivots, hipStream_t s);
+// The global form of a single-float batch (kernels_single_global.inc): one workgroup per member, the tableau in HBM,
+// pivot row and column snapshot in LDS -- for members beyond the LDS budget.
+size_t sgbatch_lds_bytes(const SbView &b);                                  // k_sg_solve's dynamic LDS
+size_t sgbatch_between_lds_bytes(const SbView &art);                        // k_sb_between's, for a global-form pair
+constexpr int64_t kSgbatchBytes1024 = 256 * 1024;                           // stored bytes from which a member takes 1024 threads
+int    sgbatch_threads_for(int64_t rows, int64_t ld);
+int    sgbatch_launch_cap_for(int64_t rows, int64_t ld);
+bool   sgbatch_available(const SbView &b, int threads, int *members_per_cu);  // fits the budget AND the attributes could be raised
+void launch_sg_solve(const SbView &b, int threads, int is_max, double fp_factor, int cap, const int32_t *gate, hipStream_t s);
+void launch_sg_between(const SbView &art, const SbView &main_b, int threads, int32_t *phase, double fp_factor,
+                       int64_t max_pivots, hipStream_t s);
 // Single-float branch-and-bound (kernels_single_bb.inc, capi_single_bb.inc): the base problem's general-form
 // tableau in floats; the node rows of the members are an XbbNodeRows, as for the exact search.
 struct SbbBaseView {

@@ -79,6 +79,7 @@
 //     kernels_launch.inc          host-side launchers, tuning state
 //     kernels_single.inc          single-float tableaux: one copy of the selection code, k_s_select / k_s_update, k_s_solve (LDS)
 //     kernels_single_batch.inc    batches of single-float tableaux: k_sb_solve (one workgroup per member, LDS), k_sb_between
+//     kernels_single_global.inc   the global form of those batches: k_sg_solve (one workgroup per member, the tableau in HBM)
 //     kernels_single_bb.inc       single-float branch-and-bound: float node tableaux into padded members, light read-back (k_sbb_assemble, k_sb_readback)
 //     kernels_single_lps.inc      single-float batches built from problem rows under Lisp's contagion (k_slp_assemble)
 #include "simplex_kernels.h"
@@ -107,6 +108,7 @@ namespace mi355x {
 #include "kernels_launch.inc"
 #include "kernels_single.inc"
 #include "kernels_single_batch.inc"
+#include "kernels_single_global.inc"
 #include "kernels_single_bb.inc"
 #include "kernels_single_lps.inc"
 

@@ -617,7 +617,7 @@ simplex_solver = mi355x_simplex_solver
 
 def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_pivots=0, errorp=True, native=False,
                           exact=False, exact_bits=0, exact_max_bits=128, pivot_rule="dantzig", device_build=False,
-                          from_rows=False, precision="double"):
+                          from_rows=False, precision="double", beyond_lds=False):
     """The glue's `mi355x-solve-problems`: a LIST of problems -> the list of their solved tableaus,
     what [solve_problem(p) for p in problems] returns, with the independent LPs side by side on the
     GPU(s).  Single-phase problems are grouped by tableau shape and sense; a group of two or more
@@ -663,9 +663,16 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
     shapes beyond the batch's LDS budget and integer problems go one by one; a member with a number no binary32
     holds is declined: unsupported-constraint-error ("single", number) in its slot.  Together with exact,
     native="many", from_rows, device_build, devices > 1 or a pivot_rule other than "dantzig" it is an argument
-    error that names the pair; so is an unknown precision."""
+    error that names the pair; so is an unknown precision.
+    beyond_lds=True (opt-in, with precision="single" only -- an argument error otherwise): a group beyond the batch's
+    LDS budget with at least single.global_batch_min_members(rows, cols) members is ONE global-form batch (one
+    workgroup per member, the member's tableau left in device memory: mi355x_sbatch_create_global) instead of going
+    one by one; every member comes back as the same SingleTableau, bit for bit."""
     if precision not in ("double", "single"):
         raise ValueError("precision=%r: \"double\" (default) or \"single\"" % (precision,))
+    if beyond_lds and precision != "single":
+        raise ValueError("beyond_lds=True needs precision=\"single\": it batches the single-float members beyond the "
+                         "LDS budget")
     if precision == "single":
         given = {"exact": exact, "native": native, "from_rows": from_rows, "device_build": device_build,
                  "devices": devices, "pivot_rule": pivot_rule}
@@ -676,8 +683,9 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
                 raise ValueError("precision=\"single\" does not go with %s=%r: the single-float batch is one device "
                                  "under the reference's rule" % (name, given[name]))
         from .single import solve_problems_single
+        kw = {"beyond_lds": True} if beyond_lds else {}                    # (the default: the call as it was)
         return solve_problems_single(problems, fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots,
-                                     errorp=errorp)
+                                     errorp=errorp, **kw)
     from .exact import pivot_rule_code
     if pivot_rule_code(pivot_rule) != 0 and not exact:
         raise ValueError("pivot_rule=%r needs exact=True: the double-precision paths keep the reference's rule"

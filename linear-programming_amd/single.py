@@ -257,16 +257,20 @@ def solve_single(problem, fp_tolerance=1024, device=0, max_pivots=0, chunk=None)
 # ------------------------------------------------------------------ batches: one workgroup per LP
 class SingleBatch:
     """n single-float tableaux of one shape behind a mi355x_sbatch: one workgroup owns one member for its whole
-    solve, the member's tableau in LDS.  Member by member the result is what the member's own SingleTableau gives
-    under the same sequence of calls."""
+    solve, the member's tableau in LDS (form "lds") or, opt-in and for members beyond the LDS budget, left in device
+    memory (form "global").  Member by member the result is what the member's own SingleTableau gives under the same
+    sequence of calls."""
 
     def __init__(self, handle, n_lps, rows, cols):
         self._handle, self.n_lps, self.rows, self.cols = handle, int(n_lps), int(rows), int(cols)
 
     @classmethod
-    def from_arrays(cls, matrices, basis, device=0):
+    def from_arrays(cls, matrices, basis, device=0, form="lds"):
         """matrices[n, rows, cols] float32, basis[n, rows - 1].  A shape the batch declines (beyond the LDS
-        budget) raises capi.Mi355xError with code MI_UNSUPPORTED."""
+        budget) raises capi.Mi355xError with code MI_UNSUPPORTED.  form="global": mi355x_sbatch_create_global, which
+        takes every shape whose pivot row and column snapshot fit the budget."""
+        if form not in ("lds", "global"):
+            raise ValueError("form=%r: \"lds\" (default) or \"global\"" % (form,))
         M = np.asarray(matrices)
         if M.dtype != np.float32:
             raise TypeError("a SingleBatch takes float32 matrices, not %s" % (M.dtype,))
@@ -278,8 +282,9 @@ class SingleBatch:
         if b.shape != (n, rows - 1):
             raise ValueError("basis shape %r does not match [n, rows - 1] = %r" % (b.shape, (n, rows - 1)))
         h = ctypes.c_void_p()
-        capi.check(capi.lib().mi355x_sbatch_create(ctypes.byref(h), n, rows, cols, _ptr(M), _ptr(b) if b.size else None,
-                                                   int(device)), "mi355x_sbatch_create")
+        name = "mi355x_sbatch_create_global" if form == "global" else "mi355x_sbatch_create"
+        capi.check(getattr(capi.lib(), name)(ctypes.byref(h), n, rows, cols, _ptr(M), _ptr(b) if b.size else None,
+                                             int(device)), name)
         return cls(h, n, rows, cols)
 
     @classmethod
@@ -350,14 +355,15 @@ class SingleBatch:
 
     def info(self):
         """mi355x_sbatch_info: {"n_lps", "rows", "cols", "ld", "workgroup_threads", "lds_bytes_per_member",
-        "members_per_cu"}."""
+        "members_per_cu", "form" (mi355x_sbatch_form: 2 LDS, 3 global)}."""
         n, r, c, ld, lds = (ctypes.c_int64() for _ in range(5))
-        thr, per_cu = ctypes.c_int(), ctypes.c_int()
+        thr, per_cu, form = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         capi.check(capi.lib().mi355x_sbatch_info(self._handle, ctypes.byref(n), ctypes.byref(r), ctypes.byref(c),
                                                  ctypes.byref(ld), ctypes.byref(thr), ctypes.byref(lds),
                                                  ctypes.byref(per_cu)), "mi355x_sbatch_info")
+        capi.check(capi.lib().mi355x_sbatch_form(self._handle, ctypes.byref(form)), "mi355x_sbatch_form")
         return {"n_lps": n.value, "rows": r.value, "cols": c.value, "ld": ld.value, "workgroup_threads": thr.value,
-                "lds_bytes_per_member": lds.value, "members_per_cu": per_cu.value}
+                "lds_bytes_per_member": lds.value, "members_per_cu": per_cu.value, "form": form.value}
 
     def cancel(self):
         """mi355x_sbatch_cancel: the running call, or the next one, stops between two rounds with MI_CANCELLED."""
@@ -383,6 +389,39 @@ def set_batch_threads(threads):
 def set_batch_launch_cap(cap):
     """mi355x_tune_set_sbatch_launch_cap (tests): pivots per member and launch, 0 the default."""
     capi.check(capi.lib().mi355x_tune_set_sbatch_launch_cap(int(cap)), "mi355x_tune_set_sbatch_launch_cap")
+
+
+def set_batch_global_threads(threads):
+    """mi355x_tune_set_sbatch_global_threads (tests and measurement): 0 auto, 256 or 1024 for global-form batches
+    created from now on."""
+    capi.check(capi.lib().mi355x_tune_set_sbatch_global_threads(int(threads)), "mi355x_tune_set_sbatch_global_threads")
+
+
+#: tests: a number here replaces global_batch_min_members' answer for every shape
+GLOBAL_BATCH_MIN_MEMBERS = None
+
+
+def global_batch_min_members(rows, cols):
+    """The fewest members of a rows x cols group (beyond the LDS budget) that go as ONE global-form batch under
+    beyond_lds=True; a smaller group goes one by one.  One workgroup per member loses to the select / update pair,
+    which puts the whole GPU on one tableau, when members are large and few: the crossover grows with the stored
+    bytes.  Read off profiles/sbatch_global_rate.txt: the batch is taken only where it was measured
+    faster than one by one by more than the one-by-one figure's own spread -- a shape between two measured ones
+    takes the larger one's count, a member beyond the largest measured one is never batched."""
+    if GLOBAL_BATCH_MIN_MEMBERS is not None:
+        return int(GLOBAL_BATCH_MIN_MEMBERS)
+    stored = int(rows) * ((int(cols) + 31) // 32 * 32) * 4
+    for limit, members in _GLOBAL_MIN_MEMBERS:
+        if stored <= limit:
+            return members
+    return GLOBAL_BATCH_NEVER
+
+
+#: (stored bytes of a measured member, the fewest members from which the batch was faster at that shape and at every
+#: larger count measured), ascending: 256 x 512 (from 2 on), 512 x 1024 (not at 2, from 8 on), 1024 x 2048
+_GLOBAL_MIN_MEMBERS = ((257 * 800 * 4, 2), (513 * 1568 * 4, 8), (1025 * 3104 * 4, 64))
+#: more members than a batch can have (mi355x_sbatch_create takes up to 2**30)
+GLOBAL_BATCH_NEVER = 1 << 31
 
 
 def group_single_problems(problems, fp_tolerance=1024, device=0):
@@ -426,23 +465,28 @@ def solve_made_batches(made, is_max, take, fp_tolerance=1024, max_pivots=0, chun
             b.close()
 
 
-def solve_problems_single(problems, fp_tolerance=1024, device=0, max_pivots=0, errorp=True, chunk=None):
+def solve_problems_single(problems, fp_tolerance=1024, device=0, max_pivots=0, errorp=True, chunk=None,
+                          beyond_lds=False):
     """mi355x_solve_problems(..., precision="single"): what [solve_single(p) for p in problems] returns, the groups
     of two or more as ONE SingleBatch (or a pair of them) in bounded chunks.  Members alone in their group, shapes
-    the batch declines and integer problems go through solve_single one by one."""
+    the batch declines and integer problems go through solve_single one by one.
+    beyond_lds=True (opt-in): a group the LDS batch declines that has at least global_batch_min_members(rows, cols)
+    members (for two-phase members: of the artificial shape) goes as ONE global-form batch (or a pair of them)
+    instead of one by one; the results are the same, bit for bit."""
     results = [None] * len(problems)
     slots, groups, groups2 = group_single_problems(problems, fp_tolerance, device)
 
     def alone(k):
         return solve_single(problems[k], fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots, chunk=chunk)
 
-    def make(*members):
+    def make(*members, form="lds"):
         """One SingleBatch per list of tableaux, or None when the batch declines a shape (beyond the LDS budget)."""
         made = []
         try:
             for tabs in members:
                 made.append(SingleBatch.from_arrays(np.stack([t.matrix for t in tabs]),
-                                                    np.stack([t.basis_columns for t in tabs]), device=device))
+                                                    np.stack([t.basis_columns for t in tabs]), device=device,
+                                                    **({"form": form} if form != "lds" else {})))
         except capi.Mi355xError as e:
             for b in made:
                 b.close()
@@ -466,7 +510,11 @@ def solve_problems_single(problems, fp_tolerance=1024, device=0, max_pivots=0, e
     for members in [*groups.values(), *groups2.values()]:
         ks, firsts, mains = [m[0] for m in members], [m[1] for m in members], [m[-1] for m in members]
         two = len(members[0]) == 3
-        made = (make(firsts, mains) if two else make(mains)) if len(members) > 1 else None
+        lists_of = (firsts, mains) if two else (mains,)
+        made = make(*lists_of) if len(members) > 1 else None
+        if made is None and beyond_lds and len(members) > 1 and \
+                len(members) >= global_batch_min_members(*firsts[0].matrix.shape):
+            made = make(*lists_of, form="global")
         if made is None:
             lists.one_by_one(results, ks, alone)
             continue
