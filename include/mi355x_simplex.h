@@ -918,6 +918,17 @@ void mi355x_sbb_base_destroy(mi355x_sbb_base *base);
 int  mi355x_sbatch_create_nodes(mi355x_sbatch **out_main, mi355x_sbatch **out_art, const mi355x_sbb_base *base,
                                 int64_t n_nodes, int64_t depth, const int64_t *var, const int32_t *sense,
                                 const int64_t *bound);
+/* The same node batches in the GLOBAL form (opt-in; mi355x_sbatch_create_global's handles: form 3 of
+ * mi355x_sbatch_form, its thread-count and launch-cap rules), for nodes beyond the LDS budget.  Arguments, checks and
+ * their order, the guard and the tableaux -- node rows (src/simplex.lisp:214-221, :230-237), the flip (:243-252),
+ * artificial columns (:257, :261, :296-300), the artificial objective row (:302-316) -- are mi355x_sbatch_create_nodes';
+ * no handle is left behind on any failure.  The assembly is spread over a grid (a row pass per node, one write pass,
+ * the artificial objective row behind it on one stream) and has NO row or depth limit of its own: every shape
+ * mi355x_sbatch_create_global accepts is taken, small ones included; MI_UNSUPPORTED for the guard and where the pivot
+ * row and column snapshot exceed the LDS budget (before anything is allocated). */
+int  mi355x_sbatch_create_nodes_global(mi355x_sbatch **out_main, mi355x_sbatch **out_art, const mi355x_sbb_base *base,
+                                       int64_t n_nodes, int64_t depth, const int64_t *var, const int32_t *sense,
+                                       const int64_t *bound);
 /* Per member the last column (rhs: rows values), the last row (obj_row: cols values) and the basis (rows - 1
  * entries), member-major: one gather kernel and one copy for the whole batch. */
 int  mi355x_sbatch_readback(mi355x_sbatch *b, float *rhs, float *obj_row, int64_t *basis);
@@ -947,6 +958,18 @@ int  mi355x_sbatch_readback(mi355x_sbatch *b, float *rhs, float *obj_row, int64_
  * mi355x_sbatch_solve_two_phase, a main batch alone to mi355x_sbatch_solve.  The caller owns both handles. */
 int  mi355x_sbatch_create_lps(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n_lps, int64_t m, int64_t ncv,
                               const float *lps, const int32_t *sense, const double *col_int_sum, int device);
+/* The same batches in the GLOBAL form (opt-in; mi355x_sbatch_create_global's handles: form 3 of mi355x_sbatch_form,
+ * its thread-count and launch-cap rules), for members beyond the LDS budget.  Arguments, checks and their order
+ * (MI_BAD_ARG before any device is looked for), the guard and what is written -- the flip (src/simplex.lisp:243-252),
+ * slack columns (:254-265), artificial columns (:257, :261, :296-300), the artificial objective row (:302-316), on
+ * rows lowered by :189-241 and :270-283 -- are mi355x_sbatch_create_lps'; no handle is left behind on any failure.
+ * The assembly is spread over a grid (a row pass per member, one write pass, the artificial objective row behind it
+ * on one stream) and has NO row limit of its own: every shape mi355x_sbatch_create_global accepts is taken, small
+ * ones included; MI_UNSUPPORTED for the guard and where the pivot row and column snapshot of the main or artificial
+ * shape exceed the LDS budget (before anything is allocated). */
+int  mi355x_sbatch_create_lps_global(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n_lps, int64_t m,
+                                     int64_t ncv, const float *lps, const int32_t *sense, const double *col_int_sum,
+                                     int device);
 
 #ifdef __cplusplus
 }

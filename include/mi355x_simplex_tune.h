@@ -226,6 +226,10 @@ int         mi355x_tune_set_sbatch_global_threads(int threads);
  * *ld (may be NULL) = the leading dimension; out NULL: only *ld.  What a create entry left in the columns
  * [cols, ld) (mi355x_sbatch_create_lps writes them itself). */
 int         mi355x_sbatch_debug_stored(mi355x_sbatch *b, int64_t lp_index, float *out, int64_t *ld);
+/* measurement aid (tools/slps_global_rate.py): enable != 0 makes every mi355x_sbatch_create_lps_global from now on
+ * record HIP events around its three passes; the call also reports the LAST timed create's milliseconds -- row pass,
+ * write pass, artificial objective row (0 without artificial rows; -1: not measured).  Any pointer may be NULL. */
+int         mi355x_sbatch_lps_global_timing(int enable, double *rows_ms, double *write_ms, double *objective_ms);
 
 /* Compiled in with -DMI355X_TEST_HOOKS (libmi355x_simplex_test.so, built next to the product
  * library by linear-programming_amd/build.py and loaded by the tests that need it); the product

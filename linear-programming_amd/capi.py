@@ -188,8 +188,10 @@ SIGNATURES = {
     "mi355x_sbb_base_create": (_int, [_pp, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _int]),
     "mi355x_sbb_base_destroy": (None, [_p]),
     "mi355x_sbatch_create_nodes": (_int, [_pp, _pp, _p, _i64, _i64, _p, _p, _p]),
+    "mi355x_sbatch_create_nodes_global": (_int, [_pp, _pp, _p, _i64, _i64, _p, _p, _p]),
     "mi355x_sbatch_readback": (_int, [_p, _p, _p, _p]),
     "mi355x_sbatch_create_lps": (_int, [_pp, _pp, _i64, _i64, _i64, _p, _p, _p, _int]),
+    "mi355x_sbatch_create_lps_global": (_int, [_pp, _pp, _i64, _i64, _i64, _p, _p, _p, _int]),
 }
 # tuning / measurement / test hooks: include/mi355x_simplex_tune.h (not the drop-in boundary)
 _EXTRA = {
@@ -231,6 +233,7 @@ _EXTRA = {
     "mi355x_batch_path_counts": (_int, [_p, _p]),
     "mi355x_batch_lps_timing": (_int, [_int, _p, _p]),
     "mi355x_sbatch_debug_stored": (_int, [_p, _i64, _p, _p]),
+    "mi355x_sbatch_lps_global_timing": (_int, [_int, _p, _p, _p]),
     "mi355x_debug_repeat_sweep": (_int, [_p, _int, _p]),
     "mi355x_tune_variant_count": (_int, []),
     "mi355x_tune_variant_name": (ctypes.c_char_p, [_int]),

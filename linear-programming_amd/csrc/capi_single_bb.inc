@@ -44,25 +44,25 @@ inline float sbb_rhs(const SbbBase &b, int64_t var, int64_t bound)
     return b.kind[var] == 2 ? f : f - b.off[var];
 }
 
-// the node's device-side arrays, freed with the scope
+// the node's device-side arrays (and the global form's scratch planes), freed with the scope
 struct SbbNodeArrays {
     int64_t *var = nullptr, *bound = nullptr;
-    int32_t *sense = nullptr;
-    ~SbbNodeArrays() { (void)hipFree(var); (void)hipFree(bound); (void)hipFree(sense); }
+    int32_t *sense = nullptr, *scratch = nullptr;
+    ~SbbNodeArrays() { (void)hipFree(var); (void)hipFree(bound); (void)hipFree(sense); (void)hipFree(scratch); }
 };
 
 // a (main, artificial) pair of n-member batches on `device` around an assembly (also capi_single_lps.inc's):
 // fill(stream, main view, artificial view) -> hipError_t allocates, uploads and launches; what it allocates has to
-// live until this function returns.  n_art == 0: no artificial batch.
+// live until this function returns.  n_art == 0: no artificial batch.  form: both handles' (kSbFormLds, kSbFormGlobal).
 template <class Fill>
 int sb_pair_build(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n, int64_t rows, int64_t cols, int64_t n_art,
-                  int device, const char *what, Fill fill)
+                  int device, const char *what, Fill fill, int form = kSbFormLds)
 {
     mi355x_sbatch *mt = nullptr, *art = nullptr;
     int rc = MI_OK;
     // (the larger shape first: a pair the budget declines allocates nothing)
-    if (n_art) rc = sb_new(&art, n, rows, cols + n_art, device, /*zero_padding=*/false);
-    if (rc == MI_OK) rc = sb_new(&mt, n, rows, cols, device, /*zero_padding=*/false);
+    if (n_art) rc = sb_new(&art, n, rows, cols + n_art, device, /*zero_padding=*/false, form);
+    if (rc == MI_OK) rc = sb_new(&mt, n, rows, cols, device, /*zero_padding=*/false, form);
     auto undo = [&](int code) { free_sbatch(mt); free_sbatch(art); return code; };
     if (rc != MI_OK) return undo(rc);
     hipError_t e = fill(mt->stream, mt->v, art ? art->v : SbView{});
@@ -135,9 +135,13 @@ int mi355x_sbb_base_create(mi355x_sbb_base **out, int64_t rows, int64_t cols, co
 
 void mi355x_sbb_base_destroy(mi355x_sbb_base *base) { delete base; }
 
-int mi355x_sbatch_create_nodes(mi355x_sbatch **out_main, mi355x_sbatch **out_art, const mi355x_sbb_base *base,
-                               int64_t n_nodes, int64_t depth, const int64_t *var, const int32_t *sense,
-                               const int64_t *bound)
+}  // extern "C"
+
+namespace {
+
+// mi355x_sbatch_create_nodes / _create_nodes_global: the checks, the guard, the pair of the form, the assembly
+int sbb_create_nodes(mi355x_sbatch **out_main, mi355x_sbatch **out_art, const mi355x_sbb_base *base, int64_t n_nodes,
+                     int64_t depth, const int64_t *var, const int32_t *sense, const int64_t *bound, int form)
 {
     if (!out_main || !out_art) return fail(MI_BAD_ARG, "out is NULL");
     *out_main = *out_art = nullptr;
@@ -186,7 +190,7 @@ int mi355x_sbatch_create_nodes(mi355x_sbatch **out_main, mi355x_sbatch **out_art
         return fail(MI_UNSUPPORTED, "a column's integer entries sum beyond 2^24: the float sum of the artificial "
                                     "objective row would not be the reference's");
     const int64_t rows = b.rows + depth, cols = b.cols + depth;
-    if (sbb_assemble_lds(rows - 1, depth) > kSbbAssembleLdsLimit)
+    if (form == kSbFormLds && sbb_assemble_lds(rows - 1, depth) > kSbbAssembleLdsLimit)
         return fail(MI_UNSUPPORTED, "%lld rows at depth %lld do not fit the assembly's LDS", (long long)rows, (long long)depth);
     SbbNodeArrays nd;
     return sb_pair_build(out_main, out_art, n_nodes, rows, cols, n_art, b.device, "node assembly",
@@ -198,12 +202,34 @@ int mi355x_sbatch_create_nodes(mi355x_sbatch **out_main, mi355x_sbatch **out_art
         if (e == hipSuccess) e = hipMemcpyAsync(nd.var, var, nk * sizeof(int64_t), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(nd.bound, bound, nk * sizeof(int64_t), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(nd.sense, sense, nk * sizeof(int32_t), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && form == kSbFormGlobal)
+            e = hipMalloc((void **)&nd.scratch, sga_nodes_scratch_bytes(n_nodes, rows - 1));
         if (e == hipSuccess) {
             const SbbBaseView bv{b.d_B, b.d_off, b.rows, b.cols, b.ncv, b.nb, b.d_basis, b.d_kind, b.d_vcol};
-            launch_sbb_assemble(mv, av, bv, XbbNodeRows{nd.var, nd.sense, nd.bound, depth}, s);
+            const XbbNodeRows nr{nd.var, nd.sense, nd.bound, depth};
+            if (form == kSbFormGlobal) launch_sga_nodes(mv, av, bv, nr, nd.scratch, s);
+            else launch_sbb_assemble(mv, av, bv, nr, s);
         }
         return e;
-    });
+    }, form);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi355x_sbatch_create_nodes(mi355x_sbatch **out_main, mi355x_sbatch **out_art, const mi355x_sbb_base *base,
+                               int64_t n_nodes, int64_t depth, const int64_t *var, const int32_t *sense,
+                               const int64_t *bound)
+{
+    return sbb_create_nodes(out_main, out_art, base, n_nodes, depth, var, sense, bound, kSbFormLds);
+}
+
+int mi355x_sbatch_create_nodes_global(mi355x_sbatch **out_main, mi355x_sbatch **out_art, const mi355x_sbb_base *base,
+                                      int64_t n_nodes, int64_t depth, const int64_t *var, const int32_t *sense,
+                                      const int64_t *bound)
+{
+    return sbb_create_nodes(out_main, out_art, base, n_nodes, depth, var, sense, bound, kSbFormGlobal);
 }
 
 int mi355x_sbatch_readback(mi355x_sbatch *b, float *rhs, float *obj_row, int64_t *basis)

@@ -16,18 +16,21 @@
 
 namespace {
 
-// the members' rows and senses on the device (one allocation), freed with the scope
+// the members' rows and senses on the device (one allocation; behind them the global form's scratch planes), freed
+// with the scope
 struct SlpRows {
     void *mem = nullptr;
     ~SlpRows() { (void)hipFree(mem); }
 };
 
-}  // namespace
+// mi355x_sbatch_lps_global_timing (measurement aid): HIP events around the three passes of the global form's assembly
+std::atomic<int> g_slpg_timing{0};
+std::mutex       g_slpg_mutex;
+double           g_slpg_ms[3] = {0.0, 0.0, 0.0};                            // the last timed create: rows, write, objective row
 
-extern "C" {
-
-int mi355x_sbatch_create_lps(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n_lps, int64_t m, int64_t ncv,
-                             const float *lps, const int32_t *sense, const double *col_int_sum, int device)
+// mi355x_sbatch_create_lps / _create_lps_global: the checks, the guard, the pair of the form, the assembly
+int slp_create(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n_lps, int64_t m, int64_t ncv, const float *lps,
+               const int32_t *sense, const double *col_int_sum, int device, int form)
 {
     if (!out_main || !out_art) return fail(MI_BAD_ARG, "out is NULL");
     *out_main = *out_art = nullptr;
@@ -41,22 +44,66 @@ int mi355x_sbatch_create_lps(mi355x_sbatch **out_main, mi355x_sbatch **out_art, 
                     return fail(MI_UNSUPPORTED, "member %lld: the integer entries of column %lld sum beyond 2^24: the float "
                                 "sum of the artificial objective row would not be the reference's", (long long)q, (long long)c);
     const int64_t rows = m + 1, cols = ncv + (m - n_eq) + 1;
-    if (m > kSlpMaxRows)                                                    // (no tableau of so many rows fits the budget)
+    if (form == kSbFormLds && m > kSlpMaxRows)                              // (no tableau of so many rows fits the budget)
         return fail(MI_UNSUPPORTED, "a %lldx%lld single-float member does not fit the LDS budget of %lld bytes",
                     (long long)rows, (long long)cols, (long long)kSingleLdsBudget);
     SlpRows d;
-    return sb_pair_build(out_main, out_art, n_lps, rows, cols, n_art, device, "assembly from rows",
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool timed = form == kSbFormGlobal && g_slpg_timing.load(std::memory_order_relaxed);
+    rc = sb_pair_build(out_main, out_art, n_lps, rows, cols, n_art, device, "assembly from rows",
                          [&](hipStream_t s, const SbView &mv, const SbView &av) {
         const size_t bL = (size_t)n_lps * (size_t)rows * (size_t)(ncv + 1) * sizeof(float), bS = (size_t)n_lps * (size_t)m * sizeof(int32_t);
-        const size_t oS = (bL + 255) & ~(size_t)255;
-        hipError_t e = hipMalloc(&d.mem, oS + bS);
+        const size_t oS = (bL + 255) & ~(size_t)255, oW = (oS + bS + 255) & ~(size_t)255;
+        hipError_t e = hipMalloc(&d.mem, form == kSbFormGlobal ? oW + sga_lps_scratch_bytes(n_lps, m) : oS + bS);
         const float *dL = (const float *)d.mem;
         const int32_t *dS = (const int32_t *)((const char *)d.mem + oS);
         if (e == hipSuccess) e = hipMemcpyAsync(d.mem, lps, bL, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync((char *)d.mem + oS, sense, bS, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) launch_slp_assemble(mv, av, SlpView{dL, dS, m, ncv, m - n_eq, n_art}, s);
+        if (e == hipSuccess) {
+            const SlpView sp{dL, dS, m, ncv, m - n_eq, n_art};
+            for (int k = 0; k < 4 && timed; ++k) timed = hipEventCreate(&ev[k]) == hipSuccess;
+            if (form == kSbFormGlobal) launch_sga_lps(mv, av, sp, (int32_t *)((char *)d.mem + oW), s, timed ? ev : nullptr);
+            else launch_slp_assemble(mv, av, sp, s);
+        }
         return e;
-    });
+    }, form);
+    if (rc == MI_OK && timed) {                                              // (sb_pair_build has waited for the stream)
+        std::lock_guard<std::mutex> lock(g_slpg_mutex);
+        for (int k = 0; k < 3; ++k) {
+            float ms = 0.0f;
+            g_slpg_ms[k] = hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess ? (double)ms : -1.0;
+        }
+    }
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi355x_sbatch_create_lps(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n_lps, int64_t m, int64_t ncv,
+                             const float *lps, const int32_t *sense, const double *col_int_sum, int device)
+{
+    return slp_create(out_main, out_art, n_lps, m, ncv, lps, sense, col_int_sum, device, kSbFormLds);
+}
+
+int mi355x_sbatch_create_lps_global(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n_lps, int64_t m, int64_t ncv,
+                                    const float *lps, const int32_t *sense, const double *col_int_sum, int device)
+{
+    return slp_create(out_main, out_art, n_lps, m, ncv, lps, sense, col_int_sum, device, kSbFormGlobal);
+}
+
+// measurement aid (include/mi355x_simplex_tune.h)
+int mi355x_sbatch_lps_global_timing(int enable, double *rows_ms, double *write_ms, double *objective_ms)
+{
+    std::lock_guard<std::mutex> lock(g_slpg_mutex);
+    if (rows_ms) *rows_ms = g_slpg_ms[0];
+    if (write_ms) *write_ms = g_slpg_ms[1];
+    if (objective_ms) *objective_ms = g_slpg_ms[2];
+    g_slpg_timing.store(enable ? 1 : 0, std::memory_order_relaxed);
+    return MI_OK;
 }
 
 // test aid (include/mi355x_simplex_tune.h): member k as stored, padding columns included

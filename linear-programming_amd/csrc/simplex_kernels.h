@@ -597,6 +597,16 @@ struct SlpView {
 constexpr int kSlpMaxRows = 256;                                            // k_slp_assemble: one row per thread, one trip
 // every member of mt and of at (at.M == nullptr: no artificial rows): tableau over the whole leading dimension, basis
 void launch_slp_assemble(const SbView &mt, const SbView &at, const SlpView &sp, hipStream_t s);
+// The same two assemblies spread over a grid, for GLOBAL-form batches (kernels_single_assemble_global.inc): a row pass
+// into per-member scratch planes (device memory of sga_*_scratch_bytes, the caller's, alive until the stream has run
+// the launches), one write pass and the artificial objective row, ordered by the stream alone.  Any m, any depth.
+size_t sga_lps_scratch_bytes(int64_t n_lps, int64_t m);
+size_t sga_nodes_scratch_bytes(int64_t n_nodes, int64_t m);                 // m: the node's constraint rows
+// (ev, measurement aid, may be nullptr: four events recorded in front of the row pass and behind each of the passes)
+void launch_sga_lps(const SbView &mt, const SbView &at, const SlpView &sp, int32_t *scratch, hipStream_t s,
+                    hipEvent_t *ev = nullptr);
+void launch_sga_nodes(const SbView &mt, const SbView &at, const SbbBaseView &b, const XbbNodeRows &nr, int32_t *scratch,
+                      hipStream_t s);
 
 int         update_variant_count();
 const char *update_variant_name(int v);

@@ -82,6 +82,7 @@
 //     kernels_single_global.inc   the global form of those batches: k_sg_solve (one workgroup per member, the tableau in HBM)
 //     kernels_single_bb.inc       single-float branch-and-bound: float node tableaux into padded members, light read-back (k_sbb_assemble, k_sb_readback)
 //     kernels_single_lps.inc      single-float batches built from problem rows under Lisp's contagion (k_slp_assemble)
+//     kernels_single_assemble_global.inc  both single-float assemblies spread over a grid, for global-form batches (k_sga_*)
 #include "simplex_kernels.h"
 #include <type_traits>
 
@@ -111,5 +112,6 @@ namespace mi355x {
 #include "kernels_single_global.inc"
 #include "kernels_single_bb.inc"
 #include "kernels_single_lps.inc"
+#include "kernels_single_assemble_global.inc"
 
 }  // namespace mi355x

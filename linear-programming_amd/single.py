@@ -288,13 +288,17 @@ class SingleBatch:
         return cls(h, n, rows, cols)
 
     @classmethod
-    def from_lps(cls, lps, sense, col_int_sum=None, device=0):
+    def from_lps(cls, lps, sense, col_int_sum=None, device=0, form="lds"):
         """mi355x_sbatch_create_lps: the members' tableaux built on the device from their rows.  lps[n, m + 1,
         ncv + 1] float32 in column space (per member m rows of coefficients and the right-hand side, then the
         objective row), sense[n, m] (0 `<=`, 1 `>=`, 2 `=`), col_int_sum[n, ncv + 1] or None: per member and column
         the sum of the absolute values of the entries Lisp holds as integers (the guard).  Every member has the same
         numbers of `=` and of artificial rows.  -> (main, art or None).  A group the library declines (the guard,
-        the LDS budget) raises capi.Mi355xError with code MI_UNSUPPORTED."""
+        the LDS budget) raises capi.Mi355xError with code MI_UNSUPPORTED.  form="global":
+        mi355x_sbatch_create_lps_global, the same tableaux as members of global-form batches -- every shape whose
+        pivot row and column snapshot fit the budget, any number of rows."""
+        if form not in ("lds", "global"):
+            raise ValueError("form=%r: \"lds\" (default) or \"global\"" % (form,))
         L = np.asarray(lps)
         if L.dtype != np.float32:
             raise TypeError("SingleBatch.from_lps takes float32 rows, not %s" % (L.dtype,))
@@ -311,9 +315,9 @@ class SingleBatch:
             if sums.shape != (n, ncv + 1):
                 raise ValueError("col_int_sum shape %r does not match [n, ncv + 1] = %r" % (sums.shape, (n, ncv + 1)))
         hm, ha = ctypes.c_void_p(), ctypes.c_void_p()
-        capi.check(capi.lib().mi355x_sbatch_create_lps(ctypes.byref(hm), ctypes.byref(ha), n, m, ncv, _ptr(L), _ptr(s),
-                                                       _ptr(sums) if sums is not None else None, int(device)),
-                   "mi355x_sbatch_create_lps")
+        name = "mi355x_sbatch_create_lps_global" if form == "global" else "mi355x_sbatch_create_lps"
+        capi.check(getattr(capi.lib(), name)(ctypes.byref(hm), ctypes.byref(ha), n, m, ncv, _ptr(L), _ptr(s),
+                                             _ptr(sums) if sums is not None else None, int(device)), name)
         n_eq, n_art = (int(x[0]) for x in lists.row_counts(L[:1, :-1, -1] < 0, s[:1]))
         cols = ncv + (m - n_eq) + 1
         return cls(hm, n, m + 1, cols), (cls(ha, n, m + 1, cols + n_art) if ha else None)

@@ -29,7 +29,8 @@ the float32 assembly is Lisp's build:
        the absolute values of a column's integer entries sum to at most 2**24 -- the guard
        (GeneralFormSingle.device_ok).  A group that fails it is built on the host (lowering.build with SINGLE) and
        goes through SingleBatch.from_arrays; a shape beyond the batch's LDS budget goes node by node through
-       SingleTableau.
+       SingleTableau -- or, with beyond_lds=True and at least single.global_batch_min_members nodes in the group,
+       as ONE global-form batch or pair, device-built (mi355x_sbatch_create_nodes_global) or host-built alike.
 """
 import ctypes
 import math
@@ -43,7 +44,7 @@ from .exact_bb import _I64_MAX, _status_of, search
 from .lowering import assemble, build, lower
 from .problem import Problem
 from .single import (EPSILON_SINGLE, SINGLE, SingleBatch, SingleTableau, build_tableau_single, check_single_problem,
-                     solve_status)
+                     global_batch_min_members, solve_status)
 from .simplex import tableau_objective_value, tableau_variable
 
 F32 = np.float32
@@ -200,10 +201,14 @@ class Base:
                    "mi355x_sbb_base_create")
         self.handle = h
 
-    def create_nodes(self, entries):
+    def create_nodes(self, entries, form="lds"):
         """mi355x_sbatch_create_nodes for entries of one depth and one number of artificial rows: (main
         SingleBatch, artificial SingleBatch or None).  A bound beyond 64 bits is declined; a group the library
-        declines (the guard, the LDS budget) raises capi.Mi355xError with code MI_UNSUPPORTED."""
+        declines (the guard, the LDS budget) raises capi.Mi355xError with code MI_UNSUPPORTED.  form="global":
+        mi355x_sbatch_create_nodes_global, the same tableaux as members of global-form batches -- every shape whose
+        pivot row and column snapshot fit the budget."""
+        if form not in ("lds", "global"):
+            raise ValueError("form=%r: \"lds\" (default) or \"global\"" % (form,))
         g, n, d = self.g, len(entries), len(entries[0])
         flat = [r for e in entries for r in e]
         if any(abs(b) > _I64_MAX for _, _, b in flat):
@@ -212,9 +217,9 @@ class Base:
         sense = np.array([s for _, s, _ in flat], dtype=np.int32)
         bound = np.array([int(b) for _, _, b in flat], dtype=np.int64)
         hm, ha = ctypes.c_void_p(), ctypes.c_void_p()
-        capi.check(capi.lib().mi355x_sbatch_create_nodes(ctypes.byref(hm), ctypes.byref(ha), self.handle, n, d,
-                                                         _ptr(var), _ptr(sense), _ptr(bound)),
-                   "mi355x_sbatch_create_nodes")
+        name = "mi355x_sbatch_create_nodes_global" if form == "global" else "mi355x_sbatch_create_nodes"
+        capi.check(getattr(capi.lib(), name)(ctypes.byref(hm), ctypes.byref(ha), self.handle, n, d, _ptr(var),
+                                             _ptr(sense), _ptr(bound)), name)
         rows, cols = g.matrix.shape[0] + d, g.matrix.shape[1] + d
         n_art = g.n_art + sum(g.row_artificial(*r) for r in entries[0])
         main = SingleBatch(hm, n, rows, cols)
@@ -284,11 +289,12 @@ class TableauSolution:
 class DeviceRounds:
     """The `solve_round` of the GPU (see the module's docstring)."""
 
-    def __init__(self, problem, fp_tolerance=1024, device=0, max_pivots=0, chunk=None):
+    def __init__(self, problem, fp_tolerance=1024, device=0, max_pivots=0, chunk=None, beyond_lds=False):
         self.problem, self.fp_tolerance, self.device = problem, fp_tolerance, device
-        self.max_pivots, self.chunk = max_pivots, chunk
+        self.max_pivots, self.chunk, self.beyond_lds = max_pivots, chunk, bool(beyond_lds)
         self.g = self.base = None
         self.host_built = self.one_by_one = self.declined = 0             # nodes that left the device-built route
+        self.global_batched = 0                                           # nodes solved in global-form batches
 
     def _alone(self, tabs):
         """One node through its own SingleTableau(s)."""
@@ -308,11 +314,12 @@ class DeviceRounds:
             return _status_of(e), None, None
         return self._alone(tabs)
 
-    def _batches(self, entries):
-        """(main, art or None) for a group, or None when no batch holds the shape."""
+    def _batches(self, entries, form="lds"):
+        """(main, art or None) for a group in that form, or None when the form does not hold the shape."""
+        kw = {"form": form} if form != "lds" else {}                      # (the default: the calls as they were)
         if all(self.g.device_ok(e) for e in entries):
             try:
-                return self.base.create_nodes(entries)
+                return self.base.create_nodes(entries, **kw)
             except capi.Mi355xError as e:
                 if e.code != capi.MI_UNSUPPORTED:
                     raise
@@ -323,7 +330,8 @@ class DeviceRounds:
         try:
             for tabs in ([t[1] for t in built], [t[0] for t in built]) if two else (built,):
                 made.append(SingleBatch.from_arrays(np.stack([t.matrix for t in tabs]),
-                                                    np.stack([t.basis_columns for t in tabs]), device=self.device))
+                                                    np.stack([t.basis_columns for t in tabs]), device=self.device,
+                                                    **kw))
         except capi.Mi355xError as e:
             for b in made:
                 b.close()
@@ -345,9 +353,15 @@ class DeviceRounds:
                 self.base = Base(self.g, self.device)
             groups.setdefault((len(e), sum(self.g.row_artificial(*r) for r in e)), []).append(k)
         is_max, f = self.problem.type == "max", self.fp_tolerance
-        for ks in groups.values():
+        for (d, n_art), ks in groups.items():
             try:
                 made = self._batches([entries[k] for k in ks])
+                # beyond the LDS budget, opt-in: ONE global-form batch (or pair) when the group is large enough
+                if made is None and self.beyond_lds and len(ks) >= global_batch_min_members(
+                        self.g.matrix.shape[0] + d, self.g.matrix.shape[1] + d + self.g.n_art + n_art):
+                    made = self._batches([entries[k] for k in ks], form="global")
+                    if made is not None:
+                        self.global_batched += len(ks)
             except SolverError as e:                                      # a bound the batch declines
                 for k in ks:
                     out[k] = (e, None, None)
@@ -380,9 +394,10 @@ class SingleBranchAndBound:
     errors; trace() / stats() as ExactBranchAndBound, `result.objectives` the trace's objectives as np.float32."""
 
     def __init__(self, problem, width=1, fp_tolerance=1024, int_tolerance=0, device=0, max_pivots=0, max_nodes=0,
-                 chunk=None):
+                 chunk=None, beyond_lds=False):
         self.problem, self.width, self.max_nodes, self.int_tolerance = problem, int(width), int(max_nodes), int_tolerance
-        self.rounds = DeviceRounds(problem, fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots, chunk=chunk)
+        self.rounds = DeviceRounds(problem, fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots, chunk=chunk,
+                                   **({"beyond_lds": True} if beyond_lds else {}))
         self.result = None
 
     def run(self):
@@ -405,11 +420,14 @@ class SingleBranchAndBound:
 
     def stats(self):
         return dict(self.result.stats(), declined=self.rounds.declined, host_built=self.rounds.host_built,
-                    one_by_one=self.rounds.one_by_one)
+                    one_by_one=self.rounds.one_by_one, global_batched=self.rounds.global_batched)
 
 
 def solve_branch_and_bound_single(problem, width=1, fp_tolerance=1024, int_tolerance=0, device=0, max_pivots=0,
-                                  max_nodes=0, chunk=None):
+                                  max_nodes=0, chunk=None, beyond_lds=False):
     """simplex-solver with integer variables (src/simplex.lisp:506-542) on a problem of integers and single-floats:
-    the incumbent as a solved SingleTableau (its read-back in np.float32)."""
-    return SingleBranchAndBound(problem, width, fp_tolerance, int_tolerance, device, max_pivots, max_nodes, chunk).run()
+    the incumbent as a solved SingleTableau (its read-back in np.float32).  beyond_lds=True (opt-in): a node group
+    the LDS batches decline that has at least single.global_batch_min_members nodes goes as ONE global-form batch or
+    pair instead of node by node; the search is the same, bit for bit."""
+    return SingleBranchAndBound(problem, width, fp_tolerance, int_tolerance, device, max_pivots, max_nodes, chunk,
+                                beyond_lds).run()

@@ -21,7 +21,7 @@ from collections import namedtuple
 
 import numpy as np
 
-from . import capi, lists
+from . import capi, lists, single
 from .batch_lps import host_reason
 from .conditions import SolverError
 from .lists import SENSES
@@ -85,12 +85,16 @@ def group_lowered_rows_single(problems):
     return host, lists.group_by_rows(lowered, host)
 
 
-def solve_problems_single_from_rows(problems, fp_tolerance=1024, device=0, max_pivots=0, errorp=True, chunk=None):
+def solve_problems_single_from_rows(problems, fp_tolerance=1024, device=0, max_pivots=0, errorp=True, chunk=None,
+                                    beyond_lds=False):
     """What solve_problems_single(problems, ...) returns, member for member -- the solved SingleTableau (matrix,
     basis, n_pivots, var_mapping, read-back in np.float32) or the member's condition -- with the tableaux of every
     group of group_lowered_rows_single built on the device (SingleBatch.from_lps) and solved in bounded chunks.
     The members that function names, and the groups the batch declines (MI_UNSUPPORTED: the LDS budget), go
-    through solve_single one by one."""
+    through solve_single one by one.
+    beyond_lds=True (opt-in): a group the LDS batch declines that has at least single.global_batch_min_members(rows,
+    cols) members (for a two-phase group: of the artificial shape) is built on the device all the same, as ONE
+    global-form batch or pair (SingleBatch.from_lps(form="global")); the results are the same, bit for bit."""
     results = [None] * len(problems)
     host, groups = group_lowered_rows_single(problems)
 
@@ -104,14 +108,27 @@ def solve_problems_single_from_rows(problems, fp_tolerance=1024, device=0, max_p
             lists.one_by_one(results, [k], alone)
     for members in groups.values():
         ks, lows = [k for k, _ in members], [low for _, low in members]
-        try:
-            main, art = SingleBatch.from_lps(np.stack([low.L for low in lows]), np.stack([low.sense for low in lows]),
-                                             np.stack([low.col_int_sum for low in lows]), device=device)
-        except capi.Mi355xError as e:
-            if e.code != capi.MI_UNSUPPORTED:
-                raise
+        arrays = (np.stack([low.L for low in lows]), np.stack([low.sense for low in lows]),
+                  np.stack([low.col_int_sum for low in lows]))
+
+        def make(form="lds"):
+            """(main, art or None), or None when the form declines the shape."""
+            try:
+                return SingleBatch.from_lps(*arrays, device=device, **({"form": form} if form != "lds" else {}))
+            except capi.Mi355xError as e:
+                if e.code != capi.MI_UNSUPPORTED:
+                    raise
+                return None
+        made = make()
+        if made is None and beyond_lds:
+            m, ncv = arrays[0].shape[1] - 1, arrays[0].shape[2] - 1
+            n_eq, n_art = (int(x[0]) for x in lists.row_counts(arrays[0][:1, :-1, -1] < 0, arrays[1][:1]))
+            if len(ks) >= single.global_batch_min_members(m + 1, ncv + (m - n_eq) + 1 + n_art):
+                made = make("global")
+        if made is None:
             lists.one_by_one(results, ks, alone)
             continue
+        main, art = made
 
         def take(sb, q, n_pivots):
             p = problems[ks[q]]
@@ -125,7 +142,7 @@ def solve_problems_single_from_rows(problems, fp_tolerance=1024, device=0, max_p
 
 
 # ------------------------------------------------------------------ the array front end
-def solve_lps_single(lps, sense, is_max=True, int_mask=None, fp_tolerance=1024, device=0, max_pivots=0):
+def solve_lps_single(lps, sense, is_max=True, int_mask=None, fp_tolerance=1024, device=0, max_pivots=0, form="lds"):
     """One group given as arrays, the float twin of batch_lps.solve_lps -- lps n x (m + 1) x (ncv + 1) float32 in
     column space (per member m rows of ncv coefficients and the right-hand side, then the objective row as
     build-tableau stores it: -c for max / min c . x over x >= 0, the constant last), sense n x m (0 `<=`, 1 `>=`,
@@ -137,8 +154,12 @@ def solve_lps_single(lps, sense, is_max=True, int_mask=None, fp_tolerance=1024, 
     with a negative right-hand side comes out +0.0, where Lisp makes -0.0 of a single-float zero.
     -> (statuses n, pivots n or n x 2 for a two-phase group, rhs n x (m + 1), obj_rows n x cols, bases n x m): the
     objective value of member q is obj_rows[q, -1], the value of column j rhs[q, i] where bases[q, i] == j (0
-    otherwise), its reduced cost obj_rows[q, j].  A member that did not end MI_OPTIMAL has no meaningful values."""
+    otherwise), its reduced cost obj_rows[q, j].  A member that did not end MI_OPTIMAL has no meaningful values.
+    form="global" (opt-in): the group as global-form batches (mi355x_sbatch_create_lps_global), for members beyond the
+    LDS budget; the caller chooses, no member-count rule applies here."""
     from .single_bb import readback
+    if form not in ("lds", "global"):
+        raise ValueError("form=%r: \"lds\" (default) or \"global\"" % (form,))
     L = np.asarray(lps)
     sums = None
     if int_mask is not None:
@@ -146,7 +167,7 @@ def solve_lps_single(lps, sense, is_max=True, int_mask=None, fp_tolerance=1024, 
         if mask.shape != L.shape:
             raise ValueError("int_mask shape %r does not match lps %r" % (mask.shape, L.shape))
         sums = np.where(mask[:, :-1, :], np.abs(L[:, :-1, :].astype(np.float64)), 0.0).sum(axis=1)
-    main, art = SingleBatch.from_lps(L, sense, sums, device=device)
+    main, art = SingleBatch.from_lps(L, sense, sums, device=device, **({"form": form} if form != "lds" else {}))
     made = [main] if art is None else [art, main]
     try:
         first = made[0]
