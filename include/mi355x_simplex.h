@@ -884,6 +884,31 @@ int  mi355x_sbatch_create_global(mi355x_sbatch **out, int64_t n_lps, int64_t row
 /* *form: 2 the members' tableaux in LDS, 3 the global form (continuing mi355x_stab_info: 1 pair, 2 LDS).  For form 3
  * mi355x_sbatch_info reports that form's workgroup, its dynamic LDS per member and its kernel's occupancy. */
 int  mi355x_sbatch_form(const mi355x_sbatch *b, int *form);
+/* The RAGGED form (opt-in): n_lps single-float tableaux of their OWN shapes and senses as one batch, for lists whose
+ * members would otherwise each be alone in a batch of one shape.  One workgroup still owns one member for its whole
+ * solve with the member's tableau in LDS, and the loop (n-solve-tableau, src/simplex.lisp:402-461) is the one of the
+ * batch of one shape; a round is ONE launch at the largest member's LDS size (measured faster than a launch per
+ * occupancy class; the classes stay behind mi355x_tune_set_sbatch_ragged_classes).
+ * rows[q], cols[q]: member q's shape; is_max[q] != 0: a `max` problem (NULL: every member is `min`, as the artificial
+ * batch of a pair is); matrices: the members' tight row-major tableaux one after the other; basis: their rows - 1
+ * entries one after the other.  MI_BAD_ARG: a NULL array, a member with rows < 1, cols < 2 or beyond
+ * mi355x_sbatch_create's limits; MI_UNSUPPORTED, naming the member: a member beyond the LDS budget
+ * (mi355x_sbatch_create's rule and budget).  Nothing is left behind on a failure.
+ * The handle is a mi355x_sbatch of form 4 (mi355x_sbatch_form): _solve, _solve_two_phase, _download, _trace, _cancel
+ * and _destroy work on it under the same member-by-member contract.  The sense is each member's own: is_max /
+ * main_is_max of a solve call must be -1 (anything else: MI_BAD_ARG).  A pair for _solve_two_phase is two form-4
+ * handles of equal n_lps on one device with, per member, equal rows and art cols >= main cols (else MI_BAD_ARG).
+ * mi355x_sbatch_info reports n_lps, rows = cols = ld = 0, the workgroup, the LARGEST member's lds_bytes_per_member
+ * and the SMALLEST class (the largest members') as members_per_cu.  mi355x_sbatch_readback, which gathers planes of one shape, answers
+ * MI_UNSUPPORTED on this form. */
+int  mi355x_sbatch_create_ragged(mi355x_sbatch **out, int64_t n_lps, const int64_t *rows, const int64_t *cols,
+                                 const int32_t *is_max, const float *matrices, const int64_t *basis, int device);
+/* member lp_index of a ragged batch: its shape, leading dimension in floats, sense (1 max, 0 min) and the workgroups
+ * resident per compute unit in the launch it goes in (its occupancy class, 1..4: by default the largest member's;
+ * under the classes hook the member's own).  On forms 2 and 3: the batch's one
+ * shape, *is_max = -1 (the sense is the solve call's) and members_per_cu.  Any pointer may be NULL. */
+int  mi355x_sbatch_member_shape(const mi355x_sbatch *b, int64_t lp_index, int64_t *rows, int64_t *cols, int64_t *ld,
+                                int32_t *is_max, int *occupancy_class);
 
 /* ---- single-float branch-and-bound (opt-in): node LPs assembled on the device ------------------
  * simplex-solver (src/simplex.lisp:462-542) on a problem whose numbers Lisp reads as integers and single-floats.

@@ -222,6 +222,14 @@ int         mi355x_stab_debug_update_time(mi355x_stab *h, int64_t entering_col, 
 int         mi355x_tune_set_sbatch_threads(int threads);
 int         mi355x_tune_set_sbatch_launch_cap(int cap);
 int         mi355x_tune_set_sbatch_global_threads(int threads);
+/* ragged batches (mi355x_sbatch_create_ragged), snapshotted per handle at create: 1 one class for all members -- one
+ * launch per round at the largest member's LDS size; 4 up to four occupancy classes (the workgroups resident per
+ * compute unit at the member's own LDS size, capped at 4), one launch per class and round, the class of the largest
+ * members first; 0 the default, which is one class: a launch per class was measured at half the rate of one launch
+ * on 256 members over all four classes, as the stream runs the classes one after the other
+ * (profiles/sbatch_ragged_rate.txt, part 4).  (The workgroup and the launch cap are _sbatch_threads' and
+ * _sbatch_launch_cap's.) */
+int         mi355x_tune_set_sbatch_ragged_classes(int classes);
 /* test aid: member lp_index of a single-float batch as it is STORED, padding columns included -- rows x ld floats;
  * *ld (may be NULL) = the leading dimension; out NULL: only *ld.  What a create entry left in the columns
  * [cols, ld) (mi355x_sbatch_create_lps writes them itself). */

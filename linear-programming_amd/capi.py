@@ -185,6 +185,8 @@ SIGNATURES = {
     "mi355x_sbatch_destroy": (None, [_p]),
     "mi355x_sbatch_create_global": (_int, [_pp, _i64, _i64, _i64, _p, _p, _int]),
     "mi355x_sbatch_form": (_int, [_p, _p]),
+    "mi355x_sbatch_create_ragged": (_int, [_pp, _i64, _p, _p, _p, _p, _p, _int]),
+    "mi355x_sbatch_member_shape": (_int, [_p, _i64, _p, _p, _p, _p, _p]),
     "mi355x_sbb_base_create": (_int, [_pp, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _int]),
     "mi355x_sbb_base_destroy": (None, [_p]),
     "mi355x_sbatch_create_nodes": (_int, [_pp, _pp, _p, _i64, _i64, _p, _p, _p]),
@@ -253,6 +255,7 @@ _EXTRA = {
     "mi355x_tune_set_sbatch_threads": (_int, [_int]),
     "mi355x_tune_set_sbatch_launch_cap": (_int, [_int]),
     "mi355x_tune_set_sbatch_global_threads": (_int, [_int]),
+    "mi355x_tune_set_sbatch_ragged_classes": (_int, [_int]),
     "mi355x_bb_debug_assemble": (_int, [_p, _i64, _i64, _p, _p, _p, _int, _p, _p, _p, _p, _p, _p, _p]),
 }
 

@@ -4,20 +4,25 @@
 // member: what a member ends with
 // -- status, pivot counts, trace, basis, every tableau entry -- is what mi355x_stab_solve / _solve_two_phase gives that
 // member alone under the same sequence of calls.  No double touches a tableau entry.
+// Form 4, the RAGGED batch (capi_single_ragged.inc makes it): every member its own shape and sense, the same entries.
 // Part of simplex_capi.hip (ONE translation unit: included there, in this order).
 
 namespace {
 int g_sbatch_threads = 0;                 // tuning / test hook: 0 auto (sbatch_threads_for), 256 or 1024
 int g_sbatch_launch_cap = 0;              // tuning / test hook: 0 = the form's default, else pivots per member and launch
 int g_sbatch_global_threads = 0;          // tuning / test hook, global form: 0 auto (sgbatch_threads_for), 256 or 1024
-constexpr int kSbFormLds = 2, kSbFormGlobal = 3;     // (continuing mi355x_stab_info's numbering: 1 pair, 2 LDS)
+int g_sbatch_ragged_classes = 0;          // tuning / test hook, ragged batches: 0 the default (one class), 1 one class, 4 up to four
+constexpr int kSbFormLds = 2, kSbFormGlobal = 3, kSbFormRagged = 4;   // (continuing mi355x_stab_info's numbering: 1 pair, 2 LDS)
+// an occupancy class of a ragged batch: `count` member indices from d_index + first, launched with `lds` bytes (the
+// class's largest member's) at `per_cu` resident workgroups per compute unit
+struct SrClass { int64_t first, count; size_t lds; int per_cu; };
 }  // namespace
 
 struct mi355x_sbatch {
     int         device = 0;
     SbView      v{};
     hipStream_t stream = nullptr;
-    int         form = 2;                 // 2: the member's tableau in LDS (k_sb_solve), 3: in HBM (k_sg_solve)
+    int         form = 2;                 // 2: the member's tableau in LDS (k_sb_solve), 3: in HBM (k_sg_solve), 4: ragged (k_sr_solve)
     int         threads = 0;              // snapshot of the form's rule (or its hook) at create
     int         launch_cap = kSingleLaunchCap;
     int         members_per_cu = 0;       // hipOccupancyMaxActiveBlocksPerMultiprocessor of the form's solve kernel at this shape
@@ -26,6 +31,14 @@ struct mi355x_sbatch {
     std::vector<Ctl>     h;               // the control blocks as the last read-back left them
     std::vector<int32_t> h_phase;
     std::atomic<int> cancel{0};
+    // form 4 only (v keeps M, basis, ctl, the traces and n_lps; its rows, cols, ld and stride are 0)
+    SrView      r{};
+    SrMember   *d_members = nullptr;      // r.members
+    int32_t    *d_index = nullptr;        // the classes' member lists, one after the other
+    size_t      lds_max = 0;              // the largest member's single_lds_bytes
+    std::vector<SrMember> hm;             // the descriptors, host copy
+    std::vector<int>      member_class;   // per member: index into classes
+    std::vector<SrClass>  classes;        // the class of the largest members first
 };
 
 namespace {
@@ -42,6 +55,8 @@ void free_sbatch(mi355x_sbatch *b)
     (void)hipFree(b->v.trace_cr);
     (void)hipFree(b->d_phase);
     (void)hipFree(b->rb);
+    (void)hipFree(b->d_members);
+    (void)hipFree(b->d_index);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }
@@ -137,11 +152,35 @@ hipError_t sb_fresh_ctl(mi355x_sbatch *b)
     return e;
 }
 
-// the form's solve kernel on every member the gate lets run
+// the form's solve kernel on every member the gate lets run (form 4: one launch per occupancy class, the members'
+// own senses)
 void sb_launch_solve(const mi355x_sbatch *b, int is_max, double f, const int32_t *gate, hipStream_t s)
 {
-    if (b->form == kSbFormGlobal) launch_sg_solve(b->v, b->threads, is_max, f, b->launch_cap, gate, s);
+    if (b->form == kSbFormRagged)
+        for (const SrClass &c : b->classes)                 // (one class holds every member: no list to go through)
+            launch_sr_solve(b->r, b->classes.size() == 1 ? nullptr : b->d_index + c.first, c.count, c.lds, b->threads, f,
+                            b->launch_cap, gate, s);
+    else if (b->form == kSbFormGlobal) launch_sg_solve(b->v, b->threads, is_max, f, b->launch_cap, gate, s);
     else launch_sb_solve(b->v, b->threads, is_max, f, b->launch_cap, gate, s);
+}
+
+// the form's step between the phases (form 4: one launch per class of the artificial batch)
+void sb_launch_between(const mi355x_sbatch *art, const mi355x_sbatch *mt, double f, int64_t max_pivots, hipStream_t s)
+{
+    if (art->form == kSbFormRagged)
+        for (const SrClass &c : art->classes)
+            launch_sr_between(art->r, mt->r, art->classes.size() == 1 ? nullptr : art->d_index + c.first, c.count, c.lds,
+                              art->threads, art->d_phase, f, max_pivots, s);
+    else if (art->form == kSbFormGlobal) launch_sg_between(art->v, mt->v, art->threads, art->d_phase, f, max_pivots, s);
+    else launch_sb_between(art->v, mt->v, art->threads, art->d_phase, f, max_pivots, s);
+}
+
+// a ragged batch carries its members' senses: the call's is_max must say so
+int sb_check_sense(const mi355x_sbatch *b, int is_max)
+{
+    if (b->form == kSbFormRagged && is_max != -1)
+        return fail(MI_BAD_ARG, "is_max=%d on a ragged batch (form 4): pass -1, the sense is each member's own", is_max);
+    return MI_OK;
 }
 
 // mi355x_sbatch_create / _create_global: the checks, the handle of the form, the upload
@@ -193,6 +232,15 @@ int mi355x_sbatch_info(const mi355x_sbatch *b, int64_t *n_lps, int64_t *rows, in
 {
     if (!b) return fail(MI_BAD_ARG, "handle is NULL");
     if (n_lps) *n_lps = b->v.n_lps;
+    if (b->form == kSbFormRagged) {                        // no one shape: 0; the largest member's LDS, the smallest class
+        if (rows) *rows = 0;
+        if (cols) *cols = 0;
+        if (ld) *ld = 0;
+        if (workgroup_threads) *workgroup_threads = b->threads;
+        if (lds_bytes_per_member) *lds_bytes_per_member = (int64_t)b->lds_max;
+        if (members_per_cu) *members_per_cu = b->members_per_cu;
+        return MI_OK;
+    }
     if (rows) *rows = b->v.rows;
     if (cols) *cols = b->v.cols;
     if (ld) *ld = b->v.ld;
@@ -216,6 +264,7 @@ int mi355x_sbatch_solve(mi355x_sbatch *b, int is_max, double f, int64_t max_pivo
 {
     if (!b) return fail(MI_BAD_ARG, "handle is NULL");
     if (max_pivots < 0) return fail(MI_BAD_ARG, "max_pivots < 0");
+    if (sb_check_sense(b, is_max) != MI_OK) return MI_BAD_ARG;
     HIP_TRY(hipSetDevice(b->device));
     const int64_t n = b->v.n_lps;
     std::vector<char> live((size_t)n);
@@ -253,6 +302,11 @@ int mi355x_sbatch_solve_two_phase(mi355x_sbatch *art, mi355x_sbatch *mt, int mai
     if (art->v.n_lps != mt->v.n_lps || art->v.rows != mt->v.rows || art->v.cols < mt->v.cols || art->device != mt->device)
         return fail(MI_BAD_ARG, "artificial and main batch do not match");
     if (art->form != mt->form) return fail(MI_BAD_ARG, "artificial and main batch are of different forms");
+    if (sb_check_sense(mt, main_is_max) != MI_OK) return MI_BAD_ARG;
+    if (art->form == kSbFormRagged)
+        for (int64_t q = 0; q < art->v.n_lps; ++q)
+            if (art->hm[q].rows != mt->hm[q].rows || art->hm[q].cols < mt->hm[q].cols)
+                return fail(MI_BAD_ARG, "artificial and main batch do not match at member %lld", (long long)q);
     if (art->form == kSbFormGlobal && sgbatch_between_lds_bytes(art->v) > kSingleLdsBudget)
         return fail(MI_UNSUPPORTED, "the step between the phases of a %lldx%lld artificial member does not fit the LDS "
                     "budget of %lld bytes", (long long)art->v.rows, (long long)art->v.cols, (long long)kSingleLdsBudget);
@@ -273,8 +327,7 @@ int mi355x_sbatch_solve_two_phase(mi355x_sbatch *art, mi355x_sbatch *mt, int mai
     for (;;) {
         if (phase1) {
             sb_launch_solve(art, /*is_max=*/0, f, nullptr, s);                                       // simplex.lisp:403
-            if (art->form == kSbFormGlobal) launch_sg_between(art->v, mt->v, art->threads, art->d_phase, f, max_pivots, s);
-            else launch_sb_between(art->v, mt->v, art->threads, art->d_phase, f, max_pivots, s);
+            sb_launch_between(art, mt, f, max_pivots, s);
         }
         sb_launch_solve(mt, main_is_max, f, art->d_phase, s);                                        // simplex.lisp:452
         HIP_TRY(hipGetLastError());
@@ -310,8 +363,14 @@ int mi355x_sbatch_download(mi355x_sbatch *b, int64_t q, float *hm, int64_t *hb, 
     if (q < 0 || q >= b->v.n_lps) return fail(MI_BAD_ARG, "lp_index %lld out of range [0,%lld)", (long long)q, (long long)b->v.n_lps);
     HIP_TRY(hipSetDevice(b->device));
     const SbView &v = b->v;
-    const int rc = download_parts(v.M + q * v.stride, v.ld, v.rows, v.cols, v.basis + q * (v.rows - 1), b->stream, hm, hb,
-                                  last_row, last_col);
+    int rc;
+    if (b->form == kSbFormRagged) {
+        const SrMember &d = b->hm[q];
+        rc = download_parts(v.M + d.m_off, d.ld, d.rows, d.cols, v.basis + d.basis_off, b->stream, hm, hb, last_row, last_col);
+    } else {
+        rc = download_parts(v.M + q * v.stride, v.ld, v.rows, v.cols, v.basis + q * (v.rows - 1), b->stream, hm, hb,
+                            last_row, last_col);
+    }
     if (rc != MI_OK) return rc;
     HIP_TRY(hipStreamSynchronize(b->stream));
     return MI_OK;

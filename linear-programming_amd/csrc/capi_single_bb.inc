@@ -236,6 +236,8 @@ int mi355x_sbatch_readback(mi355x_sbatch *b, float *rhs, float *obj_row, int64_t
 {
     if (!b) return fail(MI_BAD_ARG, "handle is NULL");
     if (!rhs || !obj_row) return fail(MI_BAD_ARG, "rhs or obj_row is NULL");
+    if (b->form == kSbFormRagged)
+        return fail(MI_UNSUPPORTED, "mi355x_sbatch_readback gathers planes of one shape: not on a ragged batch (form 4)");
     const SbView &v = b->v;
     if (v.rows > 1 && !basis) return fail(MI_BAD_ARG, "basis is NULL");
     HIP_TRY(hipSetDevice(b->device));

@@ -112,10 +112,12 @@ int mi355x_sbatch_debug_stored(mi355x_sbatch *b, int64_t k, float *out, int64_t 
     if (!b) return fail(MI_BAD_ARG, "handle is NULL");
     const SbView &v = b->v;
     if (k < 0 || k >= v.n_lps) return fail(MI_BAD_ARG, "lp_index %lld out of range", (long long)k);
-    if (ld) *ld = v.ld;
+    const bool ragged = b->form == kSbFormRagged;         // (the member's own ld and rows)
+    const int64_t m_off = ragged ? b->hm[k].m_off : k * v.stride, stored = ragged ? b->hm[k].rows * b->hm[k].ld : v.stride;
+    if (ld) *ld = ragged ? b->hm[k].ld : v.ld;
     if (!out) return MI_OK;
     HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipMemcpyAsync(out, v.M + k * v.stride, (size_t)v.stride * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(out, v.M + m_off, (size_t)stored * sizeof(float), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return MI_OK;
 }

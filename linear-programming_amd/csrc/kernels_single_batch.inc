@@ -57,14 +57,14 @@ __global__ __launch_bounds__(THREADS) void k_sb_solve(SbView b, float sgn, float
 // phase 2.  phase[2q] becomes 1 (handed over) or 2 (ended here, phase[2q+1] = MI_INFEASIBLE / MI_ART_NONZERO /
 // MI_ART_STUCK).  Dynamic LDS: a basic-column flag per main column, a row (pivot row, then the objective row) and the
 // column snapshot -- never more than the artificial shape's single_lds_bytes.
+// The body is sb_between_member: ONE copy, for a member of a batch of one shape (k_sb_between) and of a ragged batch
+// (k_sr_between, kernels_single_ragged.inc).  phase_q: the member's two entries of the pair's state.
 template <int THREADS>
-__global__ __launch_bounds__(THREADS) void k_sb_between(SbView ab, SbView mb, int32_t *phase, float feasible_tol, int64_t max_pivots)
+__device__ __forceinline__ void sb_between_member(const SView &a, const SView &mt, int32_t *phase_q, float feasible_tol,
+                                                  int64_t max_pivots)
 {
     extern __shared__ __attribute__((aligned(16))) float s_lds[];
     __shared__ int s_best;
-    const int64_t q = blockIdx.x;
-    if (phase[2 * q] != 0) return;
-    const SView a = sb_member(ab, q), mt = sb_member(mb, q);
     if (a.ctl->status != 0) return;
     const int rows = (int)a.rows, m = rows - 1, acols = (int)a.cols, nav = acols - 1, nv = (int)mt.cols - 1;
     const int ldl = (acols + 3) / 4 * 4;
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(THREADS) void k_sb_between(SbView ab, SbView mb, in
     const float art_obj = A[(int64_t)m * ald + nav];
     const float diff = 0.0f - art_obj;
     if (!((diff < 0.0f ? -diff : diff) <= feasible_tol)) {
-        if (tid == 0) { phase[2 * q] = 2; phase[2 * q + 1] = 2; }              // MI_INFEASIBLE
+        if (tid == 0) { phase_q[0] = 2; phase_q[1] = 2; }              // MI_INFEASIBLE
         return;
     }
     for (int j = tid; j < nv; j += THREADS) flag[j] = 0;
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(THREADS) void k_sb_between(SbView ab, SbView mb, in
         if (A[(int64_t)i * ald + nav] != 0.0f) {
             if (tid == 0) {
                 a.ctl->n_pivots = n; a.ctl->trace_n = trace_n;
-                phase[2 * q] = 2; phase[2 * q + 1] = 4;                         // MI_ART_NONZERO
+                phase_q[0] = 2; phase_q[1] = 4;                         // MI_ART_NONZERO
             }
             return;
         }
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(THREADS) void k_sb_between(SbView ab, SbView mb, in
         if (ec >= nv) {
             if (tid == 0) {
                 a.ctl->n_pivots = n; a.ctl->trace_n = trace_n;
-                phase[2 * q] = 2; phase[2 * q + 1] = 5;                         // MI_ART_STUCK
+                phase_q[0] = 2; phase_q[1] = 5;                         // MI_ART_STUCK
             }
             return;
         }
@@ -165,8 +165,15 @@ __global__ __launch_bounds__(THREADS) void k_sb_between(SbView ab, SbView mb, in
         mc->n_pivots = 0;
         if (max_pivots > 0 && n >= max_pivots) { mc->status = 3; mc->max_pivots = max_pivots; }
         else { mc->status = kRunning; mc->max_pivots = max_pivots > 0 ? max_pivots - n : 0; }
-        phase[2 * q] = 1; phase[2 * q + 1] = 0;
+        phase_q[0] = 1; phase_q[1] = 0;
     }
+}
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_sb_between(SbView ab, SbView mb, int32_t *phase, float feasible_tol, int64_t max_pivots)
+{
+    const int64_t q = blockIdx.x;
+    if (phase[2 * q] != 0) return;
+    sb_between_member<THREADS>(sb_member(ab, q), sb_member(mb, q), phase + 2 * q, feasible_tol, max_pivots);
 }
 
 // ------------------------------------------------------------------ host-side launchers

@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -209,6 +210,7 @@ struct mi355x_multibatch {
 #include "capi_colpart.inc"    // mi355x_colpart_*, mi355x_rccl_unique_id
 #include "capi_single.inc"     // mi355x_stab_*: single-float tableaux (the reference's single-float path)
 #include "capi_single_batch.inc"  // mi355x_sbatch_*: batches of single-float LPs, one workgroup per member
+#include "capi_single_ragged.inc"  // mi355x_sbatch_create_ragged / _member_shape: members of mixed shapes and senses as one batch
 #include "capi_single_bb.inc"  // mi355x_sbb_base_*, mi355x_sbatch_create_nodes / _readback: single-float branch-and-bound
 #include "capi_single_lps.inc"  // mi355x_sbatch_create_lps: single-float batches built from problem rows on the device
 #include "capi_tune.inc"      // mi355x_tune_*, mi355x_debug_*

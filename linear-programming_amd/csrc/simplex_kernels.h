@@ -561,6 +561,28 @@ void launch_sb_begin(const SbView &b, int64_t max_pivots, const int32_t *phase, 
 void launch_sb_solve(const SbView &b, int threads, int is_max, double fp_factor, int cap, const int32_t *gate, hipStream_t s);
 void launch_sb_between(const SbView &art, const SbView &main_b, int threads, int32_t *phase, double fp_factor,
                        int64_t max_pivots, hipStream_t s);
+// RAGGED batches of single-float tableaux (kernels_single_ragged.inc, capi_single_ragged.inc): every member its own
+// shape and sense, one workgroup per member, the loop and the step between the phases those of the batch of one shape
+// (src/simplex.lisp:402-461).  Member q: tableau at M + m_off floats (rows x ld, ld = cols rounded up to 32 floats, so
+// every m_off is a multiple of 32 and the 16-byte quad loads of s_solve_in_lds stay aligned), basis at basis +
+// basis_off, control block ctl + q, trace at trace_ec / trace_cr + q * trace_cap; sgn: +1 max, -1 min.
+struct SrMember { int64_t m_off, basis_off, ld, rows, cols; float sgn; };
+struct SrView {
+    float          *M;
+    int64_t        *basis;
+    Ctl            *ctl;
+    int64_t        *trace_ec, *trace_cr;
+    int64_t         trace_cap, n_lps;
+    const SrMember *members;              // n_lps descriptors (device)
+};
+bool   sragged_raise(int threads);                                           // the two kernels' dynamic-LDS attribute
+bool   sragged_occupancy(int threads, size_t lds, int *members_per_cu);      // k_sr_solve's residency at this LDS size
+// one occupancy class: `count` member indices at `members` (device; nullptr: members 0 .. count - 1), lds: the
+// class's largest member's bytes
+void launch_sr_solve(const SrView &b, const int32_t *members, int64_t count, size_t lds, int threads, double fp_factor,
+                     int cap, const int32_t *gate, hipStream_t s);
+void launch_sr_between(const SrView &art, const SrView &main_b, const int32_t *members, int64_t count, size_t lds,
+                       int threads, int32_t *phase, double fp_factor, int64_t max_pivots, hipStream_t s);
 // The global form of a single-float batch (kernels_single_global.inc): one workgroup per member, the tableau in HBM,
 // pivot row and column snapshot in LDS -- for members beyond the LDS budget.
 size_t sgbatch_lds_bytes(const SbView &b);                                  // k_sg_solve's dynamic LDS

@@ -109,6 +109,7 @@ namespace mi355x {
 #include "kernels_launch.inc"
 #include "kernels_single.inc"
 #include "kernels_single_batch.inc"
+#include "kernels_single_ragged.inc"
 #include "kernels_single_global.inc"
 #include "kernels_single_bb.inc"
 #include "kernels_single_lps.inc"

@@ -626,7 +626,7 @@ simplex_solver = mi355x_simplex_solver
 
 def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_pivots=0, errorp=True, native=False,
                           exact=False, exact_bits=0, exact_max_bits=128, pivot_rule="dantzig", device_build=False,
-                          from_rows=False, precision="double", beyond_lds=False):
+                          from_rows=False, precision="double", beyond_lds=False, mixed_shapes=False):
     """The glue's `mi355x-solve-problems`: a LIST of problems -> the list of their solved tableaus,
     what [solve_problem(p) for p in problems] returns, with the independent LPs side by side on the
     GPU(s).  Single-phase problems are grouped by tableau shape and sense; a group of two or more
@@ -676,12 +676,20 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
     beyond_lds=True (opt-in, with precision="single" only -- an argument error otherwise): a group beyond the batch's
     LDS budget with at least single.global_batch_min_members(rows, cols) members is ONE global-form batch (one
     workgroup per member, the member's tableau left in device memory: mi355x_sbatch_create_global) instead of going
-    one by one; every member comes back as the same SingleTableau, bit for bit."""
+    one by one; every member comes back as the same SingleTableau, bit for bit.
+    mixed_shapes=True (opt-in, with precision="single" only -- an argument error otherwise): the members are NOT
+    grouped by shape and sense; all single-phase members inside the LDS budget are ONE ragged batch
+    (mi355x_sbatch_create_ragged: every member its own shape and sense) and all two-phase members ONE ragged pair,
+    two or more members each.  Members beyond the budget and integer problems go as without the keyword; every
+    member comes back as the same SingleTableau, bit for bit."""
     if precision not in ("double", "single"):
         raise ValueError("precision=%r: \"double\" (default) or \"single\"" % (precision,))
     if beyond_lds and precision != "single":
         raise ValueError("beyond_lds=True needs precision=\"single\": it batches the single-float members beyond the "
                          "LDS budget")
+    if mixed_shapes and precision != "single":
+        raise ValueError("mixed_shapes=True needs precision=\"single\": it batches the single-float members of "
+                         "different shapes and senses")
     if precision == "single":
         given = {"exact": exact, "native": native, "from_rows": from_rows, "device_build": device_build,
                  "devices": devices, "pivot_rule": pivot_rule}
@@ -693,6 +701,8 @@ def mi355x_solve_problems(problems, fp_tolerance=1024, device=0, devices=1, max_
                                  "under the reference's rule" % (name, given[name]))
         from .single import solve_problems_single
         kw = {"beyond_lds": True} if beyond_lds else {}                    # (the default: the call as it was)
+        if mixed_shapes:
+            kw["mixed_shapes"] = True
         return solve_problems_single(problems, fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots,
                                      errorp=errorp, **kw)
     from .exact import pivot_rule_code

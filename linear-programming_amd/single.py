@@ -261,8 +261,10 @@ class SingleBatch:
     memory (form "global").  Member by member the result is what the member's own SingleTableau gives under the same
     sequence of calls."""
 
-    def __init__(self, handle, n_lps, rows, cols):
+    def __init__(self, handle, n_lps, rows, cols, ragged=False):
         self._handle, self.n_lps, self.rows, self.cols = handle, int(n_lps), int(rows), int(cols)
+        #: a ragged batch (from_ragged): every member its own shape and sense; rows, cols: the largest member's
+        self.ragged = bool(ragged)
 
     @classmethod
     def from_arrays(cls, matrices, basis, device=0, form="lds"):
@@ -322,10 +324,57 @@ class SingleBatch:
         cols = ncv + (m - n_eq) + 1
         return cls(hm, n, m + 1, cols), (cls(ha, n, m + 1, cols + n_art) if ha else None)
 
+    @classmethod
+    def from_ragged(cls, matrices, bases, is_max, device=0):
+        """mi355x_sbatch_create_ragged: ONE batch of members of different shapes and senses.  matrices: a list of
+        float32 arrays [rows_q, cols_q]; bases: a list of int64 arrays [rows_q - 1]; is_max: a list of truth values,
+        or None when every member is a `min` problem (the artificial batch of a pair).  A member beyond the LDS budget
+        raises capi.Mi355xError with code MI_UNSUPPORTED; the message names the member."""
+        Ms = [np.asarray(M) for M in matrices]
+        if not Ms:
+            raise ValueError("a ragged batch needs at least one member")
+        if len(bases) != len(Ms):
+            raise ValueError("%d bases for %d matrices" % (len(bases), len(Ms)))
+        if is_max is not None and len(is_max) != len(Ms):
+            raise ValueError("%d senses for %d matrices" % (len(is_max), len(Ms)))
+        bs = []
+        for q, (M, b) in enumerate(zip(Ms, bases)):
+            if M.dtype != np.float32:
+                raise TypeError("a SingleBatch takes float32 matrices, not %s (member %d)" % (M.dtype, q))
+            if M.ndim != 2 or M.shape[0] < 1 or M.shape[1] < 2:
+                raise ValueError("member %d must be [rows >= 1, cols >= 2], not %r" % (q, M.shape))
+            b = np.ascontiguousarray(b, dtype=np.int64)
+            if b.shape != (M.shape[0] - 1,):
+                raise ValueError("member %d: basis shape %r does not match [rows - 1] = %r" % (q, b.shape, (M.shape[0] - 1,)))
+            bs.append(b)
+        rows = np.array([M.shape[0] for M in Ms], dtype=np.int64)
+        cols = np.array([M.shape[1] for M in Ms], dtype=np.int64)
+        flat = np.concatenate([np.ascontiguousarray(M).ravel() for M in Ms])
+        basis = np.concatenate(bs)
+        sense = None if is_max is None else np.array([1 if x else 0 for x in is_max], dtype=np.int32)
+        h = ctypes.c_void_p()
+        capi.check(capi.lib().mi355x_sbatch_create_ragged(
+            ctypes.byref(h), len(Ms), _ptr(rows), _ptr(cols), _ptr(sense) if sense is not None else None, _ptr(flat),
+            _ptr(basis) if basis.size else None, int(device)), "mi355x_sbatch_create_ragged")
+        big = int(np.argmax(rows * cols))
+        return cls(h, len(Ms), rows[big], cols[big], ragged=True)
+
+    def member_shape(self, q):
+        """mi355x_sbatch_member_shape: {"rows", "cols", "ld", "is_max" (1, 0; -1 on a batch of one shape: the sense is
+        the call's), "occupancy_class" (workgroups resident per compute unit in the launch the member goes in)}."""
+        r, c, ld = (ctypes.c_int64() for _ in range(3))
+        sense, cl = ctypes.c_int32(), ctypes.c_int()
+        capi.check(capi.lib().mi355x_sbatch_member_shape(self._handle, int(q), ctypes.byref(r), ctypes.byref(c),
+                                                         ctypes.byref(ld), ctypes.byref(sense), ctypes.byref(cl)),
+                   "mi355x_sbatch_member_shape")
+        return {"rows": r.value, "cols": c.value, "ld": ld.value, "is_max": sense.value, "occupancy_class": cl.value}
+
     def solve(self, is_max, fp_tolerance=1024, max_pivots=0):
         """-> (status[n] int32, n_pivots[n] int64) of this call; self.last_return is what the call itself returned
-        (MI_OK, or MI_CANCELLED after cancel(): the unfinished members are MI_RUNNING and the next call carries them on)."""
+        (MI_OK, or MI_CANCELLED after cancel(): the unfinished members are MI_RUNNING and the next call carries them on).
+        A ragged batch passes -1 for the sense: it is each member's own."""
         st, npv = np.empty(self.n_lps, dtype=np.int32), np.empty(self.n_lps, dtype=np.int64)
+        is_max = -1 if self.ragged else is_max
         rc = capi.check(capi.lib().mi355x_sbatch_solve(self._handle, int(is_max), float(fp_tolerance), int(max_pivots),
                                                        _ptr(st), _ptr(npv)), "mi355x_sbatch_solve")
         self.last_return = rc
@@ -334,6 +383,7 @@ class SingleBatch:
     def solve_two_phase(self, main, main_is_max, fp_tolerance=1024, max_pivots=0):
         """self: the batch of artificial tableaux.  -> (status[n], n_pivots[n, 2]: phase 1 + drive-outs, phase 2)."""
         st, npv = np.empty(self.n_lps, dtype=np.int32), np.empty((self.n_lps, 2), dtype=np.int64)
+        main_is_max = -1 if main.ragged else main_is_max                    # (a ragged batch: the members' own senses)
         rc = capi.check(capi.lib().mi355x_sbatch_solve_two_phase(self._handle, main._handle, int(main_is_max),
                                                                  float(fp_tolerance), int(max_pivots), _ptr(st), _ptr(npv)),
                         "mi355x_sbatch_solve_two_phase")
@@ -341,8 +391,12 @@ class SingleBatch:
         return st, npv
 
     def download(self, q):
-        """Member q: (matrix float32 [rows, cols], basis int64 [rows - 1])."""
-        M, b = np.empty((self.rows, self.cols), dtype=np.float32), np.empty(self.rows - 1, dtype=np.int64)
+        """Member q: (matrix float32 [rows, cols], basis int64 [rows - 1]); on a ragged batch the member's own shape."""
+        rows, cols = self.rows, self.cols
+        if self.ragged:
+            shape = self.member_shape(q)
+            rows, cols = shape["rows"], shape["cols"]
+        M, b = np.empty((rows, cols), dtype=np.float32), np.empty(rows - 1, dtype=np.int64)
         capi.check(capi.lib().mi355x_sbatch_download(self._handle, int(q), _ptr(M), _ptr(b) if b.size else None, None, None),
                    "mi355x_sbatch_download")
         return M, b
@@ -359,7 +413,8 @@ class SingleBatch:
 
     def info(self):
         """mi355x_sbatch_info: {"n_lps", "rows", "cols", "ld", "workgroup_threads", "lds_bytes_per_member",
-        "members_per_cu", "form" (mi355x_sbatch_form: 2 LDS, 3 global)}."""
+        "members_per_cu", "form" (mi355x_sbatch_form: 2 LDS, 3 global, 4 ragged: rows = cols = ld = 0, the largest
+        member's LDS bytes, the smallest occupancy class)}."""
         n, r, c, ld, lds = (ctypes.c_int64() for _ in range(5))
         thr, per_cu, form = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         capi.check(capi.lib().mi355x_sbatch_info(self._handle, ctypes.byref(n), ctypes.byref(r), ctypes.byref(c),
@@ -399,6 +454,22 @@ def set_batch_global_threads(threads):
     """mi355x_tune_set_sbatch_global_threads (tests and measurement): 0 auto, 256 or 1024 for global-form batches
     created from now on."""
     capi.check(capi.lib().mi355x_tune_set_sbatch_global_threads(int(threads)), "mi355x_tune_set_sbatch_global_threads")
+
+
+def set_batch_ragged_classes(classes):
+    """mi355x_tune_set_sbatch_ragged_classes (tests and measurement): 0 the default (one class: the measured choice),
+    1 one class for all members, 4 up to four occupancy classes, for ragged batches created from now on."""
+    capi.check(capi.lib().mi355x_tune_set_sbatch_ragged_classes(int(classes)), "mi355x_tune_set_sbatch_ragged_classes")
+
+
+#: the LDS budget of the single-float LDS forms (kSingleLdsBudget) and a member's dynamic LDS (single_lds_bytes):
+#: the stored tableau with rows of whole quads, the pivot row, the column snapshot rounded up to a quad
+LDS_BUDGET = 156 * 1024
+
+
+def single_lds_bytes(rows, cols):
+    ldl, rp = (int(cols) + 3) // 4 * 4, (int(rows) + 3) // 4 * 4
+    return (int(rows) * ldl + ldl + rp) * 4
 
 
 #: tests: a number here replaces global_batch_min_members' answer for every shape
@@ -469,14 +540,48 @@ def solve_made_batches(made, is_max, take, fp_tolerance=1024, max_pivots=0, chun
             b.close()
 
 
+#: mixed_shapes=True: a (shape, sense) group of at least this many members stays a batch of ONE shape instead of
+#: joining the ragged batch; None: every member goes ragged.  Read off profiles/sbatch_ragged_rate.txt, part 1 (DESIGN
+#: 4.6m): at 256 members the ragged batch is 0.999 / 0.994 / 0.986 of the uniform batch at 24 x 40 / 61 x 97 / 96 x 300,
+#: and at 61 x 97 that is 0.2 % below the uniform figure's own smallest run, so groups from some count on stay uniform.
+#: The count: rows of 16 to 1024 members are 0.97-1.02 and move by 1-3 % from one run of the tool to the next (61 x 97
+#: at 256 was 0.985-0.994 in the last three runs), which is no more than a second batch costs -- part 2 has 16 batches
+#: of one shape at 0.62 of the one ragged batch.  The one row beyond that drift, in every run, is 4096 members of
+#: 24 x 40 at 0.90: groups of at least 4096 members stay batches of one shape.
+RAGGED_UNIFORM_MIN_MEMBERS = 4096
+
+
+def take_for_ragged(groups, art_shape=False):
+    """Takes out of groups (file_by_shape's) the members that go as ONE ragged batch under mixed_shapes=True: those
+    inside the LDS budget (for two-phase members: the artificial shape, the larger of the two), except the groups
+    RAGGED_UNIFORM_MIN_MEMBERS keeps as batches of one shape.  -> the members in list order; fewer than two are put
+    back, as a batch of one member gains nothing."""
+    taken = {}
+    for key, members in list(groups.items()):
+        rows, cols = key[0]                                   # (shape, is_max) or (art shape, main shape, is_max)
+        if single_lds_bytes(rows, cols) > LDS_BUDGET:
+            continue
+        if RAGGED_UNIFORM_MIN_MEMBERS is not None and len(members) >= RAGGED_UNIFORM_MIN_MEMBERS:
+            continue
+        taken[key] = groups.pop(key)
+    if sum(len(v) for v in taken.values()) < 2:
+        groups.update(taken)
+        return []
+    return sorted((m for v in taken.values() for m in v), key=lambda m: m[0])
+
+
 def solve_problems_single(problems, fp_tolerance=1024, device=0, max_pivots=0, errorp=True, chunk=None,
-                          beyond_lds=False):
+                          beyond_lds=False, mixed_shapes=False):
     """mi355x_solve_problems(..., precision="single"): what [solve_single(p) for p in problems] returns, the groups
     of two or more as ONE SingleBatch (or a pair of them) in bounded chunks.  Members alone in their group, shapes
     the batch declines and integer problems go through solve_single one by one.
     beyond_lds=True (opt-in): a group the LDS batch declines that has at least global_batch_min_members(rows, cols)
     members (for two-phase members: of the artificial shape) goes as ONE global-form batch (or a pair of them)
-    instead of one by one; the results are the same, bit for bit."""
+    instead of one by one; the results are the same, bit for bit.
+    mixed_shapes=True (opt-in): the members inside the LDS budget are not grouped by shape and sense -- all
+    single-phase ones go as ONE ragged batch, all two-phase ones as ONE ragged pair (SingleBatch.from_ragged), two
+    or more members each, in bounded chunks sized by the largest member; everything else goes as above, and the
+    results are the same, bit for bit."""
     results = [None] * len(problems)
     slots, groups, groups2 = group_single_problems(problems, fp_tolerance, device)
 
@@ -510,6 +615,23 @@ def solve_problems_single(problems, fp_tolerance=1024, device=0, max_pivots=0, e
             lists.one_by_one(results, [k], alone)
         elif s is not None:
             results[k] = s
+    if mixed_shapes:
+        for members in (take_for_ragged(groups), take_for_ragged(groups2)):
+            if not members:
+                continue
+            ks, firsts, mains = [m[0] for m in members], [m[1] for m in members], [m[-1] for m in members]
+            senses = [t.is_max for t in mains]
+            made = [SingleBatch.from_ragged([t.matrix for t in mains], [t.basis_columns for t in mains], senses,
+                                            device=device)]
+            if len(members[0]) == 3:
+                try:
+                    made.insert(0, SingleBatch.from_ragged([t.matrix for t in firsts], [t.basis_columns for t in firsts],
+                                                           None, device=device))
+                except BaseException:
+                    made[0].close()
+                    raise
+            lists.place(results, ks, solve_made_batches(made, -1, lambda sb, q, n, mains=mains: adopt(mains[q], sb, q, n),
+                                                        fp_tolerance, max_pivots, chunk))
     # a group of two or more is one batch, or for two-phase members a batch of artificial and one of main tableaux
     for members in [*groups.values(), *groups2.values()]:
         ks, firsts, mains = [m[0] for m in members], [m[1] for m in members], [m[-1] for m in members]
