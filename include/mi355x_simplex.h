@@ -996,6 +996,40 @@ int  mi355x_sbatch_create_lps_global(mi355x_sbatch **out_main, mi355x_sbatch **o
                                      int64_t ncv, const float *lps, const int32_t *sense, const double *col_int_sum,
                                      int device);
 
+/* ---- ragged single-float batches built on the device (opt-in): rows and nodes of mixed shapes ----
+ * mi355x_sbatch_create_ragged's form-4 handles, with the tableaux written by the device as for mi355x_sbatch_create_lps
+ * and mi355x_sbatch_create_nodes -- the same rules, the same zero of a negated row, the same 2^24 guard, bit for bit --
+ * but every member with a shape (and, from rows, a sense) of its own: one create for a list that those entries
+ * would take one group at a time.  _solve, _solve_two_phase (sense -1), _download, _trace, _cancel, _destroy and
+ * _member_shape work on the handles unchanged.
+ * ALL OR NONE: either no member has artificial rows, and *out_art = NULL, or every member has at least one -- the counts
+ * may differ from member to member -- and the result is a ragged pair.  A mixture is MI_BAD_ARG naming the first member
+ * that differs; the caller splits its list.
+ * create_lps_ragged: m[q], ncv[q], is_max[q] per member; lps: the members' (m + 1) x (ncv + 1) rows, tight, one after
+ * the other; sense: their m senses one after the other; col_int_sum: their ncv + 1 sums one after the other, or NULL.
+ * MI_BAD_ARG, before any device is looked for: a NULL array, m or ncv < 1, a sense outside 0..2, the mixture.
+ * MI_UNSUPPORTED, naming the member, before anything is allocated: the guard, and a member whose tableau -- for a
+ * member with artificial rows its ARTIFICIAL tableau -- is beyond the LDS budget (mi355x_sbatch_create's rule).  Any
+ * later failure frees both handles. */
+int  mi355x_sbatch_create_lps_ragged(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n_lps, const int64_t *m,
+                                     const int64_t *ncv, const int32_t *is_max, const float *lps, const int32_t *sense,
+                                     const double *col_int_sum, int device);
+/* A form-4 handle carries its members' senses, and every node has the base problem's: say it once per base (0 min,
+ * 1 max) before the first mi355x_sbatch_create_nodes_ragged (which answers MI_BAD_ARG without it).  The entries that
+ * take the sense with the solve call do not read it.  The call writes into the base without a lock: make it before
+ * the base is shared between threads, not beside a create on another thread. */
+int  mi355x_sbb_base_set_sense(mi355x_sbb_base *base, int is_max);
+/* create_nodes_ragged: depth[q] rows per node, the nodes' rows one after the other in var / sense / bound, newest row
+ * first per node.  With a base that has artificial rows every node is two-phase.  The argument checks, the guard, the
+ * assembly's LDS limit and the batch's budget are mi355x_sbatch_create_nodes', per node, the node named. */
+int  mi355x_sbatch_create_nodes_ragged(mi355x_sbatch **out_main, mi355x_sbatch **out_art, const mi355x_sbb_base *base,
+                                       int64_t n_nodes, const int64_t *depth, const int64_t *var, const int32_t *sense,
+                                       const int64_t *bound);
+/* mi355x_sbatch_readback for a ragged batch (form 4; MI_UNSUPPORTED on forms 2 and 3: call mi355x_sbatch_readback):
+ * per member the last column, the last row and the basis into three concatenated planes -- member q's values at the
+ * sums of rows, of cols and of rows - 1 over the members before it.  One gather launch and one copy. */
+int  mi355x_sbatch_readback_ragged(mi355x_sbatch *b, float *rhs, float *obj_row, int64_t *basis);
+
 #ifdef __cplusplus
 }
 #endif

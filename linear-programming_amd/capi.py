@@ -194,6 +194,10 @@ SIGNATURES = {
     "mi355x_sbatch_readback": (_int, [_p, _p, _p, _p]),
     "mi355x_sbatch_create_lps": (_int, [_pp, _pp, _i64, _i64, _i64, _p, _p, _p, _int]),
     "mi355x_sbatch_create_lps_global": (_int, [_pp, _pp, _i64, _i64, _i64, _p, _p, _p, _int]),
+    "mi355x_sbatch_create_lps_ragged": (_int, [_pp, _pp, _i64, _p, _p, _p, _p, _p, _p, _int]),
+    "mi355x_sbb_base_set_sense": (_int, [_p, _int]),
+    "mi355x_sbatch_create_nodes_ragged": (_int, [_pp, _pp, _p, _i64, _p, _p, _p, _p]),
+    "mi355x_sbatch_readback_ragged": (_int, [_p, _p, _p, _p]),
 }
 # tuning / measurement / test hooks: include/mi355x_simplex_tune.h (not the drop-in boundary)
 _EXTRA = {

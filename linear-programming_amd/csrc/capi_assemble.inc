@@ -5,6 +5,23 @@
 
 namespace {
 
+// one member's part of lps_check (and of the ragged create, whose members have shapes of their own): its rows
+// (m + 1) x (ncv + 1) and m senses -> its `=` rows and its artificial rows (:243-252)
+template <class T>
+int lps_member_counts(int64_t q, int64_t m, int64_t ncv, const T *rows, const int32_t *sense, int64_t *n_eq, int64_t *n_art)
+{
+    const int64_t W = ncv + 1;
+    int64_t e = 0, a = 0;
+    for (int64_t i = 0; i < m; ++i) {
+        const int32_t s = sense[i];
+        if (s < 0 || s > 2) return fail(MI_BAD_ARG, "member %lld: sense %d of row %lld", (long long)q, (int)s, (long long)i);
+        e += s == 2;
+        a += row_word_artificial(row_word(rows[i * W + ncv] < T(0), s));            // :243-252
+    }
+    *n_eq = e; *n_art = a;
+    return MI_OK;
+}
+
 // the argument checks of the create-from-rows entries (no device is looked for): the numbers of `=` rows and of
 // artificial rows every member has.  O(m) per member: only the signs of the right-hand sides are read (T: double,
 // float, or the numerators of reduced fractions).  max_lps_log2: the entry's limit on n_lps (0: none).
@@ -19,16 +36,12 @@ int lps_check(int64_t n_lps, int max_lps_log2, int64_t m, int64_t ncv, const T *
         return fail(MI_BAD_ARG, "n_lps=%lld must be in [1, 2^%d]", (long long)n_lps, max_lps_log2);
     if (m < 1 || ncv < 1) return fail(MI_BAD_ARG, "m=%lld ncv=%lld must be >= 1", (long long)m, (long long)ncv);
     if (m > (1 << 24) || ncv > (1 << 24)) return fail(MI_BAD_ARG, "m=%lld ncv=%lld out of range", (long long)m, (long long)ncv);
-    const int64_t W = ncv + 1, per = (m + 1) * W;
+    const int64_t per = (m + 1) * (ncv + 1);
     int64_t n_eq = -1, n_art = -1;
     for (int64_t q = 0; q < n_lps; ++q) {
         int64_t e = 0, a = 0;
-        for (int64_t i = 0; i < m; ++i) {
-            const int32_t s = sense[q * m + i];
-            if (s < 0 || s > 2) return fail(MI_BAD_ARG, "member %lld: sense %d of row %lld", (long long)q, (int)s, (long long)i);
-            e += s == 2;
-            a += row_word_artificial(row_word(lps[q * per + i * W + ncv] < T(0), s));     // :243-252
-        }
+        const int rc = lps_member_counts(q, m, ncv, lps + q * per, sense + q * m, &e, &a);
+        if (rc != MI_OK) return rc;
         if (n_eq >= 0 && (e != n_eq || a != n_art))
             return fail(MI_BAD_ARG, "member %lld has %lld `=` and %lld artificial rows, the members before it %lld and %lld",
                         (long long)q, (long long)e, (long long)a, (long long)n_eq, (long long)n_art);

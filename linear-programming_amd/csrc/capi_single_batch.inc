@@ -36,6 +36,8 @@ struct mi355x_sbatch {
     SrMember   *d_members = nullptr;      // r.members
     int32_t    *d_index = nullptr;        // the classes' member lists, one after the other
     size_t      lds_max = 0;              // the largest member's single_lds_bytes
+    int64_t     m_total = 0;              // floats of all members as stored
+    int64_t    *d_col_off = nullptr;      // mi355x_sbatch_readback_ragged: per member the columns of the members before it
     std::vector<SrMember> hm;             // the descriptors, host copy
     std::vector<int>      member_class;   // per member: index into classes
     std::vector<SrClass>  classes;        // the class of the largest members first
@@ -57,6 +59,7 @@ void free_sbatch(mi355x_sbatch *b)
     (void)hipFree(b->rb);
     (void)hipFree(b->d_members);
     (void)hipFree(b->d_index);
+    (void)hipFree(b->d_col_off);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
 }

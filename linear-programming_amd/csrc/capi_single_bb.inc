@@ -16,6 +16,7 @@
 struct SbbBase {
     int      device = 0;
     int64_t  rows = 0, cols = 0, ncv = 0, nb = 0, n_vars = 0, n_art = 0;
+    int      is_max = -1;             // mi355x_sbb_base_set_sense (ragged node batches carry the sense per member); -1: not said
     std::vector<int64_t> vcol;
     std::vector<int32_t> kind;
     std::vector<float>   off;
@@ -135,9 +136,53 @@ int mi355x_sbb_base_create(mi355x_sbb_base **out, int64_t rows, int64_t cols, co
 
 void mi355x_sbb_base_destroy(mi355x_sbb_base *base) { delete base; }
 
+int mi355x_sbb_base_set_sense(mi355x_sbb_base *base, int is_max)
+{
+    if (!base) return fail(MI_BAD_ARG, "base is NULL");
+    if (is_max != 0 && is_max != 1) return fail(MI_BAD_ARG, "is_max=%d must be 0 (min) or 1 (max)", is_max);
+    base->p->is_max = is_max;
+    return MI_OK;
+}
+
 }  // extern "C"
 
 namespace {
+
+// one node's rows [k0, k0 + depth) of var / sense / bound: the argument check, *n_art its artificial rows with the
+// base's, and the guard -- this node's integer entries on top of the base's, column by column (extra: one zero per
+// base column, left as it was found); *exact_sums is cleared where a column goes beyond 2^24
+int sbb_node_check(const SbbBase &b, int64_t k0, int64_t depth, const int64_t *var, const int32_t *sense, const int64_t *bound,
+                   std::vector<double> &extra, int64_t *n_art, bool *exact)
+{
+    bool exact_sums = *exact;
+    int64_t a = b.n_art;
+    for (int64_t k = k0; k < k0 + depth; ++k) {
+        if (var[k] < 0 || var[k] >= b.n_vars || sense[k] < 0 || sense[k] > 1 || bound[k] == INT64_MIN)
+            return fail(MI_BAD_ARG, "bad node row %lld", (long long)k);
+        const float rhs = sbb_rhs(b, var[k], bound[k]);
+        a += row_word_artificial(row_word(rhs < 0.0f, sense[k]));
+        const int64_t c = b.vcol[var[k]];
+        const double r = std::fabs((double)rhs);
+        extra[c] += 1.0;
+        if (b.kind[var[k]] == 2) extra[c + 1] += 1.0;
+        if (r == std::floor(r)) extra[b.cols - 1] += r;
+    }
+    for (int64_t k = k0; k < k0 + depth; ++k) {
+        const int64_t c = b.vcol[var[k]];
+        exact_sums = exact_sums && b.col_int_sum[c] + extra[c] <= kSbbExactInts;
+        if (b.kind[var[k]] == 2) exact_sums = exact_sums && b.col_int_sum[c + 1] + extra[c + 1] <= kSbbExactInts;
+    }
+    exact_sums = exact_sums && b.col_int_sum[b.cols - 1] + extra[b.cols - 1] <= kSbbExactInts;
+    for (int64_t k = k0; k < k0 + depth; ++k) {
+        const int64_t c = b.vcol[var[k]];
+        extra[c] = 0.0;
+        if (b.kind[var[k]] == 2) extra[c + 1] = 0.0;
+    }
+    extra[b.cols - 1] = 0.0;
+    *n_art = a;
+    *exact = exact_sums;
+    return MI_OK;
+}
 
 // mi355x_sbatch_create_nodes / _create_nodes_global: the checks, the guard, the pair of the form, the assembly
 int sbb_create_nodes(mi355x_sbatch **out_main, mi355x_sbatch **out_art, const mi355x_sbb_base *base, int64_t n_nodes,
@@ -158,31 +203,9 @@ int sbb_create_nodes(mi355x_sbatch **out_main, mi355x_sbatch **out_art, const mi
     }
     for (int64_t c = 0; c < b.cols; ++c) exact_sums = exact_sums && b.col_int_sum[c] <= kSbbExactInts;
     for (int64_t q = 0; q < n_nodes; ++q) {
-        int64_t a = b.n_art;
-        for (int64_t k = q * depth; k < (q + 1) * depth; ++k) {
-            if (var[k] < 0 || var[k] >= b.n_vars || sense[k] < 0 || sense[k] > 1 || bound[k] == INT64_MIN)
-                return fail(MI_BAD_ARG, "bad node row %lld", (long long)k);
-            const float rhs = sbb_rhs(b, var[k], bound[k]);
-            a += row_word_artificial(row_word(rhs < 0.0f, sense[k]));
-            // the guard: this member's integer entries on top of the base's, column by column
-            const int64_t c = b.vcol[var[k]];
-            const double r = std::fabs((double)rhs);
-            extra[c] += 1.0;
-            if (b.kind[var[k]] == 2) extra[c + 1] += 1.0;
-            if (r == std::floor(r)) extra[b.cols - 1] += r;
-        }
-        for (int64_t k = q * depth; k < (q + 1) * depth; ++k) {
-            const int64_t c = b.vcol[var[k]];
-            exact_sums = exact_sums && b.col_int_sum[c] + extra[c] <= kSbbExactInts;
-            if (b.kind[var[k]] == 2) exact_sums = exact_sums && b.col_int_sum[c + 1] + extra[c + 1] <= kSbbExactInts;
-        }
-        exact_sums = exact_sums && b.col_int_sum[b.cols - 1] + extra[b.cols - 1] <= kSbbExactInts;
-        for (int64_t k = q * depth; k < (q + 1) * depth; ++k) {
-            const int64_t c = b.vcol[var[k]];
-            extra[c] = 0.0;
-            if (b.kind[var[k]] == 2) extra[c + 1] = 0.0;
-        }
-        extra[b.cols - 1] = 0.0;
+        int64_t a = 0;
+        const int rc = sbb_node_check(b, q * depth, depth, var, sense, bound, extra, &a, &exact_sums);
+        if (rc != MI_OK) return rc;
         if (n_art >= 0 && a != n_art) return fail(MI_BAD_ARG, "the nodes have different numbers of artificial rows");
         n_art = a;
     }

@@ -13,17 +13,18 @@
 
 namespace {
 constexpr int kSrMaxClass = 4;
-}  // namespace
 
-extern "C" {
-
-int mi355x_sbatch_create_ragged(mi355x_sbatch **out, int64_t n_lps, const int64_t *rows, const int64_t *cols,
-                                const int32_t *is_max, const float *matrices, const int64_t *basis, int device)
+int sr_upload_failed(hipError_t e)
 {
-    if (!out) return fail(MI_BAD_ARG, "out is NULL");
-    *out = nullptr;
-    if (!rows || !cols) return fail(MI_BAD_ARG, "rows or cols is NULL");
-    if (!matrices) return fail(MI_BAD_ARG, "matrices is NULL");
+    return fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "ragged single-float batch allocation or upload failed: %s",
+                hipGetErrorString(e));
+}
+
+// The skeleton of a ragged batch, in two steps around the device check.
+// sr_check_shapes: the members' shapes against sb_new's limits (MI_BAD_ARG, no device is looked for); *n_basis: their
+// basis entries in all.
+int sr_check_shapes(int64_t n_lps, const int64_t *rows, const int64_t *cols, int64_t *n_basis_out)
+{
     if (n_lps < 1 || n_lps > (1LL << 30)) return fail(MI_BAD_ARG, "n_lps=%lld must be in [1, 2^30]", (long long)n_lps);
     int64_t n_basis = 0;
     for (int64_t q = 0; q < n_lps; ++q) {
@@ -34,10 +35,18 @@ int mi355x_sbatch_create_ragged(mi355x_sbatch **out, int64_t n_lps, const int64_
         if (cols[q] > (1LL << 30)) return fail(MI_BAD_ARG, "member %lld: cols=%lld exceeds the supported 2^30", (long long)q, (long long)cols[q]);
         n_basis += rows[q] - 1;
     }
-    if (n_basis > 0 && !basis) return fail(MI_BAD_ARG, "basis is NULL");
-    const int ndev = device_count_checked();
-    if (ndev <= 0) return fail(MI_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
-    if (device < 0 || device >= ndev) return fail(MI_BAD_ARG, "device %d out of range [0,%d)", device, ndev);
+    *n_basis_out = n_basis;
+    return MI_OK;
+}
+
+// sr_new: a form-4 handle of those shapes and senses (is_max NULL: every member `min`) on `device`, WITHOUT the members'
+// data -- the budget check per member (nothing is allocated before), the SrMember layout, the classes, the device
+// buffers, the descriptors and class lists on their way up the handle's stream.  The caller fills v.M and v.basis
+// (an upload, or an assembly kernel once this stream has been waited for), then calls sb_fresh_ctl, which waits for
+// the stream; `index` (the class lists' host copy) has to live until then.  On a failure nothing is left behind.
+int sr_new(mi355x_sbatch **out, int64_t n_lps, const int64_t *rows, const int64_t *cols, const int32_t *is_max, int64_t n_basis,
+           int device, std::vector<int32_t> &index)
+{
     HIP_TRY(hipSetDevice(device));
     // the same rule and the same budget as mi355x_sbatch_create, member by member (nothing is allocated before)
     std::vector<size_t> lds;
@@ -69,8 +78,6 @@ int mi355x_sbatch_create_ragged(mi355x_sbatch **out, int64_t n_lps, const int64_
     SbView &v = b->v;
     v.n_lps = n_lps;
     v.trace_cap = MI355X_SBATCH_TRACE_CAP;
-    std::vector<float> staged;                // the members as stored: rows of ld floats, padding zero
-    std::vector<int32_t> index;
     int64_t m_total = 0;
     try {
         b->h.resize((size_t)n_lps);
@@ -89,19 +96,11 @@ int mi355x_sbatch_create_ragged(mi355x_sbatch **out, int64_t n_lps, const int64_
             b_off += d.rows - 1;
             b->lds_max = std::max(b->lds_max, lds[q]);
         }
-        staged.assign((size_t)m_total, 0.0f);
     } catch (const std::bad_alloc &) {
         delete b;
         return fail(MI_NO_MEMORY, "host allocation failed");
     }
-    {
-        const float *src = matrices;
-        for (int64_t q = 0; q < n_lps; ++q) {
-            const SrMember &d = b->hm[q];
-            for (int64_t r = 0; r < d.rows; ++r, src += d.cols)
-                std::memcpy(staged.data() + d.m_off + r * d.ld, src, (size_t)d.cols * sizeof(float));
-        }
-    }
+    b->m_total = m_total;
     // the classes: one, every member at the largest member's size; under the hook the residency at the member's own
     // LDS size (queried once per distinct size), capped
     int count_of[kSrMaxClass + 1] = {0, 0, 0, 0, 0};       // members per residency
@@ -153,25 +152,71 @@ int mi355x_sbatch_create_ragged(mi355x_sbatch **out, int64_t n_lps, const int64_
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_members, (size_t)n_lps * sizeof(SrMember));
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_index, (size_t)n_lps * sizeof(int32_t));
     if (e == hipSuccess) e = hipMemsetAsync(b->d_phase, 0, (size_t)(2 * n_lps) * sizeof(int32_t), b->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(v.M, staged.data(), (size_t)m_total * sizeof(float), hipMemcpyHostToDevice, b->stream);
-    if (e == hipSuccess && n_basis > 0)
-        e = hipMemcpyAsync(v.basis, basis, (size_t)n_basis * sizeof(int64_t), hipMemcpyHostToDevice, b->stream);
     if (e == hipSuccess)
         e = hipMemcpyAsync(b->d_members, b->hm.data(), (size_t)n_lps * sizeof(SrMember), hipMemcpyHostToDevice, b->stream);
     if (e == hipSuccess)
         e = hipMemcpyAsync(b->d_index, index.data(), (size_t)n_lps * sizeof(int32_t), hipMemcpyHostToDevice, b->stream);
-    if (e == hipSuccess) e = sb_fresh_ctl(b);               // (waits for the stream: the staged copies are done)
     if (e != hipSuccess) {
         (void)hipGetLastError();
         free_sbatch(b);
-        return fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "ragged single-float batch allocation or upload failed: %s",
-                    hipGetErrorString(e));
+        return sr_upload_failed(e);
     }
     SrView &r = b->r;
     r.M = v.M; r.basis = v.basis; r.ctl = v.ctl;
     r.trace_ec = v.trace_ec; r.trace_cr = v.trace_cr; r.trace_cap = v.trace_cap;
     r.n_lps = n_lps;
     r.members = b->d_members;
+    *out = b;
+    return MI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi355x_sbatch_create_ragged(mi355x_sbatch **out, int64_t n_lps, const int64_t *rows, const int64_t *cols,
+                                const int32_t *is_max, const float *matrices, const int64_t *basis, int device)
+{
+    if (!out) return fail(MI_BAD_ARG, "out is NULL");
+    *out = nullptr;
+    if (!rows || !cols) return fail(MI_BAD_ARG, "rows or cols is NULL");
+    if (!matrices) return fail(MI_BAD_ARG, "matrices is NULL");
+    int64_t n_basis = 0;
+    int rc = sr_check_shapes(n_lps, rows, cols, &n_basis);
+    if (rc != MI_OK) return rc;
+    if (n_basis > 0 && !basis) return fail(MI_BAD_ARG, "basis is NULL");
+    const int ndev = device_count_checked();
+    if (ndev <= 0) return fail(MI_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
+    if (device < 0 || device >= ndev) return fail(MI_BAD_ARG, "device %d out of range [0,%d)", device, ndev);
+    mi355x_sbatch *b = nullptr;
+    std::vector<int32_t> index;
+    rc = sr_new(&b, n_lps, rows, cols, is_max, n_basis, device, index);
+    if (rc != MI_OK) return rc;
+    std::vector<float> staged;                // the members as stored: rows of ld floats, padding zero
+    try {
+        staged.assign((size_t)b->m_total, 0.0f);
+    } catch (const std::bad_alloc &) {
+        free_sbatch(b);
+        return fail(MI_NO_MEMORY, "host allocation failed");
+    }
+    {
+        const float *src = matrices;
+        for (int64_t q = 0; q < n_lps; ++q) {
+            const SrMember &d = b->hm[q];
+            for (int64_t r = 0; r < d.rows; ++r, src += d.cols)
+                std::memcpy(staged.data() + d.m_off + r * d.ld, src, (size_t)d.cols * sizeof(float));
+        }
+    }
+    SbView &v = b->v;
+    hipError_t e = hipMemcpyAsync(v.M, staged.data(), (size_t)b->m_total * sizeof(float), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess && n_basis > 0)
+        e = hipMemcpyAsync(v.basis, basis, (size_t)n_basis * sizeof(int64_t), hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess) e = sb_fresh_ctl(b);               // (waits for the stream: the staged copies are done)
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        free_sbatch(b);
+        return sr_upload_failed(e);
+    }
     *out = b;
     return MI_OK;
 }

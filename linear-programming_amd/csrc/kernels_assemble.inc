@@ -84,18 +84,30 @@ void launch_assemble(const TabView &mt, const TabView &at, const Src &src, const
     }
 }
 
-// ---- LDS family: member q of a workgroup of kAssembleThreads threads, ab[] (m entries, dealt) in LDS and visible to
-// every thread.  elem(R, C) is entry C < num_cols of row R <= m of the main tableau.  Both tableaux over their whole
-// leading dimension (padding +0.0), consecutive threads consecutive floats; at.M == nullptr: no artificial rows.
+// ---- LDS family: one member per workgroup of kAssembleThreads threads, ab[] (m entries, dealt) in LDS and visible to
+// every thread.  Where a member's tableau and basis live is a slot: a batch of one shape makes it from its SbView
+// (sb_slot), a ragged batch from its SrView and the member's SrMember (kernels_single_ragged_build.inc).
+struct AsmSlot {
+    float   *M;           // the member's first row (nullptr: no such tableau)
+    int64_t *basis;       // its m basis entries
+    int      ld, cols;    // leading dimension and columns, in floats
+};
+__device__ __forceinline__ AsmSlot sb_slot(const SbView &v, int64_t q, int m)
+{
+    return AsmSlot{v.M ? v.M + q * v.stride : nullptr, v.basis + q * m, (int)v.ld, (int)v.cols};
+}
+
+// elem(R, C) is entry C < num_cols of row R <= m of the main tableau.  Both tableaux over their whole leading
+// dimension (padding +0.0), consecutive threads consecutive floats; at.M == nullptr: no artificial rows.
 template <class Elem>
-__device__ __forceinline__ void assemble_member_lds(const SbView &mt, const SbView &at, int64_t q, int m, int num_cols,
+__device__ __forceinline__ void assemble_member_lds(const AsmSlot &mt, const AsmSlot &at, int m, int num_cols,
                                                     const int32_t *ab, Elem elem)
 {
     const int tid = threadIdx.x;
     {
-        const int ld = (int)mt.ld;
-        float *M = mt.M + q * mt.stride;
-        int64_t *mb = mt.basis + q * m;
+        const int ld = mt.ld;
+        float *M = mt.M;
+        int64_t *mb = mt.basis;
         for (int R = tid; R < m; R += kAssembleThreads) mb[R] = ab_main_basis(ab[R], num_cols);
         for (int k = tid; k < (m + 1) * ld; k += kAssembleThreads) {
             const int R = k / ld, C = k - R * ld;
@@ -103,9 +115,9 @@ __device__ __forceinline__ void assemble_member_lds(const SbView &mt, const SbVi
         }
     }
     if (at.M) {
-        const int nac = (int)at.cols, ld = (int)at.ld;
-        float *A = at.M + q * at.stride;
-        int64_t *abasis = at.basis + q * m;
+        const int nac = at.cols, ld = at.ld;
+        float *A = at.M;
+        int64_t *abasis = at.basis;
         for (int R = tid; R < m; R += kAssembleThreads) abasis[R] = ab[R];
         for (int k = tid; k < m * ld; k += kAssembleThreads) {
             const int R = k / ld, C = k - R * ld;

@@ -51,26 +51,27 @@ __device__ __forceinline__ float sbb_main_elem(const SbbBaseView &b, const SbbLd
     return row[C - d];
 }
 
-// Member blockIdx.x.  at.M == nullptr: the group has no artificial rows.  Dynamic LDS: sbb_assemble_lds(m, d).
-__global__ __launch_bounds__(kSbbThreads) void k_sbb_assemble(SbView mt, SbView at, SbbBaseView b, XbbNodeRows nr)
+// One node of depth d, the whole workgroup: its rows (var, sense, bound: the node's own d entries, newest first) and
+// the base's classified into lds (m + 3 d words, m = base constraint rows + d), the artificial columns dealt, then the
+// write pass into the node's slots.
+__device__ __forceinline__ void sbb_assemble_member(const AsmSlot &mt, const AsmSlot &at, const SbbBaseView &b, const int64_t *var,
+                                                    const int32_t *sense, const int64_t *bound, int d, int32_t *lds)
 {
-    extern __shared__ __attribute__((aligned(16))) int32_t sbb_lds[];
     const int tid = threadIdx.x;
-    const int64_t q = blockIdx.x;
-    const int d = (int)nr.d, nb = (int)b.nb, ncv = (int)b.ncv;
+    const int nb = (int)b.nb, ncv = (int)b.ncv;
     const int m = (int)(b.rows - 1) + d, num_cols = (int)b.cols + d;
     SbbLds l;
-    l.ab = sbb_lds;
-    l.rhs = reinterpret_cast<float *>(sbb_lds + m);
-    l.col = sbb_lds + m + d;
-    l.flags = sbb_lds + m + 2 * d;
+    l.ab = lds;
+    l.rhs = reinterpret_cast<float *>(lds + m);
+    l.col = lds + m + d;
+    l.flags = lds + m + 2 * d;
     for (int k = tid; k < d; k += kSbbThreads) {
-        const int64_t i = q * d + k, v = nr.var[i];
+        const int64_t v = var[k];
         const int kind = b.kind[v];
-        float rhs = (float)nr.bound[i];                                     // (a floor or ceiling of a float: exact)
+        float rhs = (float)bound[k];                                        // (a floor or ceiling of a float: exact)
         if (kind != 2) rhs = rhs - b.voff[v];                               // coef 1, :230-237
         const bool flip = rhs < 0.0f;
-        const int op = row_word(flip, nr.sense[i]) >> 1;
+        const int op = row_word(flip, sense[k]) >> 1;
         l.rhs[k] = flip ? -rhs : rhs;
         l.col[k] = (int32_t)b.vcol[v];
         l.flags[k] = kind | (flip ? 4 : 0) | (op ? 8 : 0);
@@ -89,7 +90,16 @@ __global__ __launch_bounds__(kSbbThreads) void k_sbb_assemble(SbView mt, SbView 
     __syncthreads();
     if (tid == 0) deal_artificial_columns(l.ab, m, num_cols);
     __syncthreads();
-    assemble_member_lds(mt, at, q, m, num_cols, l.ab, [&](int R, int C) { return sbb_main_elem(b, l, d, R, C); });
+    assemble_member_lds(mt, at, m, num_cols, l.ab, [&](int R, int C) { return sbb_main_elem(b, l, d, R, C); });
+}
+
+// Member blockIdx.x.  at.M == nullptr: the group has no artificial rows.  Dynamic LDS: sbb_assemble_lds(m, d).
+__global__ __launch_bounds__(kSbbThreads) void k_sbb_assemble(SbView mt, SbView at, SbbBaseView b, XbbNodeRows nr)
+{
+    extern __shared__ __attribute__((aligned(16))) int32_t sbb_lds[];
+    const int64_t q = blockIdx.x;
+    const int d = (int)nr.d, m = (int)(b.rows - 1) + d;
+    sbb_assemble_member(sb_slot(mt, q, m), sb_slot(at, q, m), b, nr.var + q * d, nr.sense + q * d, nr.bound + q * d, d, sbb_lds);
 }
 
 // Member blockIdx.x: rhs + q * rows its last column, obj + q * cols its last row, basis + q * (rows - 1) its basis.

@@ -44,46 +44,59 @@ __device__ __forceinline__ float slp_main_elem(const float *Lr, int ncv, int wor
     return 0.0f;
 }
 
-// Member blockIdx.x.  at.M == nullptr: the group has no artificial rows.  sp.m <= kSlpMaxRows.
-__global__ __launch_bounds__(kSlpThreads) void k_slp_assemble(SbView mt, SbView at, SlpView sp)
+// per row of a member: its word (row_word), slack column (-1: none), artificial-basis entry (simplex_kernels.h); the
+// wave totals of the prefix counts
+struct SlpLds {
+    int32_t word[kSlpMaxRows], scol[kSlpMaxRows], ab[kSlpMaxRows];
+    int32_t wave_slack[kSlpThreads / 64], wave_art[kSlpThreads / 64];
+};
+
+// One member, the whole workgroup: the row pass over its m <= kSlpMaxRows rows (L, sense: the member's own, tight),
+// then the write pass into its slots.  cols: the main tableau's columns, ncv + slack columns + 1.
+__device__ __forceinline__ void slp_assemble_member(const AsmSlot &mt, const AsmSlot &at, const float *L, const int32_t *sense,
+                                                    int m, int ncv, int cols, SlpLds &l)
 {
-    // per row: its word (row_word), slack column (-1: none), artificial-basis entry (simplex_kernels.h)
-    __shared__ int32_t word[kSlpMaxRows], scol[kSlpMaxRows], ab[kSlpMaxRows];
-    __shared__ int32_t wave_slack[kSlpThreads / 64], wave_art[kSlpThreads / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t q = blockIdx.x;
-    const int m = (int)sp.m, ncv = (int)sp.ncv, W = ncv + 1, cols = ncv + (int)sp.n_slack + 1;
-    const float *L = sp.L + q * (int64_t)(m + 1) * W;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = ncv + 1;
     // ---- the row pass
     int w = 0;
     bool slack = false, art = false;
     if (tid < m) {
-        w = row_word(L[(int64_t)tid * W + ncv] < 0.0f, sp.sense[q * m + tid]);      // :243
+        w = row_word(L[(int64_t)tid * W + ncv] < 0.0f, sense[tid]);                 // :243
         slack = (w >> 1) != 2;
         art = row_word_artificial(w);
     }
     const unsigned long long bs = __ballot(slack), ba = __ballot(art), below = (1ull << lane) - 1ull;
     if (lane == 0) {
-        wave_slack[wave] = __popcll(bs);
-        wave_art[wave] = __popcll(ba);
+        l.wave_slack[wave] = __popcll(bs);
+        l.wave_art[wave] = __popcll(ba);
     }
     __syncthreads();
     int slack_before = __popcll(bs & below), art_through = __popcll(ba & below) + (art ? 1 : 0), art_all = 0;
     for (int k = 0; k < kSlpThreads / 64; ++k) {
-        if (k < wave) { slack_before += wave_slack[k]; art_through += wave_art[k]; }
-        art_all += wave_art[k];
+        if (k < wave) { slack_before += l.wave_slack[k]; art_through += l.wave_art[k]; }
+        art_all += l.wave_art[k];
     }
     if (tid < m) {
-        word[tid] = w;
-        scol[tid] = slack ? ncv + slack_before : -1;
+        l.word[tid] = w;
+        l.scol[tid] = slack ? ncv + slack_before : -1;
         // what deal_artificial_columns leaves: cols - 1 + the artificial rows with a greater index
-        ab[tid] = art ? cols - 1 + (art_all - art_through) : ncv + slack_before;
+        l.ab[tid] = art ? cols - 1 + (art_all - art_through) : ncv + slack_before;
     }
     __syncthreads();
     // ---- the write pass
-    assemble_member_lds(mt, at, q, m, cols, ab, [&](int R, int C) {
-        return slp_main_elem(L + (int64_t)R * W, ncv, R < m ? word[R] : 0, R < m ? scol[R] : -1, C, cols);
+    assemble_member_lds(mt, at, m, cols, l.ab, [&](int R, int C) {
+        return slp_main_elem(L + (int64_t)R * W, ncv, R < m ? l.word[R] : 0, R < m ? l.scol[R] : -1, C, cols);
     });
+}
+
+// Member blockIdx.x.  at.M == nullptr: the group has no artificial rows.  sp.m <= kSlpMaxRows.
+__global__ __launch_bounds__(kSlpThreads) void k_slp_assemble(SbView mt, SbView at, SlpView sp)
+{
+    __shared__ SlpLds l;
+    const int64_t q = blockIdx.x;
+    const int m = (int)sp.m, ncv = (int)sp.ncv, cols = ncv + (int)sp.n_slack + 1;
+    slp_assemble_member(sb_slot(mt, q, m), sb_slot(at, q, m), sp.L + q * (int64_t)(m + 1) * (ncv + 1), sp.sense + q * m, m, ncv,
+                        cols, l);
 }
 
 void launch_slp_assemble(const SbView &mt, const SbView &at, const SlpView &sp, hipStream_t s)

@@ -213,4 +213,5 @@ struct mi355x_multibatch {
 #include "capi_single_ragged.inc"  // mi355x_sbatch_create_ragged / _member_shape: members of mixed shapes and senses as one batch
 #include "capi_single_bb.inc"  // mi355x_sbb_base_*, mi355x_sbatch_create_nodes / _readback: single-float branch-and-bound
 #include "capi_single_lps.inc"  // mi355x_sbatch_create_lps: single-float batches built from problem rows on the device
+#include "capi_single_ragged_build.inc"  // mi355x_sbatch_create_lps_ragged / _create_nodes_ragged / _readback_ragged: ragged batches built on the device
 #include "capi_tune.inc"      // mi355x_tune_*, mi355x_debug_*

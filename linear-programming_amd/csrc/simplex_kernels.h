@@ -619,6 +619,22 @@ struct SlpView {
 constexpr int kSlpMaxRows = 256;                                            // k_slp_assemble: one row per thread, one trip
 // every member of mt and of at (at.M == nullptr: no artificial rows): tableau over the whole leading dimension, basis
 void launch_slp_assemble(const SbView &mt, const SbView &at, const SlpView &sp, hipStream_t s);
+// RAGGED batches built on the device (kernels_single_ragged_build.inc, capi_single_ragged_build.inc): the two
+// assemblies above with a shape per member, and the light read-back of a ragged batch.
+// From rows: L and sense tight and concatenated, member q's (m + 1) x (ncv + 1) floats at L + l_off, its m senses at
+// sense + s_off; n_slack of its rows are not `=`, n_art end up `>=` or `=`.  m <= kSlpMaxRows.
+struct SrlpMember { int64_t l_off, s_off; int32_t m, ncv, n_slack, n_art; };
+// From nodes: node q's d rows (newest first) at off in the concatenated var / sense / bound arrays.
+struct SrbbNode { int64_t off; int32_t d; };
+// every member of mt and of at (at.M == nullptr: no member has artificial rows); all pointers are device pointers
+void launch_srlp_assemble(const SrView &mt, const SrView &at, const float *L, const int32_t *sense, const SrlpMember *members,
+                          hipStream_t s);
+// lds: sbb_assemble_lds of the largest member of the launch
+void launch_srbb_assemble(const SrView &mt, const SrView &at, const SbbBaseView &b, const int64_t *var, const int32_t *sense,
+                          const int64_t *bound, const SrbbNode *nodes, size_t lds, hipStream_t s);
+// per member: last column, last row, basis, into three concatenated planes at the running sums of rows, cols (col_off,
+// device, n_lps entries) and rows - 1
+void launch_sr_readback(const SrView &b, const int64_t *col_off, float *rhs, float *obj, int64_t *basis, hipStream_t s);
 // The same two assemblies spread over a grid, for GLOBAL-form batches (kernels_single_assemble_global.inc): a row pass
 // into per-member scratch planes (device memory of sga_*_scratch_bytes, the caller's, alive until the stream has run
 // the launches), one write pass and the artificial objective row, ordered by the stream alone.  Any m, any depth.

@@ -69,7 +69,7 @@
 //     kernels_batch.inc           k_batch_solve, k_batch_block
 //     kernels_resident.inc        k_resident
 //     kernels_layout.inc          dense <-> compact, control block, two-phase hand-over, synthetic LPs
-//     kernels_assemble.inc        build-tableau's layout, one copy: k_assemble<Src>, k_art_objective, assemble_member_lds
+//     kernels_assemble.inc        build-tableau's layout, one copy: k_assemble<Src>, k_art_objective, assemble_member_lds over a member slot
 //     kernels_bb.inc              branch-and-bound node tableaux assembled in HBM (k_bb_rows, BbSrc)
 //     kernels_exact.inc           exact rational solves on fraction-free integer tableaux (k_x_*)
 //     kernels_exact_batch.inc     batches of exact LPs, one workgroup per LP (k_xb_solve, k_xb_between)
@@ -82,6 +82,7 @@
 //     kernels_single_global.inc   the global form of those batches: k_sg_solve (one workgroup per member, the tableau in HBM)
 //     kernels_single_bb.inc       single-float branch-and-bound: float node tableaux into padded members, light read-back (k_sbb_assemble, k_sb_readback)
 //     kernels_single_lps.inc      single-float batches built from problem rows under Lisp's contagion (k_slp_assemble)
+//     kernels_single_ragged_build.inc  ragged batches built on the device from rows or node rows, their light read-back (k_srlp_assemble, k_srbb_assemble, k_sr_readback)
 //     kernels_single_assemble_global.inc  both single-float assemblies spread over a grid, for global-form batches (k_sga_*)
 #include "simplex_kernels.h"
 #include <type_traits>
@@ -113,6 +114,7 @@ namespace mi355x {
 #include "kernels_single_global.inc"
 #include "kernels_single_bb.inc"
 #include "kernels_single_lps.inc"
+#include "kernels_single_ragged_build.inc"
 #include "kernels_single_assemble_global.inc"
 
 }  // namespace mi355x

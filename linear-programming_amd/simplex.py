@@ -492,7 +492,7 @@ def _native_numbers(problem):
 def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_pivots=0,
                           full_tableau=False, native="auto", chunk=None, branch_and_bound=False,
                           bb_width=1, int_tolerance=0, max_nodes=0, exact=False, exact_bits=0, exact_max_bits=128,
-                          pivot_rule="dantzig", precision="double", beyond_lds=False, **_ignored):
+                          pivot_rule="dantzig", precision="double", beyond_lds=False, mixed_shapes=False, **_ignored):
     """What the Lisp glue installs as `*solver*` (src/solver.lisp:39-56): takes a problem and
     backend keyword arguments, returns a solution object answering the four solution-*
     generics -- on the NATIVE route (default whenever the problem's numbers are floats / integers
@@ -547,7 +547,11 @@ def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_p
     branch_and_bound an integer problem is declined: unsupported-constraint-error ("integer" ...).
     beyond_lds=True (opt-in, with that pair only -- an argument error anywhere else on this function): a node group
     beyond the batches' LDS budget that has at least single.global_batch_min_members nodes goes as ONE global-form
-    batch (or pair) instead of node by node; the search and its result are the same, bit for bit."""
+    batch (or pair) instead of node by node; the search and its result are the same, bit for bit.
+    mixed_shapes=True (opt-in, with that pair only -- an argument error anywhere else on this function): the node LPs
+    of a round that fit the LDS budget go as ONE ragged batch and ONE ragged pair built on the device, whatever their
+    depths, instead of one batch per (depth, artificial rows) group; the search and its result are the same, bit for
+    bit."""
     if precision not in ("double", "single"):
         raise ValueError("precision=%r: \"double\" (default) or \"single\"" % (precision,))
     single_bb_route = precision == "single" and branch_and_bound and problem.integer_vars and not exact and \
@@ -555,13 +559,17 @@ def mi355x_simplex_solver(problem, fp_tolerance=1024, device=0, devices=1, max_p
     if beyond_lds and not single_bb_route:
         raise ValueError("beyond_lds=True needs precision=\"single\", branch_and_bound=True and a problem with integer "
                          "variables: it batches the single-float node LPs beyond the LDS budget")
+    if mixed_shapes and not single_bb_route:
+        raise ValueError("mixed_shapes=True needs precision=\"single\", branch_and_bound=True and a problem with integer "
+                         "variables: it batches the single-float node LPs of a round whatever their depths")
     if precision == "single" and branch_and_bound and problem.integer_vars and not exact and devices <= 1 and \
             native is not True and not full_tableau and pivot_rule == "dantzig":
         from .single_bb import solve_branch_and_bound_single
         return solve_branch_and_bound_single(problem, width=bb_width, fp_tolerance=fp_tolerance,
                                              int_tolerance=int_tolerance, device=device, max_pivots=max_pivots,
                                              max_nodes=max_nodes, chunk=chunk,
-                                             **({"beyond_lds": True} if beyond_lds else {}))
+                                             **({"beyond_lds": True} if beyond_lds else {}),
+                                             **({"mixed_shapes": True} if mixed_shapes else {}))
     if precision == "single":
         for name, clash in (("exact", bool(exact)), ("branch_and_bound", bool(branch_and_bound)),
                             ("devices", devices > 1), ("native", native is True), ("full_tableau", bool(full_tableau)),

@@ -359,6 +359,58 @@ class SingleBatch:
         big = int(np.argmax(rows * cols))
         return cls(h, len(Ms), rows[big], cols[big], ragged=True)
 
+    @classmethod
+    def from_lps_ragged(cls, lps_list, sense_list, is_max, col_int_sum_list=None, device=0):
+        """mi355x_sbatch_create_lps_ragged: ONE ragged batch (or pair) whose tableaux the device builds from the
+        members' rows -- from_lps with a shape and a sense per member.  lps_list: float32 arrays [m_q + 1, ncv_q + 1] in
+        column space; sense_list: arrays [m_q] (0 `<=`, 1 `>=`, 2 `=`); is_max: a truth value per member;
+        col_int_sum_list: arrays [ncv_q + 1] or None (the guard).  Either no member has artificial rows or every
+        member has at least one (the counts may differ): a mixture is declined with MI_BAD_ARG, the caller splits its
+        list.  -> (main, art or None), both ragged.  The guard and a member beyond the LDS budget (a two-phase member:
+        its artificial shape) raise capi.Mi355xError with code MI_UNSUPPORTED; the message names the member."""
+        Ls = [np.asarray(L) for L in lps_list]
+        if not Ls:
+            raise ValueError("a ragged batch needs at least one member")
+        if len(sense_list) != len(Ls):
+            raise ValueError("%d sense arrays for %d members" % (len(sense_list), len(Ls)))
+        if len(is_max) != len(Ls):
+            raise ValueError("%d senses for %d members" % (len(is_max), len(Ls)))
+        if col_int_sum_list is not None and len(col_int_sum_list) != len(Ls):
+            raise ValueError("%d col_int_sum arrays for %d members" % (len(col_int_sum_list), len(Ls)))
+        ss, sums = [], []
+        for q, L in enumerate(Ls):
+            if L.dtype != np.float32:
+                raise TypeError("SingleBatch.from_lps_ragged takes float32 rows, not %s (member %d)" % (L.dtype, q))
+            if L.ndim != 2 or L.shape[0] < 2 or L.shape[1] < 2:
+                raise ValueError("member %d must be [m + 1 >= 2, ncv + 1 >= 2], not %r" % (q, L.shape))
+            s = np.ascontiguousarray(sense_list[q], dtype=np.int32)
+            if s.shape != (L.shape[0] - 1,):
+                raise ValueError("member %d: sense shape %r does not match [m] = %r" % (q, s.shape, (L.shape[0] - 1,)))
+            ss.append(s)
+            if col_int_sum_list is not None:
+                c = np.ascontiguousarray(col_int_sum_list[q], dtype=np.float64)
+                if c.shape != (L.shape[1],):
+                    raise ValueError("member %d: col_int_sum shape %r does not match [ncv + 1] = %r"
+                                     % (q, c.shape, (L.shape[1],)))
+                sums.append(c)
+        m = np.array([L.shape[0] - 1 for L in Ls], dtype=np.int64)
+        ncv = np.array([L.shape[1] - 1 for L in Ls], dtype=np.int64)
+        flat = np.concatenate([np.ascontiguousarray(L).ravel() for L in Ls])
+        sense = np.concatenate(ss)
+        sums = np.concatenate(sums) if sums else None
+        senses = np.array([1 if x else 0 for x in is_max], dtype=np.int32)
+        hm, ha = ctypes.c_void_p(), ctypes.c_void_p()
+        capi.check(capi.lib().mi355x_sbatch_create_lps_ragged(
+            ctypes.byref(hm), ctypes.byref(ha), len(Ls), _ptr(m), _ptr(ncv), _ptr(senses), _ptr(flat), _ptr(sense),
+            _ptr(sums) if sums is not None else None, int(device)), "mi355x_sbatch_create_lps_ragged")
+        counts = [lists.row_counts(L[:-1, -1] < 0, s) for L, s in zip(Ls, ss)]
+        rows = m + 1
+        cols = np.array([n + (k - int(e)) + 1 for n, k, (e, _) in zip(ncv, m, counts)], dtype=np.int64)
+        acols = cols + np.array([int(a) for _, a in counts], dtype=np.int64)
+        big, abig = int(np.argmax(rows * cols)), int(np.argmax(rows * acols))
+        return (cls(hm, len(Ls), rows[big], cols[big], ragged=True),
+                cls(ha, len(Ls), rows[abig], acols[abig], ragged=True) if ha else None)
+
     def member_shape(self, q):
         """mi355x_sbatch_member_shape: {"rows", "cols", "ld", "is_max" (1, 0; -1 on a batch of one shape: the sense is
         the call's), "occupancy_class" (workgroups resident per compute unit in the launch the member goes in)}."""

@@ -43,8 +43,8 @@ from .conditions import SolverError, UnsupportedConstraintError
 from .exact_bb import _I64_MAX, _status_of, search
 from .lowering import assemble, build, lower
 from .problem import Problem
-from .single import (EPSILON_SINGLE, SINGLE, SingleBatch, SingleTableau, build_tableau_single, check_single_problem,
-                     global_batch_min_members, solve_status)
+from .single import (EPSILON_SINGLE, LDS_BUDGET, SINGLE, SingleBatch, SingleTableau, build_tableau_single,
+                     check_single_problem, global_batch_min_members, single_lds_bytes, solve_status)
 from .simplex import tableau_objective_value, tableau_variable
 
 F32 = np.float32
@@ -188,7 +188,7 @@ class Base:
     """mi355x_sbb_base: the float32 general form on the device."""
 
     def __init__(self, g, device=0):
-        self.g, self.handle = g, None
+        self.g, self.handle, self._sense_said = g, None, False
         M = np.ascontiguousarray(g.matrix, dtype=F32)
         basis = np.ascontiguousarray(g.basis, dtype=np.int64)
         kind, col = np.array(g.kind, dtype=np.int32), np.array(g.col, dtype=np.int64)
@@ -225,6 +225,33 @@ class Base:
         main = SingleBatch(hm, n, rows, cols)
         return main, (SingleBatch(ha, n, rows, cols + n_art) if ha else None)
 
+    def create_nodes_ragged(self, entries):
+        """mi355x_sbatch_create_nodes_ragged for entries of ANY depths: (main SingleBatch, artificial SingleBatch or
+        None), both ragged.  Either no node has artificial rows or every node has at least one (the counts may
+        differ): the library declines a mixture with MI_BAD_ARG.  The guard, the assembly's LDS and the batch's budget
+        decline with MI_UNSUPPORTED, the node named; a bound beyond 64 bits is declined as in create_nodes."""
+        g, n = self.g, len(entries)
+        flat = [r for e in entries for r in e]
+        if any(abs(b) > _I64_MAX for _, _, b in flat):
+            raise UnsupportedConstraintError(("single", "bound", "64 bits"), "mi355x-simplex")
+        depth = np.array([len(e) for e in entries], dtype=np.int64)
+        var = np.array([g.index[v] for v, _, _ in flat], dtype=np.int64)
+        sense = np.array([s for _, s, _ in flat], dtype=np.int32)
+        bound = np.array([int(b) for _, _, b in flat], dtype=np.int64)
+        if not self._sense_said:                                          # (a form-4 handle carries the sense per member)
+            capi.check(capi.lib().mi355x_sbb_base_set_sense(self.handle, 1 if g.problem.type == "max" else 0),
+                       "mi355x_sbb_base_set_sense")
+            self._sense_said = True
+        hm, ha = ctypes.c_void_p(), ctypes.c_void_p()
+        capi.check(capi.lib().mi355x_sbatch_create_nodes_ragged(ctypes.byref(hm), ctypes.byref(ha), self.handle, n,
+                                                                _ptr(depth), _ptr(var), _ptr(sense), _ptr(bound)),
+                   "mi355x_sbatch_create_nodes_ragged")
+        rows, cols = g.matrix.shape[0] + depth, g.matrix.shape[1] + depth
+        acols = cols + g.n_art + np.array([sum(g.row_artificial(*r) for r in e) for e in entries], dtype=np.int64)
+        big, abig = int(np.argmax(rows * cols)), int(np.argmax(rows * acols))
+        return (SingleBatch(hm, n, rows[big], cols[big], ragged=True),
+                SingleBatch(ha, n, rows[abig], acols[abig], ragged=True) if ha else None)
+
     def close(self):
         h, self.handle = self.handle, None
         if h:
@@ -238,7 +265,20 @@ class Base:
 
 
 def readback(sb):
-    """mi355x_sbatch_readback: (rhs[n, rows], objective rows[n, cols], bases[n, rows - 1])."""
+    """mi355x_sbatch_readback: (rhs[n, rows], objective rows[n, cols], bases[n, rows - 1]).  On a ragged batch
+    (sb.ragged) mi355x_sbatch_readback_ragged, one gather and one copy as well: three lists of per-member arrays."""
+    if sb.ragged:
+        shapes = [sb.member_shape(q) for q in range(sb.n_lps)]
+        r = np.cumsum([0] + [s["rows"] for s in shapes])
+        c = np.cumsum([0] + [s["cols"] for s in shapes])
+        rhs, obj = np.empty(int(r[-1]), dtype=F32), np.empty(int(c[-1]), dtype=F32)
+        basis = np.empty(int(r[-1]) - sb.n_lps, dtype=np.int64)
+        capi.check(capi.lib().mi355x_sbatch_readback_ragged(sb._handle, _ptr(rhs), _ptr(obj),
+                                                            _ptr(basis) if basis.size else None),
+                   "mi355x_sbatch_readback_ragged")
+        n = range(sb.n_lps)
+        return ([rhs[r[q]:r[q + 1]] for q in n], [obj[c[q]:c[q + 1]] for q in n],
+                [basis[r[q] - q:r[q + 1] - q - 1] for q in n])
     rhs, obj = np.empty((sb.n_lps, sb.rows), dtype=F32), np.empty((sb.n_lps, sb.cols), dtype=F32)
     basis = np.empty((sb.n_lps, max(sb.rows - 1, 0)), dtype=np.int64)
     capi.check(capi.lib().mi355x_sbatch_readback(sb._handle, _ptr(rhs), _ptr(obj), _ptr(basis) if basis.size else None),
@@ -254,7 +294,7 @@ class LightSolution:
 
     def __init__(self, g, fp_tolerance, device, rhs, obj_row, basis, batch, q):
         self.g, self.fp_tolerance, self.device, self.batch, self.q = g, fp_tolerance, device, batch, q
-        self.instance_problem, self.var_mapping, self.var_count = g.problem, g.mapping, batch.cols - 1
+        self.instance_problem, self.var_mapping, self.var_count = g.problem, g.mapping, len(obj_row) - 1
         self._light = (obj_row, rhs, basis)
         self.objective = tableau_objective_value(self)
 
@@ -286,12 +326,21 @@ class TableauSolution:
         return self.t
 
 
+#: mixed_shapes=True: the fewest nodes of a round that make a device-built ragged batch (or pair): a batch of one
+#: node gains nothing, so two.  What was measured on whole searches is in DESIGN 4.6n.
+RAGGED_NODES_MIN = 2
+
+
 class DeviceRounds:
     """The `solve_round` of the GPU (see the module's docstring)."""
 
-    def __init__(self, problem, fp_tolerance=1024, device=0, max_pivots=0, chunk=None, beyond_lds=False):
+    def __init__(self, problem, fp_tolerance=1024, device=0, max_pivots=0, chunk=None, beyond_lds=False,
+                 mixed_shapes=False):
         self.problem, self.fp_tolerance, self.device = problem, fp_tolerance, device
         self.max_pivots, self.chunk, self.beyond_lds = max_pivots, chunk, bool(beyond_lds)
+        self.mixed_shapes = bool(mixed_shapes)
+        self.ragged_batched = 0                                           # nodes solved in device-built ragged batches
+        self.n_creates = self.n_create_rounds = 0                         # batches (or pairs) created; rounds that created any
         self.g = self.base = None
         self.host_built = self.one_by_one = self.declined = 0             # nodes that left the device-built route
         self.global_batched = 0                                           # nodes solved in global-form batches
@@ -341,9 +390,61 @@ class DeviceRounds:
         self.host_built += len(entries)
         return made[0], (made[1] if two else None)
 
+    def _solved(self, ks, st, main, out):
+        """The members of a solved main batch into their slots: one light read-back."""
+        rhs, obj, basis = readback(main)
+        for q, k in enumerate(ks):
+            if st[q] == capi.MI_OPTIMAL:
+                s = LightSolution(self.g, self.fp_tolerance, self.device, rhs[q], obj[q], basis[q], main, q)
+                out[k] = (capi.MI_OPTIMAL, s.objective, s)
+            else:
+                out[k] = (int(st[q]), None, None)
+
+    def _in_chunks(self, main, art):
+        is_max, f = self.problem.type == "max", self.fp_tolerance
+        first = art or main
+        st, _ = lists.batch_in_chunks(
+            lambda cap: (False,) + (art.solve_two_phase(main, is_max, f, cap) if art else main.solve(is_max, f, cap)),
+            first.rows, first.cols, self.max_pivots, self.chunk)
+        if art:
+            art.close()
+        return st
+
+    def _take_ragged(self, entries, groups, out):
+        """mixed_shapes=True: the entries of `groups` that pass the guard and fit the LDS budget leave their (depth,
+        artificial rows) groups and go as ONE device-built ragged batch (no artificial rows) and ONE ragged pair, each
+        of RAGGED_NODES_MIN or more nodes, with one read-back each."""
+        g, sets = self.g, ([], [])
+        for (d, n_art), ks in groups.items():
+            a = g.n_art + n_art
+            if single_lds_bytes(g.matrix.shape[0] + d, g.matrix.shape[1] + d + a) > LDS_BUDGET:
+                continue
+            for k in ks:
+                if g.device_ok(entries[k]) and all(abs(b) <= _I64_MAX for _, _, b in entries[k]):
+                    sets[1 if a else 0].append(k)
+        for ks in sets:
+            if len(ks) < RAGGED_NODES_MIN:
+                continue
+            ks.sort()
+            try:
+                main, art = self.base.create_nodes_ragged([entries[k] for k in ks])
+            except capi.Mi355xError as e:                                 # declined all the same: the groups keep them
+                if e.code != capi.MI_UNSUPPORTED:
+                    raise
+                continue
+            taken = set(ks)
+            for key in list(groups):
+                groups[key] = [k for k in groups[key] if k not in taken]
+                if not groups[key]:
+                    del groups[key]
+            self.n_creates += 1
+            self.ragged_batched += len(ks)
+            self._solved(ks, self._in_chunks(main, art), main, out)
+
     def __call__(self, entries):
         out = [None] * len(entries)
         groups = {}
+        created = self.n_creates
         for k, e in enumerate(entries):
             if not e:
                 out[k] = self._root()
@@ -352,7 +453,9 @@ class DeviceRounds:
                 self.g = GeneralFormSingle(self.problem)
                 self.base = Base(self.g, self.device)
             groups.setdefault((len(e), sum(self.g.row_artificial(*r) for r in e)), []).append(k)
-        is_max, f = self.problem.type == "max", self.fp_tolerance
+        f = self.fp_tolerance
+        if self.mixed_shapes and groups:
+            self._take_ragged(entries, groups, out)
         for (d, n_art), ks in groups.items():
             try:
                 made = self._batches([entries[k] for k in ks])
@@ -373,19 +476,9 @@ class DeviceRounds:
                     out[k] = self._alone(host_tableaux(self.problem, entries[k], f, self.device))
                 continue
             main, art = made
-            first = art or main
-            st, _ = lists.batch_in_chunks(
-                lambda cap: (False,) + (art.solve_two_phase(main, is_max, f, cap) if art else main.solve(is_max, f, cap)),
-                first.rows, first.cols, self.max_pivots, self.chunk)
-            if art:
-                art.close()
-            rhs, obj, basis = readback(main)
-            for q, k in enumerate(ks):
-                if st[q] == capi.MI_OPTIMAL:
-                    s = LightSolution(self.g, f, self.device, rhs[q], obj[q], basis[q], main, q)
-                    out[k] = (capi.MI_OPTIMAL, s.objective, s)
-                else:
-                    out[k] = (int(st[q]), None, None)
+            self.n_creates += 1
+            self._solved(ks, self._in_chunks(main, art), main, out)
+        self.n_create_rounds += self.n_creates > created
         return out
 
 
@@ -394,10 +487,11 @@ class SingleBranchAndBound:
     errors; trace() / stats() as ExactBranchAndBound, `result.objectives` the trace's objectives as np.float32."""
 
     def __init__(self, problem, width=1, fp_tolerance=1024, int_tolerance=0, device=0, max_pivots=0, max_nodes=0,
-                 chunk=None, beyond_lds=False):
+                 chunk=None, beyond_lds=False, mixed_shapes=False):
         self.problem, self.width, self.max_nodes, self.int_tolerance = problem, int(width), int(max_nodes), int_tolerance
         self.rounds = DeviceRounds(problem, fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots, chunk=chunk,
-                                   **({"beyond_lds": True} if beyond_lds else {}))
+                                   **({"beyond_lds": True} if beyond_lds else {}),
+                                   **({"mixed_shapes": True} if mixed_shapes else {}))
         self.result = None
 
     def run(self):
@@ -420,14 +514,17 @@ class SingleBranchAndBound:
 
     def stats(self):
         return dict(self.result.stats(), declined=self.rounds.declined, host_built=self.rounds.host_built,
-                    one_by_one=self.rounds.one_by_one, global_batched=self.rounds.global_batched)
+                    one_by_one=self.rounds.one_by_one, global_batched=self.rounds.global_batched,
+                    ragged_batched=self.rounds.ragged_batched)
 
 
 def solve_branch_and_bound_single(problem, width=1, fp_tolerance=1024, int_tolerance=0, device=0, max_pivots=0,
-                                  max_nodes=0, chunk=None, beyond_lds=False):
+                                  max_nodes=0, chunk=None, beyond_lds=False, mixed_shapes=False):
     """simplex-solver with integer variables (src/simplex.lisp:506-542) on a problem of integers and single-floats:
     the incumbent as a solved SingleTableau (its read-back in np.float32).  beyond_lds=True (opt-in): a node group
     the LDS batches decline that has at least single.global_batch_min_members nodes goes as ONE global-form batch or
-    pair instead of node by node; the search is the same, bit for bit."""
+    pair instead of node by node; the search is the same, bit for bit.  mixed_shapes=True (opt-in): the nodes of a
+    round are not grouped by depth and artificial rows -- those that pass the guard and fit the LDS budget go as ONE
+    device-built ragged batch and ONE ragged pair (two or more nodes each); the search is the same, bit for bit."""
     return SingleBranchAndBound(problem, width, fp_tolerance, int_tolerance, device, max_pivots, max_nodes, chunk,
-                                beyond_lds).run()
+                                beyond_lds, mixed_shapes).run()

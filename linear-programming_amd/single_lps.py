@@ -60,12 +60,10 @@ def lower_problem_rows_single(problem):
     return LoweredRowsSingle(L, sense, SINGLE.mapping(mapping), problem.type == "max", col_int_sum, float_zero)
 
 
-def group_lowered_rows_single(problems):
-    """The grouping of solve_problems_single_from_rows, host only: (host, groups).  host {k: why the member goes one
-    by one} -- batch_lps.host_reason's words, "float zero" and "integer sum" (the module docstring), "alone" for a
-    member alone in its group, or the condition check_single_problem raised (it stays in the member's slot);
-    groups {(m, ncv, `=` rows, artificial rows, is_max): [(k, LoweredRowsSingle)]}, each of two or more members.
-    There is no "basis" reason: the single-float path has no compact form."""
+def lower_list_single(problems):
+    """The first half of group_lowered_rows_single, host only: (host, lowered).  host {k: why the member goes one by
+    one} as there, without "alone"; lowered [(k, rows, `=` rows, artificial rows, LoweredRowsSingle)] in list order,
+    what lists.group_by_rows takes."""
     host, lowered = {}, []
     for k, p in enumerate(problems):
         try:
@@ -82,11 +80,55 @@ def group_lowered_rows_single(problems):
         else:
             n_eq, n_art = lists.row_counts(low.L[:-1, -1] < 0, low.sense)
             lowered.append((k, low.L, n_eq, n_art, low))
+    return host, lowered
+
+
+def group_lowered_rows_single(problems):
+    """The grouping of solve_problems_single_from_rows, host only: (host, groups).  host {k: why the member goes one
+    by one} -- batch_lps.host_reason's words, "float zero" and "integer sum" (the module docstring), "alone" for a
+    member alone in its group, or the condition check_single_problem raised (it stays in the member's slot);
+    groups {(m, ncv, `=` rows, artificial rows, is_max): [(k, LoweredRowsSingle)]}, each of two or more members.
+    There is no "basis" reason: the single-float path has no compact form."""
+    host, lowered = lower_list_single(problems)
     return host, lists.group_by_rows(lowered, host)
 
 
+#: mixed_shapes=True: the fewest members that make a device-built ragged batch (or pair): a batch of one member gains
+#: nothing, so two.  What was measured by member count is in DESIGN 4.6n.
+RAGGED_ROWS_MIN_MEMBERS = 2
+
+
+def take_rows_for_ragged(lowered):
+    """Takes out of lowered (lower_list_single's) the members that go as device-built ragged batches under
+    mixed_shapes=True: those whose tableau -- for a member with artificial rows the artificial one -- is inside the
+    LDS budget, except the (m, ncv, `=` rows, artificial rows, sense) groups that single.RAGGED_UNIFORM_MIN_MEMBERS
+    keeps as batches of one shape.  -> (what is left, the single-phase set, the two-phase set), each set in list order
+    and of RAGGED_ROWS_MIN_MEMBERS or more members, else empty and its members left."""
+    sizes = {}
+    for k, rows, n_eq, n_art, low in lowered:
+        key = (rows.shape, int(n_eq), int(n_art), low.is_max)
+        sizes[key] = sizes.get(key, 0) + 1
+    sets, rest = ([], []), []
+    for item in lowered:
+        k, rows, n_eq, n_art, low = item
+        m, ncv = rows.shape[0] - 1, rows.shape[1] - 1
+        uniform = single.RAGGED_UNIFORM_MIN_MEMBERS is not None and \
+            sizes[(rows.shape, int(n_eq), int(n_art), low.is_max)] >= single.RAGGED_UNIFORM_MIN_MEMBERS
+        if uniform or single.single_lds_bytes(m + 1, ncv + (m - int(n_eq)) + 1 + int(n_art)) > single.LDS_BUDGET:
+            rest.append(item)
+        else:
+            sets[1 if n_art else 0].append(item)
+    out = []
+    for members in sets:
+        if len(members) < RAGGED_ROWS_MIN_MEMBERS:
+            rest.extend(members)
+            members = []
+        out.append(members)
+    return sorted(rest, key=lambda item: item[0]), out[0], out[1]
+
+
 def solve_problems_single_from_rows(problems, fp_tolerance=1024, device=0, max_pivots=0, errorp=True, chunk=None,
-                                    beyond_lds=False):
+                                    beyond_lds=False, mixed_shapes=False):
     """What solve_problems_single(problems, ...) returns, member for member -- the solved SingleTableau (matrix,
     basis, n_pivots, var_mapping, read-back in np.float32) or the member's condition -- with the tableaux of every
     group of group_lowered_rows_single built on the device (SingleBatch.from_lps) and solved in bounded chunks.
@@ -94,18 +136,51 @@ def solve_problems_single_from_rows(problems, fp_tolerance=1024, device=0, max_p
     through solve_single one by one.
     beyond_lds=True (opt-in): a group the LDS batch declines that has at least single.global_batch_min_members(rows,
     cols) members (for a two-phase group: of the artificial shape) is built on the device all the same, as ONE
-    global-form batch or pair (SingleBatch.from_lps(form="global")); the results are the same, bit for bit."""
+    global-form batch or pair (SingleBatch.from_lps(form="global")); the results are the same, bit for bit.
+    mixed_shapes=True (opt-in): the members inside the LDS budget are not grouped by shape and sense -- all
+    single-phase ones go as ONE device-built ragged batch, all two-phase ones as ONE device-built ragged pair
+    (SingleBatch.from_lps_ragged; take_rows_for_ragged), in bounded chunks sized by the largest member; everything
+    else goes as above, and the results are the same, bit for bit."""
     results = [None] * len(problems)
-    host, groups = group_lowered_rows_single(problems)
+    if mixed_shapes:
+        host, lowered = lower_list_single(problems)
+        lowered, *ragged_sets = take_rows_for_ragged(lowered)
+        groups = lists.group_by_rows(lowered, host)
+    else:
+        (host, groups), ragged_sets = group_lowered_rows_single(problems), ()
 
     def alone(k):
         return solve_single(problems[k], fp_tolerance=fp_tolerance, device=device, max_pivots=max_pivots, chunk=chunk)
+
+    def taker(ks, lows):
+        def take(sb, q, n_pivots):
+            p = problems[ks[q]]
+            M, b = sb.download(q)
+            t = SingleTableau(p, p, M, b, M.shape[1] - 1, M.shape[0] - 1, lows[q].mapping, fp_tolerance, device)
+            t.n_pivots = n_pivots
+            return t
+        return take
 
     for k in sorted(host):
         if isinstance(host[k], Exception):
             results[k] = host[k]
         else:
             lists.one_by_one(results, [k], alone)
+    for members in ragged_sets:
+        if not members:
+            continue
+        ks, lows = [item[0] for item in members], [item[-1] for item in members]
+        try:
+            main, art = SingleBatch.from_lps_ragged([low.L for low in lows], [low.sense for low in lows],
+                                                    [low.is_max for low in lows], [low.col_int_sum for low in lows],
+                                                    device=device)
+        except capi.Mi355xError as e:                                     # declined all the same: one by one
+            if e.code != capi.MI_UNSUPPORTED:
+                raise
+            lists.one_by_one(results, ks, alone)
+            continue
+        lists.place(results, ks, solve_made_batches([main] if art is None else [art, main], -1, taker(ks, lows),
+                                                    fp_tolerance, max_pivots, chunk))
     for members in groups.values():
         ks, lows = [k for k, _ in members], [low for _, low in members]
         arrays = (np.stack([low.L for low in lows]), np.stack([low.sense for low in lows]),
@@ -129,15 +204,8 @@ def solve_problems_single_from_rows(problems, fp_tolerance=1024, device=0, max_p
             lists.one_by_one(results, ks, alone)
             continue
         main, art = made
-
-        def take(sb, q, n_pivots):
-            p = problems[ks[q]]
-            M, b = sb.download(q)
-            t = SingleTableau(p, p, M, b, sb.cols - 1, sb.rows - 1, lows[q].mapping, fp_tolerance, device)
-            t.n_pivots = n_pivots
-            return t
-        lists.place(results, ks, solve_made_batches([main] if art is None else [art, main], lows[0].is_max, take,
-                                                    fp_tolerance, max_pivots, chunk))
+        lists.place(results, ks, solve_made_batches([main] if art is None else [art, main], lows[0].is_max,
+                                                    taker(ks, lows), fp_tolerance, max_pivots, chunk))
     return lists.finish(results, errorp)
 
 
