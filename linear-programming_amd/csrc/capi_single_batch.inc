@@ -22,7 +22,7 @@ struct mi355x_sbatch {
     int         device = 0;
     SbView      v{};
     hipStream_t stream = nullptr;
-    int         form = 2;                 // 2: the member's tableau in LDS (k_sb_solve), 3: in HBM (k_sg_solve), 4: ragged (k_sr_solve)
+    int         form = 2;                 // 2: the member's tableau in LDS (k_sb_solve), 3: in HBM (SolveInHbm), 4: ragged (SrView)
     int         threads = 0;              // snapshot of the form's rule (or its hook) at create
     int         launch_cap = kSingleLaunchCap;
     int         members_per_cu = 0;       // hipOccupancyMaxActiveBlocksPerMultiprocessor of the form's solve kernel at this shape
@@ -31,11 +31,11 @@ struct mi355x_sbatch {
     std::vector<Ctl>     h;               // the control blocks as the last read-back left them
     std::vector<int32_t> h_phase;
     std::atomic<int> cancel{0};
-    // form 4 only (v keeps M, basis, ctl, the traces and n_lps; its rows, cols, ld and stride are 0)
+    // form 4 (v keeps M, basis, ctl, the traces and n_lps; its rows, cols, ld and stride are 0)
     SrView      r{};
     SrMember   *d_members = nullptr;      // r.members
     int32_t    *d_index = nullptr;        // the classes' member lists, one after the other
-    size_t      lds_max = 0;              // the largest member's single_lds_bytes
+    size_t      lds_max = 0;              // the dynamic LDS of the form's solve kernel for the largest member (forms 2, 3: every member)
     int64_t     m_total = 0;              // floats of all members as stored
     int64_t    *d_col_off = nullptr;      // mi355x_sbatch_readback_ragged: per member the columns of the members before it
     std::vector<SrMember> hm;             // the descriptors, host copy
@@ -64,6 +64,15 @@ void free_sbatch(mi355x_sbatch *b)
     delete b;
 }
 
+// the ONE failure path of a create: the handle(s) freed, "<what> failed: <the runtime's words>"
+int sb_failed(mi355x_sbatch *b, mi355x_sbatch *other, hipError_t e, const char *what)
+{
+    (void)hipGetLastError();
+    free_sbatch(b);
+    free_sbatch(other);
+    return fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "%s failed: %s", what, hipGetErrorString(e));
+}
+
 int sb_read(mi355x_sbatch *b, hipStream_t s, bool with_phase)
 {
     HIP_TRY(hipMemcpyAsync(b->h.data(), b->v.ctl, b->h.size() * sizeof(Ctl), hipMemcpyDeviceToHost, s));
@@ -74,6 +83,43 @@ int sb_read(mi355x_sbatch *b, hipStream_t s, bool with_phase)
 }
 
 inline bool sb_carried_on(int32_t st) { return st == kRunning || st == MI_MAX_PIVOTS; }
+
+// Member q's descriptor for any form: computed for a batch of one shape (sb_descriptor, the kernels' own rule; hm is
+// not made for those -- n_lps goes to 2^30), read from hm for a ragged one.
+SrMember sb_host_member(const mi355x_sbatch *b, int64_t q)
+{
+    return b->form == kSbFormRagged ? b->hm[(size_t)q] : sb_descriptor(b->v, q);
+}
+
+// The ONE skeleton of a handle, for every form: the host copies of the control blocks and the phase state, the stream,
+// the device buffers for n_lps members of n_floats floats and n_basis basis entries in all, the phase state zeroed
+// (zero_tableaux: the tableaux as well).  b is the caller's new handle with its form's fields filled in; on a failure
+// it is freed here.  what: the failure message's subject.
+int sb_alloc(mi355x_sbatch *b, int64_t n_lps, int64_t n_floats, int64_t n_basis, bool zero_tableaux, const char *what)
+{
+    SbView &v = b->v;
+    v.n_lps = n_lps;
+    v.trace_cap = MI355X_SBATCH_TRACE_CAP;
+    try {
+        b->h.resize((size_t)n_lps);
+        b->h_phase.assign((size_t)(2 * n_lps), 0);
+    } catch (const std::bad_alloc &) {
+        delete b;
+        return fail(MI_NO_MEMORY, "host allocation failed");
+    }
+    const size_t mbytes = (size_t)n_floats * sizeof(float);
+    hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc((void **)&v.M, mbytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&v.basis, (size_t)std::max<int64_t>(n_basis, 1) * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.ctl, (size_t)n_lps * sizeof(Ctl));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.trace_ec, (size_t)(n_lps * v.trace_cap) * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&v.trace_cr, (size_t)(n_lps * v.trace_cap) * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&b->d_phase, (size_t)(2 * n_lps) * sizeof(int32_t));
+    if (e == hipSuccess && zero_tableaux) e = hipMemsetAsync(v.M, 0, mbytes, b->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_phase, 0, (size_t)(2 * n_lps) * sizeof(int32_t), b->stream);
+    if (e != hipSuccess) return sb_failed(b, nullptr, e, what);
+    return MI_OK;
+}
 
 // An empty batch of the shape: the checks of mi355x_sbatch_create, the handle, its stream and its device buffers
 // (zero_padding: the tableaux zeroed where a row has padding -- for members that are uploaded tight).
@@ -93,21 +139,21 @@ int sb_new(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, int d
     if (!b) return fail(MI_NO_MEMORY, "host allocation failed");
     b->device = device;
     SbView &v = b->v;
-    v.n_lps = n_lps;
     v.rows = rows;
     v.cols = cols;
     v.ld = (cols + kSingleLdAlign - 1) / kSingleLdAlign * kSingleLdAlign;
     v.stride = rows * v.ld;
-    v.trace_cap = MI355X_SBATCH_TRACE_CAP;
     b->form = form;
     bool fits;
     if (form == kSbFormGlobal) {
         b->threads = g_sbatch_global_threads ? g_sbatch_global_threads : sgbatch_threads_for(rows, v.ld);
         b->launch_cap = g_sbatch_launch_cap ? g_sbatch_launch_cap : sgbatch_launch_cap_for(rows, v.ld);
+        b->lds_max = sgbatch_lds_bytes(v);
         fits = sgbatch_available(v, b->threads, &b->members_per_cu);
     } else {
         b->threads = g_sbatch_threads ? g_sbatch_threads : sbatch_threads_for(rows, cols);
         b->launch_cap = g_sbatch_launch_cap ? g_sbatch_launch_cap : kSingleLaunchCap;
+        b->lds_max = sbatch_lds_bytes(v);
         fits = sbatch_available(v, b->threads, &b->members_per_cu);
     }
     // the shapes the form does not hold (or may not have) are declined: the LDS form's members go one by one
@@ -117,29 +163,9 @@ int sb_new(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, int d
                     form == kSbFormGlobal ? "the pivot row and column snapshot of a" : "a",
                     (long long)rows, (long long)cols, (long long)kSingleLdsBudget);
     }
-    const int64_t nb = std::max<int64_t>(rows - 1, 1);
-    try {
-        b->h.resize((size_t)n_lps);
-        b->h_phase.assign((size_t)(2 * n_lps), 0);
-    } catch (const std::bad_alloc &) {
-        delete b;
-        return fail(MI_NO_MEMORY, "host allocation failed");
-    }
-    const size_t mbytes = (size_t)n_lps * (size_t)v.stride * sizeof(float);
-    hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&v.M, mbytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&v.basis, (size_t)(n_lps * nb) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.ctl, (size_t)n_lps * sizeof(Ctl));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.trace_ec, (size_t)(n_lps * v.trace_cap) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.trace_cr, (size_t)(n_lps * v.trace_cap) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_phase, (size_t)(2 * n_lps) * sizeof(int32_t));
-    if (e == hipSuccess && zero_padding && v.ld != v.cols) e = hipMemsetAsync(v.M, 0, mbytes, b->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(b->d_phase, 0, (size_t)(2 * n_lps) * sizeof(int32_t), b->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        free_sbatch(b);
-        return fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "single-float batch allocation failed: %s", hipGetErrorString(e));
-    }
+    const int rc = sb_alloc(b, n_lps, n_lps * v.stride, n_lps * std::max<int64_t>(rows - 1, 1), zero_padding && v.ld != v.cols,
+                            "single-float batch allocation");
+    if (rc != MI_OK) return rc;
     *out = b;
     return MI_OK;
 }
@@ -161,7 +187,7 @@ void sb_launch_solve(const mi355x_sbatch *b, int is_max, double f, const int32_t
 {
     if (b->form == kSbFormRagged)
         for (const SrClass &c : b->classes)                 // (one class holds every member: no list to go through)
-            launch_sr_solve(b->r, b->classes.size() == 1 ? nullptr : b->d_index + c.first, c.count, c.lds, b->threads, f,
+            launch_sb_solve(b->r, b->classes.size() == 1 ? nullptr : b->d_index + c.first, c.count, c.lds, b->threads, f,
                             b->launch_cap, gate, s);
     else if (b->form == kSbFormGlobal) launch_sg_solve(b->v, b->threads, is_max, f, b->launch_cap, gate, s);
     else launch_sb_solve(b->v, b->threads, is_max, f, b->launch_cap, gate, s);
@@ -172,7 +198,7 @@ void sb_launch_between(const mi355x_sbatch *art, const mi355x_sbatch *mt, double
 {
     if (art->form == kSbFormRagged)
         for (const SrClass &c : art->classes)
-            launch_sr_between(art->r, mt->r, art->classes.size() == 1 ? nullptr : art->d_index + c.first, c.count, c.lds,
+            launch_sb_between(art->r, mt->r, art->classes.size() == 1 ? nullptr : art->d_index + c.first, c.count, c.lds,
                               art->threads, art->d_phase, f, max_pivots, s);
     else if (art->form == kSbFormGlobal) launch_sg_between(art->v, mt->v, art->threads, art->d_phase, f, max_pivots, s);
     else launch_sb_between(art->v, mt->v, art->threads, art->d_phase, f, max_pivots, s);
@@ -203,12 +229,88 @@ int sb_create(mi355x_sbatch **out, int64_t n_lps, int64_t rows, int64_t cols, co
     if (e == hipSuccess && rows > 1)
         e = hipMemcpyAsync(v.basis, basis, (size_t)(n_lps * (rows - 1)) * sizeof(int64_t), hipMemcpyHostToDevice, b->stream);
     if (e == hipSuccess) e = sb_fresh_ctl(b);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        free_sbatch(b);
-        return fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "single-float batch upload failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return sb_failed(b, nullptr, e, "single-float batch upload");
     *out = b;
+    return MI_OK;
+}
+
+// device memory of a create, freed with the scope (the creates of capi_single_bb.inc, capi_single_lps.inc and capi_single_ragged_build.inc)
+struct SbDeviceMem {
+    void *mem = nullptr;
+    ~SbDeviceMem() { (void)hipFree(mem); }
+};
+inline size_t sb_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// The ONE (main, artificial) pair of batches around an assembly, for every form.  make(&handle, artificial) makes an
+// empty handle (sb_new, sr_new); two == false: no artificial batch.  The larger shape first: a pair the budget declines
+// allocates nothing.  fill(main, artificial or nullptr) -> hipError_t allocates, uploads and launches on the main
+// handle's stream; what it allocates has to live until this function returns.
+template <class Make, class Fill>
+int sb_pair_build(mi355x_sbatch **out_main, mi355x_sbatch **out_art, bool two, const char *what, Make make, Fill fill)
+{
+    mi355x_sbatch *mt = nullptr, *art = nullptr;
+    int rc = MI_OK;
+    if (two) rc = make(&art, true);
+    if (rc == MI_OK) rc = make(&mt, false);
+    if (rc != MI_OK) {
+        free_sbatch(mt);
+        free_sbatch(art);
+        return rc;
+    }
+    // the assembly runs on the main handle's stream and reads the artificial handle's descriptors where there are any
+    // (a ragged batch): they have landed
+    hipError_t e = art && art->d_members ? hipStreamSynchronize(art->stream) : hipSuccess;
+    if (e == hipSuccess) e = fill(mt, art);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = sb_fresh_ctl(mt);                              // (waits for the assembly as well)
+    if (e == hipSuccess && art) e = sb_fresh_ctl(art);
+    if (e != hipSuccess) return sb_failed(mt, art, e, what);
+    *out_main = mt;
+    *out_art = art;
+    return MI_OK;
+}
+// the pair of one shape (rows, cols) and n_art more columns in the artificial batch; form: both handles'
+template <class Fill>
+int sb_pair_build(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n, int64_t rows, int64_t cols, int64_t n_art,
+                  int device, const char *what, Fill fill, int form)
+{
+    return sb_pair_build(out_main, out_art, n_art != 0, what, [&](mi355x_sbatch **h, bool artificial) {
+        return sb_new(h, n, rows, artificial ? cols + n_art : cols, device, /*zero_padding=*/false, form);
+    }, [&](mi355x_sbatch *mt, mi355x_sbatch *art) { return fill(mt->stream, mt->v, art ? art->v : SbView{}); });
+}
+
+// The ONE body of the light read-back, for every form: the members' rows and columns in all say the three plane sizes
+// (a member has rows - 1 basis entries).  One buffer, the basis plane first (8-byte entries), then the two float
+// planes; one gather, one copy.
+int sb_readback(mi355x_sbatch *b, int64_t n_rows, int64_t n_cols, float *rhs, float *obj_row, int64_t *basis)
+{
+    HIP_TRY(hipSetDevice(b->device));
+    const int64_t n = b->v.n_lps;
+    const size_t nbasis = (size_t)(n_rows - n) * sizeof(int64_t), nrhs = (size_t)n_rows * sizeof(float), nobj = (size_t)n_cols * sizeof(float);
+    std::vector<char> host;
+    try {
+        if (b->form == kSbFormRagged && !b->d_col_off) {                    // (once per handle: the running sums of cols)
+            std::vector<int64_t> off((size_t)n);
+            int64_t c = 0;
+            for (int64_t q = 0; q < n; ++q) { off[q] = c; c += b->hm[q].cols; }
+            HIP_TRY(hipMalloc((void **)&b->d_col_off, (size_t)n * sizeof(int64_t)));
+            HIP_TRY(hipMemcpy(b->d_col_off, off.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
+        }
+        host.resize(nbasis + nrhs + nobj);
+    } catch (const std::bad_alloc &) {
+        return fail(MI_NO_MEMORY, "host allocation failed");
+    }
+    if (!b->rb) HIP_TRY(hipMalloc(&b->rb, nbasis + nrhs + nobj));
+    char *d = (char *)b->rb;
+    float *d_rhs = (float *)(d + nbasis), *d_obj = (float *)(d + nbasis + nrhs);
+    if (b->form == kSbFormRagged) launch_sb_readback(b->r, b->d_col_off, d_rhs, d_obj, (int64_t *)d, b->stream);
+    else launch_sb_readback(b->v, d_rhs, d_obj, (int64_t *)d, b->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host.data(), d, host.size(), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (nbasis > 0) std::memcpy(basis, host.data(), nbasis);
+    std::memcpy(rhs, host.data() + nbasis, nrhs);
+    std::memcpy(obj_row, host.data() + nbasis + nrhs, nobj);
     return MI_OK;
 }
 
@@ -234,22 +336,13 @@ int mi355x_sbatch_info(const mi355x_sbatch *b, int64_t *n_lps, int64_t *rows, in
                        int *workgroup_threads, int64_t *lds_bytes_per_member, int *members_per_cu)
 {
     if (!b) return fail(MI_BAD_ARG, "handle is NULL");
+    // (a ragged batch has no one shape: its v says 0; the largest member's LDS, the smallest class's residency)
     if (n_lps) *n_lps = b->v.n_lps;
-    if (b->form == kSbFormRagged) {                        // no one shape: 0; the largest member's LDS, the smallest class
-        if (rows) *rows = 0;
-        if (cols) *cols = 0;
-        if (ld) *ld = 0;
-        if (workgroup_threads) *workgroup_threads = b->threads;
-        if (lds_bytes_per_member) *lds_bytes_per_member = (int64_t)b->lds_max;
-        if (members_per_cu) *members_per_cu = b->members_per_cu;
-        return MI_OK;
-    }
     if (rows) *rows = b->v.rows;
     if (cols) *cols = b->v.cols;
     if (ld) *ld = b->v.ld;
     if (workgroup_threads) *workgroup_threads = b->threads;
-    if (lds_bytes_per_member)
-        *lds_bytes_per_member = (int64_t)(b->form == kSbFormGlobal ? sgbatch_lds_bytes(b->v) : sbatch_lds_bytes(b->v));
+    if (lds_bytes_per_member) *lds_bytes_per_member = (int64_t)b->lds_max;
     if (members_per_cu) *members_per_cu = b->members_per_cu;
     return MI_OK;
 }
@@ -306,7 +399,7 @@ int mi355x_sbatch_solve_two_phase(mi355x_sbatch *art, mi355x_sbatch *mt, int mai
         return fail(MI_BAD_ARG, "artificial and main batch do not match");
     if (art->form != mt->form) return fail(MI_BAD_ARG, "artificial and main batch are of different forms");
     if (sb_check_sense(mt, main_is_max) != MI_OK) return MI_BAD_ARG;
-    if (art->form == kSbFormRagged)
+    if (art->form == kSbFormRagged)                        // (one shape: the test above has said it for every member)
         for (int64_t q = 0; q < art->v.n_lps; ++q)
             if (art->hm[q].rows != mt->hm[q].rows || art->hm[q].cols < mt->hm[q].cols)
                 return fail(MI_BAD_ARG, "artificial and main batch do not match at member %lld", (long long)q);
@@ -365,15 +458,9 @@ int mi355x_sbatch_download(mi355x_sbatch *b, int64_t q, float *hm, int64_t *hb, 
     if (!b) return fail(MI_BAD_ARG, "handle is NULL");
     if (q < 0 || q >= b->v.n_lps) return fail(MI_BAD_ARG, "lp_index %lld out of range [0,%lld)", (long long)q, (long long)b->v.n_lps);
     HIP_TRY(hipSetDevice(b->device));
-    const SbView &v = b->v;
-    int rc;
-    if (b->form == kSbFormRagged) {
-        const SrMember &d = b->hm[q];
-        rc = download_parts(v.M + d.m_off, d.ld, d.rows, d.cols, v.basis + d.basis_off, b->stream, hm, hb, last_row, last_col);
-    } else {
-        rc = download_parts(v.M + q * v.stride, v.ld, v.rows, v.cols, v.basis + q * (v.rows - 1), b->stream, hm, hb,
-                            last_row, last_col);
-    }
+    const SrMember d = sb_host_member(b, q);
+    const int rc = download_parts(b->v.M + d.m_off, d.ld, d.rows, d.cols, b->v.basis + d.basis_off, b->stream, hm, hb,
+                                  last_row, last_col);
     if (rc != MI_OK) return rc;
     HIP_TRY(hipStreamSynchronize(b->stream));
     return MI_OK;

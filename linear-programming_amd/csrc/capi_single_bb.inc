@@ -1,6 +1,6 @@
 // capi_single_bb.inc -- single-float branch-and-bound (simplex-solver in single-float, src/simplex.lisp:462-542):
 // node batches assembled on the device and the light read-back.  Part of simplex_capi.hip (ONE translation unit:
-// included there after capi_single_batch.inc, whose handle and sb_new / sb_fresh_ctl it uses).
+// included there after capi_single_batch.inc, whose handle, sb_pair_build, SbDeviceMem and sb_readback it uses).
 //
 // The search itself, build-tableau of the base problem (with Lisp's contagion) and the reading of a solution stay in
 // the host language; the library turns (base, node rows) into the members of two mi355x_sbatch handles
@@ -43,40 +43,6 @@ inline float sbb_rhs(const SbbBase &b, int64_t var, int64_t bound)
 {
     const float f = (float)bound;
     return b.kind[var] == 2 ? f : f - b.off[var];
-}
-
-// the node's device-side arrays (and the global form's scratch planes), freed with the scope
-struct SbbNodeArrays {
-    int64_t *var = nullptr, *bound = nullptr;
-    int32_t *sense = nullptr, *scratch = nullptr;
-    ~SbbNodeArrays() { (void)hipFree(var); (void)hipFree(bound); (void)hipFree(sense); (void)hipFree(scratch); }
-};
-
-// a (main, artificial) pair of n-member batches on `device` around an assembly (also capi_single_lps.inc's):
-// fill(stream, main view, artificial view) -> hipError_t allocates, uploads and launches; what it allocates has to
-// live until this function returns.  n_art == 0: no artificial batch.  form: both handles' (kSbFormLds, kSbFormGlobal).
-template <class Fill>
-int sb_pair_build(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n, int64_t rows, int64_t cols, int64_t n_art,
-                  int device, const char *what, Fill fill, int form = kSbFormLds)
-{
-    mi355x_sbatch *mt = nullptr, *art = nullptr;
-    int rc = MI_OK;
-    // (the larger shape first: a pair the budget declines allocates nothing)
-    if (n_art) rc = sb_new(&art, n, rows, cols + n_art, device, /*zero_padding=*/false, form);
-    if (rc == MI_OK) rc = sb_new(&mt, n, rows, cols, device, /*zero_padding=*/false, form);
-    auto undo = [&](int code) { free_sbatch(mt); free_sbatch(art); return code; };
-    if (rc != MI_OK) return undo(rc);
-    hipError_t e = fill(mt->stream, mt->v, art ? art->v : SbView{});
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = sb_fresh_ctl(mt);                              // (waits for the assembly as well)
-    if (e == hipSuccess && art) e = sb_fresh_ctl(art);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return undo(fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "%s failed: %s", what, hipGetErrorString(e)));
-    }
-    *out_main = mt;
-    *out_art = art;
-    return MI_OK;
 }
 
 }  // namespace
@@ -215,22 +181,21 @@ int sbb_create_nodes(mi355x_sbatch **out_main, mi355x_sbatch **out_art, const mi
     const int64_t rows = b.rows + depth, cols = b.cols + depth;
     if (form == kSbFormLds && sbb_assemble_lds(rows - 1, depth) > kSbbAssembleLdsLimit)
         return fail(MI_UNSUPPORTED, "%lld rows at depth %lld do not fit the assembly's LDS", (long long)rows, (long long)depth);
-    SbbNodeArrays nd;
+    SbDeviceMem nd;                                                         // var, bound, sense, the global form's scratch planes
     return sb_pair_build(out_main, out_art, n_nodes, rows, cols, n_art, b.device, "node assembly",
                          [&](hipStream_t s, const SbView &mv, const SbView &av) {
         const size_t nk = (size_t)(n_nodes * depth);
-        hipError_t e = hipMalloc((void **)&nd.var, nk * sizeof(int64_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&nd.bound, nk * sizeof(int64_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&nd.sense, nk * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMemcpyAsync(nd.var, var, nk * sizeof(int64_t), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(nd.bound, bound, nk * sizeof(int64_t), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(nd.sense, sense, nk * sizeof(int32_t), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess && form == kSbFormGlobal)
-            e = hipMalloc((void **)&nd.scratch, sga_nodes_scratch_bytes(n_nodes, rows - 1));
+        const size_t oB = sb_align(nk * sizeof(int64_t)), oS = oB + sb_align(nk * sizeof(int64_t));
+        const size_t oW = oS + sb_align(nk * sizeof(int32_t));
+        hipError_t e = hipMalloc(&nd.mem, form == kSbFormGlobal ? oW + sga_nodes_scratch_bytes(n_nodes, rows - 1) : oW);
+        char *p = (char *)nd.mem;
+        if (e == hipSuccess) e = hipMemcpyAsync(p, var, nk * sizeof(int64_t), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(p + oB, bound, nk * sizeof(int64_t), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(p + oS, sense, nk * sizeof(int32_t), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) {
             const SbbBaseView bv{b.d_B, b.d_off, b.rows, b.cols, b.ncv, b.nb, b.d_basis, b.d_kind, b.d_vcol};
-            const XbbNodeRows nr{nd.var, nd.sense, nd.bound, depth};
-            if (form == kSbFormGlobal) launch_sga_nodes(mv, av, bv, nr, nd.scratch, s);
+            const XbbNodeRows nr{(const int64_t *)p, (const int32_t *)(p + oS), (const int64_t *)(p + oB), depth};
+            if (form == kSbFormGlobal) launch_sga_nodes(mv, av, bv, nr, (int32_t *)(p + oW), s);
             else launch_sbb_assemble(mv, av, bv, nr, s);
         }
         return e;
@@ -263,26 +228,7 @@ int mi355x_sbatch_readback(mi355x_sbatch *b, float *rhs, float *obj_row, int64_t
         return fail(MI_UNSUPPORTED, "mi355x_sbatch_readback gathers planes of one shape: not on a ragged batch (form 4)");
     const SbView &v = b->v;
     if (v.rows > 1 && !basis) return fail(MI_BAD_ARG, "basis is NULL");
-    HIP_TRY(hipSetDevice(b->device));
-    // one buffer: the basis plane first (8-byte entries), then the two float planes
-    const size_t n = (size_t)v.n_lps, m = (size_t)v.rows - 1;
-    const size_t nbasis = n * m * sizeof(int64_t), nrhs = n * (size_t)v.rows * sizeof(float), nobj = n * (size_t)v.cols * sizeof(float);
-    if (!b->rb) HIP_TRY(hipMalloc(&b->rb, nbasis + nrhs + nobj));
-    char *d = (char *)b->rb;
-    launch_sb_readback(v, (float *)(d + nbasis), (float *)(d + nbasis + nrhs), (int64_t *)d, b->stream);
-    HIP_TRY(hipGetLastError());
-    std::vector<char> host;
-    try {
-        host.resize(nbasis + nrhs + nobj);
-    } catch (const std::bad_alloc &) {
-        return fail(MI_NO_MEMORY, "host allocation failed");
-    }
-    HIP_TRY(hipMemcpyAsync(host.data(), d, host.size(), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    if (m > 0) std::memcpy(basis, host.data(), nbasis);
-    std::memcpy(rhs, host.data() + nbasis, nrhs);
-    std::memcpy(obj_row, host.data() + nbasis + nrhs, nobj);
-    return MI_OK;
+    return sb_readback(b, v.n_lps * v.rows, v.n_lps * v.cols, rhs, obj_row, basis);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // capi_single_lps.inc -- mi355x_sbatch_create_lps: batches of single-float LPs whose tableaux the device builds from
 // the members' problem rows (build-tableau, src/simplex.lisp:243-328, under Lisp's int / single-float contagion:
 // kernels_single_lps.inc).  Part of simplex_capi.hip (ONE translation unit: included there after capi_single_bb.inc;
-// the handle is capi_single_batch.inc's, kSbbExactInts and sb_pair_build capi_single_bb.inc's, lps_check
+// the handle, sb_pair_build and SbDeviceMem are capi_single_batch.inc's, kSbbExactInts capi_single_bb.inc's, lps_check
 // capi_assemble.inc's).
 //
 // A zero in a negated row is read as Lisp's INTEGER zero and comes out +0.0; a single-float zero the user wrote
@@ -16,12 +16,15 @@
 
 namespace {
 
-// the members' rows and senses on the device (one allocation; behind them the global form's scratch planes), freed
-// with the scope
-struct SlpRows {
-    void *mem = nullptr;
-    ~SlpRows() { (void)hipFree(mem); }
-};
+// The guard of one member from rows (sums: its ncv + 1 column sums; see the head of this file), with its message
+int slp_guard(int64_t q, int64_t ncv, const double *sums)
+{
+    for (int64_t c = 0; c <= ncv; ++c)
+        if (!(sums[c] <= kSbbExactInts))
+            return fail(MI_UNSUPPORTED, "member %lld: the integer entries of column %lld sum beyond 2^24: the float "
+                        "sum of the artificial objective row would not be the reference's", (long long)q, (long long)c);
+    return MI_OK;
+}
 
 // mi355x_sbatch_lps_global_timing (measurement aid): HIP events around the three passes of the global form's assembly
 std::atomic<int> g_slpg_timing{0};
@@ -37,23 +40,19 @@ int slp_create(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n_lps,
     int64_t n_eq = 0, n_art = 0;
     int rc = lps_check(n_lps, 30, m, ncv, lps, sense, &n_eq, &n_art);
     if (rc != MI_OK) return rc;
-    if (col_int_sum)                                                        // the guard (NULL: no entry is an integer)
-        for (int64_t q = 0; q < n_lps; ++q)
-            for (int64_t c = 0; c <= ncv; ++c)
-                if (!(col_int_sum[q * (ncv + 1) + c] <= kSbbExactInts))
-                    return fail(MI_UNSUPPORTED, "member %lld: the integer entries of column %lld sum beyond 2^24: the float "
-                                "sum of the artificial objective row would not be the reference's", (long long)q, (long long)c);
+    for (int64_t q = 0; col_int_sum && q < n_lps; ++q)                      // the guard (NULL: no entry is an integer)
+        if (slp_guard(q, ncv, col_int_sum + q * (ncv + 1)) != MI_OK) return MI_UNSUPPORTED;
     const int64_t rows = m + 1, cols = ncv + (m - n_eq) + 1;
     if (form == kSbFormLds && m > kSlpMaxRows)                              // (no tableau of so many rows fits the budget)
         return fail(MI_UNSUPPORTED, "a %lldx%lld single-float member does not fit the LDS budget of %lld bytes",
                     (long long)rows, (long long)cols, (long long)kSingleLdsBudget);
-    SlpRows d;
+    SbDeviceMem d;                                                          // rows, senses, the global form's scratch planes
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed = form == kSbFormGlobal && g_slpg_timing.load(std::memory_order_relaxed);
     rc = sb_pair_build(out_main, out_art, n_lps, rows, cols, n_art, device, "assembly from rows",
                          [&](hipStream_t s, const SbView &mv, const SbView &av) {
         const size_t bL = (size_t)n_lps * (size_t)rows * (size_t)(ncv + 1) * sizeof(float), bS = (size_t)n_lps * (size_t)m * sizeof(int32_t);
-        const size_t oS = (bL + 255) & ~(size_t)255, oW = (oS + bS + 255) & ~(size_t)255;
+        const size_t oS = sb_align(bL), oW = sb_align(oS + bS);
         hipError_t e = hipMalloc(&d.mem, form == kSbFormGlobal ? oW + sga_lps_scratch_bytes(n_lps, m) : oS + bS);
         const float *dL = (const float *)d.mem;
         const int32_t *dS = (const int32_t *)((const char *)d.mem + oS);
@@ -112,12 +111,11 @@ int mi355x_sbatch_debug_stored(mi355x_sbatch *b, int64_t k, float *out, int64_t 
     if (!b) return fail(MI_BAD_ARG, "handle is NULL");
     const SbView &v = b->v;
     if (k < 0 || k >= v.n_lps) return fail(MI_BAD_ARG, "lp_index %lld out of range", (long long)k);
-    const bool ragged = b->form == kSbFormRagged;         // (the member's own ld and rows)
-    const int64_t m_off = ragged ? b->hm[k].m_off : k * v.stride, stored = ragged ? b->hm[k].rows * b->hm[k].ld : v.stride;
-    if (ld) *ld = ragged ? b->hm[k].ld : v.ld;
+    const SrMember d = sb_host_member(b, k);
+    if (ld) *ld = d.ld;
     if (!out) return MI_OK;
     HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipMemcpyAsync(out, v.M + m_off, (size_t)stored * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(out, v.M + d.m_off, (size_t)(d.rows * d.ld) * sizeof(float), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return MI_OK;
 }

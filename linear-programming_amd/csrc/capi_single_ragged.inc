@@ -1,6 +1,6 @@
 // capi_single_ragged.inc -- mi355x_sbatch_create_ragged: n_lps SINGLE-FLOAT tableaux of their OWN shapes and senses
 // behind ONE mi355x_sbatch handle (form 4), one workgroup per member for its whole solve, the member's tableau in LDS
-// (kernels_single_ragged.inc).  The solve, download, trace, cancel and destroy entries are capi_single_batch.inc's,
+// (kernels_single_batch.inc over an SrView).  The solve, download, trace, cancel and destroy entries are capi_single_batch.inc's,
 // with their member-by-member contract: what a member ends with is what mi355x_stab_solve / _solve_two_phase
 // (n-solve-tableau, src/simplex.lisp:402-461) gives that member alone under the same sequence of calls.
 // A launch has one dynamic-LDS size.  The members are sorted at create into occupancy classes and a round is one
@@ -14,11 +14,7 @@
 namespace {
 constexpr int kSrMaxClass = 4;
 
-int sr_upload_failed(hipError_t e)
-{
-    return fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "ragged single-float batch allocation or upload failed: %s",
-                hipGetErrorString(e));
-}
+constexpr const char *kSrUpload = "ragged single-float batch allocation or upload";
 
 // The skeleton of a ragged batch, in two steps around the device check.
 // sr_check_shapes: the members' shapes against sb_new's limits (MI_BAD_ARG, no device is looked for); *n_basis: their
@@ -76,12 +72,8 @@ int sr_new(mi355x_sbatch **out, int64_t n_lps, const int64_t *rows, const int64_
                     (long long)kSingleLdsBudget);
     }
     SbView &v = b->v;
-    v.n_lps = n_lps;
-    v.trace_cap = MI355X_SBATCH_TRACE_CAP;
     int64_t m_total = 0;
     try {
-        b->h.resize((size_t)n_lps);
-        b->h_phase.assign((size_t)(2 * n_lps), 0);
         b->hm.resize((size_t)n_lps);
         b->member_class.resize((size_t)n_lps);
         index.resize((size_t)n_lps);
@@ -141,26 +133,15 @@ int sr_new(mi355x_sbatch **out, int64_t n_lps, const int64_t *rows, const int64_
     }
     b->members_per_cu = b->classes.front().per_cu;          // the smallest class
 
-    const size_t nb_alloc = (size_t)std::max<int64_t>(n_basis, 1);
-    hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&v.M, (size_t)m_total * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.basis, nb_alloc * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.ctl, (size_t)n_lps * sizeof(Ctl));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.trace_ec, (size_t)(n_lps * v.trace_cap) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&v.trace_cr, (size_t)(n_lps * v.trace_cap) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_phase, (size_t)(2 * n_lps) * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_members, (size_t)n_lps * sizeof(SrMember));
+    const int rc = sb_alloc(b, n_lps, m_total, n_basis, /*zero_tableaux=*/false, kSrUpload);
+    if (rc != MI_OK) return rc;
+    hipError_t e = hipMalloc((void **)&b->d_members, (size_t)n_lps * sizeof(SrMember));
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_index, (size_t)n_lps * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(b->d_phase, 0, (size_t)(2 * n_lps) * sizeof(int32_t), b->stream);
     if (e == hipSuccess)
         e = hipMemcpyAsync(b->d_members, b->hm.data(), (size_t)n_lps * sizeof(SrMember), hipMemcpyHostToDevice, b->stream);
     if (e == hipSuccess)
         e = hipMemcpyAsync(b->d_index, index.data(), (size_t)n_lps * sizeof(int32_t), hipMemcpyHostToDevice, b->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        free_sbatch(b);
-        return sr_upload_failed(e);
-    }
+    if (e != hipSuccess) return sb_failed(b, nullptr, e, kSrUpload);
     SrView &r = b->r;
     r.M = v.M; r.basis = v.basis; r.ctl = v.ctl;
     r.trace_ec = v.trace_ec; r.trace_cr = v.trace_cr; r.trace_cap = v.trace_cap;
@@ -212,11 +193,7 @@ int mi355x_sbatch_create_ragged(mi355x_sbatch **out, int64_t n_lps, const int64_
     if (e == hipSuccess && n_basis > 0)
         e = hipMemcpyAsync(v.basis, basis, (size_t)n_basis * sizeof(int64_t), hipMemcpyHostToDevice, b->stream);
     if (e == hipSuccess) e = sb_fresh_ctl(b);               // (waits for the stream: the staged copies are done)
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        free_sbatch(b);
-        return sr_upload_failed(e);
-    }
+    if (e != hipSuccess) return sb_failed(b, nullptr, e, kSrUpload);
     *out = b;
     return MI_OK;
 }
@@ -226,20 +203,13 @@ int mi355x_sbatch_member_shape(const mi355x_sbatch *b, int64_t q, int64_t *rows,
 {
     if (!b) return fail(MI_BAD_ARG, "handle is NULL");
     if (q < 0 || q >= b->v.n_lps) return fail(MI_BAD_ARG, "lp_index %lld out of range [0,%lld)", (long long)q, (long long)b->v.n_lps);
-    if (b->form != kSbFormRagged) {                        // one shape, the sense is the solve call's
-        if (rows) *rows = b->v.rows;
-        if (cols) *cols = b->v.cols;
-        if (ld) *ld = b->v.ld;
-        if (is_max) *is_max = -1;
-        if (occupancy_class) *occupancy_class = b->members_per_cu;
-        return MI_OK;
-    }
-    const SrMember &d = b->hm[(size_t)q];
+    const bool ragged = b->form == kSbFormRagged;         // (one shape: the sense is the solve call's, one class)
+    const SrMember d = sb_host_member(b, q);
     if (rows) *rows = d.rows;
     if (cols) *cols = d.cols;
     if (ld) *ld = d.ld;
-    if (is_max) *is_max = d.sgn > 0.0f ? 1 : 0;
-    if (occupancy_class) *occupancy_class = b->classes[(size_t)b->member_class[(size_t)q]].per_cu;
+    if (is_max) *is_max = !ragged ? -1 : d.sgn > 0.0f ? 1 : 0;
+    if (occupancy_class) *occupancy_class = ragged ? b->classes[(size_t)b->member_class[(size_t)q]].per_cu : b->members_per_cu;
     return MI_OK;
 }
 

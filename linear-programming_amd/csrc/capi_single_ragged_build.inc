@@ -3,7 +3,7 @@
 // under Lisp's int / single-float contagion), mi355x_sbatch_create_nodes_ragged from a branch-and-bound base and node
 // rows of any depths (:214-221, :230-237), and mi355x_sbatch_readback_ragged, the light read-back (:74-107).
 // The rules, the zero of a negated row and the 2^24 guard are those of capi_single_lps.inc and capi_single_bb.inc;
-// the kernels are theirs around a ragged member's slot (kernels_single_ragged_build.inc).  The handles are ordinary
+// the kernels are theirs, instantiated for a ragged view.  The handles are ordinary
 // form-4 handles: sr_new makes them, every entry of capi_single_batch.inc works on them.
 // All or none: either no member has artificial rows (*out_art = NULL), or every member has at least one -- the counts
 // may differ -- and the result is a pair.  A mixture is MI_BAD_ARG; the caller splits its list.
@@ -11,48 +11,25 @@
 
 namespace {
 
-// device memory of a create, freed with the scope
-struct SrBuildMem {
-    void *mem = nullptr;
-    ~SrBuildMem() { (void)hipFree(mem); }
-};
-
-inline size_t sr_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// the pair of form-4 handles of main shapes (rows, cols) and n_art more columns per member (two == false: no artificial
-// batch) around an assembly: fill(stream, main view, artificial view) -> hipError_t allocates, uploads and launches on
-// the main handle's stream; what it allocates has to live until this function returns.  The larger shapes first: a
-// pair the budget declines allocates nothing.
+// the pair of form-4 handles of main shapes (rows, cols) and artificial shapes (rows, acols) (two == false: no
+// artificial batch) around an assembly: sb_pair_build behind the shapes' and the device's checks.  fill(stream, main
+// view, artificial view) as for a pair of one shape.
 template <class Fill>
 int sr_pair_build(mi355x_sbatch **out_main, mi355x_sbatch **out_art, int64_t n, const std::vector<int64_t> &rows,
                   const std::vector<int64_t> &cols, const std::vector<int64_t> &acols, const int32_t *is_max, bool two, int device,
                   const char *what, Fill fill)
 {
     int64_t n_basis = 0;
-    int rc = sr_check_shapes(n, rows.data(), two ? acols.data() : cols.data(), &n_basis);
+    const int rc = sr_check_shapes(n, rows.data(), two ? acols.data() : cols.data(), &n_basis);
     if (rc != MI_OK) return rc;
     const int ndev = device_count_checked();
     if (ndev <= 0) return fail(MI_NO_DEVICE, "no HIP device visible (this library has no CPU path)");
     if (device < 0 || device >= ndev) return fail(MI_BAD_ARG, "device %d out of range [0,%d)", device, ndev);
-    mi355x_sbatch *mt = nullptr, *art = nullptr;
-    std::vector<int32_t> index_m, index_a;
-    if (two) rc = sr_new(&art, n, rows.data(), acols.data(), nullptr, n_basis, device, index_a);
-    if (rc == MI_OK) rc = sr_new(&mt, n, rows.data(), cols.data(), is_max, n_basis, device, index_m);
-    auto undo = [&](int code) { free_sbatch(mt); free_sbatch(art); return code; };
-    if (rc != MI_OK) return undo(rc);
-    // the assembly runs on the main handle's stream and reads the artificial handle's descriptors: they have landed
-    hipError_t e = art ? hipStreamSynchronize(art->stream) : hipSuccess;
-    if (e == hipSuccess) e = fill(mt->stream, mt->r, art ? art->r : SrView{});
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = sb_fresh_ctl(mt);                              // (waits for the assembly as well)
-    if (e == hipSuccess && art) e = sb_fresh_ctl(art);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return undo(fail(e == hipErrorOutOfMemory ? MI_NO_MEMORY : MI_HIP_ERROR, "%s failed: %s", what, hipGetErrorString(e)));
-    }
-    *out_main = mt;
-    *out_art = art;
-    return MI_OK;
+    std::vector<int32_t> index_m, index_a;                                  // (alive until the streams have been waited for)
+    return sb_pair_build(out_main, out_art, two, what, [&](mi355x_sbatch **h, bool artificial) {
+        return artificial ? sr_new(h, n, rows.data(), acols.data(), nullptr, n_basis, device, index_a)
+                          : sr_new(h, n, rows.data(), cols.data(), is_max, n_basis, device, index_m);
+    }, [&](mi355x_sbatch *mt, mi355x_sbatch *art) { return fill(mt->stream, mt->r, art ? art->r : SrView{}); });
 }
 
 // the all-or-none rule: member q has n_art artificial rows, the members before it were `two` (-1: q is the first)
@@ -119,29 +96,24 @@ int mi355x_sbatch_create_lps_ragged(mi355x_sbatch **out_main, mi355x_sbatch **ou
         l_off += (m[q] + 1) * (ncv[q] + 1);
         s_off += m[q];
     }
-    if (col_int_sum) {                                                      // the guard (NULL: no entry is an integer)
-        const double *sums = col_int_sum;
-        for (int64_t q = 0; q < n_lps; sums += ncv[q] + 1, ++q)
-            for (int64_t c = 0; c <= ncv[q]; ++c)
-                if (!(sums[c] <= kSbbExactInts))
-                    return fail(MI_UNSUPPORTED, "member %lld: the integer entries of column %lld sum beyond 2^24: the float "
-                                "sum of the artificial objective row would not be the reference's", (long long)q, (long long)c);
-    }
+    const double *sums = col_int_sum;                                       // the guard (NULL: no entry is an integer)
+    for (int64_t q = 0; sums && q < n_lps; sums += ncv[q] + 1, ++q)
+        if (slp_guard(q, ncv[q], sums) != MI_OK) return MI_UNSUPPORTED;
     for (int64_t q = 0; q < n_lps; ++q)                                     // (a two-phase member: its artificial shape)
         if (m[q] > kSlpMaxRows || !sr_fits(rows[q], two ? acols[q] : cols[q]))
             return sr_budget_declined("member", q, rows[q], two ? acols[q] : cols[q]);
-    SrBuildMem d;
+    SbDeviceMem d;
     return sr_pair_build(out_main, out_art, n_lps, rows, cols, acols, is_max, two == 1, device, "ragged assembly from rows",
                          [&](hipStream_t s, const SrView &mv, const SrView &av) {
         const size_t bL = (size_t)l_off * sizeof(float), bS = (size_t)s_off * sizeof(int32_t), bD = (size_t)n_lps * sizeof(SrlpMember);
-        const size_t oS = sr_align(bL), oD = sr_align(oS + bS);
+        const size_t oS = sb_align(bL), oD = sb_align(oS + bS);
         hipError_t e = hipMalloc(&d.mem, oD + bD);
         if (e == hipSuccess) e = hipMemcpyAsync(d.mem, lps, bL, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync((char *)d.mem + oS, sense, bS, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync((char *)d.mem + oD, desc.data(), bD, hipMemcpyHostToDevice, s);
         if (e == hipSuccess)
-            launch_srlp_assemble(mv, av, (const float *)d.mem, (const int32_t *)((const char *)d.mem + oS),
-                                 (const SrlpMember *)((const char *)d.mem + oD), s);
+            launch_slp_assemble(mv, av, SrlpView{(const float *)d.mem, (const int32_t *)((const char *)d.mem + oS),
+                                                 (const SrlpMember *)((const char *)d.mem + oD)}, s);
         return e;
     });
 }
@@ -201,12 +173,12 @@ int mi355x_sbatch_create_nodes_ragged(mi355x_sbatch **out_main, mi355x_sbatch **
     if (budget_declined >= 0)
         return sr_budget_declined("node", budget_declined, rows[budget_declined], (two ? acols : cols)[budget_declined]);
     for (int64_t q = 0; q < n_nodes; ++q) senses[q] = b.is_max;
-    SrBuildMem d;
+    SbDeviceMem d;
     return sr_pair_build(out_main, out_art, n_nodes, rows, cols, acols, senses.data(), two == 1, b.device, "ragged node assembly",
                          [&](hipStream_t s, const SrView &mv, const SrView &av) {
         const size_t nk = (size_t)off;
-        const size_t oB = sr_align(nk * sizeof(int64_t)), oS = oB + sr_align(nk * sizeof(int64_t));
-        const size_t oD = oS + sr_align(nk * sizeof(int32_t)), bD = (size_t)n_nodes * sizeof(SrbbNode);
+        const size_t oB = sb_align(nk * sizeof(int64_t)), oS = oB + sb_align(nk * sizeof(int64_t));
+        const size_t oD = oS + sb_align(nk * sizeof(int32_t)), bD = (size_t)n_nodes * sizeof(SrbbNode);
         hipError_t e = hipMalloc(&d.mem, oD + bD);
         char *p = (char *)d.mem;
         if (e == hipSuccess) e = hipMemcpyAsync(p, var, nk * sizeof(int64_t), hipMemcpyHostToDevice, s);
@@ -215,8 +187,8 @@ int mi355x_sbatch_create_nodes_ragged(mi355x_sbatch **out_main, mi355x_sbatch **
         if (e == hipSuccess) e = hipMemcpyAsync(p + oD, desc.data(), bD, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) {
             const SbbBaseView bv{b.d_B, b.d_off, b.rows, b.cols, b.ncv, b.nb, b.d_basis, b.d_kind, b.d_vcol};
-            launch_srbb_assemble(mv, av, bv, (const int64_t *)p, (const int32_t *)(p + oS), (const int64_t *)(p + oB),
-                                 (const SrbbNode *)(p + oD), lds, s);
+            launch_sbb_assemble(mv, av, bv, SrbbNodeRows{(const int64_t *)p, (const int32_t *)(p + oS), (const int64_t *)(p + oB),
+                                                         (const SrbbNode *)(p + oD)}, lds, s);
         }
         return e;
     });
@@ -232,34 +204,8 @@ int mi355x_sbatch_readback_ragged(mi355x_sbatch *b, float *rhs, float *obj_row, 
     const int64_t n = b->v.n_lps;
     int64_t n_rows = 0, n_cols = 0;
     for (int64_t q = 0; q < n; ++q) { n_rows += b->hm[q].rows; n_cols += b->hm[q].cols; }
-    const int64_t n_basis = n_rows - n;
-    if (n_basis > 0 && !basis) return fail(MI_BAD_ARG, "basis is NULL");
-    HIP_TRY(hipSetDevice(b->device));
-    // one buffer: the basis plane first (8-byte entries), then the two float planes
-    const size_t nbasis = (size_t)n_basis * sizeof(int64_t), nrhs = (size_t)n_rows * sizeof(float), nobj = (size_t)n_cols * sizeof(float);
-    std::vector<char> host;
-    try {
-        if (!b->d_col_off) {                                                // (once per handle: the running sums of cols)
-            std::vector<int64_t> off((size_t)n);
-            int64_t c = 0;
-            for (int64_t q = 0; q < n; ++q) { off[q] = c; c += b->hm[q].cols; }
-            HIP_TRY(hipMalloc((void **)&b->d_col_off, (size_t)n * sizeof(int64_t)));
-            HIP_TRY(hipMemcpy(b->d_col_off, off.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
-        }
-        host.resize(nbasis + nrhs + nobj);
-    } catch (const std::bad_alloc &) {
-        return fail(MI_NO_MEMORY, "host allocation failed");
-    }
-    if (!b->rb) HIP_TRY(hipMalloc(&b->rb, nbasis + nrhs + nobj));
-    char *d = (char *)b->rb;
-    launch_sr_readback(b->r, b->d_col_off, (float *)(d + nbasis), (float *)(d + nbasis + nrhs), (int64_t *)d, b->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(host.data(), d, host.size(), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    if (n_basis > 0) std::memcpy(basis, host.data(), nbasis);
-    std::memcpy(rhs, host.data() + nbasis, nrhs);
-    std::memcpy(obj_row, host.data() + nbasis + nrhs, nobj);
-    return MI_OK;
+    if (n_rows - n > 0 && !basis) return fail(MI_BAD_ARG, "basis is NULL");
+    return sb_readback(b, n_rows, n_cols, rhs, obj_row, basis);
 }
 
 }  // extern "C"

@@ -9,12 +9,29 @@
 //   * its objective row is the sum of the artificial rows in INCREASING row order from +0.0, one rounded addition
 //     per row (:302-316), over the structural and slack columns and the right-hand side, +0.0 elsewhere;
 //   * the main basis of an artificial row is the member's num-cols, the artificial basis is ab[] itself.
-// The HBM family (doubles, kernels_bb.inc and kernels_batch_lps.inc) has ab[] in a per-member scratch plane and
-// spreads a member over a grid; the LDS family (floats, kernels_single_bb.inc and kernels_single_lps.inc) has it in
-// LDS, one workgroup per member.  The exact kernels share only the rules of simplex_kernels.h: their entries carry
-// a scale and an overflow status of their own.
+// The HBM family has ab[] in a per-member scratch plane and spreads a member over a grid: doubles (k_assemble<Src> here,
+// sources in kernels_bb.inc and kernels_batch_lps.inc) and floats (k_sga_write<Src> of
+// kernels_single_assemble_global.inc, the global form of a single-float batch, with quad stores and a grid of its own).
+// The LDS family (floats, kernels_single_bb.inc and kernels_single_lps.inc) has ab[] in LDS, one workgroup per member.
+// All three write passes state the artificial tableau's entry and its objective row's columns through art_entry and
+// art_objective_column below.  The exact kernels share only the rules of simplex_kernels.h: their entries carry a
+// scale and an overflow status of their own.
 
 constexpr int kAssembleThreads = 256;
+
+// ---- the artificial tableau, ONE statement for every write pass (T: the scalar, I: the pass's index type).
+// Entry C of constraint row R, whose ab[] entry is acol (a slack column is < num_cols - 1); main(c): entry c <
+// num_cols of that row of the main tableau; nac: the artificial tableau's columns.
+template <class T, class I, class Main>
+__device__ __forceinline__ T art_entry(I C, I num_cols, I nac, I acol, Main main)
+{
+    if (C < num_cols - 1) return main(C);
+    if (C == nac - 1) return main(num_cols - 1);
+    return C == acol ? T(1) : T(0);
+}
+// the columns of the artificial objective row that are a sum over the artificial rows (+0.0 elsewhere)
+template <class I>
+__device__ __forceinline__ bool art_objective_column(I C, I num_cols, I nac) { return C < num_cols - 1 || C == nac - 1; }
 
 // ---- HBM family.  A source Src is passed by value and has
 //   kWords                      int32 words of scratch per constraint row: plane 0 is ab[], written by the source's
@@ -39,13 +56,8 @@ __global__ __launch_bounds__(kAssembleThreads) void k_assemble(TabView mt, TabVi
             M[R * mt.ld + C] = C < num_cols ? src.elem(row, C) : 0.0;
         if (!A || R == m) continue;
         const int64_t acol = ab[R];                                         // (a slack column is < num_cols - 1)
-        for (int64_t C = c0; C < at.ld; C += cstep) {
-            double x = 0.0;
-            if (C < num_cols - 1) x = src.elem(row, C);
-            else if (C == nac - 1) x = src.elem(row, num_cols - 1);
-            else if (C == acol) x = 1.0;
-            A[R * at.ld + C] = x;
-        }
+        for (int64_t C = c0; C < at.ld; C += cstep)
+            A[R * at.ld + C] = art_entry<double>(C, num_cols, nac, acol, [&](int64_t c) { return src.elem(row, c); });
     }
 }
 
@@ -58,7 +70,7 @@ __global__ __launch_bounds__(kAssembleThreads) void k_art_objective(TabView at, 
     double *A = at.M + z * at.zs_M;
     for (int64_t C = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; C < at.ld; C += (int64_t)gridDim.x * blockDim.x) {
         double s = 0.0;
-        if (C < num_cols - 1 || C == nac - 1)
+        if (art_objective_column(C, num_cols, nac))
             for (int64_t R = 0; R < m; ++R)
                 if (ab_artificial(ab[R], (int32_t)num_cols)) s = __dadd_rn(s, A[R * at.ld + C]);
         A[m * at.ld + C] = s;
@@ -85,17 +97,13 @@ void launch_assemble(const TabView &mt, const TabView &at, const Src &src, const
 }
 
 // ---- LDS family: one member per workgroup of kAssembleThreads threads, ab[] (m entries, dealt) in LDS and visible to
-// every thread.  Where a member's tableau and basis live is a slot: a batch of one shape makes it from its SbView
-// (sb_slot), a ragged batch from its SrView and the member's SrMember (kernels_single_ragged_build.inc).
+// every thread.  Where a member's tableau and basis live is a slot: sb_slot of the member view
+// (kernels_single_batch.inc) makes it from a batch's view and the member's descriptor.
 struct AsmSlot {
     float   *M;           // the member's first row (nullptr: no such tableau)
     int64_t *basis;       // its m basis entries
     int      ld, cols;    // leading dimension and columns, in floats
 };
-__device__ __forceinline__ AsmSlot sb_slot(const SbView &v, int64_t q, int m)
-{
-    return AsmSlot{v.M ? v.M + q * v.stride : nullptr, v.basis + q * m, (int)v.ld, (int)v.cols};
-}
 
 // elem(R, C) is entry C < num_cols of row R <= m of the main tableau.  Both tableaux over their whole leading
 // dimension (padding +0.0), consecutive threads consecutive floats; at.M == nullptr: no artificial rows.
@@ -121,16 +129,12 @@ __device__ __forceinline__ void assemble_member_lds(const AsmSlot &mt, const Asm
         for (int R = tid; R < m; R += kAssembleThreads) abasis[R] = ab[R];
         for (int k = tid; k < m * ld; k += kAssembleThreads) {
             const int R = k / ld, C = k - R * ld;
-            float x = 0.0f;
-            if (C < num_cols - 1) x = elem(R, C);
-            else if (C == nac - 1) x = elem(R, num_cols - 1);
-            else if (C == ab[R]) x = 1.0f;
-            A[k] = x;
+            A[k] = art_entry<float>(C, num_cols, nac, (int)ab[R], [&](int c) { return elem(R, c); });
         }
         // the artificial objective row, recomputed from the entries (the rows above may not have landed yet)
         for (int C = tid; C < ld; C += kAssembleThreads) {
             float acc = 0.0f;
-            if (C < num_cols - 1 || C == nac - 1) {
+            if (art_objective_column(C, num_cols, nac)) {
                 const int src = C == nac - 1 ? num_cols - 1 : C;
                 for (int R = 0; R < m; ++R)
                     if (ab_artificial(ab[R], num_cols)) acc = acc + elem(R, src);

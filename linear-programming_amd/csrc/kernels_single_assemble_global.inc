@@ -18,8 +18,8 @@
 //                       right-hand side is < 0.0f (false for -0.0 and NaN) flips, slack columns in row order, the
 //                       artificial ranks from prefix counts.  One workgroup per member; a thread owns a chunk of rows
 //                       and the counts before the chunk come through LDS, so any m goes.
-//   k_sga_node_rows     row pass for node rows: k_sbb_assemble's classification -- rhs = float(bound) - offset, the
-//                       flip, the base's artificial rows renumbered -- with the same chunks and prefix counts in
+//   k_sga_node_rows     row pass for node rows: k_sbb_assemble's classification (sbb_node_row: rhs = float(bound) -
+//                       offset, the flip, the base's artificial rows renumbered) with the same chunks and prefix counts in
 //                       place of the serial deal.  Its LDS is static (two counts per thread): it has NO limit of the
 //                       kind k_sbb_assemble has (m + 3 d words in 48 KiB), every m and depth go.
 //   k_sga_write<Src>    the ONE write pass, templated over the source as k_assemble<Src> is: every entry of both
@@ -106,25 +106,24 @@ __global__ __launch_bounds__(kSgaThreads) void k_sga_lps_rows(SbView mt, SbView 
     int64_t *abasis = at.M ? at.basis + z * m : nullptr;
     for (int i = i0; i < i1; ++i) {
         const int w = sga_lps_word(sp, z, i), op = w >> 1;
-        const int32_t sc = op != 2 ? ncv + slack_before : -1;
-        slack_before += op != 2;
         art_through += op != 0;
-        // an artificial row's column: cols - 1 + the artificial rows with a greater index
-        const int32_t a = op == 0 ? sc : cols - 1 + (art_all - art_through);
+        int32_t sc, a;
+        slp_row_columns(w, ncv, cols, slack_before, art_through, art_all, sc, a);
+        slack_before += op != 2;
         ab[i] = a; word[i] = w; scol[i] = sc;
         mb[i] = ab_main_basis(a, cols);
         if (abasis) abasis[i] = a;
     }
 }
 
-// ---- source: a base tableau plus node rows.  Per row in scratch: ab[], and for a node row its right-hand side after
-// the flip (float bits), its variable's first column, its flags (kind bits 0-1, flipped bit 2, sense after the flip
-// bit 3: 1 `>=`) -- SbbLds' words, one plane each, read only at the node rows.
+// ---- source: a base tableau plus node rows.  Per row in scratch: ab[], and for a node row the words of SbbRow
+// (kernels_single_bb.inc: right-hand side after the flip as float bits, the variable's first column, the flags), one
+// plane each, read only at the node rows.  The classification and the entries are that file's sbb_node_row / sbb_elem.
 struct SgaNodeSrc {
     SbbBaseView b;
     int d;
     static constexpr int kWords = 4;
-    struct Row { const float *Br; float rhs; int col, flags, scol; };       // Br == nullptr: a node row
+    using Row = SbbRow;
     __host__ __device__ int m() const { return (int)(b.rows - 1) + d; }
     __host__ __device__ int num_cols() const { return (int)b.cols + d; }
     __device__ Row row(int64_t, int R, const int32_t *priv) const
@@ -134,65 +133,31 @@ struct SgaNodeSrc {
             return Row{nullptr, __int_as_float(priv[R]), priv[mm + R], priv[2 * mm + R], (int)b.ncv + R};
         return Row{b.B + (int64_t)(R < nb ? R : R - d) * b.cols, 0.0f, 0, 0, -1};   // base row (rows_b - 1: objective)
     }
-    __device__ float elem(const Row &r, int C) const
-    {
-        const int nb = (int)b.nb, ncv = (int)b.ncv, cols_b = (int)b.cols, last = cols_b + d - 1;
-        if (!r.Br) {
-            const int kind = r.flags & 3;
-            const bool flip = (r.flags & 4) != 0;
-            if (C == last) return r.rhs;
-            if (C == r.col) return ((kind == 1) != flip) ? -1.0f : 1.0f;
-            if (kind == 2 && C == r.col + 1) return flip ? 1.0f : -1.0f;
-            if (C == r.scol) return (r.flags & 8) ? -1.0f : 1.0f;
-            return 0.0f;
-        }
-        if (C == last) return r.Br[cols_b - 1];
-        if (C < ncv + nb) return r.Br[C];
-        if (C < ncv + nb + d) return 0.0f;                                   // (+0.0 also in a row build-tableau negated)
-        return r.Br[C - d];
-    }
+    __device__ float elem(const Row &r, int C) const { return sbb_elem(b, d, r, C); }
 };
-
-// row R of node q before the artificial columns are dealt: its ab[] entry (num_cols for an artificial row) and,
-// for a node row, the three words of SgaNodeSrc
-__device__ __forceinline__ int32_t sga_node_row(const SbbBaseView &b, const XbbNodeRows &nr, int64_t q, int R, float &rhs_out,
-                                                int32_t &col, int32_t &flags)
-{
-    const int d = (int)nr.d, nb = (int)b.nb, ncv = (int)b.ncv, num_cols = (int)b.cols + d;
-    if (R >= nb && R < nb + d) {
-        const int64_t i = q * d + (R - nb), v = nr.var[i];
-        const int kind = b.kind[v];
-        float rhs = (float)nr.bound[i];                                     // (a floor or ceiling of a float: exact)
-        if (kind != 2) rhs = rhs - b.voff[v];                               // coef 1, :230-237
-        const bool flip = rhs < 0.0f;
-        const int op = row_word(flip, nr.sense[i]) >> 1;
-        rhs_out = flip ? -rhs : rhs;
-        col = (int32_t)b.vcol[v];
-        flags = kind | (flip ? 4 : 0) | (op ? 8 : 0);
-        return op ? num_cols : ncv + R;
-    }
-    const int64_t bb = b.basis[R < nb ? R : R - d];
-    return (int32_t)(bb == b.cols ? num_cols : (bb >= ncv + nb ? bb + d : bb));
-}
 
 // Node blockIdx.x: the node rows' words, ab[] and both bases.  at.M == nullptr: no artificial rows.
 __global__ __launch_bounds__(kSgaThreads) void k_sga_node_rows(SbView mt, SbView at, SbbBaseView b, XbbNodeRows nr, int32_t *scratch)
 {
     const int64_t q = blockIdx.x;
     const int d = (int)nr.d, m = (int)(b.rows - 1) + d, num_cols = (int)b.cols + d;
+    const SbbNode nd = sbb_node(nr, q);
+    auto classify = [&](int R, float &rhs, int32_t &col, int32_t &flags) {
+        return sbb_node_row(b, nd.var, nd.sense, nd.bound, d, R, rhs, col, flags);
+    };
     int32_t *ab = scratch + q * SgaNodeSrc::kWords * m, *rhs_w = ab + m, *col_w = rhs_w + m, *flags_w = col_w + m;
     int i0, i1;
     sga_chunk(m, i0, i1);
     float rhs = 0.0f;
     int32_t col = 0, flags = 0, na = 0;
-    for (int R = i0; R < i1; ++R) na += sga_node_row(b, nr, q, R, rhs, col, flags) == num_cols;
+    for (int R = i0; R < i1; ++R) na += classify(R, rhs, col, flags) == num_cols;
     int32_t unused, art_through, art_all;
     sga_counts_before(0, na, unused, art_through, art_all);
     int64_t *mb = mt.basis + q * m;
     int64_t *abasis = at.M ? at.basis + q * m : nullptr;
     for (int R = i0; R < i1; ++R) {
         rhs = 0.0f; col = 0; flags = 0;
-        int32_t a = sga_node_row(b, nr, q, R, rhs, col, flags);
+        int32_t a = classify(R, rhs, col, flags);
         if (a == num_cols) {
             ++art_through;
             a = num_cols - 1 + (art_all - art_through);                     // what deal_artificial_columns leaves
@@ -226,11 +191,7 @@ __global__ __launch_bounds__(kSgaThreads) void k_sga_write(SbView mt, SbView at,
         }
         if (!A || R == (unsigned)m) continue;
         const int acol = ab[R];                                             // (a slack column is < num_cols - 1)
-        auto art_at = [&](int C) {
-            if (C < num_cols - 1) return src.elem(row, C);
-            if (C == nac - 1) return src.elem(row, num_cols - 1);
-            return C == acol ? 1.0f : 0.0f;
-        };
+        auto art_at = [&](int C) { return art_entry<float>(C, num_cols, nac, acol, [&](int c) { return src.elem(row, c); }); };
         for (unsigned C = c0; C < lda; C += cstep) {
             const int c = (int)C;
             const float4 v = make_float4(art_at(c), art_at(c + 1), art_at(c + 2), art_at(c + 3));
@@ -250,7 +211,7 @@ __global__ __launch_bounds__(kSgaThreads) void k_sga_art_objective(SbView at, in
     const unsigned ld = (unsigned)at.ld, nac = (unsigned)at.cols;
     for (unsigned C = blockIdx.z * kSgaThreads + threadIdx.x; C < ld; C += gridDim.z * kSgaThreads) {
         float s = 0.0f;
-        if (C < (unsigned)num_cols - 1u || C == nac - 1u)
+        if (art_objective_column(C, (unsigned)num_cols, nac))
             for (unsigned R = 0; R < (unsigned)m; ++R)
                 if (ab_artificial(ab[R], num_cols)) s = s + A[R * ld + C];
         A[(unsigned)m * ld + C] = s;

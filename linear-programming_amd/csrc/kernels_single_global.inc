@@ -105,17 +105,15 @@ __device__ __forceinline__ void s_solve_in_hbm(const SView &t, float sgn, float 
     }
 }
 
-// One member per workgroup: n-solve-tableau on member blockIdx.x in HBM, at most `cap` pivots in this launch.
-// gate: as for k_sb_solve.
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void k_sg_solve(SbView b, float sgn, float price_tol, float ratio_thr, int cap,
-                                                      const int32_t *gate)
-{
-    const int64_t q = blockIdx.x;
-    if (gate && gate[2 * q] != 1) return;
-    if (b.ctl[q].status != kRunning) return;
-    s_solve_in_hbm<THREADS>(sb_member(b, q), sgn, price_tol, ratio_thr, cap);
-}
+// the global form's Loop of k_sb_solve (kernels_single_batch.inc): k_sb_solve<THREADS, SbView, SolveInHbm> is what the
+// docs call k_sg_solve
+struct SolveInHbm {
+    template <int THREADS>
+    static __device__ __forceinline__ void run(const SView &t, float sgn, float price_tol, float ratio_thr, int cap)
+    {
+        s_solve_in_hbm<THREADS>(t, sgn, price_tol, ratio_thr, cap);
+    }
+};
 
 // ------------------------------------------------------------------ host-side launchers
 // dynamic LDS of k_sg_solve: pivot row + column snapshot
@@ -145,47 +143,20 @@ int sgbatch_launch_cap_for(int64_t rows, int64_t ld)
     const double cap = (double)kSingleLaunchCap * (double)kSingleLdsBudget / stored;
     return cap >= (double)kSingleLaunchCap ? kSingleLaunchCap : cap < 1.0 ? 1 : (int)cap;
 }
-namespace {
-template <int THREADS> bool sg_raise(int *members_per_cu, size_t lds)
-{
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sg_solve<THREADS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSingleLdsBudget);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sb_between<THREADS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSingleLdsBudget);
-    int nb = 0;
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_sg_solve<THREADS>, THREADS, lds);
-    if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-    *members_per_cu = nb;
-    return true;
-}
-}  // namespace
 // false: pivot row + column snapshot do not fit the budget, or the attributes could not be raised
 bool sgbatch_available(const SbView &b, int threads, int *members_per_cu)
 {
     const size_t lds = sgbatch_lds_bytes(b);
     if (lds > kSingleLdsBudget) return false;
     if ((uint64_t)b.rows * (uint64_t)b.ld * sizeof(float) >= (1ull << 32)) return false;   // (implied by the budget: k_sg_solve's offsets)
-    return threads == 256 ? sg_raise<256>(members_per_cu, lds) : sg_raise<1024>(members_per_cu, lds);
+    return sb_kernel_attributes<SbView, SolveInHbm>(threads, true, lds, members_per_cu);
 }
 void launch_sg_solve(const SbView &b, int threads, int is_max, double f, int cap, const int32_t *gate, hipStream_t s)
 {
-    const SingleThresholds th = single_thresholds(f);
-    const size_t lds = sgbatch_lds_bytes(b);
-    if (threads == 256)
-        hipLaunchKernelGGL(k_sg_solve<256>, dim3((unsigned)b.n_lps), dim3(256), lds, s, b, s_sgn_of(is_max), th.price,
-                           th.ratio, cap, gate);
-    else
-        hipLaunchKernelGGL(k_sg_solve<1024>, dim3((unsigned)b.n_lps), dim3(1024), lds, s, b, s_sgn_of(is_max), th.price,
-                           th.ratio, cap, gate);
+    sb_solve_launch<SbView, SolveInHbm>(b, nullptr, b.n_lps, sgbatch_lds_bytes(b), threads, is_max, f, cap, gate, s);
 }
 // k_sb_between for a pair of global-form batches: the body is the LDS form's, the LDS what it uses
 void launch_sg_between(const SbView &art, const SbView &mb, int threads, int32_t *phase, double f, int64_t max_pivots, hipStream_t s)
 {
-    const float feasible = single_thresholds(f).feasible;
-    const size_t lds = sgbatch_between_lds_bytes(art);
-    if (threads == 256)
-        hipLaunchKernelGGL(k_sb_between<256>, dim3((unsigned)art.n_lps), dim3(256), lds, s, art, mb, phase, feasible, max_pivots);
-    else
-        hipLaunchKernelGGL(k_sb_between<1024>, dim3((unsigned)art.n_lps), dim3(1024), lds, s, art, mb, phase, feasible, max_pivots);
+    sb_between_launch(art, mb, nullptr, art.n_lps, sgbatch_between_lds_bytes(art), threads, phase, f, max_pivots, s);
 }

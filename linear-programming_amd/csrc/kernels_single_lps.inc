@@ -51,17 +51,42 @@ struct SlpLds {
     int32_t wave_slack[kSlpThreads / 64], wave_art[kSlpThreads / 64];
 };
 
-// One member, the whole workgroup: the row pass over its m <= kSlpMaxRows rows (L, sense: the member's own, tight),
-// then the write pass into its slots.  cols: the main tableau's columns, ncv + slack columns + 1.
-__device__ __forceinline__ void slp_assemble_member(const AsmSlot &mt, const AsmSlot &at, const float *L, const int32_t *sense,
-                                                    int m, int ncv, int cols, SlpLds &l)
+// ONE copy of a problem row's columns, for both assembly families (slp_assemble_member here, k_sga_lps_rows of
+// kernels_single_assemble_global.inc): from the row's word, the rows before it that are not `=`, the artificial rows
+// up to and including it and those of the whole member -> its slack column (-1: none) and its ab[] entry, which for an
+// artificial row is what deal_artificial_columns leaves: cols - 1 + the artificial rows with a greater index.
+__device__ __forceinline__ void slp_row_columns(int word, int ncv, int cols, int slack_before, int art_through, int art_all,
+                                                int32_t &scol, int32_t &ab)
 {
+    scol = (word >> 1) != 2 ? ncv + slack_before : -1;
+    ab = row_word_artificial(word) ? cols - 1 + (art_all - art_through) : scol;
+}
+
+// the rows of a batch's members: every member of one shape (SlpView), or each of its own (a ragged batch)
+struct SlpMember { const float *L; const int32_t *sense; int m, ncv, cols; };       // cols: ncv + slack columns + 1
+__device__ __forceinline__ SlpMember slp_member(const SlpView &sp, int64_t q)
+{
+    const int m = (int)sp.m, ncv = (int)sp.ncv;
+    return SlpMember{sp.L + q * (int64_t)(m + 1) * (ncv + 1), sp.sense + q * m, m, ncv, ncv + (int)sp.n_slack + 1};
+}
+__device__ __forceinline__ SlpMember slp_member(const SrlpView &sp, int64_t q)
+{
+    const SrlpMember d = sp.members[q];
+    return SlpMember{sp.L + d.l_off, sp.sense + d.s_off, d.m, d.ncv, d.ncv + d.n_slack + 1};
+}
+
+// One member, the whole workgroup: the row pass over its m <= kSlpMaxRows rows (L, sense: the member's own, tight),
+// then the write pass into its slots.
+__device__ __forceinline__ void slp_assemble_member(const AsmSlot &mt, const AsmSlot &at, const SlpMember &sp, SlpLds &l)
+{
+    const float *L = sp.L;
+    const int m = sp.m, ncv = sp.ncv, cols = sp.cols;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = ncv + 1;
     // ---- the row pass
     int w = 0;
     bool slack = false, art = false;
     if (tid < m) {
-        w = row_word(L[(int64_t)tid * W + ncv] < 0.0f, sense[tid]);                 // :243
+        w = row_word(L[(int64_t)tid * W + ncv] < 0.0f, sp.sense[tid]);              // :243
         slack = (w >> 1) != 2;
         art = row_word_artificial(w);
     }
@@ -78,9 +103,7 @@ __device__ __forceinline__ void slp_assemble_member(const AsmSlot &mt, const Asm
     }
     if (tid < m) {
         l.word[tid] = w;
-        l.scol[tid] = slack ? ncv + slack_before : -1;
-        // what deal_artificial_columns leaves: cols - 1 + the artificial rows with a greater index
-        l.ab[tid] = art ? cols - 1 + (art_all - art_through) : ncv + slack_before;
+        slp_row_columns(w, ncv, cols, slack_before, art_through, art_all, l.scol[tid], l.ab[tid]);
     }
     __syncthreads();
     // ---- the write pass
@@ -89,17 +112,22 @@ __device__ __forceinline__ void slp_assemble_member(const AsmSlot &mt, const Asm
     });
 }
 
-// Member blockIdx.x.  at.M == nullptr: the group has no artificial rows.  sp.m <= kSlpMaxRows.
-__global__ __launch_bounds__(kSlpThreads) void k_slp_assemble(SbView mt, SbView at, SlpView sp)
+// The member the workgroup owns (blockIdx.x).  at.M == nullptr: no member has artificial rows.  Every m <= kSlpMaxRows.
+template <class View, class Rows>
+__global__ __launch_bounds__(kSlpThreads) void k_slp_assemble(View mt, View at, Rows sp)
 {
     __shared__ SlpLds l;
     const int64_t q = blockIdx.x;
-    const int m = (int)sp.m, ncv = (int)sp.ncv, cols = ncv + (int)sp.n_slack + 1;
-    slp_assemble_member(sb_slot(mt, q, m), sb_slot(at, q, m), sp.L + q * (int64_t)(m + 1) * (ncv + 1), sp.sense + q * m, m, ncv,
-                        cols, l);
+    const SlpMember rows = slp_member(sp, q);
+    const SrMember dm = sb_descriptor(mt, q), da = sb_descriptor_art(at, q, dm);
+    slp_assemble_member(sb_slot(mt, dm), sb_slot(at, da), rows, l);
 }
 
-void launch_slp_assemble(const SbView &mt, const SbView &at, const SlpView &sp, hipStream_t s)
+namespace {
+template <class View, class Rows> void slp_assemble_launch(const View &mt, const View &at, const Rows &sp, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_slp_assemble, dim3((unsigned)mt.n_lps), dim3(kSlpThreads), 0, s, mt, at, sp);
+    hipLaunchKernelGGL((k_slp_assemble<View, Rows>), dim3((unsigned)mt.n_lps), dim3(kSlpThreads), 0, s, mt, at, sp);
 }
+}  // namespace
+void launch_slp_assemble(const SbView &mt, const SbView &at, const SlpView &sp, hipStream_t s) { slp_assemble_launch(mt, at, sp, s); }
+void launch_slp_assemble(const SrView &mt, const SrView &at, const SrlpView &sp, hipStream_t s) { slp_assemble_launch(mt, at, sp, s); }

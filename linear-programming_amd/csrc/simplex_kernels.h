@@ -539,8 +539,8 @@ void launch_s_handover_copy(const SView &art, const SView &mt, hipStream_t s);
 
 // Batches of single-float tableaux of one shape (kernels_single_batch.inc, capi_single_batch.inc): one workgroup owns
 // one member for its whole solve (s_solve_in_lds, the loop of k_s_solve).  Member q: tableau at M + q * stride (stride
-// = rows * ld floats, a multiple of 32), basis at basis + q * max(rows - 1, 1), control block ctl + q, trace at
-// trace_ec / trace_cr + q * trace_cap.
+// = rows * ld floats, a multiple of 32), basis at basis + q * max(rows - 1, 1) (a member of one row has no basis entry: nothing reads one there),
+// control block ctl + q, trace at trace_ec / trace_cr + q * trace_cap.
 struct SbView {
     float   *M;
     int64_t  stride, ld, rows, cols, n_lps;
@@ -561,7 +561,9 @@ void launch_sb_begin(const SbView &b, int64_t max_pivots, const int32_t *phase, 
 void launch_sb_solve(const SbView &b, int threads, int is_max, double fp_factor, int cap, const int32_t *gate, hipStream_t s);
 void launch_sb_between(const SbView &art, const SbView &main_b, int threads, int32_t *phase, double fp_factor,
                        int64_t max_pivots, hipStream_t s);
-// RAGGED batches of single-float tableaux (kernels_single_ragged.inc, capi_single_ragged.inc): every member its own
+// Every kernel of the family is ONE template over the batch's view (SbView, SrView below); the launchers are overloads
+// on the view.
+// RAGGED batches of single-float tableaux (kernels_single_batch.inc over an SrView, capi_single_ragged.inc): every member its own
 // shape and sense, one workgroup per member, the loop and the step between the phases those of the batch of one shape
 // (src/simplex.lisp:402-461).  Member q: tableau at M + m_off floats (rows x ld, ld = cols rounded up to 32 floats, so
 // every m_off is a multiple of 32 and the 16-byte quad loads of s_solve_in_lds stay aligned), basis at basis +
@@ -575,13 +577,19 @@ struct SrView {
     int64_t         trace_cap, n_lps;
     const SrMember *members;              // n_lps descriptors (device)
 };
+// A batch of one shape is a ragged batch whose descriptors can be computed: member q of b (sgn: the call says it).
+// The kernels and the host (capi_single_batch.inc: sb_host_member) ask this ONE function.
+XW_HD inline SrMember sb_descriptor(const SbView &b, int64_t q)
+{
+    return SrMember{q * b.stride, q * (b.rows > 1 ? b.rows - 1 : 1), b.ld, b.rows, b.cols, 0.0f};
+}
 bool   sragged_raise(int threads);                                           // the two kernels' dynamic-LDS attribute
-bool   sragged_occupancy(int threads, size_t lds, int *members_per_cu);      // k_sr_solve's residency at this LDS size
+bool   sragged_occupancy(int threads, size_t lds, int *members_per_cu);      // the ragged solve kernel's residency at this LDS size
 // one occupancy class: `count` member indices at `members` (device; nullptr: members 0 .. count - 1), lds: the
 // class's largest member's bytes
-void launch_sr_solve(const SrView &b, const int32_t *members, int64_t count, size_t lds, int threads, double fp_factor,
+void launch_sb_solve(const SrView &b, const int32_t *members, int64_t count, size_t lds, int threads, double fp_factor,
                      int cap, const int32_t *gate, hipStream_t s);
-void launch_sr_between(const SrView &art, const SrView &main_b, const int32_t *members, int64_t count, size_t lds,
+void launch_sb_between(const SrView &art, const SrView &main_b, const int32_t *members, int64_t count, size_t lds,
                        int threads, int32_t *phase, double fp_factor, int64_t max_pivots, hipStream_t s);
 // The global form of a single-float batch (kernels_single_global.inc): one workgroup per member, the tableau in HBM,
 // pivot row and column snapshot in LDS -- for members beyond the LDS budget.
@@ -619,22 +627,22 @@ struct SlpView {
 constexpr int kSlpMaxRows = 256;                                            // k_slp_assemble: one row per thread, one trip
 // every member of mt and of at (at.M == nullptr: no artificial rows): tableau over the whole leading dimension, basis
 void launch_slp_assemble(const SbView &mt, const SbView &at, const SlpView &sp, hipStream_t s);
-// RAGGED batches built on the device (kernels_single_ragged_build.inc, capi_single_ragged_build.inc): the two
-// assemblies above with a shape per member, and the light read-back of a ragged batch.
+// RAGGED batches built on the device (capi_single_ragged_build.inc): the two assemblies above with a shape per member
+// (the same kernel templates over SrView and the sources below), and the light read-back of a ragged batch.
 // From rows: L and sense tight and concatenated, member q's (m + 1) x (ncv + 1) floats at L + l_off, its m senses at
 // sense + s_off; n_slack of its rows are not `=`, n_art end up `>=` or `=`.  m <= kSlpMaxRows.
 struct SrlpMember { int64_t l_off, s_off; int32_t m, ncv, n_slack, n_art; };
+struct SrlpView { const float *L; const int32_t *sense; const SrlpMember *members; };
 // From nodes: node q's d rows (newest first) at off in the concatenated var / sense / bound arrays.
 struct SrbbNode { int64_t off; int32_t d; };
+struct SrbbNodeRows { const int64_t *var; const int32_t *sense; const int64_t *bound; const SrbbNode *nodes; };
 // every member of mt and of at (at.M == nullptr: no member has artificial rows); all pointers are device pointers
-void launch_srlp_assemble(const SrView &mt, const SrView &at, const float *L, const int32_t *sense, const SrlpMember *members,
-                          hipStream_t s);
+void launch_slp_assemble(const SrView &mt, const SrView &at, const SrlpView &sp, hipStream_t s);
 // lds: sbb_assemble_lds of the largest member of the launch
-void launch_srbb_assemble(const SrView &mt, const SrView &at, const SbbBaseView &b, const int64_t *var, const int32_t *sense,
-                          const int64_t *bound, const SrbbNode *nodes, size_t lds, hipStream_t s);
+void launch_sbb_assemble(const SrView &mt, const SrView &at, const SbbBaseView &b, const SrbbNodeRows &nr, size_t lds, hipStream_t s);
 // per member: last column, last row, basis, into three concatenated planes at the running sums of rows, cols (col_off,
 // device, n_lps entries) and rows - 1
-void launch_sr_readback(const SrView &b, const int64_t *col_off, float *rhs, float *obj, int64_t *basis, hipStream_t s);
+void launch_sb_readback(const SrView &b, const int64_t *col_off, float *rhs, float *obj, int64_t *basis, hipStream_t s);
 // The same two assemblies spread over a grid, for GLOBAL-form batches (kernels_single_assemble_global.inc): a row pass
 // into per-member scratch planes (device memory of sga_*_scratch_bytes, the caller's, alive until the stream has run
 // the launches), one write pass and the artificial objective row, ordered by the stream alone.  Any m, any depth.

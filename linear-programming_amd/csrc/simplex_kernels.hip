@@ -78,11 +78,10 @@
 //     kernels_batch_lps.inc       double-precision batches built from problem rows (k_blp_*), k_batch_readback
 //     kernels_launch.inc          host-side launchers, tuning state
 //     kernels_single.inc          single-float tableaux: one copy of the selection code, k_s_select / k_s_update, k_s_solve (LDS)
-//     kernels_single_batch.inc    batches of single-float tableaux: k_sb_solve (one workgroup per member, LDS), k_sb_between
-//     kernels_single_global.inc   the global form of those batches: k_sg_solve (one workgroup per member, the tableau in HBM)
-//     kernels_single_bb.inc       single-float branch-and-bound: float node tableaux into padded members, light read-back (k_sbb_assemble, k_sb_readback)
-//     kernels_single_lps.inc      single-float batches built from problem rows under Lisp's contagion (k_slp_assemble)
-//     kernels_single_ragged_build.inc  ragged batches built on the device from rows or node rows, their light read-back (k_srlp_assemble, k_srbb_assemble, k_sr_readback)
+//     kernels_single_batch.inc    batches of single-float tableaux, of one shape or ragged: the member view, k_sb_solve<THREADS, View, Loop> (one workgroup per member), k_sb_between
+//     kernels_single_global.inc   the global form of those batches: the loop with the tableau in HBM (SolveInHbm)
+//     kernels_single_bb.inc       single-float branch-and-bound: float node tableaux into padded members, light read-back (k_sbb_assemble<View, Nodes>, k_sb_readback<View>)
+//     kernels_single_lps.inc      single-float batches built from problem rows under Lisp's contagion (k_slp_assemble<View, Rows>)
 //     kernels_single_assemble_global.inc  both single-float assemblies spread over a grid, for global-form batches (k_sga_*)
 #include "simplex_kernels.h"
 #include <type_traits>
@@ -110,11 +109,9 @@ namespace mi355x {
 #include "kernels_launch.inc"
 #include "kernels_single.inc"
 #include "kernels_single_batch.inc"
-#include "kernels_single_ragged.inc"
 #include "kernels_single_global.inc"
 #include "kernels_single_bb.inc"
 #include "kernels_single_lps.inc"
-#include "kernels_single_ragged_build.inc"
 #include "kernels_single_assemble_global.inc"
 
 }  // namespace mi355x

@@ -1,4 +1,4 @@
-"""Ragged batches of single-float LPs on the GPU (kernels_single_ragged.inc behind mi355x_sbatch_create_ragged) against
+"""Ragged batches of single-float LPs on the GPU (kernels_single_batch.inc over an SrView behind mi355x_sbatch_create_ragged) against
 the float32 model of tests/single_cases.py, member by member: status, pivot count, trace, basis and EVERY entry of the
 final tableau bit for bit (any NaN equals any NaN); no tolerance appears anywhere.  The lists are those of
 tests/single_ragged_cases.py.  Every case runs with the workgroup forced to 256 and to 1024 threads, and with the

@@ -1,4 +1,4 @@
-"""Ragged single-float batches BUILT ON THE DEVICE (k_srlp_assemble / k_srbb_assemble / k_sr_readback behind
+"""Ragged single-float batches BUILT ON THE DEVICE (k_slp_assemble / k_sbb_assemble / k_sb_readback over an SrView behind
 mi355x_sbatch_create_lps_ragged, _create_nodes_ragged and _readback_ragged) against the float32 model of
 tests/single_cases.py, single_lps_cases.assemble_rows and single_bb_cases.build_node, member by member and bit for bit:
 what a member starts from (every stored entry, padding included, both bases) and what it ends with (status, pivot
